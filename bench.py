@@ -11,6 +11,10 @@ VGG-16 conv1_1..conv4_3 on B*T frames -> 64-point gather + serialise -> NTM forw
 (T*65 steps) -> offsets loss -> BPTT -> gradient all-reduce (N > 1) -> clip + RMSProp.
 Workload = BASELINE.json configs[1]: batch 32 sequences / GPU, seq_len 20, 224x224 frames,
 NTMCell(128x20, hidden 200, 4 read / 1 write heads), fp32 (weak scaling: per-GPU work fixed).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes runs of its own: the
+recurrent kernels and the trunk alone (memory_step, memory_step_bptt, breakdown_ms.trunk_alone / cu_seconds) and the CPU
+baseline (unless --no-cpu-baseline).  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -328,6 +332,38 @@ def trunk_alone_probe(trk, frames):
     return _median_ms(lambda: trk.vgg(frames, out=trk._slots[0]["buf"]))
 
 
+DUMP_MAX_ELEMS = 1 << 22          # per array (16 MB of float32); larger outputs are dumped as a fixed, seeded sample
+
+
+def _dump_array(t, seed):
+    """`t` flattened to float32 on the host, or DUMP_MAX_ELEMS of its elements at fixed seeded positions (sorted)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(flat.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, trk, last, mode):
+    """What the last timed step computed, as out_dir/<name>.npy.  train: the step's loss, the gradient it computed and the
+    parameters after its optimiser update; infer: the logits of the forward pass.  Both: a sample of the trunk's conv4_3
+    features of the last batch."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if mode == "train":
+        arrays["loss"] = _dump_array(last["loss"], 1)
+        arrays["grad"] = _dump_array(trk._flat_grad(), 2)
+        arrays["params"] = _dump_array(trk._ckpt_params().flat, 3)
+    else:
+        arrays["logits"] = _dump_array(last["logits"], 4)
+    arrays["features_sample"] = _dump_array(trk._slots[trk._next_slot ^ 1]["buf"], 5)     # the slot submitted last
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step written to %s: %s" % (out_dir, ", ".join("%s %s" % (k, a.shape) for k, a in arrays.items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -338,7 +374,12 @@ def main():
                          "which computes the whole map: an optional optimisation, never the headline number)")
     ap.add_argument("--batch", type=int, default=32, help="sequences per GPU")
     ap.add_argument("--seq-len", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: memory_step / memory_step_bptt, breakdown_ms.trunk_alone / "
+                         "cu_seconds and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--mode", default="train", choices=["train", "infer"])
     ap.add_argument("--model", default="ntm", choices=["ntm", "dnc"],
                     help="ntm = BASELINE configs[1] (the headline metric); dnc = configs[2] (DNC 256x64, 4 read heads), reported for reference")
@@ -405,6 +446,7 @@ def main():
 
     ev = lambda: torch.cuda.Event(enable_timing=True)
     marks_vgg, marks_ntm = [], []
+    last = {}                       # what the latest step returned (--dump-outputs)
     s_vgg, s_ntm = trk._streams()
 
     def submit(timed):
@@ -427,17 +469,18 @@ def main():
                 e0, e1 = ev(), ev()
                 with torch.cuda.stream(s_ntm):
                     e0.record()
-                trk.train_on_submitted(gts0, offs)
+                last["loss"] = trk.train_on_submitted(gts0, offs)
                 with torch.cuda.stream(s_ntm):
                     e1.record()
                 marks_ntm.append((e0, e1))
             else:
-                trk.train_on_submitted(gts0, offs)
+                last["loss"] = trk.train_on_submitted(gts0, offs)
         else:
             slot, done = trk._pending.pop(0)
             s_ntm.wait_event(done)
             with torch.cuda.stream(s_ntm):
-                trk.forward_features(slot["buf"], gts0)
+                res = trk.forward_features(slot["buf"], gts0)
+                last["logits"] = res[2] if args.model == "ntm" else res[0]     # NTM: (X, st0, logits, rec); DNC: (logits, state)
                 slot["free"] = torch.cuda.Event()
                 slot["free"].record(s_ntm)
 
@@ -471,6 +514,8 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trk, last, args.mode)
 
     if rank == 0:
         frames_total = world * B * T * args.steps
@@ -568,30 +613,31 @@ def main():
         if args.model == "dnc":
             ch = getattr(trk, "cluster_choice", None)
             out["config"]["cluster_choice"] = ("%s, k = %d (constructor's choice for a step with a trunk to overlap)" % ch) if ch else "core's automatic choice"
-        out["memory_step"], out["memory_step_bptt"] = memory_step_probe(trk, args.model, gts0, offs, B, T)
-        # The step is bound by total CU-time once both streams are busy: the trunk's workgroups fill whatever CUs the
-        # persistent core workgroups (one per sequence; B * k for the DNC cluster forms) do not hold.
-        from ntmtrack import _lib as L_
-        cus = int(L_.lib().ntk_cu_count())
-        trunk_alone = trunk_alone_probe(trk, frames)
-        core_wgs = B * (getattr(trk.core, "last_cluster_k", 1) if args.model == "dnc" else 1)
-        # the persistent recurrent kernels alone (the probes above): what the core's workgroups hold their CUs for; the per-stream
-        # event time `ntm_fwd_bwd_opt_stream` also contains the core stream's wait for its features when the trunk is the bound
-        core_ms = out["memory_step"]["ms"] + (out["memory_step_bptt"]["ms"] if args.mode == "train" else 0.0)
-        cu_trunk, cu_core = trunk_alone * 1e-3 * cus, core_ms * 1e-3 * min(core_wgs, cus)
-        serial = bool(getattr(trk, "serial_trunk", False))          # trunk and core on ONE stream (a cooperative core over every CU): nothing overlaps
-        out["breakdown_ms"]["trunk_alone"] = round(trunk_alone, 3)
-        out["breakdown_ms"]["cu_seconds"] = {
-            "trunk": round(cu_trunk, 3), "core": round(cu_core, 3), "compute_units": cus, "core_workgroups": core_wgs,
-            "cu_time_bound_ms": None if serial else round((cu_trunk + cu_core) / cus * 1e3, 3),
-            "schedule": "serial: trunk pass and core pass alternate on one stream" if serial else "overlapped: the trunk pass of batch i + 1 runs beside the core pass of batch i",
-            "note": "trunk = the trunk pass alone on the idle device x every CU (its grids fill the chip); core = the recurrent forward + "
-                    "BPTT kernels alone (memory_step.ms + memory_step_bptt.ms) x the CUs their persistent workgroups hold; "
-                    "cu_time_bound_ms = (trunk + core) / CUs: what the step cannot beat while both streams overlap"}
-        if not args.no_cpu_baseline and world == 1:
-            # the DNC restatement costs ~15 ms per step on the host: a 4-frame sequence keeps the sample inside its time budget
-            out["cpu_baseline"] = cpu_baseline(ws, T=20 if args.model == "ntm" else 4, model=args.model,
-                                               dnc_shape=(args.mem_size or 256, args.mem_dim or 64))
+        if args.full:          # probes that take runs of their own, outside the timed region
+            out["memory_step"], out["memory_step_bptt"] = memory_step_probe(trk, args.model, gts0, offs, B, T)
+            # The step is bound by total CU-time once both streams are busy: the trunk's workgroups fill whatever CUs the
+            # persistent core workgroups (one per sequence; B * k for the DNC cluster forms) do not hold.
+            from ntmtrack import _lib as L_
+            cus = int(L_.lib().ntk_cu_count())
+            trunk_alone = trunk_alone_probe(trk, frames)
+            core_wgs = B * (getattr(trk.core, "last_cluster_k", 1) if args.model == "dnc" else 1)
+            # the persistent recurrent kernels alone (the probes above): what the core's workgroups hold their CUs for; the per-stream
+            # event time `ntm_fwd_bwd_opt_stream` also contains the core stream's wait for its features when the trunk is the bound
+            core_ms = out["memory_step"]["ms"] + (out["memory_step_bptt"]["ms"] if args.mode == "train" else 0.0)
+            cu_trunk, cu_core = trunk_alone * 1e-3 * cus, core_ms * 1e-3 * min(core_wgs, cus)
+            serial = bool(getattr(trk, "serial_trunk", False))          # trunk and core on ONE stream (a cooperative core over every CU): nothing overlaps
+            out["breakdown_ms"]["trunk_alone"] = round(trunk_alone, 3)
+            out["breakdown_ms"]["cu_seconds"] = {
+                "trunk": round(cu_trunk, 3), "core": round(cu_core, 3), "compute_units": cus, "core_workgroups": core_wgs,
+                "cu_time_bound_ms": None if serial else round((cu_trunk + cu_core) / cus * 1e3, 3),
+                "schedule": "serial: trunk pass and core pass alternate on one stream" if serial else "overlapped: the trunk pass of batch i + 1 runs beside the core pass of batch i",
+                "note": "trunk = the trunk pass alone on the idle device x every CU (its grids fill the chip); core = the recurrent forward + "
+                        "BPTT kernels alone (memory_step.ms + memory_step_bptt.ms) x the CUs their persistent workgroups hold; "
+                        "cu_time_bound_ms = (trunk + core) / CUs: what the step cannot beat while both streams overlap"}
+            if not args.no_cpu_baseline and world == 1:
+                # the DNC restatement costs ~15 ms per step on the host: a 4-frame sequence keeps the sample inside its time budget
+                out["cpu_baseline"] = cpu_baseline(ws, T=20 if args.model == "ntm" else 4, model=args.model,
+                                                   dnc_shape=(args.mem_size or 256, args.mem_dim or 64))
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

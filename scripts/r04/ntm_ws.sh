@@ -12,8 +12,8 @@ timeout -k 10 120 python scripts/dev_ntm_timing.py 32 20 >> $OUT/timing.txt 2>&1
 echo "== res forms" >> $OUT/timing.txt
 NTK_NTM_FWD_FORM=res NTK_NTM_BWD_FORM=res timeout -k 10 120 python scripts/dev_ntm_timing.py 32 20 >> $OUT/timing.txt 2>&1 || exit 1
 grep -v amdgpu.ids $OUT/timing.txt
-timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_ws.json 2> $OUT/bench_ws.err || exit 1
-NTK_NTM_FWD_FORM=res NTK_NTM_BWD_FORM=res timeout -k 10 300 python bench.py --no-cpu-baseline > $OUT/bench_res.json 2> $OUT/bench_res.err || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_ws.json 2> $OUT/bench_ws.err || exit 1
+NTK_NTM_FWD_FORM=res NTK_NTM_BWD_FORM=res timeout -k 10 300 python bench.py --full --no-cpu-baseline > $OUT/bench_res.json 2> $OUT/bench_res.err || exit 1
 python - <<PY
 import json
 for n in ("ws","res"):

@@ -17,7 +17,7 @@ def test_bench_emits_contract_json(cuda, capsys, monkeypatch, model):
         sys.path.insert(0, ROOT)
     bench = importlib.import_module("bench")
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
-                                      "--seq-len", "2", "--no-cpu-baseline", "--model", model])
+                                      "--seq-len", "2", "--no-cpu-baseline", "--full", "--model", model])
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         monkeypatch.delenv(k, raising=False)
     bench.main()
@@ -52,6 +52,45 @@ def test_bench_emits_contract_json(cuda, capsys, monkeypatch, model):
     # frames/s = frames per step / seconds per step
     assert abs(out["value"] - 2 * 2 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-2
 
+
+
+@pytest.mark.parametrize("mode", ["train", "infer"])
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(cuda, capsys, monkeypatch, tmp_path, mode):
+    """A plain run (no --full) prints the headline keys without the probes that take runs of their own, and
+    --dump-outputs writes what the last timed step computed as float32 .npy files."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import numpy as np
+    bench = importlib.import_module("bench")
+    out_dir = tmp_path / "outputs"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                                      "--seq-len", "2", "--mode", mode, "--dump-outputs", str(out_dir)])
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main()
+    lines = [l for l in capsys.readouterr().out.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 1
+    assert abs(out["value"] - 2 * 2 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-2
+    for key in ("memory_step", "memory_step_bptt", "cpu_baseline"):
+        assert key not in out, key
+    assert "trunk_alone" not in out["breakdown_ms"] and "cu_seconds" not in out["breakdown_ms"]
+    names = {"loss", "grad", "params", "features_sample"} if mode == "train" else {"logits", "features_sample"}
+    assert {p.stem for p in out_dir.glob("*.npy")} == names
+    total = 0
+    for name in names:
+        a = np.load(out_dir / (name + ".npy"))
+        assert a.dtype == np.float32 and a.ndim == 1 and a.size > 0 and np.isfinite(a).all(), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    if mode == "train":
+        assert np.load(out_dir / "loss.npy").shape == (1,) and np.abs(np.load(out_dir / "grad.npy")).max() > 0
+    else:
+        assert np.load(out_dir / "logits.npy").size == 2 * 2 * 65 * 2        # [B, T * 65, 2]
+    assert np.load(out_dir / "features_sample.npy").max() > 0                  # post-ReLU conv4_3 features
 
 def test_bench_two_ranks_print_one_json_line(cuda, tmp_path):
     """The N > 1 contract, rehearsed on the one-GPU box: `python -m torch.distributed.run --nproc-per-node 2 bench.py --gpus 2`
