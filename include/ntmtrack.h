@@ -211,6 +211,99 @@ int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shi
                     float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                     void* stream);
 
+/* ------------------------------------------------------------------------
+ * NTM cell with a deep controller: a MultiRNNCell of L >= 2 BasicLSTMCell
+ * layers (ntm_cell.py:45-50, :101-105) inside the persistent sequence kernels.
+ * Layer 0 reads [x_t ; read_{t-1}] and h_0(t-1), layer k >= 1 reads h_{k-1}(t)
+ * and h_k(t-1), h_{L-1}(t) drives the unpack / output linear; addressing and
+ * memory as ntk_ntm_seq_fwd.  Controller state [B][2*hid*L] = c_0, h_0, c_1,
+ * h_1, ... (MultiRNNCell concatenation).
+ *
+ * Sizes (align4(n) = n rounded up to a multiple of 4; RM = R*Md; hid % 4 == 0):
+ *   ldx = align4(D)              ldxt = align4(hid)       ldz, ldh, PP: ntk_ntm_padded_dims
+ *   ld0 = align4(D + RM + hid + 1)                        ld1 = align4(2*hid + 1)
+ *   rf0 = align4(RM + hid + 1)   rf1 = align4(2*hid + 1)  cb0 = align4(RM + hid)   cb1 = 2*hid
+ * Gate columns n' = unit*4 + gate (gate order i,j,f,o) unless noted.
+ *
+ * Every entry validates on the host before any launch: NTK_ERR_BAD_SHAPE
+ * (L < 2, non-positive sizes), NTK_ERR_UNSUPPORTED (a shape outside
+ * ntk_ntm_seq_deep_supported), NTK_ERR_BAD_PTR (null or misaligned pointer);
+ * the reason is in ntk_last_error().
+ * --------------------------------------------------------------------- */
+
+/* 1 if the deep kernels run this configuration (forward AND BPTT), else 0 with
+ * the reason in ntk_last_error().  Host arithmetic only: the same limits as
+ * ntk_ntm_seq_fwd, hid % 4 == 0, and every layer's state within the LDS. */
+int ntk_ntm_seq_deep_supported(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L);
+
+/* Float counts of the three packed weight buffers:
+ *   n_wx0 = 4*hid*ldx   n_wf = 4*hid*(rf0 + (L-1)*rf1)   n_wb = 4*hid*(cb0 + (L-1)*cb1) */
+int ntk_ntm_seq_deep_packed_floats(int D, int R, int Md, int hid, int L, size_t* n_wx0, size_t* n_wf, size_t* n_wb);
+
+/* Pack the controller weights into the kernels' layouts (one launch; run it
+ * whenever the weights change -- nothing is cached).  In:
+ *   lowerT   the L-1 lower layers back to back, TF gate-major rows (g*hid + unit):
+ *            layer 0 [4*hid][ld0]  columns x (D) | read (RM) | h_0 (hid) | bias | 0..
+ *            layer k [4*hid][ld1]  columns h_{k-1} (hid) | h_k (hid) | bias | 0..   (k = 1 .. L-2)
+ *   top_WxT  [4*hid][ldxt]          top layer, input h_{L-2} (the single-layer WxT layout)
+ *   top_Wr   [align4(RM+hid+1)][4*hid]  top layer: rows 0..RM-1 unused, rows RM..RM+hid-1
+ *            multiply h_{L-1}, row RM+hid = bias (the single-layer Wr layout)
+ * Out (16-byte aligned):
+ *   Wx0 [4*hid][ldx]     layer 0's x part, zero columns from D on; xproj = X * Wx0^T
+ *   Wf  forward blocks [4*hid] wide: layer 0 [rf0] rows read | h_0 | bias | 0..,
+ *       then layers 1..L-1 [rf1] rows each h_{k-1} | h_k | bias | 0..
+ *   Wb  the blocks transposed, no bias: layer 0 [4*hid][cb0] columns read | h_0 | 0..,
+ *       then layers 1..L-1 [4*hid][cb1] columns h_{k-1} | h_k */
+int ntk_ntm_seq_deep_pack(int D, int R, int Md, int hid, int L, const float* lowerT, const float* top_WxT,
+                          const float* top_Wr, float* Wx0, float* Wf, float* Wb, void* stream);
+
+/* S steps for B sequences, one persistent workgroup per sequence.  In:
+ * X [B,S,ldx] (read only for st_buf0), xproj [B,S,4*hid] = X * Wx0^T (no bias),
+ * Wf, Wa [ldh][PP], M0 [B,N,Md], w0 [B,H,N], read0 [B,R,Md], cs0 [B,2*hid*L].
+ * Out: logits [B,S,O], outputs (softmax, nullable), final state (cs_out [B,2*hid*L]).
+ * Records (each nullable; st_gates with st_c): the top layer's as ntk_ntm_seq_fwd
+ *   st_z [B,S,ldz] = [read_{t-1} | h_{L-1}(t-1) | 1 | 0..], st_gates [B,S,hid,4],
+ *   st_c [B,S,hid], st_h [B,S,ldh] = [h_{L-1}(t) | 1 | 0..], st_u [B,S,PP],
+ *   st_wc / st_wv / st_w [B,S,H,N], st_M [B,S,N,Md], st_read [B,S,R,Md];
+ * and the lower layers'
+ *   st_xtop   [B,S,ldxt]       h_{L-2}(t) | 0..  (the top layer's input)
+ *   st_buf0   [B,S,ld0]        x_t (D) | read_{t-1} | h_0(t-1) | 1 | 0..
+ *   st_bufk   [L-2][B,S,ld1]   layer k = 1..L-2: h_{k-1}(t) | h_k(t-1) | 1 | 0..  (unused at L = 2)
+ *   st_lgates [L-1][B,S,hid,4] activated gates of layers 0..L-2 (16-byte aligned)
+ *   st_lc     [L-1][B,S,hid]   c_k(t) of layers 0..L-2 */
+int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                         int write_first, int D,
+                         const float* X, const float* xproj, const float* Wf, const float* Wa,
+                         const float* M0, const float* w0, const float* read0, const float* cs0,
+                         float* logits, float* outputs,
+                         float* M_out, float* w_out, float* read_out, float* cs_out,
+                         float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                         float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                         float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
+                         void* stream);
+
+/* Full BPTT through a recorded deep sequence.  In: Wb, WaT [PP][ldhT] (Wa
+ * transposed, ldhT >= hid, multiple of 4), M0, w0, cs0 [B,2*hid*L], the forward's
+ * records st_gates .. st_M (top layer and heads) and st_lgates, st_lc (lower
+ * layers), dlogits [B,S,O], optional gradient of the final state (dcs_fin
+ * [B,2*hid*L]).  Out: dgates [B,S,4*hid] (top layer, raw, n' = unit*4 + gate),
+ * dpre [L-1][B,S,4*hid] (layers 0..L-2, raw, TF gate-major g*hid + unit),
+ * du [B,S,PP], gradient of the initial state (dcs0 [B,2*hid*L]).  Weight
+ * gradients are k-major GEMMs of these with the records (dgates with st_xtop and
+ * st_z, du with st_h, dpre with st_buf0 / st_bufk).  Fixed summation order, no
+ * atomics: bitwise reproducible. */
+int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                         int write_first,
+                         const float* Wb, const float* WaT, int ldhT,
+                         const float* M0, const float* w0, const float* cs0,
+                         const float* st_gates, const float* st_c, const float* st_u,
+                         const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                         const float* st_lgates, const float* st_lc,
+                         const float* dlogits,
+                         const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
+                         float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
+                         void* stream);
+
 /* Stand-alone addressing ops (ops.py, called by ops_test.py): batched_smooth_cosine_similarity (:135-158) --
  * mode 0 = as coded (quirk Q1: feature columns normalised over the slot axis; what NTMCell computes),
  * mode 1 = true smooth cosine dot/(|m||k| + 1e-3) (what ops_test.py:20-34 pins); memory [B,N,Md], keys [B,H,Md],

@@ -46,6 +46,11 @@ def _sig(lib):
         "ntk_ntm_seq_fwd": (c_int, [c_int] * 10 + [P] * 23 + [P]),
         "ntk_transpose_pad": (c_int, [P, c_int, P, c_int, c_int, c_int, P]),
         "ntk_ntm_seq_bwd": (c_int, [c_int] * 10 + [P, c_int, P, c_int] + [P] * 21 + [P]),
+        "ntk_ntm_seq_deep_supported": (c_int, [c_int] * 9),
+        "ntk_ntm_seq_deep_packed_floats": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 3),
+        "ntk_ntm_seq_deep_pack": (c_int, [c_int] * 5 + [P] * 6 + [P]),
+        "ntk_ntm_seq_fwd_deep": (c_int, [c_int] * 12 + [P] * 29 + [P]),
+        "ntk_ntm_seq_bwd_deep": (c_int, [c_int] * 11 + [P, P, c_int] + [P] * 24 + [P]),
         "ntk_dnc_padded_dims": (c_int, [c_int] * 6 + [ctypes.POINTER(c_int)] * 8),
         "ntk_dnc_seq_fwd": (c_int, [c_int] * 8 + [ctypes.c_float] + [P] * 13 + [P] * 18 + [P]),
         "ntk_dnc_cluster_plan": (c_int, [c_int] * 8 + [ctypes.POINTER(c_int), ctypes.POINTER(c_size_t)]),

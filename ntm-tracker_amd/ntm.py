@@ -14,6 +14,7 @@ State lives in device tensors; every arithmetic step runs in
 libntmtrack_hip.so (no torch math on the path, no CPU fallback).
 """
 import ctypes
+import os
 
 import torch
 
@@ -176,7 +177,8 @@ class NTMCell(object):
 
     ``controller_num_layers == 1`` (what every reference script runs, direct_offset_output.py:24) is the fused
     persistent kernel with forward, BPTT and training.  A deeper MultiRNNCell controller (the constructor's default
-    is 10) returns a ``StackedNTMCell``: forward / step() only, lower layers as separate LSTM steps."""
+    is 10) returns a ``StackedNTMCell``: forward, BPTT and training on the deep persistent kernels (every layer inside
+    the launch), step() layer by layer."""
 
     def __new__(cls, output_dim=None, mem_size=128, mem_dim=20, shift_range=1, controller_hidden_size=100,
                 controller_num_layers=10, *args, **kwargs):
@@ -450,14 +452,23 @@ class _StackedFlat(object):
 
 class StackedNTMCell(NTMCell):
     """NTMCell with a MultiRNNCell controller of L > 1 BasicLSTMCell layers (ntm_cell.py:45-50, :101-105): layer 0 reads
-    concat(x, read_prev), layer k reads h_{k-1}, the top layer's h drives the heads.  Layers 0 .. L-2 run as separate
-    LSTM steps (ntk_gemm_nt_f32 + ntk_lstm_step_fwd/bwd); the top layer, the addressing and the memory update run in
-    the fused cell kernel one step at a time (ntk_ntm_step_fwd/bwd; its read_prev rows of the recurrent matrix are
-    zero here, because read_prev enters at layer 0).  Forward, BPTT (tf.gradients through every layer, direct_offset_
-    output.py:611-621) and training are step-wise launches from Python: functional parity for the reference's deep
-    constructor default, not a tuned path (every reference script runs one layer).
+    concat(x, read_prev), layer k reads h_{k-1}, the top layer's h drives the heads.
+    run_sequence / backward_sequence run the whole sequence in the deep persistent kernels (ntk_ntm_seq_fwd_deep /
+    ntk_ntm_seq_bwd_deep: every layer's state resident on the CU, one launch each; the weights are packed from this
+    cell's flat buffer on every call) wherever ntk_ntm_seq_deep_supported says so -- ``last_form == "fused"``.
+    Otherwise, with ``fused = False`` or NTK_NTM_DEEP_FORM=stepwise (read per call), and always in __call__, they run
+    step-wise from Python (``last_form == "stepwise"``): layers 0 .. L-2 as separate LSTM steps (ntk_gemm_nt_f32 +
+    ntk_lstm_step_fwd/bwd), the top layer, the addressing and the memory update in the fused cell kernel one step at a
+    time (ntk_ntm_step_fwd/bwd; its read_prev rows of the recurrent matrix are zero here, because read_prev enters at
+    layer 0).  Both forms compute forward and BPTT (tf.gradients through every layer, direct_offset_output.py:611-621)
+    into the same parameter and gradient layout.
     controller_state layout = [c_0, h_0, c_1, h_1, ...] (state_is_tuple=False, MultiRNNCell concatenation).
     Lower layer k is stored as WT_k [4*hid][ld_k]: columns [input | h_prev | bias (the matching input column is 1)]."""
+
+    #: None: the deep persistent kernels wherever the shape is supported; False: always the step-wise loop
+    fused = None
+    #: "fused" or "stepwise": the form the last run_sequence / backward_sequence took
+    last_form = None
 
     def __init__(self, output_dim, mem_size=128, mem_dim=20, shift_range=1, controller_hidden_size=100,
                  controller_num_layers=10, write_head_size=3, read_head_size=3, write_first=False,
@@ -608,9 +619,81 @@ class StackedNTMCell(NTMCell):
 
     step = __call__
 
+    def _fused_ok(self, B):
+        if self.fused is False or os.environ.get("NTK_NTM_DEEP_FORM", "") == "stepwise":
+            return False
+        d = self.dims
+        return bool(_lib.lib().ntk_ntm_seq_deep_supported(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L))
+
+    def _pack(self):
+        """The controller weights in the deep kernels' layouts (ntk_ntm_seq_deep_pack), from the flat buffer as it is now."""
+        d, hid, L, lib = self.dims, self.controller_hidden_size, self.L, _lib.lib()
+        n = [ctypes.c_size_t() for _ in range(3)]
+        _lib.check(lib.ntk_ntm_seq_deep_packed_floats(self.D, d.R, d.Md, hid, L, *[ctypes.byref(v) for v in n]),
+                   "ntk_ntm_seq_deep_packed_floats")
+        Wx0, Wf, Wb = [torch.empty(v.value, device=self.device) for v in n]
+        o0 = self.params.lower_off[0][0]
+        o1, shp = self.params.lower_off[-1]
+        lowerT = self.params.flat[o0:o1 + shp[0] * shp[1]]              # the lower layers lie back to back
+        TP = self.top.params
+        _lib.check(lib.ntk_ntm_seq_deep_pack(self.D, d.R, d.Md, hid, L, _P(lowerT), _P(TP.view("WxT")), _P(TP.view("Wr")),
+                                             _P(Wx0), _P(Wf), _P(Wb), _lib.stream()), "ntk_ntm_seq_deep_pack")
+        return Wx0.view(4 * hid, -1), Wf, Wb
+
+    def _run_fused(self, X, state, record, want_outputs, after_projection):
+        d, dev, hid, L = self.dims, self.device, self.controller_hidden_size, self.L
+        B, S, D = X.shape
+        ldx = self.input_ldx
+        if D != ldx or not X.is_contiguous():
+            if D not in (self.D, ldx):
+                raise _lib.NtkError("inputs have %d features, the cell was built for %d" % (D, self.D))
+            Xp = torch.zeros((B, S, ldx), device=dev)
+            Xp[:, :, :self.D] = X[:, :, :self.D]
+            X = Xp
+        Wx0, Wf, Wb = self._pack()
+        xproj = gemm_nt(X.view(B * S, ldx), Wx0)
+        if after_projection is not None:
+            after_projection()
+        logits = torch.empty((B, S, d.O), device=dev)
+        outputs = torch.empty((B, S, d.O), device=dev) if want_outputs else None
+        new = self.state_placeholder(B)
+        rec = {}
+        if record:
+            ldxt, ld0, ld1 = (hid + 3) // 4 * 4, self.params.lower_off[0][1][1], (2 * hid + 1 + 3) // 4 * 4
+            e = lambda *shape: torch.empty(shape, device=dev)
+            rec = {
+                "z": e(B, S, d.ldz), "gates": e(B, S, hid, 4), "c": e(B, S, hid), "h": e(B, S, d.ldh), "u": e(B, S, d.PP),
+                "wc": e(B, S, d.H, d.N), "wv": e(B, S, d.H, d.N), "w": e(B, S, d.H, d.N), "M": e(B, S, d.N, d.Md),
+                "read": e(B, S, d.R, d.Md),
+                # the lower layers (k = 0 .. L-2) and the top layer's input
+                "xtop": e(B, S, ldxt), "buf0": e(B, S, ld0), "bufk": e(L - 2, B, S, ld1) if L > 2 else None,
+                "lgates": e(L - 1, B, S, hid, 4), "lc": e(L - 1, B, S, hid),
+            }
+        g = lambda k: _np(rec.get(k))
+        keep = []
+
+        def cp(t):
+            keep.append(t.contiguous())
+            return _P(keep[-1])
+        _lib.check(_lib.lib().ntk_ntm_seq_fwd_deep(
+            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self.D,
+            _P(X), _P(xproj), _P(Wf), _P(self.top.params.view("Wa")),
+            cp(state["M"]), cp(state["w"]), cp(state["read"]), cp(state["controller_state"]),
+            _P(logits), _np(outputs), _P(new["M"]), _P(new["w"]), _P(new["read"]), _P(new["controller_state"]),
+            g("z"), g("gates"), g("c"), g("h"), g("u"), g("wc"), g("wv"), g("w"), g("M"), g("read"),
+            g("xtop"), g("buf0"), g("bufk"), g("lgates"), g("lc"), _lib.stream()), "ntk_ntm_seq_fwd_deep")
+        if record:
+            rec["Wb"] = Wb                              # the packed weights the BPTT of this pass streams
+        self.last_form = "fused"
+        return logits, outputs, new, rec
+
     def run_sequence(self, X, state, record=False, want_outputs=True, after_projection=None):
-        """Python loop over steps (the LoopNTMTracker fallback for deep controllers).  record=True keeps what
-        backward_sequence needs."""
+        """The whole sequence in the deep persistent kernel where supported (see the class note), else a Python loop
+        over steps.  record=True keeps what backward_sequence needs (and what per_step_states / per_step_debugs read).
+        after_projection: called once layer 0's input projection GEMM is enqueued (fused form)."""
+        if self._fused_ok(X.shape[0]):
+            return self._run_fused(X, state, record, want_outputs, after_projection)
+        self.last_form = "stepwise"
         B, S, _ = X.shape
         logits, outs, steps, states = [], [], [], []
         for t in range(S):
@@ -629,7 +712,11 @@ class StackedNTMCell(NTMCell):
 
     def backward_sequence(self, X, state0, rec, dlogits, dfinal=None, workspace=None):
         """BPTT through a recorded sequence of the deep controller: fills ``self.params.grad`` (top cell in kernel
-        layout, lower layers as WT_k) and returns the gradient w.r.t. the initial state tensors."""
+        layout, lower layers as WT_k) and returns the gradient w.r.t. the initial state tensors.  Takes the form of the
+        forward that recorded ``rec``."""
+        if "lgates" in rec:
+            return self._backward_fused(state0, rec, dlogits, dfinal, workspace)
+        self.last_form = "stepwise"
         steps = rec["steps"]
         S, B = len(steps), X.shape[0]
         hid, L, dev = self.controller_hidden_size, self.L, self.device
@@ -698,6 +785,43 @@ class StackedNTMCell(NTMCell):
             gemm_tn(dpre_all[k].view(BS, 4 * hid), bufs.view(BS, ld), self.params.lower(k, grad=True), workspace=workspace)
         g0 = {"M": dM, "w": dw, "read": dread,
               "controller_state": torch.cat([t_ for k in range(L - 1) for t_ in (dc_low[k], dh_low[k])] + [dcs_top], dim=1)}
+        return g0
+
+    def _backward_fused(self, state0, rec, dlogits, dfinal, workspace):
+        d, dev, hid, L, lib, st = self.dims, self.device, self.controller_hidden_size, self.L, _lib.lib(), _lib.stream()
+        B, S = rec["c"].shape[:2]
+        TP = self.top.params
+        ldhT = (hid + 3) // 4 * 4
+        WaT = torch.empty((d.PP, ldhT), device=dev)
+        _lib.check(lib.ntk_transpose_pad(_P(TP.view("Wa")), d.PP, _P(WaT), ldhT, hid, d.PP, st), "ntk_transpose_pad")
+        dgates = torch.empty((B, S, 4 * hid), device=dev)
+        dpre = torch.empty((L - 1, B, S, 4 * hid), device=dev)
+        du = torch.empty((B, S, d.PP), device=dev)
+        g0 = self.state_placeholder(B)
+        df = dfinal or {}
+        keep = []
+
+        def cp(t):
+            keep.append(t.contiguous())
+            return _P(keep[-1])
+        _lib.check(lib.ntk_ntm_seq_bwd_deep(
+            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0,
+            _P(rec["Wb"]), _P(WaT), ldhT, cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
+            _P(rec["gates"]), _P(rec["c"]), _P(rec["u"]), _P(rec["wc"]), _P(rec["wv"]), _P(rec["w"]), _P(rec["M"]),
+            _P(rec["lgates"]), _P(rec["lc"]), cp(dlogits),
+            _np(df.get("M")), _np(df.get("w")), _np(df.get("read")), _np(df.get("controller_state")),
+            _P(dgates), _P(dpre), _P(du), _P(g0["M"]), _P(g0["w"]), _P(g0["read"]), _P(g0["controller_state"]), st),
+            "ntk_ntm_seq_bwd_deep")
+        BS = B * S
+        # weight gradients: the step-wise form's k-major contractions over all recorded rows, into the same layout
+        gemm_tn(dgates.view(BS, 4 * hid), rec["xtop"].view(BS, -1), TP.view("WxT", grad=True), workspace=workspace)
+        gemm_tn(rec["z"].view(BS, d.ldz), dgates.view(BS, 4 * hid), TP.view("Wr", grad=True), workspace=workspace)
+        gemm_tn(rec["h"].view(BS, d.ldh), du.view(BS, d.PP), TP.view("Wa", grad=True), workspace=workspace)
+        TP.view("Wr", grad=True)[:d.RM].zero_()                        # structural zeros (read_prev enters at layer 0)
+        for k in range(L - 1):
+            buf = rec["buf0"] if k == 0 else rec["bufk"][k - 1]
+            gemm_tn(dpre[k].view(BS, 4 * hid), buf.view(BS, buf.shape[-1]), self.params.lower(k, grad=True), workspace=workspace)
+        self.last_form = "fused"
         return g0
 
     def init_state_backward(self, g0, batch_size):
@@ -770,6 +894,18 @@ def per_step_states(cell, rec, final):
     hid = cell.dims.hid
     S = rec["M"].shape[1]
     out = []
+    if "lgates" in rec:        # the deep kernel's records: h_k(t) is the input part of layer k+1's record (the top's: xtop)
+        L = rec["lc"].shape[0] + 1
+        for t in range(S - 1):
+            cs = []
+            for k in range(L - 1):
+                hk = rec["bufk"][k][:, t, :hid] if k < L - 2 else rec["xtop"][:, t, :hid]
+                cs += [rec["lc"][k][:, t], hk]
+            cs += [rec["c"][:, t], rec["h"][:, t, :hid]]
+            out.append({"M": rec["M"][:, t], "w": rec["w"][:, t], "read": rec["read"][:, t],
+                        "controller_state": torch.cat(cs, dim=1)})
+        out.append(final)
+        return out
     for t in range(S - 1):
         out.append({"M": rec["M"][:, t], "w": rec["w"][:, t], "read": rec["read"][:, t],
                     "controller_state": torch.cat([rec["c"][:, t], rec["h"][:, t, :hid]], dim=1)})

@@ -83,7 +83,7 @@ class NTMTracker(object):
         if is_first_frame:
             gt = generate_gt(apply_transformation(self.normalized_bbox, self.transformation), self.cropbox_grid, self.bbox_grid)
             gts0 = torch.as_tensor(gt.reshape(1, -1), dtype=torch.float32).to(self.device).contiguous()
-        ldx = self.cell.dims.ldx
+        ldx = self.cell.input_ldx
         X = torch.empty((1, NUM_FEATURES + 1, ldx), device=self.device)
         _lib.check(_lib.lib().ntk_gather_serialize_online(_P(fmap), _np(gts0), _P(X), 1, 1, fmap.shape[1], fmap.shape[2],
                                                           fmap.shape[3], ldx, GRID_START, GRID_STEP, GRID_N, _lib.stream()),
