@@ -84,12 +84,16 @@ int ntk_vgg_conv3x3_relu_f32_to_bf16(const float* in, const float* w_packed, con
                                      int frames, int H, int W, int cin, int cout, void* stream);
 
 /* The SPLIT form of the fp32 trunk (csrc/conv_bf16p.hip, template flag X3; round 4): the same fp32 operator (vgg.py:155-161) on the
- * bf16 matrix pipe.  Every fp32 value v travels as hi = bf16(v), lo = bf16(v - hi); a product x w is accumulated in fp32 as
- * xh wh + xh wl + xl wh (relative error of the split 2^-17: per layer 4e-6 .. 5e-6 of the activation scale, what the F(4x4) Winograd
- * kernel has).  A split map is [frames][H][W][C / 16][2][16] bf16 (hi x16 | lo x16 per group of 16 channels: the bytes of the fp32 map).
- * Shapes: H, W multiples of 8, or W = 28 with H >= 20 (not a multiple of 8) and no pool; cin a multiple of 16, cout of 64.  Packed weights:
- * 18 * cin * cout bf16 elements, packed per layer and frame shape.  out_f32 = 1 writes fp32 NHWC (where the trunk leaves the split
- * form); in_f32 = 1 reads an fp32 NHWC map and splits it while staging (where the trunk enters it: cin <= 64 and cout = 64 only). */
+ * fp16 matrix pipe.  Every fp32 value v travels as two fp16 numbers, hi = fp16(v) rounded toward zero and lo = fp16(v - hi) rounded to
+ * nearest (v = hi + lo to 2^-22 |v|); a product x w is accumulated in fp32 as xh wh + xh wl + xl wh (per layer 0.7e-6 .. 1.7e-6 of the
+ * activation scale).  A split map is [frames][H][W][C / 16][2][16] fp16 (hi x16 | lo x16 per group of 16 channels: the bytes of the fp32
+ * map); it holds magnitudes up to 131008 (hi saturates at 65504, lo carries the rest): larger activations saturate there instead of
+ * overflowing.  The weights are scaled by a power of two when packed (exact; the epilogue multiplies the sums by the inverse).
+ * Shapes (ntk_vgg_split3_supported): H, W multiples of 8, or W = 28 with H >= 20 and no pool (runs of rows); cin a multiple of 16, cout
+ * of 64.  Packed weights: ntk_vgg_split3_packed_elems(cin, cout) = 18 * cin * cout + 8 fp16 elements, packed per layer and frame shape:
+ * the hi / lo parts, then a 16-byte tail the packing writes its scales into -- size the buffer with ntk_vgg_split3_packed_elems
+ * (18 * cin * cout elements are 16 bytes short).  out_f32 = 1 writes fp32 NHWC (where the trunk leaves the split form); in_f32 = 1 reads
+ * an fp32 NHWC map and splits it while staging (where the trunk enters it: cin <= 64, cout = 64, H and W multiples of 8 only). */
 size_t ntk_vgg_split3_packed_elems(int cin, int cout);
 int ntk_vgg_split3_supported(int H, int W, int cin, int cout, int fuse_pool);
 int ntk_vgg_pack_weights_split3(const float* w_hwio, void* w_packed, int cin, int cout, int H, int W, void* stream);

@@ -699,7 +699,7 @@ template <int BN, int KC, int NW, bool X3 = false, bool INF32 = false>
 int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipStream_t st) {
     Bf16pArgs a = a0;
     if constexpr (X3 && !INF32) {
-        if (W == 28 && !(H % 8 == 0)) {                                         // runs of 512 consecutive pixels over 28-wide rows
+        if (W == 28) {                                                          // runs of 512 consecutive pixels over 28-wide rows
             if (pool || NW != 8 || H < 20) return NTK_ERR_UNSUPPORTED;
             a.bxN = 1; a.byN = 1;
             const long long NQ = (long long)a.frames * H * W, NS = (NQ + 511) / 512;
@@ -767,7 +767,7 @@ int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipSt
 // rectangular sub-block shapes, 16-channel chunks on 4x4 sub-blocks (frames whose sides are multiples of 4 but not of 8); a layer of
 // 64 -> 64 channels (conv1_2: two chunks) on four-wave workgroups, two per CU
 static int bf16p_form(int H, int W, int cin, int cout, int pool, int* bn, int* kc, int* nw) {
-    if ((H % 4) || (W % 4) || cin % 32 || cout % 64) return 0;
+    if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || (H % 4) || (W % 4) || cin % 32 || cout % 64) return 0;
     const bool rect = (W % 8 == 0 && H % 8 == 0);
     if (!rect && pool) return 0;
     *nw = (rect && cin <= 64 && cout == 64) ? 4 : 8;       // (measured: conv2_1, 64 -> 128 columns, LOSES 4 % as two 64-column halves that both stage the patch)
@@ -832,10 +832,10 @@ extern "C" int ntk_vgg_conv3x3_relu_bf16p(const void* in_bf16, const void* w_pac
 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// The SPLIT form (X3): the fp32 trunk on the bf16 matrix pipe.  Maps are "split" maps: [frames][H][W][C / 16][hi x16 | lo x16] bf16.
+// The SPLIT form (X3): the fp32 trunk on the fp16 matrix pipe.  Maps are "split" maps: [frames][H][W][C / 16][hi x16 | lo x16] fp16.
 // ---------------------------------------------------------------------------------------------------------------------------------
 static int split3_form(int H, int W, int cin, int cout, int pool, int* bn, int* nw) {
-    if (H <= 0 || W <= 0 || cin % 16 || cout % 64) return 0;
+    if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || cin % 16 || cout % 64) return 0;
     const bool rect = (W % 8 == 0 && H % 8 == 0);
     if (!rect && (pool || W != 28 || H < 20)) return 0;                          // 28-wide maps: runs of rows (conv4_x), un-pooled
     *nw = (rect && cin <= 64 && cout == 64) ? 4 : 8;
@@ -852,7 +852,8 @@ extern "C" int ntk_vgg_split3_supported(int H, int W, int cin, int cout, int fus
     return split3_form(H, W, cin, cout, fuse_pool, &bn, &nw);
 }
 
-// HWIO fp32 weights -> the stage images of ntk_vgg_conv3x3_relu_split3 (bf16 high and low parts; 18 cin cout elements)
+// HWIO fp32 weights -> the stage images of ntk_vgg_conv3x3_relu_split3 (fp16 high and low parts: 18 cin cout elements, then the
+// 16-byte scale tail: ntk_vgg_split3_packed_elems)
 extern "C" int ntk_vgg_pack_weights_split3(const float* w_hwio, void* w_packed, int cin, int cout, int H, int W, void* stream) {
     NTK_REQUIRE(w_hwio && w_packed, NTK_ERR_BAD_PTR, "ntk_vgg_pack_weights_split3: null pointer");
     int bn = 0, nw = 0;

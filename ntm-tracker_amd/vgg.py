@@ -59,11 +59,12 @@ def pack_weights(w_hwio):
 
 
 def wino_supported(cin, cout, H, W, frames=1):
-    """Shapes the fused Winograd kernel takes (otherwise the direct kernel runs): channel multiples, H and W
-    multiples of 4, and an input small enough for its 32-bit element offsets."""
+    """Shapes the fused Winograd kernel takes (otherwise the direct kernel runs): channel multiples, at most 1024 input
+    channels (WINO_MAX_CIN: the zero page padding pixels read from), H and W multiples of 4, and an input small enough for
+    its 32-bit element offsets."""
     nCB = cout // 64
-    return (cin % 16 == 0 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
-            and H % 4 == 0 and W % 4 == 0 and frames * H * W * cin < 0xffffffff)
+    return (cin % 16 == 0 and 0 < cin <= 1024 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
+            and H > 0 and W > 0 and H % 4 == 0 and W % 4 == 0 and frames * H * W * cin < 0xffffffff)
 
 
 def pack_weights_wino(w_hwio):
@@ -94,8 +95,8 @@ def conv3x3_relu_wino(x, u_packed, bias, cin, cout, fuse_pool=False, out=None):
 def wino43_supported(cin, cout, H, W, frames=1):
     """Shapes the fused Winograd F(4x4,3x3) kernel takes."""
     nCB = cout // 64
-    return (cin % 16 == 0 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
-            and H % 4 == 0 and W % 4 == 0 and 2 * H * W * cin * 4 <= 0x40000000)
+    return (cin % 16 == 0 and cin > 0 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
+            and H > 0 and W > 0 and H % 4 == 0 and W % 4 == 0 and 2 * H * W * cin * 4 <= 0x40000000)
 
 
 def pack_weights_wino43(w_hwio):
@@ -505,11 +506,16 @@ class VGG16Conv43(object):
         return x
 
     def __call__(self, frames, out=None, latency=False):
-        """frames [F,224,224,3] mean-subtracted fp32 NHWC -> [F,28,28,512].  latency=True: a call of a few frames may run the form with
-        the shorter critical path (split3_latency_frames) -- same operator, results equal to fp32 rounding, not bit for bit."""
+        """frames [F,H,W,3] mean-subtracted fp32 NHWC, H and W multiples of 32 (the reference's frames: 224 x 224) -> [F,H/8,W/8,512].
+        Frames with other sides are refused before anything is launched: conv4_x runs on H/8 x W/8 maps, and every conv form needs
+        sides that are multiples of 4.  latency=True: a call of a few frames may run the form with the shorter critical path
+        (split3_latency_frames) -- same operator, results equal to fp32 rounding, not bit for bit."""
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise _lib.NtkError("frames must be [F,H,W,3] NHWC")
         F, H, W, _ = frames.shape
+        if H < 32 or W < 32 or H % 32 or W % 32:
+            raise _lib.NtkError("frames of %d x %d: H and W must be multiples of 32 (conv4_x runs on H/8 x W/8 maps, whose sides "
+                                "every conv form needs to be multiples of 4)" % (H, W))
         if out is None:
             # with a features_window the window kernel leaves everything outside the window untouched: the map a caller
             # gets back must be zero there, not uninitialised memory

@@ -141,6 +141,16 @@ def loss_and_grads(cfg, params_np, inputs_np, offsets_np, num_features=64, dtype
     return float(loss.detach()), {k: v.grad.numpy() for k, v in p.items()}, logits.detach().numpy(), pred.detach().numpy()
 
 
+def conv3x3_same_relu(x, w, b):
+    """One VGG layer in float64 on torch-CPU: x [F,H,W,Cin] NHWC, w [3,3,Cin,Cout] HWIO, b [Cout] (numpy) -> relu(conv3x3_same(x, w)
+    + b) as float64 numpy [F,H,W,Cout].  ntm_oracle.conv3x3_same_relu restated: the same sums, in seconds less at 512 channels."""
+    xt = torch.as_tensor(np.asarray(x, np.float64)).permute(0, 3, 1, 2)
+    wt = torch.as_tensor(np.asarray(w, np.float64)).permute(3, 2, 0, 1)
+    with torch.no_grad():
+        y = torch.relu(torch.nn.functional.conv2d(xt, wt, torch.as_tensor(np.asarray(b, np.float64)), padding=1))
+    return y.permute(0, 2, 3, 1).contiguous().numpy()
+
+
 def vgg16_conv43(frames, weights):
     """VGG conv1_1..conv4_3 on torch-CPU ops (conv2d SAME + bias + ReLU, 2x2/2 max-pool):
     the op granularity TF-CPU would execute for the frozen graph

@@ -154,6 +154,17 @@ def test_autograd_oracle_gradients_by_finite_differences():
             np.testing.assert_allclose(g[idx], (up - dn) / (2 * d), rtol=2e-4, atol=1e-9)
 
 
+def test_conv_layer_numpy_vs_torch_restatement():
+    rng = np.random.default_rng(4)
+    for F, H, W, cin, cout in ((3, 8, 12, 16, 64), (1, 4, 28, 3, 64), (2, 20, 28, 64, 128)):
+        x = np.maximum(rng.standard_normal((F, H, W, cin)), 0)
+        w = rng.standard_normal((3, 3, cin, cout)) * np.sqrt(2.0 / (9 * cin))
+        b = rng.standard_normal(cout) * 0.1
+        a, t = O.conv3x3_same_relu(x, w, b), OT.conv3x3_same_relu(x, w, b)
+        assert t.dtype == np.float64 and t.shape == (F, H, W, cout)
+        np.testing.assert_allclose(t, a, rtol=0, atol=1e-12 * np.abs(a).max())
+
+
 def test_vgg_numpy_vs_torch_conv_restatement():
     rng = np.random.default_rng(3)
     ws = O.init_vgg_weights(rng)

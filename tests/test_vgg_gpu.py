@@ -168,6 +168,8 @@ def test_vgg_trunk_bf16_matches_bf16_oracle(cuda):
     (3, 28, 28, 256, 512, False, False, False),   # 28-wide maps: runs of 512 consecutive pixels (18.3 rows), five workgroups, two of them across a frame boundary
     (2, 28, 28, 512, 512, False, False, True),    # conv4_3's form: fp32 output
     (5, 20, 28, 16, 64, False, False, False),     # 28 wide, 20 rows (the shortest frame the form takes), one chunk, 64 columns on eight waves
+    (2, 24, 28, 256, 512, False, False, False),   # 28 wide, a multiple of 8 rows: runs of rows too (conv4_1 of 192 x 224 frames)
+    (2, 32, 28, 512, 512, False, False, True),    # ... 32 rows, fp32 output (conv4_3 of 256 x 224 frames)
 ])
 def test_conv3x3_relu_split_form_matches_float64_oracle(cuda, F, H, W, cin, cout, pool, in_f32, out_f32):
     from ntmtrack import vgg
@@ -621,3 +623,114 @@ def test_blocked_trunk_layers_equal_nhwc_layers_bit_for_bit(cuda):
     net.layout = "nhwc"
     assert torch.equal(net(frames), yb)
     assert not vgg.blocked_trunk_supported(1, 36, 36)          # falls back to NHWC where a layer is outside the kernel's shapes
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the trunk on frames other than 224 x 224
+_OTHER_FRAMES = [      # (frames, H, W, layers the default trunk runs in the split form -- the rest run on the F(4x4) kernel)
+    (2, 192, 224, 9),  # conv4 maps 24 x 28: conv4_x in runs of rows
+    (2, 256, 224, 9),  # 32 x 28: the same
+    (2, 160, 224, 9),  # 20 x 28: runs of rows at the least height the form takes
+    (1, 128, 224, 6),  # 16 x 28: too short for runs of rows -- conv3_3 hands fp32 NHWC to the F(4x4) kernel
+    (1, 224, 192, 6),  # 28 x 24: neither 28 wide nor multiples of 8 -- conv4_x on the F(4x4) kernel
+    (2, 64, 64, 9),    # 8 x 8: the split form through conv4_3
+    (2, 64, 96, 6),    # 8 x 12: the split form until conv3_3, then F(4x4)
+]
+
+
+@pytest.fixture(scope="module")
+def trunks(cuda):
+    """One set of weights (nonzero biases) and every form of the trunk on it."""
+    from ntmtrack import vgg
+    rng = np.random.default_rng(41)
+    ws = O.init_vgg_weights(rng)
+    for k in ws:
+        ws[k] = (ws[k][0], (rng.standard_normal(ws[k][1].shape) * 0.05).astype(np.float32))
+    nets = {"default": vgg.VGG16Conv43(ws, device=cuda)}
+    for algo in ("winograd", "winograd2", "direct"):
+        nets[algo] = vgg.VGG16Conv43(ws, device=cuda, algo=algo)
+    nets["winograd nhwc"] = vgg.VGG16Conv43(ws, device=cuda, algo="winograd")
+    nets["winograd nhwc"].layout = "nhwc"
+    for form in ("patch", "tile"):
+        nets["bf16 " + form] = vgg.VGG16Conv43(ws, device=cuda, dtype="bf16")
+        nets["bf16 " + form].bf16_form = form
+    return ws, nets
+
+
+def _count_calls(monkeypatch, module, names):
+    log = []
+    for name in names:
+        def spy(*a, _real=getattr(module, name), _name=name, **k):
+            log.append(_name)
+            return _real(*a, **k)
+        monkeypatch.setattr(module, name, spy)
+    return log
+
+
+@pytest.mark.parametrize("F,H,W,n_split", _OTHER_FRAMES)
+def test_vgg_trunk_other_frame_shapes_match_float64_oracle(cuda, trunks, monkeypatch, F, H, W, n_split):
+    """Every form of the trunk on frames other than 224 x 224 against the float64 oracles, with the bounds of the 224 x 224 tests
+    above; and the route of the default trunk: where split3_trunk_supported says yes it runs the split form on the layers the table
+    says and F(4x4) on the rest -- counted, so that a silent fall-back to another form cannot pass."""
+    from ntmtrack import vgg
+    from oracle import ntm_oracle_torch as OT
+    ws, nets = trunks
+    rng = np.random.default_rng(H * 1000 + W)
+    frames = (rng.uniform(0, 255, size=(F, H, W, 3)).astype(np.float32) - O.VGG_MEAN)
+    ref = OT.vgg16_conv43(frames.astype(np.float64), {k: (w.astype(np.float64), b.astype(np.float64)) for k, (w, b) in ws.items()})
+    assert ref.shape == (F, H // 8, W // 8, 512)
+    x = torch.from_numpy(frames).to(cuda)
+    net = nets["default"]
+    assert net.split3 and net.split3_trunk_supported(x.shape)
+    launched = _count_calls(monkeypatch, vgg, ("conv3x3_relu_split3", "conv3x3_relu_wino43_blocked"))
+    got = {"split3": net(x)}
+    monkeypatch.undo()
+    assert launched == ["conv3x3_relu_split3"] * n_split + ["conv3x3_relu_wino43_blocked"] * (9 - n_split), launched
+    got["latency"] = net(x, latency=True)
+    for name in ("winograd", "winograd nhwc", "winograd2", "direct"):
+        got[name] = nets[name](x)
+    assert torch.equal(got["latency"], got["winograd"])         # a call of fewer than 12 frames: the Winograd form's bits
+    assert torch.equal(got["winograd nhwc"], got["winograd"])   # channel-blocked maps between the layers change addresses only
+    bounds = {"split3": 1e-5, "latency": 2e-5, "winograd": 2e-5, "winograd nhwc": 2e-5, "winograd2": 1e-5, "direct": 1e-5}
+    errs = {}
+    for name, y in got.items():
+        assert y.shape == ref.shape, (name, y.shape)
+        errs[name] = _rel(y.cpu().numpy(), ref)
+    ref_b = OT.vgg16_conv43_bf16(frames, ws)
+    scale = np.max(np.abs(ref_b))
+    for form in ("patch", "tile"):
+        y = nets["bf16 " + form](x).cpu().numpy()
+        assert y.shape == ref.shape
+        errs["bf16 " + form] = (np.max(np.abs(y - ref_b)) / scale, np.mean(np.abs(y - ref_b)) / scale, _rel(y, ref))
+    print("%d x %d x %d frames vs float64: %s" % (F, H, W, ", ".join(
+        "%s %s" % (k, " / ".join("%.2e" % e for e in (v if isinstance(v, tuple) else (v,)))) for k, v in errs.items())))
+    for name, bound in bounds.items():
+        assert errs[name] < bound, (name, errs[name])
+    for form in ("patch", "tile"):
+        e_max, e_mean, e32 = errs["bf16 " + form]
+        assert e_max < 2e-2 and e_mean < 1e-3 and e32 < 3e-2, (form, e_max, e_mean, e32)
+
+
+def test_vgg_trunk_runs_of_rows_are_frame_invariant(cuda, trunks):
+    """Three 192 x 224 frames: conv4_x's 24 x 28 maps go in four runs of 512 pixels, two of them across a frame boundary -- each
+    frame's features equal its own one-frame call bit for bit."""
+    nets = trunks[1]
+    rng = np.random.default_rng(43)
+    x = torch.from_numpy(rng.uniform(0, 255, size=(3, 192, 224, 3)).astype(np.float32) - O.VGG_MEAN).to(cuda)
+    full = nets["default"](x)
+    for f in range(3):
+        assert torch.equal(full[f:f + 1], nets["default"](x[f:f + 1].contiguous())), f
+
+
+def test_vgg_trunk_refuses_frames_whose_sides_are_not_multiples_of_32(cuda, trunks, monkeypatch):
+    """conv4_x runs on H/8 x W/8 maps and every conv form needs sides that are multiples of 4 there: every form of the trunk refuses
+    other frames before anything reaches the library."""
+    from ntmtrack import _lib
+    nets = trunks[1]
+    calls = []
+    monkeypatch.setattr(_lib, "check", lambda rc, what: calls.append(what))
+    for H, W in ((112, 112), (224, 200), (200, 224), (16, 16), (48, 64)):
+        for name, net in nets.items():
+            with pytest.raises(_lib.NtkError):
+                net(torch.zeros((1, H, W, 3), device=cuda))
+    assert not calls, calls
