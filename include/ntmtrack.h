@@ -184,6 +184,52 @@ int ntk_transpose_pad(const float* in, int ldi, float* out, int ldo, int rows, i
 int ntk_ntm_padded_dims(int N, int Md, int R, int Wh, int hid, int shift_range, int O,
                         int* P, int* PP, int* K, int* ldz, int* ldh);
 
+/* Limits of the single-layer sequence kernels.  Every entry below checks them on the host before any launch; a shape outside
+ * them is refused with NTK_ERR_BAD_SHAPE / NTK_ERR_UNSUPPORTED and the reason in ntk_last_error(), never computed wrongly.
+ * H = R + Wh heads, SS = 2*shift_range + 1, P / PP / K from ntk_ntm_padded_dims, T = threads of the workgroup.
+ *
+ * Forward (ntk_ntm_seq_fwd, ntk_ntm_step_fwd):
+ *   B >= 1, S >= 1, O >= 1, R >= 1, Wh >= 1                        (else NTK_ERR_BAD_SHAPE)
+ *   mem_size N a multiple of 64 in [64, 1024];  mem_dim Md in [1, 256]
+ *   H <= 15 (one wave per head);  hid in [1, 960];  shift_range <= 4 and SS < N (SS >= N: NTK_ERR_BAD_SHAPE)
+ *   hid + Md <= 1024,  PP + Md <= 1024,  H*Md + H + 1 <= 1024,  R*Md <= 1024
+ *   the state within 160 KiB of LDS: roughly 4 * (N*(Md|1) + 3*H*N + max(nsl*4*hid, nslB*PP, nslR*R*Md) + K + hid + PP + H*Md + Md)
+ *   bytes, where the three slice counts are T/hid, min(T/(PP/4), hid) and min(T/(R*Md), N).
+ *   T = min(1024, the largest of H*N, 3*hid, PP + Md, H*Md + H + 1, (ceil(hid/64) + 1)*64, (H + 1)*64, rounded up to whole
+ *   waves): H*N may exceed T (every mem_size above 512 does).
+ *
+ * BPTT (ntk_ntm_seq_bwd, ntk_ntm_step_bwd) -- narrower: a shape may run forward and still be refused here, so a training caller
+ * asks ntk_ntm_seq_plan BEFORE the forward pass:
+ *   every forward limit, and
+ *   hid a multiple of 4;  ldkT >= K, ldhT >= hid, both multiples of 4 (else NTK_ERR_BAD_SHAPE)
+ *   T = the largest of H*N, 3*hid, PP, K, H*Md + Md + 2*Wh*Md, rounded up to whole waves, must be <= 1024: so H*N <= 1024
+ *   (mem_size above 512 never trains), 3*hid <= 1024 (hid <= 340), PP <= 1024, K <= 1024
+ *   N*Md <= 8*T (a thread prefetches at most 8 memory elements)
+ *   the BPTT state within 160 KiB of LDS: roughly 4 * (4*N*(Md|1) + 8*H*N + 9*hid + ...) bytes, one more N*(Md|1) with write_first.
+ *
+ * Kernel ids ntk_ntm_seq_plan reports (0 = refused): */
+#define NTK_NTM_FWD_WS           1   /* wave-specialised forward, tracker shape without write_first (768 threads) */
+#define NTK_NTM_FWD_FIX512       2   /* fixed-dims forward with resident gate rows, tracker shape otherwise (512 threads) */
+#define NTK_NTM_FWD_GENERIC768   3   /* generic forward, T <= 768 */
+#define NTK_NTM_FWD_GENERIC1024  4   /* generic forward, 768 < T <= 1024 */
+#define NTK_NTM_FWD_FIX640_DEV   5   /* development builds only (-DNTK_NTM_FWD_STREAM_ONLY) */
+#define NTK_NTM_BWD_WS           1   /* wave-specialised BPTT: tracker shape, not write_first, ldkT 280, ldhT 200 (768 threads) */
+#define NTK_NTM_BWD_FIX          2   /* fixed-dims BPTT: the same shapes under NTK_NTM_BWD_FORM=res (640 threads) */
+#define NTK_NTM_BWD_GENERIC768   3   /* generic BPTT, T <= 768 */
+#define NTK_NTM_BWD_GENERIC1024  4   /* generic BPTT, 768 < T <= 1024 */
+/* bits of the value ntk_ntm_seq_plan / ntk_ntm_seq_deep_plan return */
+#define NTK_NTM_PLAN_FWD 1
+#define NTK_NTM_PLAN_BWD 2
+
+/* What ntk_ntm_seq_fwd / ntk_ntm_seq_bwd would do with a shape, host arithmetic only (no device call): returns a mask of
+ * NTK_NTM_PLAN_FWD (the forward runs) and NTK_NTM_PLAN_BWD (the BPTT runs) and, through the nullable out pointers, the kernel
+ * id and the workgroup size of each direction (0 where refused).  The reason for a refusal is in ntk_last_error() (the
+ * forward's where both refuse).  ldkT / ldhT: the leading dimensions the caller will hand ntk_ntm_seq_bwd; <= 0 stands for the
+ * smallest valid ones, align4(K) and align4(hid).  The two entries decide through the same function, so the answer cannot
+ * drift from the launch; it honours the development switches NTK_NTM_FWD_FORM / NTK_NTM_BWD_FORM as they are when it is called. */
+int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                     int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads);
+
 /* S steps of the cell for B sequences, one persistent workgroup per sequence.
  * xproj [B,S,4*hid] = X * WxT^T (no bias).  State in: M0 [B,N,Md], w0 [B,H,N],
  * read0 [B,R,Md], cs0 [B,2*hid] (c then h).  Out: logits [B,S,O], outputs
@@ -237,8 +283,18 @@ int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shi
 
 /* 1 if the deep kernels run this configuration (forward AND BPTT), else 0 with
  * the reason in ntk_last_error().  Host arithmetic only: the same limits as
- * ntk_ntm_seq_fwd, hid % 4 == 0, and every layer's state within the LDS. */
+ * ntk_ntm_seq_fwd, hid % 4 == 0, and every layer's state within the LDS.
+ * Answers for write_first = 0; a write_first cell keeps one more copy of the memory (N*(Md|1) floats) in the BPTT's LDS, so
+ * close to the 160 KiB bound ask ntk_ntm_seq_deep_plan, which takes the flag. */
 int ntk_ntm_seq_deep_supported(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L);
+
+/* The deep form's ntk_ntm_seq_plan: the mask is NTK_NTM_PLAN_FWD | NTK_NTM_PLAN_BWD or 0 (the deep kernels take a shape in both
+ * directions or not at all: every BPTT limit of the single-layer form applies to the deep forward too, and Tb also covers
+ * 2*hid, so 3*hid <= 1024).  Kernel ids: the instantiation by workgroup size, for the forward (Tf) and the BPTT (Tb). */
+#define NTK_NTM_DEEP_768   1   /* T <= 768 */
+#define NTK_NTM_DEEP_1024  2   /* 768 < T <= 1024 */
+int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
+                          int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads);
 
 /* Float counts of the three packed weight buffers:
  *   n_wx0 = 4*hid*ldx   n_wf = 4*hid*(rf0 + (L-1)*rf1)   n_wb = 4*hid*(cb0 + (L-1)*cb1) */

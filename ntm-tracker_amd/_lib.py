@@ -47,6 +47,8 @@ def _sig(lib):
         "ntk_transpose_pad": (c_int, [P, c_int, P, c_int, c_int, c_int, P]),
         "ntk_ntm_seq_bwd": (c_int, [c_int] * 10 + [P, c_int, P, c_int] + [P] * 21 + [P]),
         "ntk_ntm_seq_deep_supported": (c_int, [c_int] * 9),
+        "ntk_ntm_seq_plan": (c_int, [c_int] * 11 + [ctypes.POINTER(c_int)] * 4),
+        "ntk_ntm_seq_deep_plan": (c_int, [c_int] * 10 + [ctypes.POINTER(c_int)] * 4),
         "ntk_ntm_seq_deep_packed_floats": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 3),
         "ntk_ntm_seq_deep_pack": (c_int, [c_int] * 5 + [P] * 6 + [P]),
         "ntk_ntm_seq_fwd_deep": (c_int, [c_int] * 12 + [P] * 29 + [P]),

@@ -53,3 +53,13 @@ static inline void ntm_fwd_lds(const NtmDims& d, int T, NtmLds& L) {
     L.total = o;
 }
 
+
+// What ntk_ntm_seq_fwd launches for a shape: decided by ntm_fwd_plan (ntm_seq_fwd.hip), host arithmetic only, for the launcher
+// and for the query ntk_ntm_seq_plan alike.
+struct NtmFwdPlan {
+    int kernel;            // NTK_NTM_FWD_*
+    int T;                 // threads of the workgroup
+    NtmLds L;
+    size_t lds_bytes;
+};
+int ntm_fwd_plan(const NtmDims& d, NtmFwdPlan& p, const char* who);

@@ -14,6 +14,7 @@
 // with log(x) -> 0 for x <= 0; l2_normalize differentiates through
 // rsqrt(max(sum x^2, 1e-12)) (zero through the norm when clamped).
 #include "ntm_common.h"
+#include "ntm_fwd_args.h"           // NtmFwdPlan: ntk_ntm_seq_plan answers for both directions
 #include <stdlib.h>
 #include <type_traits>
 
@@ -704,7 +705,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     }
 }
 
-int ntm_validate_dims(const NtmDims& d, const char* who);
+int ntm_validate_dims(const NtmDims& d, const char* who);          // ntm_seq_fwd.hip
 
 // [rows][cols] -> [cols][ldo] (zero padded), used for WrT / WaT once per optimiser step
 __global__ void transpose_pad_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out, int ldo,
@@ -732,6 +733,67 @@ extern "C" int ntk_transpose_pad(const float* in, int ldi, float* out, int ldo, 
     return NTK_OK;
 }
 
+// What ntk_ntm_seq_bwd launches for a shape: every limit of the BPTT kernels and the kernel a shape takes, host arithmetic only,
+// for the launcher and for the query ntk_ntm_seq_plan alike.
+struct NtmBwdPlan {
+    int kernel;            // NTK_NTM_BWD_*
+    int T;                 // threads the shape's work is laid out over (NtmBwdLds)
+    int threads;           // threads of the workgroup: T, or 768 in the wave-specialised form (two stream waves beside T = 640)
+    NtmBwdLds L;
+    size_t lds_bytes;
+};
+
+static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, const char* who) {
+    int rc = ntm_validate_dims(d, who);
+    if (rc != NTK_OK) return rc;
+    NTK_REQUIRE((d.hid % 4) == 0, NTK_ERR_UNSUPPORTED, "%s: hidden=%d must be a multiple of 4", who, d.hid);
+    NTK_REQUIRE(ldkT >= d.K && (ldkT % 4) == 0 && ldhT >= d.hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE,
+                "%s: ldkT=%d (K=%d) ldhT=%d (hid=%d)", who, ldkT, d.K, ldhT, d.hid);
+    NTK_REQUIRE(d.SS + 1 <= NQ, NTK_ERR_UNSUPPORTED, "%s: shift_range=%d too wide", who, (d.SS - 1) / 2);
+    int T = d.H * d.N;
+    T = ntm_imax(T, 3 * d.hid);
+    T = ntm_imax(T, d.PP);
+    T = ntm_imax(T, d.K);
+    T = ((T + 63) / 64) * 64;
+    T = ntm_imax(T, d.H * d.Md + d.Md + 2 * d.Wh * d.Md);
+    T = ((T + 63) / 64) * 64;
+    NTK_REQUIRE(T <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= MAXM * T, NTK_ERR_UNSUPPORTED,
+                "%s: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d (max %d per thread of %d) / hidden=%d (3*hidden <= 1024) exceed "
+                "one workgroup", who, d.H * d.N, d.N * d.Md, MAXM, T, d.hid);
+    ntm_bwd_lds(d, T, ldkT, ldhT, p.L);
+    const bool fix = (d.N == 128 && d.Md == 20 && d.R == 4 && d.Wh == 1 && d.hid == 200 && d.SS == 3 && d.O == 2 &&
+                      T == 640 && !d.write_first && ldkT == 280 && ldhT == 200);
+    p.lds_bytes = (size_t)p.L.total * sizeof(float) + 128;                // + the diagnostic build's stamp words
+    if (fix) p.lds_bytes += (size_t)NTMB_RES_WA * (T / (ldhT / 4)) * (ldhT / 4) * sizeof(f32x4);     // resident rows of Wa^T
+    // benchmark shape: the form whose h columns of Wr^T stream beside the step (NTK_NTM_BWD_FORM=res: round 2's kernel, for comparison)
+    const char* form_env = getenv("NTK_NTM_BWD_FORM");               // read per call (development switch)
+    const bool ws = fix && !(form_env && form_env[0] == 'r');
+    if (ws) p.lds_bytes += (size_t)2 * d.hid * sizeof(float);
+    NTK_REQUIRE(p.lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "%s: needs %zu B of LDS (> 160 KiB)", who, p.lds_bytes);
+    p.kernel = ws ? NTK_NTM_BWD_WS : fix ? NTK_NTM_BWD_FIX : T <= 768 ? NTK_NTM_BWD_GENERIC768 : NTK_NTM_BWD_GENERIC1024;
+    p.T = T;
+    p.threads = ws ? 768 : T;
+    return NTK_OK;
+}
+
+extern "C" int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                                int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    NtmDims d;
+    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first);
+    if (ldkT <= 0) ldkT = ntm_align4(d.K);
+    if (ldhT <= 0) ldhT = ntm_align4(hid);
+    NtmBwdPlan pb;
+    NtmFwdPlan pf;
+    // the BPTT first: where both refuse, ntk_last_error() keeps the forward's reason
+    const bool bwd = ntm_bwd_plan(d, ldkT, ldhT, pb, "ntk_ntm_seq_bwd") == NTK_OK;
+    const bool fwd = ntm_fwd_plan(d, pf, "ntk_ntm_seq_fwd") == NTK_OK;
+    if (fwd_kernel) *fwd_kernel = fwd ? pf.kernel : 0;
+    if (fwd_threads) *fwd_threads = fwd ? pf.T : 0;
+    if (bwd_kernel) *bwd_kernel = bwd ? pb.kernel : 0;
+    if (bwd_threads) *bwd_threads = bwd ? pb.threads : 0;
+    return (fwd ? NTK_NTM_PLAN_FWD : 0) | (bwd ? NTK_NTM_PLAN_BWD : 0);
+}
+
 extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
                                int write_first,
                                const float* WrT, int ldkT, const float* WaT, int ldhT,
@@ -744,42 +806,18 @@ extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int h
                                void* stream) {
     NtmBwdArgs a;
     ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
-    int rc = ntm_validate_dims(a.d, "ntk_ntm_seq_bwd");
+    NtmBwdPlan p;
+    int rc = ntm_bwd_plan(a.d, ldkT, ldhT, p, "ntk_ntm_seq_bwd");
     if (rc != NTK_OK) return rc;
     NTK_REQUIRE(WrT && WaT && M0 && w0 && cs0 && st_gates && st_c && st_u && st_wc && st_wv && st_w && st_M &&
                     dlogits && dgates && du && dM0 && dw0 && dread0 && dcs0,
                 NTK_ERR_BAD_PTR, "ntk_ntm_seq_bwd: null pointer");
     NTK_REQUIRE(ntk_aligned16(WrT) && ntk_aligned16(WaT) && ntk_aligned16(st_gates) && ntk_aligned16(dgates),
                 NTK_ERR_BAD_PTR, "ntk_ntm_seq_bwd: WrT/WaT/st_gates/dgates must be 16-byte aligned");
-    NTK_REQUIRE((hid % 4) == 0, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_bwd: hidden=%d must be a multiple of 4", hid);
-    NTK_REQUIRE(ldkT >= a.d.K && (ldkT % 4) == 0 && ldhT >= hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE,
-                "ntk_ntm_seq_bwd: ldkT=%d (K=%d) ldhT=%d (hid=%d)", ldkT, a.d.K, ldhT, hid);
-    NTK_REQUIRE(a.d.SS + 1 <= NQ, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_bwd: shift_range=%d too wide", shift_range);
-    int T = a.d.H * a.d.N;
-    T = ntm_imax(T, 3 * hid);
-    T = ntm_imax(T, a.d.PP);
-    T = ntm_imax(T, a.d.K);
-    T = ((T + 63) / 64) * 64;
-    T = ntm_imax(T, a.d.H * a.d.Md + a.d.Md + 2 * a.d.Wh * a.d.Md);
-    T = ((T + 63) / 64) * 64;
-    NTK_REQUIRE(T <= 1024 && a.d.H * a.d.N <= 1024 && a.d.N * a.d.Md <= MAXM * T, NTK_ERR_UNSUPPORTED,
-                "ntk_ntm_seq_bwd: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d exceed one workgroup",
-                a.d.H * a.d.N, a.d.N * a.d.Md);
     a.WrT = WrT; a.WaT = WaT; a.ldkT = ldkT; a.ldhT = ldhT; a.M0 = M0; a.w0 = w0; a.cs0 = cs0;
     a.st_gates = st_gates; a.st_c = st_c; a.st_u = st_u; a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M;
     a.dlogits = dlogits; a.dM_fin = dM_fin; a.dw_fin = dw_fin; a.dread_fin = dread_fin; a.dcs_fin = dcs_fin;
     a.dgates = dgates; a.du = du; a.dM0 = dM0; a.dw0 = dw0; a.dread0 = dread0; a.dcs0 = dcs0;
-    NtmBwdLds L;
-    ntm_bwd_lds(a.d, T, ldkT, ldhT, L);
-    const bool fix = (N == 128 && Md == 20 && R == 4 && Wh == 1 && hid == 200 && shift_range == 1 && O == 2 &&
-                      T == 640 && !write_first && ldkT == 280 && ldhT == 200);
-    size_t lds_bytes = (size_t)L.total * sizeof(float) + 128;                // + the diagnostic build's stamp words
-    if (fix) lds_bytes += (size_t)NTMB_RES_WA * (T / (ldhT / 4)) * (ldhT / 4) * sizeof(f32x4);     // resident rows of Wa^T
-    // benchmark shape: the form whose h columns of Wr^T stream beside the step (NTK_NTM_BWD_FORM=res: round 2's kernel, for comparison)
-    const char* form_env = getenv("NTK_NTM_BWD_FORM");
-    const bool ws = fix && !(form_env && form_env[0] == 'r');
-    if (ws) lds_bytes += (size_t)2 * hid * sizeof(float);
-    NTK_REQUIRE(lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_bwd: needs %zu B of LDS (> 160 KiB)", lds_bytes);
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)ntm_seq_bwd_kernel<768, false>, (const void*)ntm_seq_bwd_kernel<1024, false>, (const void*)ntm_seq_bwd_kernel<768, true>,
@@ -787,10 +825,11 @@ extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int h
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_ntm_seq_bwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    if (ws) ntm_seq_bwd_kernel<768, true, true><<<B, 768, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else if (fix) ntm_seq_bwd_kernel<768, true><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else if (T <= 768) ntm_seq_bwd_kernel<768, false><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else ntm_seq_bwd_kernel<1024, false><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
+    const hipStream_t st = (hipStream_t)stream;
+    if (p.kernel == NTK_NTM_BWD_WS) ntm_seq_bwd_kernel<768, true, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+    else if (p.kernel == NTK_NTM_BWD_FIX) ntm_seq_bwd_kernel<768, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+    else if (p.kernel == NTK_NTM_BWD_GENERIC768) ntm_seq_bwd_kernel<768, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+    else ntm_seq_bwd_kernel<1024, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
     NTK_CHECK_LAUNCH("ntk_ntm_seq_bwd");
     return NTK_OK;
 }

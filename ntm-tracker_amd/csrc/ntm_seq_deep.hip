@@ -940,6 +940,9 @@ struct NtmDeepPlan {
     size_t lds_f, lds_b;
 };
 
+// the instantiation a workgroup size takes (both deep kernels): the launchers and ntk_ntm_seq_deep_plan read it here
+static inline int ntm_deep_kernel_id(int T) { return T <= 768 ? NTK_NTM_DEEP_768 : NTK_NTM_DEEP_1024; }
+
 // every limit of the two deep kernels, host arithmetic only
 static int ntm_deep_plan(const NtmDims& d, const NtmDeepShape& s, NtmDeepPlan& p, const char* who) {
     NTK_REQUIRE(s.L >= 2, NTK_ERR_BAD_SHAPE, "%s: L=%d layers (the deep kernels take L >= 2; one layer is ntk_ntm_seq_fwd/bwd)", who, s.L);
@@ -968,6 +971,21 @@ extern "C" int ntk_ntm_seq_deep_supported(int B, int N, int Md, int R, int Wh, i
     ntm_deep_shape(s, 1, R * Md, hid, L);
     NtmDeepPlan p;
     return ntm_deep_plan(d, s, p, "ntk_ntm_seq_deep_supported") == NTK_OK ? 1 : 0;
+}
+
+extern "C" int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
+                                     int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    NtmDims d;
+    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first);
+    NtmDeepShape s;
+    ntm_deep_shape(s, 1, R * Md, hid, L);
+    NtmDeepPlan p;
+    const bool ok = ntm_deep_plan(d, s, p, "ntk_ntm_seq_deep_plan") == NTK_OK;
+    if (fwd_kernel) *fwd_kernel = !ok ? 0 : ntm_deep_kernel_id(p.Tf);
+    if (fwd_threads) *fwd_threads = ok ? p.Tf : 0;
+    if (bwd_kernel) *bwd_kernel = !ok ? 0 : ntm_deep_kernel_id(p.Tb);
+    if (bwd_threads) *bwd_threads = ok ? p.Tb : 0;
+    return ok ? (NTK_NTM_PLAN_FWD | NTK_NTM_PLAN_BWD) : 0;
 }
 
 extern "C" int ntk_ntm_seq_deep_packed_floats(int D, int R, int Md, int hid, int L, size_t* n_wx0, size_t* n_wf, size_t* n_wb) {
@@ -1036,7 +1054,7 @@ extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, 
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, who);
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    if (p.Tf <= 768) ntm_seq_fwd_deep_kernel<768><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
+    if (ntm_deep_kernel_id(p.Tf) == NTK_NTM_DEEP_768) ntm_seq_fwd_deep_kernel<768><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
     else ntm_seq_fwd_deep_kernel<1024><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
     NTK_CHECK_LAUNCH(who);
     return NTK_OK;
@@ -1080,7 +1098,7 @@ extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, 
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, who);
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    if (p.Tb <= 768) ntm_seq_bwd_deep_kernel<768><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
+    if (ntm_deep_kernel_id(p.Tb) == NTK_NTM_DEEP_768) ntm_seq_bwd_deep_kernel<768><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
     else ntm_seq_bwd_deep_kernel<1024><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
     NTK_CHECK_LAUNCH(who);
     return NTK_OK;

@@ -386,7 +386,8 @@ static int ntm_pick_threads(const NtmDims& d) {
 }
 
 bool ntm_seq_fwd_ws_takes(const NtmDims& d);                        // ntm_seq_fwd_ws.hip
-int ntm_seq_fwd_ws_launch(const NtmFwdArgs& a, void* stream);
+int ntm_seq_fwd_ws_plan(const NtmDims& d, NtmLds& L, size_t& lds_bytes);
+int ntm_seq_fwd_ws_launch(const NtmFwdArgs& a, const NtmLds& L, size_t lds_bytes, void* stream);
 
 int ntm_validate_dims(const NtmDims& d, const char* who) {
     NTK_REQUIRE(d.B > 0 && d.S > 0, NTK_ERR_BAD_SHAPE, "%s: B=%d S=%d", who, d.B, d.S);
@@ -404,6 +405,36 @@ int ntm_validate_dims(const NtmDims& d, const char* who) {
                 NTM_MAX_SHIFT_TAPS);
     NTK_REQUIRE((d.H + 1) * 64 <= 1024, NTK_ERR_UNSUPPORTED, "%s: %d heads (one wave per head: at most 15)", who, d.H);
     NTK_REQUIRE(((d.hid + 63) / 64 + 1) * 64 <= 1024, NTK_ERR_UNSUPPORTED, "%s: hidden=%d (at most 960)", who, d.hid);
+    return NTK_OK;
+}
+
+// every limit of the forward kernels and the kernel a shape takes, host arithmetic only
+int ntm_fwd_plan(const NtmDims& d, NtmFwdPlan& p, const char* who) {
+    int rc = ntm_validate_dims(d, who);
+    if (rc != NTK_OK) return rc;
+    // benchmark shape: the kernel whose recurrent weight stream runs beside the step instead of in front of it (ntm_seq_fwd_ws.hip;
+    // NTK_NTM_FWD_FORM=res selects round 2's resident-rows kernel below, for comparison)
+    const char* form_env = getenv("NTK_NTM_FWD_FORM");               // read per call (development switch)
+    const bool ws_off = form_env && form_env[0] == 'r';
+    if (!ws_off && ntm_seq_fwd_ws_takes(d)) {
+        p.kernel = NTK_NTM_FWD_WS;
+        p.T = ntm_seq_fwd_ws_plan(d, p.L, p.lds_bytes);
+    } else {
+        p.T = ntm_pick_threads(d);
+        NTK_REQUIRE(p.T >= d.N, NTK_ERR_UNSUPPORTED, "%s: mem_size %d exceeds the workgroup", who, d.N);
+        const bool fixdims = (d.N == 128 && d.Md == 20 && d.R == 4 && d.Wh == 1 && d.hid == 200 && d.SS == 3 && d.O == 2);
+#ifdef NTK_NTM_FWD_STREAM_ONLY                                              // dev build: the all-streaming 640-thread specialisation of round 1
+        p.kernel = (fixdims && p.T == 640) ? NTK_NTM_FWD_FIX640_DEV : 0;
+#else
+        p.kernel = fixdims ? NTK_NTM_FWD_FIX512 : 0;
+#endif
+        if (p.kernel == NTK_NTM_FWD_FIX512) p.T = 512;
+        if (p.kernel == 0) p.kernel = p.T <= 768 ? NTK_NTM_FWD_GENERIC768 : NTK_NTM_FWD_GENERIC1024;
+        ntm_fwd_lds(d, p.T, p.L);
+        p.lds_bytes = (size_t)p.L.total * sizeof(float) + 128;                   // + the diagnostic build's stamp words
+        if (p.kernel == NTK_NTM_FWD_FIX512) p.lds_bytes += (size_t)20 * 2 * d.hid * sizeof(f32x4);
+    }
+    NTK_REQUIRE(p.lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "%s: state needs %zu B of LDS (> 160 KiB)", who, p.lds_bytes);
     return NTK_OK;
 }
 
@@ -430,40 +461,20 @@ extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int h
                                void* stream) {
     NtmFwdArgs a;
     ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
-    int rc = ntm_validate_dims(a.d, "ntk_ntm_seq_fwd");
+    NtmFwdPlan p;
+    int rc = ntm_fwd_plan(a.d, p, "ntk_ntm_seq_fwd");
     if (rc != NTK_OK) return rc;
     NTK_REQUIRE(xproj && Wr && Wa && M0 && w0 && read0 && cs0 && logits && M_out && w_out && read_out && cs_out,
                 NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: null pointer");
     NTK_REQUIRE(ntk_aligned16(xproj) && ntk_aligned16(Wr) && ntk_aligned16(Wa) &&
                     (!st_gates || ntk_aligned16(st_gates)),
                 NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: xproj/Wr/Wa/st_gates must be 16-byte aligned");
-    const bool any = st_z || st_gates || st_c || st_h || st_u || st_wc || st_wv || st_w || st_M || st_read;
     NTK_REQUIRE(!st_gates == !st_c, NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: st_gates and st_c go together");
-    (void)any;
     a.xproj = xproj; a.Wr = Wr; a.Wa = Wa; a.M0 = M0; a.w0 = w0; a.read0 = read0; a.cs0 = cs0;
     a.logits = logits; a.outputs = outputs; a.M_out = M_out; a.w_out = w_out; a.read_out = read_out; a.cs_out = cs_out;
     a.st_z = st_z; a.st_gates = st_gates; a.st_c = st_c; a.st_h = st_h; a.st_u = st_u;
     a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M; a.st_read = st_read;
-    // benchmark shape: the kernel whose recurrent weight stream runs beside the step instead of in front of it (ntm_seq_fwd_ws.hip;
-    // NTK_NTM_FWD_FORM=res selects round 2's resident-rows kernel below, for comparison)
-    const char* form_env = getenv("NTK_NTM_FWD_FORM");               // read per launch (development switch)
-    const bool ws_off = form_env && form_env[0] == 'r';
-    if (!ws_off && ntm_seq_fwd_ws_takes(a.d)) return ntm_seq_fwd_ws_launch(a, stream);
-    int T = ntm_pick_threads(a.d);
-    NTK_REQUIRE(T >= a.d.N, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_fwd: mem_size %d exceeds the workgroup", a.d.N);
-    NtmLds L;
-    ntm_fwd_lds(a.d, T, L);
-    const bool fixdims = (N == 128 && Md == 20 && R == 4 && Wh == 1 && hid == 200 && shift_range == 1 && O == 2);
-#ifdef NTK_NTM_FWD_STREAM_ONLY                                              // dev build: the all-streaming 640-thread specialisation of round 1
-    const int variant = 0;
-#else
-    const int variant = fixdims ? 1 : 0;
-#endif
-    if (variant == 1) { T = 512; ntm_fwd_lds(a.d, T, L); }
-    size_t lds_bytes = (size_t)L.total * sizeof(float) + 128;                    // + the diagnostic build's stamp words
-    if (variant == 1) lds_bytes += (size_t)20 * 2 * hid * sizeof(f32x4);
-    NTK_REQUIRE(lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED,
-                "ntk_ntm_seq_fwd: state needs %zu B of LDS (> 160 KiB)", lds_bytes);
+    if (p.kernel == NTK_NTM_FWD_WS) return ntm_seq_fwd_ws_launch(a, p.L, p.lds_bytes, stream);
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)ntm_seq_fwd_kernel<768, 0>, (const void*)ntm_seq_fwd_kernel<1024, 0>, (const void*)ntm_seq_fwd_kernel<768, 640>,
@@ -471,10 +482,11 @@ extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int h
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_ntm_seq_fwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    if (variant == 1) ntm_seq_fwd_kernel<512, 512, 24, 20><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else if (fixdims && T == 640) ntm_seq_fwd_kernel<768, 640><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else if (T <= 768) ntm_seq_fwd_kernel<768, 0><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
-    else ntm_seq_fwd_kernel<1024, 0><<<B, T, lds_bytes, (hipStream_t)stream>>>(a, L);
+    const hipStream_t st = (hipStream_t)stream;
+    if (p.kernel == NTK_NTM_FWD_FIX512) ntm_seq_fwd_kernel<512, 512, 24, 20><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+    else if (p.kernel == NTK_NTM_FWD_FIX640_DEV) ntm_seq_fwd_kernel<768, 640><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+    else if (p.kernel == NTK_NTM_FWD_GENERIC768) ntm_seq_fwd_kernel<768, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+    else ntm_seq_fwd_kernel<1024, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
     NTK_CHECK_LAUNCH("ntk_ntm_seq_fwd");
     return NTK_OK;
 }

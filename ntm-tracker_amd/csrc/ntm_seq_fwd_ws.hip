@@ -379,15 +379,18 @@ bool ntm_seq_fwd_ws_takes(const NtmDims& d) {
     return d.N == WN && d.Md == WMd && d.R == WR && d.Wh == 1 && d.hid == Whid && d.SS == WSS && d.O == WO && !d.write_first;
 }
 
-// the launch of the benchmark-shape kernel (ntm_seq_fwd.hip validates the arguments and dispatches here)
-int ntm_seq_fwd_ws_launch(const NtmFwdArgs& a, void* stream) {
-    NtmLds L;
-    ntm_fwd_lds(a.d, TC, L);
-    size_t lds_bytes = (size_t)L.total * sizeof(float) + 128 + (size_t)RESL * 400 * sizeof(f32x4) + (size_t)Whid * sizeof(f32x4);
+// workgroup size and LDS of the benchmark-shape kernel (ntm_fwd_plan asks; the launch below takes its answer)
+int ntm_seq_fwd_ws_plan(const NtmDims& d, NtmLds& L, size_t& lds_bytes) {
+    ntm_fwd_lds(d, TC, L);
+    lds_bytes = (size_t)L.total * sizeof(float) + 128 + (size_t)RESL * 400 * sizeof(f32x4) + (size_t)Whid * sizeof(f32x4);
 #ifdef NTK_CL_PROF
     lds_bytes += 256;
 #endif
-    NTK_REQUIRE(lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_fwd: state needs %zu B of LDS (> 160 KiB)", lds_bytes);
+    return TA;
+}
+
+// the launch of the benchmark-shape kernel (ntm_seq_fwd.hip validates the arguments and dispatches here)
+int ntm_seq_fwd_ws_launch(const NtmFwdArgs& a, const NtmLds& L, size_t lds_bytes, void* stream) {
     // stream batches beside: the unpack product (its own 137 KB stream has the pipe), the activations, the addressing, the read,
     // the write; the other five at the top of the next step (beside the read rows of its gate product)
     // (NTK_NTM_WS_SPLIT=n: development variants of the split and of the ring depth, same results)

@@ -267,6 +267,26 @@ class NTMCell(object):
             "controller_state": torch.empty((batch_size, 2 * d.hid), device=dev),
         }
 
+    # ---- what the kernels will do with this cell
+    FWD_KERNELS = {0: None, 1: "ws", 2: "fixdims-512", 3: "generic-768", 4: "generic-1024", 5: "fixdims-640-dev"}
+    BWD_KERNELS = {0: None, 1: "ws", 2: "fix", 3: "generic-768", 4: "generic-1024"}
+
+    def plan(self, batch):
+        """ntk_ntm_seq_plan for this cell (host arithmetic, nothing is launched): a dict with ``forward`` / ``bptt`` (does the
+        direction run), ``fwd_kernel`` / ``bwd_kernel`` (names of the header's kernel ids, None where refused), ``fwd_threads`` /
+        ``bwd_threads`` and ``reason`` (why a direction is refused, else "").  A cell whose plan has forward but not bptt
+        runs run_sequence and raises in backward_sequence."""
+        d = self.dims
+        if d is None:
+            raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
+        v = [ctypes.c_int() for _ in range(4)]
+        mask = _lib.lib().ntk_ntm_seq_plan(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
+                                           (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4, *[ctypes.byref(x) for x in v])
+        msg = _lib.lib().ntk_last_error() if mask != 3 else b""
+        return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.FWD_KERNELS[v[0].value],
+                "fwd_threads": v[1].value, "bwd_kernel": self.BWD_KERNELS[v[2].value], "bwd_threads": v[3].value,
+                "reason": msg.decode() if msg else ""}
+
     # ---- sequence kernel
     def _pad_inputs(self, inputs):
         d = self.dims
@@ -331,6 +351,10 @@ class NTMCell(object):
         B, S, _ = X.shape
         P = self.params
         ldkT, ldhT = (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4
+        # a shape that runs forward only (see include/ntmtrack.h) is refused here, before anything is launched
+        if not L.ntk_ntm_seq_plan(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, ldkT, ldhT,
+                                  None, None, None, None) & 2:
+            _lib.check(-3, "ntk_ntm_seq_bwd")
         WrT = torch.empty((4 * d.hid, ldkT), device=dev)
         WaT = torch.empty((d.PP, ldhT), device=dev)
         st = _lib.stream()
@@ -623,7 +647,24 @@ class StackedNTMCell(NTMCell):
         if self.fused is False or os.environ.get("NTK_NTM_DEEP_FORM", "") == "stepwise":
             return False
         d = self.dims
-        return bool(_lib.lib().ntk_ntm_seq_deep_supported(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L))
+        # the plan, not ntk_ntm_seq_deep_supported: that one answers for write_first = 0, and a write_first cell needs more LDS
+        return _lib.lib().ntk_ntm_seq_deep_plan(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
+                                                1 if self.write_first else 0, None, None, None, None) == 3
+
+    DEEP_KERNELS = {0: None, 1: "deep-768", 2: "deep-1024"}
+
+    def plan(self, batch):
+        """ntk_ntm_seq_deep_plan for this cell: as NTMCell.plan; a refused shape runs step-wise from Python instead."""
+        d = self.dims
+        if d is None:
+            raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
+        v = [ctypes.c_int() for _ in range(4)]
+        mask = _lib.lib().ntk_ntm_seq_deep_plan(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
+                                                1 if self.write_first else 0, *[ctypes.byref(x) for x in v])
+        msg = _lib.lib().ntk_last_error() if mask != 3 else b""
+        return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.DEEP_KERNELS[v[0].value],
+                "fwd_threads": v[1].value, "bwd_kernel": self.DEEP_KERNELS[v[2].value], "bwd_threads": v[3].value,
+                "reason": msg.decode() if msg else ""}
 
     def _pack(self):
         """The controller weights in the deep kernels' layouts (ntk_ntm_seq_deep_pack), from the flat buffer as it is now."""

@@ -141,6 +141,29 @@ def loss_and_grads(cfg, params_np, inputs_np, offsets_np, num_features=64, dtype
     return float(loss.detach()), {k: v.grad.numpy() for k, v in p.items()}, logits.detach().numpy(), pred.detach().numpy()
 
 
+STATE_KEYS = ("M", "w", "read", "controller_state")
+
+
+def grads_with_state(cfg, params_np, inputs_np, state_np, dlogits_np, dfinal_np=None, dtype=torch.float64):
+    """BPTT from an explicit initial state.  ``state_np`` {M [B,N,Md], w [B,H,N], read [B,R,Md], controller_state
+    [B,2*hid*layers]} enters as leaf tensors, ``dlogits_np`` [B,S,O] is the cotangent of the logits and ``dfinal_np``
+    (optional, any subset of the state keys) the cotangent of the final state: the gradient of
+    sum(dlogits * logits) + sum_k sum(dfinal_k * final_k).  Returns ({name: grad} over the parameters in the TF variable layout --
+    zero for the init_state variables, which an explicit state does not read --, {key: grad} over the initial state tensors,
+    logits, final state), all numpy."""
+    p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in params_np.items()}
+    st = {k: torch.tensor(state_np[k], dtype=dtype, requires_grad=True) for k in STATE_KEYS}
+    x = torch.tensor(inputs_np, dtype=dtype)
+    logits, fin = loop(cfg, p, x, state=dict(st))
+    obj = (torch.tensor(dlogits_np, dtype=dtype) * logits).sum()
+    for k, g in (dfinal_np or {}).items():
+        obj = obj + (torch.tensor(g, dtype=dtype) * fin[k]).sum()
+    obj.backward()
+    grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).numpy() for k, v in p.items()}
+    g0 = {k: (v.grad if v.grad is not None else torch.zeros_like(v)).numpy() for k, v in st.items()}
+    return grads, g0, logits.detach().numpy(), {k: v.detach().numpy() for k, v in fin.items()}
+
+
 def conv3x3_same_relu(x, w, b):
     """One VGG layer in float64 on torch-CPU: x [F,H,W,Cin] NHWC, w [3,3,Cin,Cout] HWIO, b [Cout] (numpy) -> relu(conv3x3_same(x, w)
     + b) as float64 numpy [F,H,W,Cout].  ntm_oracle.conv3x3_same_relu restated: the same sums, in seconds less at 512 channels."""

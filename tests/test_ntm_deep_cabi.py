@@ -6,7 +6,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ntmtrack.h")
-ENTRIES = ("ntk_ntm_seq_deep_supported", "ntk_ntm_seq_deep_packed_floats", "ntk_ntm_seq_deep_pack",
+ENTRIES = ("ntk_ntm_seq_deep_supported", "ntk_ntm_seq_deep_plan", "ntk_ntm_seq_deep_packed_floats", "ntk_ntm_seq_deep_pack",
            "ntk_ntm_seq_fwd_deep", "ntk_ntm_seq_bwd_deep")
 OK, BAD_SHAPE, BAD_PTR, UNSUPPORTED = 0, -1, -2, -3
 TRACKER = (128, 20, 4, 1, 200, 1, 2)          # N, Md, R, Wh, hid, shift_range, O (direct_offset_output.py:21-27)
@@ -43,6 +43,14 @@ def test_supported_answers_the_named_shapes_and_refuses_beyond_the_bound():
     assert L.ntk_ntm_seq_deep_supported(32, N, Md, R, Wh, 202, sr, O, 2) == 0
     assert L.ntk_ntm_seq_deep_supported(32, 100, Md, R, Wh, hid, sr, O, 2) == 0     # mem_size % 64
     assert L.ntk_ntm_seq_deep_supported(32, N, Md, R, Wh, hid, 5, O, 2) == 0        # shift_range 5
+    # the plan gives the same answers (mask 3 = forward and BPTT) and the workgroup sizes: 5 x 128 slots at the tracker's shape
+    v = [ctypes.c_int() for _ in range(4)]
+    for wf in (0, 1):
+        assert L.ntk_ntm_seq_deep_plan(32, N, Md, R, Wh, hid, sr, O, 2, wf, *[ctypes.byref(x) for x in v]) == 3
+        assert [x.value for x in v] == [1, 640, 1, 640]                             # NTK_NTM_DEEP_768 both ways
+    assert L.ntk_ntm_seq_deep_plan(32, N, Md, R, Wh, hid, sr, O, 1, 0, *[ctypes.byref(x) for x in v]) == 0
+    assert [x.value for x in v] == [0, 0, 0, 0] and b"L=1" in L.ntk_last_error()
+    assert L.ntk_ntm_seq_deep_plan(32, N, Md, R, Wh, 202, sr, O, 2, 0, None, None, None, None) == 0
 
 
 def _fwd(L, layers=2, N=128, hid=200, ptr=None, wf=None):

@@ -154,6 +154,61 @@ def test_autograd_oracle_gradients_by_finite_differences():
             np.testing.assert_allclose(g[idx], (up - dn) / (2 * d), rtol=2e-4, atol=1e-9)
 
 
+@pytest.mark.parametrize("layers,write_first", [(1, False), (2, True)])
+def test_state_gradients_by_finite_differences(layers, write_first):
+    """OT.grads_with_state: the gradient of sum(dlogits * logits) + sum_k sum(dfinal_k * final_k) with respect to an explicit,
+    non-trivial initial state and to the parameters, against central differences of the independent numpy restatement in float64
+    (step and bound of test_autograd_oracle_gradients_by_finite_differences)."""
+    cfg = O.NTMConfig(6, 2, mem_size=8, mem_dim=4, shift_range=1, controller_hidden_size=5, controller_num_layers=layers,
+                      write_head_size=1, read_head_size=2, write_first=write_first)
+    rng = np.random.default_rng(7 + layers)
+    p = O.init_params(cfg, rng, scale=0.5, dtype=np.float64)
+    B, S = 2, 4
+    x = rng.standard_normal((B, S, 6))
+    st = {k: v + rng.uniform(0, 0.3, size=v.shape) for k, v in O.zero_state(cfg, p, B).items()}
+    st["controller_state"] = rng.uniform(-0.5, 0.5, size=st["controller_state"].shape)
+    dlog = rng.standard_normal((B, S, 2))
+    dfin = {k: rng.standard_normal(v.shape) for k, v in st.items()}
+
+    def objective(pp, ss, with_final=True):
+        _, l, fin = O.loop_ntm_tracker(cfg, pp, x, state={k: v.copy() for k, v in ss.items()})
+        return float((dlog * l).sum()) + (sum(float((dfin[k] * fin[k]).sum()) for k in dfin) if with_final else 0.0)
+
+    grads, g0, logits, fin = OT.grads_with_state(cfg, p, x, st, dlog, dfin)
+    _, l_np, fin_np = O.loop_ntm_tracker(cfg, p, x, state={k: v.copy() for k, v in st.items()})
+    np.testing.assert_allclose(logits, l_np, atol=1e-12)
+    for k in fin_np:
+        np.testing.assert_allclose(fin[k], fin_np[k], atol=1e-12, err_msg=k)
+    assert set(g0) == set(OT.STATE_KEYS) and all(g0[k].shape == st[k].shape for k in g0)
+    d = 1e-6
+    for key in OT.STATE_KEYS:                                         # a few entries of every state tensor
+        for idx in [tuple(rng.integers(0, s) for s in st[key].shape) for _ in range(4)]:
+            ss = {k: v.copy() for k, v in st.items()}
+            ss[key][idx] += d
+            up = objective(p, ss)
+            ss[key][idx] -= 2 * d
+            dn = objective(p, ss)
+            np.testing.assert_allclose(g0[key][idx], (up - dn) / (2 * d), rtol=2e-4, atol=1e-9, err_msg="%s%s" % (key, idx))
+    for name in ("addressing/weights", "lstm/cell_%d/weights" % (layers - 1), "lstm/cell_0/biases", "output/biases"):
+        for idx in [tuple(rng.integers(0, s) for s in p[name].shape) for _ in range(3)]:
+            pp = {k: v.copy() for k, v in p.items()}
+            pp[name][idx] += d
+            up = objective(pp, st)
+            pp[name][idx] -= 2 * d
+            dn = objective(pp, st)
+            np.testing.assert_allclose(grads[name][idx], (up - dn) / (2 * d), rtol=2e-4, atol=1e-9, err_msg="%s%s" % (name, idx))
+    for name in ("init_state/M", "init_state/w", "init_state/read"):  # an explicit state does not read the trainable one
+        assert not grads[name].any()
+    # without a final-state cotangent the same call is the gradient of the logits term alone
+    g_l, g0_l, _, _ = OT.grads_with_state(cfg, p, x, st, dlog)
+    ss = {k: v.copy() for k, v in st.items()}
+    ss["M"][0, 1, 2] += d
+    up = objective(p, ss, with_final=False)
+    ss["M"][0, 1, 2] -= 2 * d
+    np.testing.assert_allclose(g0_l["M"][0, 1, 2], (up - objective(p, ss, with_final=False)) / (2 * d), rtol=2e-4, atol=1e-9)
+    assert np.max(np.abs(g0_l["M"] - g0["M"])) > 1e-3
+
+
 def test_conv_layer_numpy_vs_torch_restatement():
     rng = np.random.default_rng(4)
     for F, H, W, cin, cout in ((3, 8, 12, 16, 64), (1, 4, 28, 3, 64), (2, 20, 28, 64, 128)):
