@@ -202,9 +202,9 @@ int ntk_ntm_padded_dims(int N, int Md, int R, int Wh, int hid, int shift_range, 
  * asks ntk_ntm_seq_plan BEFORE the forward pass:
  *   every forward limit, and
  *   hid a multiple of 4;  ldkT >= K, ldhT >= hid, both multiples of 4 (else NTK_ERR_BAD_SHAPE)
- *   T = the largest of H*N, 3*hid, PP, K, H*Md + Md + 2*Wh*Md, rounded up to whole waves, must be <= 1024: so H*N <= 1024
- *   (mem_size above 512 never trains), 3*hid <= 1024 (hid <= 340), PP <= 1024, K <= 1024
- *   N*Md <= 8*T (a thread prefetches at most 8 memory elements)
+ *   T = the largest of H*N, 3*hid, PP, K, H*Md + Md + 2*Wh*Md, N*Md/8 (a thread prefetches at most 8 memory elements), rounded
+ *   up to whole waves, must be <= 1024: so H*N <= 1024 (mem_size above 512 never trains), 3*hid <= 1024 (hid <= 340),
+ *   PP <= 1024, K <= 1024, N*Md <= 8192
  *   the BPTT state within 160 KiB of LDS: roughly 4 * (4*N*(Md|1) + 8*H*N + 9*hid + ...) bytes, one more N*(Md|1) with write_first.
  *
  * Kernel ids ntk_ntm_seq_plan reports (0 = refused): */
@@ -398,6 +398,90 @@ int ntk_ntm_step_bwd(int B, int N, int Md, int R, int Wh, int hid, int shift_ran
                      const float* dM, const float* dw, const float* dread, const float* dcs,
                      float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
                      void* stream);
+
+/* ------------------------------------------------------------------------
+ * Similarity mode of the content addressing.  The entries above compute the reference's as-coded similarity (quirk Q1: every
+ * feature column of the memory l2-normalised over the slots).  Their *_sim siblings take one more argument, `similarity`,
+ * right after write_first, and are otherwise the same call:
+ *   NTK_NTM_SIM_AS_CODED       what the entry without the suffix computes (which forwards here with this value)
+ *   NTK_NTM_SIM_SMOOTH_COSINE  row-wise sim[h][n] = k_h . M[n] / (|k_h| |M[n]| + 1e-3) on the memory BEFORE this step's write
+ *                              (with and without write_first), no clamp on either norm -- the content addressing of the NTM
+ *                              paper and of the reference's ops_test.py, ntk_ntm_cosine_similarity's mode 1.
+ * Any other value is refused with NTK_ERR_UNSUPPORTED before anything else is looked at (no pointer is read, nothing is
+ * launched).  The mode is an argument of every call: the library keeps no mode state and reads no environment switch for it.
+ * Forward and BPTT of one sequence must be given the same mode (the BPTT recomputes sim from the records u and M_prev; there
+ * are no additional records).  In the BPTT the gradient through a norm that is exactly zero (an all-zero memory row, an
+ * all-zero key) is defined as 0, where automatic differentiation yields NaN; sim itself is 0 there.
+ * Shape limits are those of the as-coded entries, except that the normaliser takes N floats of LDS where it took Md
+ * (forward: once; BPTT: twice), which the plans account for.  Smooth cosine has no wave-specialised form: the plans report
+ * NTK_NTM_FWD_FIX512 / NTK_NTM_BWD_FIX for the tracker shape and never NTK_NTM_FWD_WS / NTK_NTM_BWD_WS.
+ * --------------------------------------------------------------------- */
+#define NTK_NTM_SIM_AS_CODED       0
+#define NTK_NTM_SIM_SMOOTH_COSINE  1
+
+/* ntk_ntm_seq_plan for a similarity mode; NTK_ERR_UNSUPPORTED (negative, not a mask) for an unknown mode */
+int ntk_ntm_seq_plan_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first, int similarity,
+                         int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads);
+/* ntk_ntm_seq_fwd / ntk_ntm_seq_bwd in a similarity mode */
+int ntk_ntm_seq_fwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                        int write_first, int similarity,
+                        const float* xproj, const float* Wr, const float* Wa,
+                        const float* M0, const float* w0, const float* read0, const float* cs0,
+                        float* logits, float* outputs,
+                        float* M_out, float* w_out, float* read_out, float* cs_out,
+                        float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                        float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                        void* stream);
+int ntk_ntm_seq_bwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                        int write_first, int similarity,
+                        const float* WrT, int ldkT, const float* WaT, int ldhT,
+                        const float* M0, const float* w0, const float* cs0,
+                        const float* st_gates, const float* st_c, const float* st_u,
+                        const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                        const float* dlogits,
+                        const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
+                        float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
+                        void* stream);
+/* ntk_ntm_step_fwd / ntk_ntm_step_bwd in a similarity mode (the *_sim sequence entries with S = 1) */
+int ntk_ntm_step_fwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first, int similarity,
+                         const float* xproj, const float* Wr, const float* Wa,
+                         const float* M_prev, const float* w_prev, const float* read_prev, const float* cs_prev,
+                         float* logits, float* outputs, float* M, float* w, float* read, float* cs,
+                         float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                         float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read, void* stream);
+int ntk_ntm_step_bwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first, int similarity,
+                         const float* WrT, int ldkT, const float* WaT, int ldhT,
+                         const float* M_prev, const float* w_prev, const float* cs_prev,
+                         const float* st_gates, const float* st_c, const float* st_u,
+                         const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                         const float* dlogits,
+                         const float* dM, const float* dw, const float* dread, const float* dcs,
+                         float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
+                         void* stream);
+/* ntk_ntm_seq_deep_plan / ntk_ntm_seq_fwd_deep / ntk_ntm_seq_bwd_deep in a similarity mode */
+int ntk_ntm_seq_deep_plan_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
+                              int similarity, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads);
+int ntk_ntm_seq_fwd_deep_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                             int write_first, int similarity, int D,
+                             const float* X, const float* xproj, const float* Wf, const float* Wa,
+                             const float* M0, const float* w0, const float* read0, const float* cs0,
+                             float* logits, float* outputs,
+                             float* M_out, float* w_out, float* read_out, float* cs_out,
+                             float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                             float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                             float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
+                             void* stream);
+int ntk_ntm_seq_bwd_deep_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                             int write_first, int similarity,
+                             const float* Wb, const float* WaT, int ldhT,
+                             const float* M0, const float* w0, const float* cs0,
+                             const float* st_gates, const float* st_c, const float* st_u,
+                             const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                             const float* st_lgates, const float* st_lc,
+                             const float* dlogits,
+                             const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
+                             float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
+                             void* stream);
 
 /* tf.contrib.rnn.BasicLSTMCell pointwise step (ntm_cell.py:45-50; gate pre-activations pre [B,4*hid] = [x,h] W + b from
  * ntk_gemm_nt_f32, TF block order i | j | f | o): c = c_prev*sigmoid(f + forget_bias) + sigmoid(i)*tanh(j),

@@ -90,6 +90,15 @@ def _sig(lib):
         "ntk_ntm_step_debug": (c_int, [P] + [c_int] * 7 + [P] * 9 + [c_int] * 5 + [P]),
         "ntk_ntm_step_fwd": (c_int, [c_int] * 9 + [P] * 24),
         "ntk_ntm_step_bwd": (c_int, [c_int] * 9 + [P, c_int, P, c_int] + [P] * 22),
+        # the same entries with `int similarity` after write_first (0 = as coded, 1 = smooth cosine)
+        "ntk_ntm_seq_plan_sim": (c_int, [c_int] * 12 + [ctypes.POINTER(c_int)] * 4),
+        "ntk_ntm_seq_fwd_sim": (c_int, [c_int] * 11 + [P] * 23 + [P]),
+        "ntk_ntm_seq_bwd_sim": (c_int, [c_int] * 11 + [P, c_int, P, c_int] + [P] * 21 + [P]),
+        "ntk_ntm_step_fwd_sim": (c_int, [c_int] * 10 + [P] * 24),
+        "ntk_ntm_step_bwd_sim": (c_int, [c_int] * 10 + [P, c_int, P, c_int] + [P] * 22),
+        "ntk_ntm_seq_deep_plan_sim": (c_int, [c_int] * 11 + [ctypes.POINTER(c_int)] * 4),
+        "ntk_ntm_seq_fwd_deep_sim": (c_int, [c_int] * 13 + [P] * 29 + [P]),
+        "ntk_ntm_seq_bwd_deep_sim": (c_int, [c_int] * 12 + [P, P, c_int] + [P] * 24 + [P]),
         "ntk_lstm_step_fwd": (c_int, [P, P, ctypes.c_float, P, P, P, c_int, c_int, P]),
         "ntk_lstm_step_bwd": (c_int, [P] * 7 + [c_int, c_int, P]),
         "ntk_vgg_wino_packed_floats": (ctypes.c_size_t, [c_int, c_int]),

@@ -29,13 +29,13 @@ def make_batch(bits):
 class CopyTask(object):
     def __init__(self, batch_size, length, width=3, mem_size=128, mem_dim=20, hidden_size=100, read_head_size=1,
                  write_head_size=1, init_scale=0.05, learning_rate=1e-4, decay=0.95, momentum=0.9,
-                 max_gradient_norm=5.0, device="cuda", seed=0):
+                 max_gradient_norm=5.0, device="cuda", seed=0, similarity="as_coded"):
         self.B, self.L, self.width = batch_size, length, width
         self.S = 2 * length + 1
         self.device = torch.device(device)
         self.cell = NTMCell(width + 1, mem_size=mem_size, mem_dim=mem_dim, controller_hidden_size=hidden_size,
                             controller_num_layers=1, write_head_size=write_head_size, read_head_size=read_head_size,
-                            input_dim=width + 1, device=self.device, init_scale=init_scale, seed=seed)
+                            input_dim=width + 1, device=self.device, init_scale=init_scale, seed=seed, similarity=similarity)
         self.opt = RMSPropClip(self.cell.params, learning_rate, decay, momentum, 1e-10, max_gradient_norm)
 
     def loss_and_grads(self, x, y):

@@ -20,6 +20,8 @@
 // shift taps the sequence kernels hold in registers: shift_range <= 4 (the reference's default and every BASELINE config use 1)
 constexpr int NTM_MAX_SHIFT_TAPS = 9;
 
+constexpr int NTM_SIM_AS_CODED = 0, NTM_SIM_SMOOTH_COSINE = 1;
+
 struct NtmDims {
     int B, S;          // sequences, steps
     int N, Md;         // memory slots, word size          (mem_size, mem_dim)
@@ -31,12 +33,13 @@ struct NtmDims {
     int K, ldz;        // R*Md+hid, padded K+1 (multiple of 4)
     int ldh;           // padded hid+1 (multiple of 4)
     int write_first;
+    int similarity;    // NTM_SIM_AS_CODED (quirk Q1) or NTM_SIM_SMOOTH_COSINE (row-wise k.M[n] / (|k||M[n]| + 1e-3))
     // control offsets inside the unpacked vector (ntm_cell.py:128-130)
     int oK, oB, oG, oS, oY, oE, oA;   // k, beta, g, shift, gamma, erase, add
 };
 
 static inline void ntm_fill_dims(NtmDims& d, int B, int S, int N, int Md, int R, int Wh, int hid,
-                                 int shift_range, int O, int write_first) {
+                                 int shift_range, int O, int write_first, int similarity = NTM_SIM_AS_CODED) {
     d.B = B; d.S = S; d.N = N; d.Md = Md; d.R = R; d.Wh = Wh; d.H = R + Wh; d.hid = hid;
     d.SS = 2 * shift_range + 1; d.O = O;
     d.oK = 0;
@@ -52,7 +55,17 @@ static inline void ntm_fill_dims(NtmDims& d, int B, int S, int N, int Md, int R,
     d.ldz = ((d.K + 1 + 3) / 4) * 4;
     d.ldh = ((hid + 1 + 3) / 4) * 4;
     d.write_first = write_first;
+    d.similarity = similarity;
 }
+
+// the similarity argument of the *_sim entry points, checked before anything else
+#define NTM_REQUIRE_SIMILARITY(similarity, who)                                                                       \
+    NTK_REQUIRE((similarity) == NTM_SIM_AS_CODED || (similarity) == NTM_SIM_SMOOTH_COSINE, NTK_ERR_UNSUPPORTED,        \
+                "%s: similarity=%d (0 = as coded, 1 = smooth cosine)", who, similarity)
+
+// floats of the per-step normaliser of the content addressing: the Md column norms of M over the slots as coded, the N row
+// norms in smooth-cosine mode
+static inline int ntm_norm_floats(const NtmDims& d) { return d.similarity == NTM_SIM_SMOOTH_COSINE ? d.N : d.Md; }
 
 // LDS carve-up shared by forward and backward (offsets in floats)
 struct NtmLds {

@@ -48,7 +48,7 @@ static inline void ntm_fwd_lds(const NtmDims& d, int T, NtmLds& L) {
     L.C = o; o += ntm_align4(d.hid);
     L.U = o; o += ntm_align4(d.PP);
     L.Ks = o; o += ntm_align4(d.H * d.Md);
-    L.Cn = o; o += ntm_align4(d.Md);
+    L.Cn = o; o += ntm_align4(ntm_norm_floats(d));
     L.Pw = o; o += ntm_align4(d.H * d.N);
     L.total = o;
 }

@@ -58,7 +58,7 @@ struct NtmBwdLds {
 
 constexpr int NQ = 1 + NTM_MAX_SHIFT_TAPS;   // max simultaneous per-head reductions in one stage (d gamma + one per shift tap)
 constexpr int QR1 = 0, QR2 = 2, QR3 = QR2 + NQ, QR4 = QR3 + 2;
-constexpr int NQT = QR4 + 1; // reduction slots per head; every stage owns its own slots (no read/write reuse inside a step)
+constexpr int NQT = QR4 + 1; // (smooth cosine: one more, QR4 + 1 = sum_n b |M[n]|) reduction slots per head; every stage owns its own slots (no read/write reuse inside a step)
 constexpr int MAXM = 8;      // max memory elements prefetched per thread
 constexpr int NTMB_RES_WA = 7;   // benchmark shape: rows of Wa^T per thread (of its 15) kept in the LDS the state leaves free
 
@@ -82,9 +82,9 @@ static void ntm_bwd_lds(const NtmDims& d, int T, int ldkT, int ldhT, NtmBwdLds& 
     L.U = take(d.PP); L.DU = take(d.PP); L.DG = take(4 * d.hid); L.dZ = take(ldkT); L.dC = take(d.hid);
     L.Gt = take(4 * d.hid); L.Ct = take(d.hid); L.Cp = take(d.hid);
     L.Khat = take(d.H * d.Md); L.Ks = take(d.H * d.Md); L.Kinv = take(d.H); L.Kss = take(d.H);
-    L.Cinv = take(d.Md); L.Css = take(d.Md); L.C2 = take(d.Md); L.Dkhat = take(d.H * d.Md);
+    L.Cinv = take(ntm_norm_floats(d)); L.Css = take(d.Md); L.C2 = take(ntm_norm_floats(d)); L.Dkhat = take(d.H * d.Md);
     L.Sw = take(d.H * d.SS);
-    L.Red = take(d.H * NQT * (d.N / 64));
+    L.Red = take(d.H * (NQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
     L.Dmh = take(d.N * (d.Md | 1));
     L.total = o;
 }
@@ -108,10 +108,16 @@ __device__ __forceinline__ void bws_for(F&& f) {
     if constexpr (I0 < I1) { f(bwsic<I0>{}); bws_for<I0 + 1, I1>(f); }
 }
 
-template <int MAXT, bool FIX, bool WS = false>
+// SIM (NTM_SIM_*): the similarity of the content addressing, a compile-time mode as in ntm_seq_fwd.hip.  Smooth cosine
+// recomputes sim = k.M_prev[n] / (|k||M_prev[n]| + 1e-3) from the same records and differentiates it through both norms, with
+// the gradient of a norm at exactly zero defined as 0 (the pow convention above; autograd yields NaN there).
+template <int MAXT, bool FIX, bool WS = false, int SIM = NTM_SIM_AS_CODED>
 __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     static_assert(!WS || FIX, "the wave-specialised form exists for the benchmark shape only");
+    constexpr bool SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
+    constexpr int NQS = NQT + (SMOOTH ? 1 : 0);         // reduction slots per head
+    static_assert(!WS || !SMOOTH, "the wave-specialised form is as coded only");
     const int b = blockIdx.x, tid0 = threadIdx.x, T = FIX ? 640 : blockDim.x;
     const int N = FIX ? 128 : a.d.N, Md = FIX ? 20 : a.d.Md, MP = Md | 1, R = FIX ? 4 : a.d.R, Wh = FIX ? 1 : a.d.Wh;
     const int H = R + Wh, hid = FIX ? 200 : a.d.hid, SS = FIX ? 3 : a.d.SS;
@@ -137,6 +143,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     float* sKhat = smem + L.Khat; float* sKs = smem + L.Ks; float* sKinv = smem + L.Kinv; float* sKss = smem + L.Kss;
     float* sCinv = smem + L.Cinv; float* sCss = smem + L.Css; float* sC2 = smem + L.C2; float* sDkhat = smem + L.Dkhat;
     float* sSw = smem + L.Sw;  float* sRed = smem + L.Red;  float* sDmh = smem + L.Dmh;
+    float* sRn = sCinv; float* sRc = sC2;  // smooth cosine: [N] row norms |M_prev[n]| and the row-norm coefficients where the [Md] column terms are
     f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart);
     // WS: d h_{t-1} partials of the stream waves, [2 row halves][200] floats, behind the resident rows of Wa^T
     float* sPartH = smem + L.total + 32 + NTMB_RES_WA * 600 * 4;
@@ -283,13 +290,13 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
         for (int q = 0; q < NQ; ++q) {
             if (q < nq) {
                 const float s = wave_sum(hn ? v[q] : 0.f);
-                if (hn && lane == 0) sRed[(hh * NQT + base + q) * NW + wi] = s;
+                if (hn && lane == 0) sRed[(hh * NQS + base + q) * NW + wi] = s;
             }
         }
     };
     auto red_read = [&](int h, int q) -> float {
         float s = 0.f;
-        for (int w = 0; w < NW; ++w) s += sRed[(h * NQT + q) * NW + w];
+        for (int w = 0; w < NW; ++w) s += sRed[(h * NQS + q) * NW + w];
         return s;
     };
 
@@ -362,6 +369,13 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
             sG[ai] = dMt;
             sdM[ai] = dMt * E + (wf ? 0.f : dMr);
         }
+        if constexpr (SMOOTH) {
+            if (tid < N) {         // row norms of M_prev, no clamp
+                float s = 0.f;
+                for (int m = 0; m < Md; ++m) { const float v = sMp[tid * MP + m]; s += v * v; }
+                sRn[tid] = sqrtf(s);
+            }
+        } else
         if (tid < nslC * Md) {     // column sum of squares of M_prev (quirk Q1 normaliser)
             const int m = tid % Md, sl = tid / Md;
             const int n0 = sl * nperC, n1 = min(N, n0 + nperC);
@@ -374,7 +388,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
             float ss = 0.f;
             for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; ss += kv * kv; }
             sKss[h] = ss;
-            sKinv[h] = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+            sKinv[h] = SMOOTH ? sqrtf(ss) : 1.0f / sqrtf(fmaxf(ss, 1e-12f));        // smooth cosine: |k| itself
             float mx = -INFINITY;
             for (int j = 0; j < SS; ++j) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
             float sum = 0.f;
@@ -387,7 +401,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
         // ------------------------------------------------ X2: d(w_t) for every head; R1 sums
         float dwt = 0.f, pw = 0.f, wv = 0.f, wt = 0.f, wc = 0.f, wp = 0.f, gam = 1.f, gate = 0.f;
         float rv[NQ];
-        if (tid < Md) {
+        if (!SMOOTH && tid < Md) {
             float s = 0.f;
             for (int sl = 0; sl < nslC; ++sl) s += sPart[sl * Md + tid];
             sCss[tid] = s;
@@ -423,11 +437,11 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
 
         // ------------------------------------------------ R2: sharpen backward, shift-weight sums
         float dpw = 0.f, dwv = 0.f;
-        if (tid < H * Md) {        // normalised keys (needed from R4 on)
+        if (tid < H * Md) {        // normalised keys (needed from R4 on); smooth cosine: the keys as they are
             const int h = tid / Md, m = tid - h * Md;
-            const float kh = sU[d.oK + tid] * sKinv[h];
+            const float kh = SMOOTH ? sU[d.oK + tid] : sU[d.oK + tid] * sKinv[h];
             sKhat[tid] = kh;
-            sKs[tid] = kh * sCinv[m];
+            sKs[tid] = SMOOTH ? kh : kh * sCinv[m];
         }
         if (hn) {
             const float den = red_read(hh, QR1) + 1e-3f;
@@ -478,12 +492,33 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
             dv = wc * (dwc - Bs);
             float sim = 0.f;
             for (int m = 0; m < Md; ++m) sim += sKs[hh * Md + m] * sMp[nn * MP + m];
-            rv[0] = dv * sim;                                       // d beta
-            sDsim[tid] = dv * sU[d.oB + hh];
+            if constexpr (SMOOTH) {
+                // sim = dot / den, den = |M[n]||k| + 1e-3:  d dot = a = dsim / den,  d den = b = -dsim sim / den.  sDsim keeps a
+                // (B7 and the key sums below read it where they read dsim as coded); b |k| goes to the row-norm term of d M_prev
+                // (sDwv is free: its readers passed R3's barrier) and b |M[n]|, summed over the slots, to the norm term of d k
+                const float rn = sRn[nn], kn = sKinv[hh], den = rn * kn + 1e-3f;
+                sim = sim / den;
+                const float da = dv * sU[d.oB + hh] / den, db = -da * sim;
+                rv[0] = dv * sim;                                   // d beta
+                sDsim[tid] = da;
+                sDwv[tid] = db * kn;
+                rv[1] = db * rn;
+            } else {
+                rv[0] = dv * sim;                                   // d beta
+                sDsim[tid] = dv * sU[d.oB + hh];
+            }
         }
-        red_write(rv, 1, QR4);
+        red_write(rv, SMOOTH ? 2 : 1, QR4);
         __syncthreads();
         NTMB_STAMP(4);
+        if constexpr (SMOOTH) {
+            if (tid < N) {         // row-norm term: d M_prev[n][:] += M_prev[n][:] * (sum_h b[h][n] |k_h|) / |M[n]|, 0 at a zero row
+                float s = 0.f;
+                for (int h = 0; h < H; ++h) s += sDwv[h * N + tid];
+                const float rn = sRn[tid];
+                sRc[tid] = (rn > 0.f) ? s / rn : 0.f;
+            }
+        }
         if (hn && nn == 0) {       // per-head scalar controls -> raw gradients
             const int h = hh;
             const float beta = sU[d.oB + h];
@@ -577,6 +612,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
         __syncthreads();
         NTMB_STAMP(5);
         // column-norm term: s_m = sum_n dMhat[n][m] * M_prev[n][m], one wave_sum per column (waves stride over m)
+        if constexpr (!SMOOTH)
         for (int m = (tid >> 6); m < Md; m += (T >> 6)) {
             float s = 0.f;
             for (int n = lane; n < N; n += 64) s += sDmh[n * MP + m] * sMp[n * MP + m];
@@ -590,7 +626,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
             float s = 0.f;
             for (int sl = 0; sl < (FIX ? 1 : nslP); ++sl) s += sPart[sl * nout + tid];
             if (tid < H * Md) {
-                sDkhat[tid] = s * sCinv[tid % Md];
+                sDkhat[tid] = SMOOTH ? s : s * sCinv[tid % Md];
             } else {
                 const int o2 = tid - H * Md;
                 const int which = o2 / (Wh * Md);
@@ -603,17 +639,24 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
         NTMB_STAMP(6);
         if (tid < H * Md) {
             const int h = tid / Md;
-            float dot = 0.f;
-            for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
-            const float ki = sKinv[h];
-            const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
-            const float kv = sU[d.oK + tid];
-            const float dk = ki * sDkhat[tid] + kv * ck;
-            sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            if constexpr (SMOOTH) {                                 // d k = sum_n a M_prev[n] + k / |k| * sum_n b |M[n]|, 0 through |k| = 0
+                const float kn = sKinv[h], kv = sU[d.oK + tid];
+                const float dk = sDkhat[tid] + ((kn > 0.f) ? kv / kn * red_read(h, QR4 + 1) : 0.f);
+                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            } else {
+                float dot = 0.f;
+                for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
+                const float ki = sKinv[h];
+                const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
+                const float kv = sU[d.oK + tid];
+                const float dk = ki * sDkhat[tid] + kv * ck;
+                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            }
         }
         for (int idx = tid; idx < NMd; idx += T) {
             const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
+            if constexpr (SMOOTH) sdM[ai] += sDmh[ai] + sMp[ai] * sRc[n];
+            else sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
         }
         __syncthreads();
         NTMB_STAMP(7);
@@ -756,6 +799,9 @@ static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, con
     T = ntm_imax(T, d.K);
     T = ((T + 63) / 64) * 64;
     T = ntm_imax(T, d.H * d.Md + d.Md + 2 * d.Wh * d.Md);
+    // a thread prefetches at most MAXM elements of the memory: a wide memory under few heads (64 x 72 under two) takes the threads
+    // it needs for that, where it was refused
+    T = ntm_imax(T, (d.N * d.Md + MAXM - 1) / MAXM);
     T = ((T + 63) / 64) * 64;
     NTK_REQUIRE(T <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= MAXM * T, NTK_ERR_UNSUPPORTED,
                 "%s: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d (max %d per thread of %d) / hidden=%d (3*hidden <= 1024) exceed "
@@ -767,7 +813,7 @@ static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, con
     if (fix) p.lds_bytes += (size_t)NTMB_RES_WA * (T / (ldhT / 4)) * (ldhT / 4) * sizeof(f32x4);     // resident rows of Wa^T
     // benchmark shape: the form whose h columns of Wr^T stream beside the step (NTK_NTM_BWD_FORM=res: round 2's kernel, for comparison)
     const char* form_env = getenv("NTK_NTM_BWD_FORM");               // read per call (development switch)
-    const bool ws = fix && !(form_env && form_env[0] == 'r');
+    const bool ws = fix && d.similarity == NTM_SIM_AS_CODED && !(form_env && form_env[0] == 'r');     // (no wave-specialised smooth-cosine form)
     if (ws) p.lds_bytes += (size_t)2 * d.hid * sizeof(float);
     NTK_REQUIRE(p.lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "%s: needs %zu B of LDS (> 160 KiB)", who, p.lds_bytes);
     p.kernel = ws ? NTK_NTM_BWD_WS : fix ? NTK_NTM_BWD_FIX : T <= 768 ? NTK_NTM_BWD_GENERIC768 : NTK_NTM_BWD_GENERIC1024;
@@ -776,10 +822,12 @@ static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, con
     return NTK_OK;
 }
 
-extern "C" int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
-                                int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+extern "C" int ntk_ntm_seq_plan_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                                    int similarity,
+                                    int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_plan");
     NtmDims d;
-    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     if (ldkT <= 0) ldkT = ntm_align4(d.K);
     if (ldhT <= 0) ldhT = ntm_align4(hid);
     NtmBwdPlan pb;
@@ -794,8 +842,14 @@ extern "C" int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, in
     return (fwd ? NTK_NTM_PLAN_FWD : 0) | (bwd ? NTK_NTM_PLAN_BWD : 0);
 }
 
-extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
-                               int write_first,
+extern "C" int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                                int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    return ntk_ntm_seq_plan_sim(B, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED, ldkT, ldhT, fwd_kernel, fwd_threads,
+                                bwd_kernel, bwd_threads);
+}
+
+extern "C" int ntk_ntm_seq_bwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                               int write_first, int similarity,
                                const float* WrT, int ldkT, const float* WaT, int ldhT,
                                const float* M0, const float* w0, const float* cs0,
                                const float* st_gates, const float* st_c, const float* st_u,
@@ -804,8 +858,9 @@ extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int h
                                const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
                                float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                void* stream) {
+    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_bwd");
     NtmBwdArgs a;
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     NtmBwdPlan p;
     int rc = ntm_bwd_plan(a.d, ldkT, ldhT, p, "ntk_ntm_seq_bwd");
     if (rc != NTK_OK) return rc;
@@ -821,15 +876,40 @@ extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int h
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)ntm_seq_bwd_kernel<768, false>, (const void*)ntm_seq_bwd_kernel<1024, false>, (const void*)ntm_seq_bwd_kernel<768, true>,
-                                  (const void*)ntm_seq_bwd_kernel<768, true, true>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_ntm_seq_bwd");
+                                  (const void*)ntm_seq_bwd_kernel<768, true, true>,
+                                  (const void*)ntm_seq_bwd_kernel<768, false, false, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_bwd_kernel<1024, false, false, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_bwd_kernel<768, true, false, NTM_SIM_SMOOTH_COSINE>};
+        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 7, "ntk_ntm_seq_bwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
     const hipStream_t st = (hipStream_t)stream;
+    if (similarity == NTM_SIM_SMOOTH_COSINE) {
+        constexpr int SC = NTM_SIM_SMOOTH_COSINE;
+        if (p.kernel == NTK_NTM_BWD_FIX) ntm_seq_bwd_kernel<768, true, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+        else if (p.kernel == NTK_NTM_BWD_GENERIC768) ntm_seq_bwd_kernel<768, false, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+        else if (p.kernel == NTK_NTM_BWD_GENERIC1024) ntm_seq_bwd_kernel<1024, false, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
+        else NTK_REQUIRE(false, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_bwd: kernel %d has no smooth-cosine form", p.kernel);
+    } else
     if (p.kernel == NTK_NTM_BWD_WS) ntm_seq_bwd_kernel<768, true, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
     else if (p.kernel == NTK_NTM_BWD_FIX) ntm_seq_bwd_kernel<768, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
     else if (p.kernel == NTK_NTM_BWD_GENERIC768) ntm_seq_bwd_kernel<768, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
     else ntm_seq_bwd_kernel<1024, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
     NTK_CHECK_LAUNCH("ntk_ntm_seq_bwd");
     return NTK_OK;
+}
+
+extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                               int write_first,
+                               const float* WrT, int ldkT, const float* WaT, int ldhT,
+                               const float* M0, const float* w0, const float* cs0,
+                               const float* st_gates, const float* st_c, const float* st_u,
+                               const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                               const float* dlogits,
+                               const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
+                               float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
+                               void* stream) {
+    return ntk_ntm_seq_bwd_sim(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED, WrT, ldkT, WaT, ldhT, M0, w0, cs0,
+                               st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM_fin, dw_fin, dread_fin, dcs_fin,
+                               dgates, du, dM0, dw0, dread0, dcs0, stream);
 }

@@ -123,14 +123,15 @@ static inline void ntm_deep_fwd_lds(const NtmDims& d, int NL, int T, NtmLds& L) 
     L.C = o; o += ntm_align4(NL * d.hid);
     L.U = o; o += ntm_align4(d.PP);
     L.Ks = o; o += ntm_align4(d.H * d.Md);
-    L.Cn = o; o += ntm_align4(d.Md);
+    L.Cn = o; o += ntm_align4(ntm_norm_floats(d));
     L.Pw = o; o += ntm_align4(d.H * d.N);
     L.total = o;
 }
 
-template <int MAXT>
+template <int MAXT, int SIM = NTM_SIM_AS_CODED>             // SIM: the similarity of the content addressing, as ntm_seq_fwd.hip
 __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, NtmDeepFwdArgs dp, NtmLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr bool SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
     const int b = blockIdx.x, tid0 = threadIdx.x, T = blockDim.x;
     const int N = a.d.N, Md = a.d.Md, MP = Md | 1, R = a.d.R, Wh = a.d.Wh;
     const int H = R + Wh, hid = a.d.hid, SS = a.d.SS, NL = dp.s.L;
@@ -250,6 +251,15 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
             }
             if (l == NL - 1) {  // waves not running the LSTM normalise the feature columns of M over the slots (ops.py:150)
                 const int w0 = (hid + 63) >> 6;
+                if constexpr (SMOOTH) {     // smooth cosine: the row norms |M[n]|, a lane per slot, no clamp
+                    if (wave >= w0) {
+                        for (int n = (wave - w0) * 64 + lane; n < N; n += (nwaves - w0) * 64) {
+                            float sq = 0.f;
+                            for (int m = 0; m < Md; ++m) { const float v = sM[n * MP + m]; sq += v * v; }
+                            sCn[n] = sqrtf(sq);
+                        }
+                    }
+                } else
                 if (wave >= w0) {
                     for (int m = wave - w0; m < Md; m += nwaves - w0) {
                         float sq = 0.f;
@@ -290,8 +300,13 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
             const int h = wave;
             float kss = 0.f;
             for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; kss += kv * kv; }
-            const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
-            for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
+            const float kn = sqrtf(kss);                           // |k|, smooth cosine only
+            if constexpr (SMOOTH) {
+                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m];
+            } else {
+                const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
+                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
+            }
             const float beta = sU[d.oB + h], g = sU[d.oG + h], gamma = sU[d.oY + h];
             float swv[NTM_MAX_SHIFT_TAPS];
             {
@@ -310,6 +325,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
             for (int n = lane; n < N; n += 64) {
                 float sim = 0.f;
                 for (int m = 0; m < Md; ++m) sim += sKs[h * Md + m] * sM[n * MP + m];
+                if constexpr (SMOOTH) sim = sim / (sCn[n] * kn + 1e-3f);
                 const float v = sim * beta;
                 sWg[h * N + n] = v;
                 mxv = fmaxf(mxv, v);
@@ -438,7 +454,7 @@ struct NtmDeepBwdLds {
 // per-head reduction slots and the record prefetch depth, as ntm_seq_bwd.hip
 constexpr int DNQ = 1 + NTM_MAX_SHIFT_TAPS;
 constexpr int DQR1 = 0, DQR2 = 2, DQR3 = DQR2 + DNQ, DQR4 = DQR3 + 2;
-constexpr int DNQT = DQR4 + 1;
+constexpr int DNQT = DQR4 + 1;    // (smooth cosine: one more, DQR4 + 1 = sum_n b rn)
 constexpr int DMAXM = 8;
 
 static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int ldhT, NtmDeepBwdLds& L) {
@@ -460,16 +476,18 @@ static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int
     L.dZ = take(s.RM + s.L * d.hid); L.dC = take(s.L * d.hid);
     L.Gt = take(4 * d.hid); L.Ct = take(d.hid); L.Cp = take(d.hid);
     L.Khat = take(d.H * d.Md); L.Ks = take(d.H * d.Md); L.Kinv = take(d.H); L.Kss = take(d.H);
-    L.Cinv = take(d.Md); L.Css = take(d.Md); L.C2 = take(d.Md); L.Dkhat = take(d.H * d.Md);
+    L.Cinv = take(ntm_norm_floats(d)); L.Css = take(d.Md); L.C2 = take(ntm_norm_floats(d)); L.Dkhat = take(d.H * d.Md);
     L.Sw = take(d.H * d.SS);
-    L.Red = take(d.H * DNQT * (d.N / 64));
+    L.Red = take(d.H * (DNQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
     L.Dmh = take(d.N * (d.Md | 1));
     L.total = o;
 }
 
-template <int MAXT>
+template <int MAXT, int SIM = NTM_SIM_AS_CODED>             // SIM: as ntm_seq_bwd.hip
 __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a, NtmDeepBwdLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr bool SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
+    constexpr int NQS = DNQT + (SMOOTH ? 1 : 0);         // reduction slots per head
     const int b = blockIdx.x, tid0 = threadIdx.x, T = blockDim.x;
     const int N = a.d.N, Md = a.d.Md, MP = Md | 1, R = a.d.R, Wh = a.d.Wh;
     const int H = R + Wh, hid = a.d.hid, SS = a.d.SS, NL = a.s.L;
@@ -498,6 +516,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
     float* sKhat = smem + L.Khat; float* sKs = smem + L.Ks; float* sKinv = smem + L.Kinv; float* sKss = smem + L.Kss;
     float* sCinv = smem + L.Cinv; float* sCss = smem + L.Css; float* sC2 = smem + L.C2; float* sDkhat = smem + L.Dkhat;
     float* sSw = smem + L.Sw;  float* sRed = smem + L.Red;  float* sDmh = smem + L.Dmh;
+    float* sRn = sCinv; float* sRc = sC2;  // smooth cosine: [N] row norms |M_prev[n]| and the row-norm coefficients where the [Md] column terms are
     f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart);
     const f32x4* Wb4 = reinterpret_cast<const f32x4*>(a.Wb);
 
@@ -583,13 +602,13 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
         for (int q = 0; q < DNQ; ++q) {
             if (q < nq) {
                 const float s = wave_sum(hn ? v[q] : 0.f);
-                if (hn && lane == 0) sRed[(hh * DNQT + base + q) * NW + wi] = s;
+                if (hn && lane == 0) sRed[(hh * NQS + base + q) * NW + wi] = s;
             }
         }
     };
     auto red_read = [&](int h, int q) -> float {
         float s = 0.f;
-        for (int w = 0; w < NW; ++w) s += sRed[(h * DNQT + q) * NW + w];
+        for (int w = 0; w < NW; ++w) s += sRed[(h * NQS + q) * NW + w];
         return s;
     };
 
@@ -615,6 +634,13 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
             sG[ai] = dMt;
             sdM[ai] = dMt * E + (wf ? 0.f : dMr);
         }
+        if constexpr (SMOOTH) {
+            if (tid < N) {         // row norms of M_prev, no clamp
+                float s = 0.f;
+                for (int m = 0; m < Md; ++m) { const float v = sMp[tid * MP + m]; s += v * v; }
+                sRn[tid] = sqrtf(s);
+            }
+        } else
         if (tid < nslC * Md) {     // column sum of squares of M_prev (quirk Q1 normaliser)
             const int m = tid % Md, sl = tid / Md;
             const int n0 = sl * nperC, n1 = min(N, n0 + nperC);
@@ -627,7 +653,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
             float ss = 0.f;
             for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; ss += kv * kv; }
             sKss[h] = ss;
-            sKinv[h] = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
+            sKinv[h] = SMOOTH ? sqrtf(ss) : 1.0f / sqrtf(fmaxf(ss, 1e-12f));        // smooth cosine: |k| itself
             float mx = -INFINITY;
             for (int j = 0; j < SS; ++j) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
             float sum = 0.f;
@@ -639,7 +665,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
         // ------------------------------------------------ X2: d(w_t) for every head; R1 sums
         float dwt = 0.f, pw = 0.f, wv = 0.f, wt = 0.f, wc = 0.f, wp = 0.f, gam = 1.f, gate = 0.f;
         float rv[DNQ];
-        if (tid < Md) {
+        if (!SMOOTH && tid < Md) {
             float s = 0.f;
             for (int sl = 0; sl < nslC; ++sl) s += sPart[sl * Md + tid];
             sCss[tid] = s;
@@ -674,11 +700,11 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
 
         // ------------------------------------------------ R2: sharpen backward, shift-weight sums
         float dpw = 0.f, dwv = 0.f;
-        if (tid < H * Md) {        // normalised keys (needed from R4 on)
+        if (tid < H * Md) {        // normalised keys (needed from R4 on); smooth cosine: the keys as they are
             const int h = tid / Md, m = tid - h * Md;
-            const float kh = sU[d.oK + tid] * sKinv[h];
+            const float kh = SMOOTH ? sU[d.oK + tid] : sU[d.oK + tid] * sKinv[h];
             sKhat[tid] = kh;
-            sKs[tid] = kh * sCinv[m];
+            sKs[tid] = SMOOTH ? kh : kh * sCinv[m];
         }
         if (hn) {
             const float den = red_read(hh, DQR1) + 1e-3f;
@@ -727,11 +753,32 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
             dv = wc * (dwc - Bs);
             float sim = 0.f;
             for (int m = 0; m < Md; ++m) sim += sKs[hh * Md + m] * sMp[nn * MP + m];
-            rv[0] = dv * sim;                                       // d beta
-            sDsim[tid] = dv * sU[d.oB + hh];
+            if constexpr (SMOOTH) {
+                // sim = dot / den, den = |M[n]||k| + 1e-3:  d dot = a = dsim / den,  d den = b = -dsim sim / den.  sDsim keeps a
+                // (B7 and the key sums below read it where they read dsim as coded); b |k| goes to the row-norm term of d M_prev
+                // (sDwv is free: its readers passed R3's barrier) and b |M[n]|, summed over the slots, to the norm term of d k
+                const float rn = sRn[nn], kn = sKinv[hh], den = rn * kn + 1e-3f;
+                sim = sim / den;
+                const float da = dv * sU[d.oB + hh] / den, db = -da * sim;
+                rv[0] = dv * sim;                                   // d beta
+                sDsim[tid] = da;
+                sDwv[tid] = db * kn;
+                rv[1] = db * rn;
+            } else {
+                rv[0] = dv * sim;                                   // d beta
+                sDsim[tid] = dv * sU[d.oB + hh];
+            }
         }
-        red_write(rv, 1, DQR4);
+        red_write(rv, SMOOTH ? 2 : 1, DQR4);
         __syncthreads();
+        if constexpr (SMOOTH) {
+            if (tid < N) {         // row-norm term: d M_prev[n][:] += M_prev[n][:] * (sum_h b[h][n] |k_h|) / |M[n]|, 0 at a zero row
+                float s = 0.f;
+                for (int h = 0; h < H; ++h) s += sDwv[h * N + tid];
+                const float rn = sRn[tid];
+                sRc[tid] = (rn > 0.f) ? s / rn : 0.f;
+            }
+        }
         if (hn && nn == 0) {       // per-head scalar controls -> raw gradients
             const int h = hh;
             const float beta = sU[d.oB + h];
@@ -794,6 +841,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
         }
         __syncthreads();
         // column-norm term: s_m = sum_n dMhat[n][m] * M_prev[n][m], one wave_sum per column (waves stride over m)
+        if constexpr (!SMOOTH)
         for (int m = (tid >> 6); m < Md; m += (T >> 6)) {
             float s = 0.f;
             for (int n = lane; n < N; n += 64) s += sDmh[n * MP + m] * sMp[n * MP + m];
@@ -807,7 +855,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
             float s = 0.f;
             for (int sl = 0; sl < nslP; ++sl) s += sPart[sl * nout + tid];
             if (tid < H * Md) {
-                sDkhat[tid] = s * sCinv[tid % Md];
+                sDkhat[tid] = SMOOTH ? s : s * sCinv[tid % Md];
             } else {
                 const int o2 = tid - H * Md;
                 const int which = o2 / (Wh * Md);
@@ -819,17 +867,24 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
         __syncthreads();
         if (tid < H * Md) {
             const int h = tid / Md;
-            float dot = 0.f;
-            for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
-            const float ki = sKinv[h];
-            const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
-            const float kv = sU[d.oK + tid];
-            const float dk = ki * sDkhat[tid] + kv * ck;
-            sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            if constexpr (SMOOTH) {                                 // d k = sum_n a M_prev[n] + k / |k| * sum_n b |M[n]|, 0 through |k| = 0
+                const float kn = sKinv[h], kv = sU[d.oK + tid];
+                const float dk = sDkhat[tid] + ((kn > 0.f) ? kv / kn * red_read(h, DQR4 + 1) : 0.f);
+                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            } else {
+                float dot = 0.f;
+                for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
+                const float ki = sKinv[h];
+                const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
+                const float kv = sU[d.oK + tid];
+                const float dk = ki * sDkhat[tid] + kv * ck;
+                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
+            }
         }
         for (int idx = tid; idx < NMd; idx += T) {
             const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
+            if constexpr (SMOOTH) sdM[ai] += sDmh[ai] + sMp[ai] * sRc[n];
+            else sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
         }
         __syncthreads();
         if (tid < PP) a.du[bt * PP + tid] = sDU[tid];
@@ -973,10 +1028,11 @@ extern "C" int ntk_ntm_seq_deep_supported(int B, int N, int Md, int R, int Wh, i
     return ntm_deep_plan(d, s, p, "ntk_ntm_seq_deep_supported") == NTK_OK ? 1 : 0;
 }
 
-extern "C" int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
-                                     int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+extern "C" int ntk_ntm_seq_deep_plan_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
+                                         int similarity, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_deep_plan");
     NtmDims d;
-    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     NtmDeepShape s;
     ntm_deep_shape(s, 1, R * Md, hid, L);
     NtmDeepPlan p;
@@ -986,6 +1042,12 @@ extern "C" int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hi
     if (bwd_kernel) *bwd_kernel = !ok ? 0 : ntm_deep_kernel_id(p.Tb);
     if (bwd_threads) *bwd_threads = ok ? p.Tb : 0;
     return ok ? (NTK_NTM_PLAN_FWD | NTK_NTM_PLAN_BWD) : 0;
+}
+
+extern "C" int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
+                                     int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
+    return ntk_ntm_seq_deep_plan_sim(B, N, Md, R, Wh, hid, shift_range, O, L, write_first, NTM_SIM_AS_CODED, fwd_kernel, fwd_threads,
+                                     bwd_kernel, bwd_threads);
 }
 
 extern "C" int ntk_ntm_seq_deep_packed_floats(int D, int R, int Md, int hid, int L, size_t* n_wx0, size_t* n_wf, size_t* n_wb) {
@@ -1016,8 +1078,8 @@ extern "C" int ntk_ntm_seq_deep_pack(int D, int R, int Md, int hid, int L, const
     return NTK_OK;
 }
 
-extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
-                                    int write_first, int D,
+extern "C" int ntk_ntm_seq_fwd_deep_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                                    int write_first, int similarity, int D,
                                     const float* X, const float* xproj, const float* Wf, const float* Wa,
                                     const float* M0, const float* w0, const float* read0, const float* cs0,
                                     float* logits, float* outputs,
@@ -1027,8 +1089,9 @@ extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, 
                                     float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
                                     void* stream) {
     const char* who = "ntk_ntm_seq_fwd_deep";
+    NTM_REQUIRE_SIMILARITY(similarity, who);
     NtmFwdArgs a = {};
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     NTK_REQUIRE(D >= 1, NTK_ERR_BAD_SHAPE, "%s: D=%d", who, D);
     NtmDeepFwdArgs dp = {};
     ntm_deep_shape(dp.s, D, R * Md, hid, L);
@@ -1050,18 +1113,24 @@ extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, 
     dp.st_xtop = st_xtop; dp.st_buf0 = st_buf0; dp.st_bufk = (L > 2) ? st_bufk : nullptr; dp.st_lgates = st_lgates; dp.st_lc = st_lc;
     {
         static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_fwd_deep_kernel<768>, (const void*)ntm_seq_fwd_deep_kernel<1024>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, who);
+        const void* const ks[] = {(const void*)ntm_seq_fwd_deep_kernel<768>, (const void*)ntm_seq_fwd_deep_kernel<1024>,
+                                  (const void*)ntm_seq_fwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_fwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE>};
+        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, who);
         if (rc_lds != NTK_OK) return rc_lds;
     }
+    if (similarity == NTM_SIM_SMOOTH_COSINE) {
+        if (ntm_deep_kernel_id(p.Tf) == NTK_NTM_DEEP_768) ntm_seq_fwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
+        else ntm_seq_fwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
+    } else
     if (ntm_deep_kernel_id(p.Tf) == NTK_NTM_DEEP_768) ntm_seq_fwd_deep_kernel<768><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
     else ntm_seq_fwd_deep_kernel<1024><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
     NTK_CHECK_LAUNCH(who);
     return NTK_OK;
 }
 
-extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
-                                    int write_first,
+extern "C" int ntk_ntm_seq_bwd_deep_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                                    int write_first, int similarity,
                                     const float* Wb, const float* WaT, int ldhT,
                                     const float* M0, const float* w0, const float* cs0,
                                     const float* st_gates, const float* st_c, const float* st_u,
@@ -1072,8 +1141,9 @@ extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, 
                                     float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                     void* stream) {
     const char* who = "ntk_ntm_seq_bwd_deep";
+    NTM_REQUIRE_SIMILARITY(similarity, who);
     NtmDeepBwdArgs a = {};
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     ntm_deep_shape(a.s, 1, R * Md, hid, L);
     NtmDeepPlan p;
     int rc = ntm_deep_plan(a.d, a.s, p, who);
@@ -1094,12 +1164,49 @@ extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, 
     a.dgates = dgates; a.dpre = dpre; a.du = du; a.dM0 = dM0; a.dw0 = dw0; a.dread0 = dread0; a.dcs0 = dcs0;
     {
         static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_bwd_deep_kernel<768>, (const void*)ntm_seq_bwd_deep_kernel<1024>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, who);
+        const void* const ks[] = {(const void*)ntm_seq_bwd_deep_kernel<768>, (const void*)ntm_seq_bwd_deep_kernel<1024>,
+                                  (const void*)ntm_seq_bwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_bwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE>};
+        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, who);
         if (rc_lds != NTK_OK) return rc_lds;
     }
+    if (similarity == NTM_SIM_SMOOTH_COSINE) {
+        if (ntm_deep_kernel_id(p.Tb) == NTK_NTM_DEEP_768) ntm_seq_bwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
+        else ntm_seq_bwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
+    } else
     if (ntm_deep_kernel_id(p.Tb) == NTK_NTM_DEEP_768) ntm_seq_bwd_deep_kernel<768><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
     else ntm_seq_bwd_deep_kernel<1024><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
     NTK_CHECK_LAUNCH(who);
     return NTK_OK;
+}
+
+extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                                    int write_first, int D,
+                                    const float* X, const float* xproj, const float* Wf, const float* Wa,
+                                    const float* M0, const float* w0, const float* read0, const float* cs0,
+                                    float* logits, float* outputs,
+                                    float* M_out, float* w_out, float* read_out, float* cs_out,
+                                    float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                                    float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                                    float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
+                                    void* stream) {
+    return ntk_ntm_seq_fwd_deep_sim(B, S, N, Md, R, Wh, hid, shift_range, O, L, write_first, NTM_SIM_AS_CODED, D, X, xproj, Wf, Wa,
+                                    M0, w0, read0, cs0, logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h,
+                                    st_u, st_wc, st_wv, st_w, st_M, st_read, st_xtop, st_buf0, st_bufk, st_lgates, st_lc, stream);
+}
+
+extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                                    int write_first,
+                                    const float* Wb, const float* WaT, int ldhT,
+                                    const float* M0, const float* w0, const float* cs0,
+                                    const float* st_gates, const float* st_c, const float* st_u,
+                                    const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                                    const float* st_lgates, const float* st_lc,
+                                    const float* dlogits,
+                                    const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
+                                    float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
+                                    void* stream) {
+    return ntk_ntm_seq_bwd_deep_sim(B, S, N, Md, R, Wh, hid, shift_range, O, L, write_first, NTM_SIM_AS_CODED, Wb, WaT, ldhT, M0, w0, cs0,
+                                    st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, st_lgates, st_lc, dlogits, dM_fin, dw_fin,
+                                    dread_fin, dcs_fin, dgates, dpre, du, dM0, dw0, dread0, dcs0, stream);
 }

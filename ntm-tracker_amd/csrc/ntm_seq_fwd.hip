@@ -9,10 +9,12 @@
 //   P1 gate partials      z=[read_prev;h_prev] (K) x Wr[K][4*hid]   (K-sliced over thread groups)
 //   P2 LSTM cell          BasicLSTMCell, gate order i,j,f,o, forget_bias 0 (ntm_cell.py:45-50)
 //                         || the other waves l2-normalise the feature columns of M over the slots (quirk Q1)
+//                         (SIM = smooth cosine: they take the N row norms |M[n]| instead)
 //   P3 unpack partials    h' x Wa[hid][PP]                           (ntm_cell.py:124-126, :220)
 //   P4 control activations tanh/softplus/sigmoid/1+softplus           (:133,140,151,169,193,195)
 //   P5-P7 ONE WAVE PER HEAD, no workgroup barrier: key scaling, shift softmax (ops.py:150-152, ntm_cell.py:161),
-//      similarity (Q1: feature columns normalised over slots), beta, softmax over N, gate (:136-156),
+//      similarity (Q1: feature columns normalised over slots; SIM = smooth cosine: k.M[n] / (|k||M[n]| + 1e-3), the
+//      content addressing of the reference's ops_test.py), beta, softmax over N, gate (:136-156),
 //      circular shift with taps -(r+1)..r-1 (Q2), sharpen with +1e-3 (Q4)   (ops.py:204-213, ntm_cell.py:173-176)
 //   P8 erase/add write and read (reads see the pre-write memory unless write_first, Q6) (:202-215)
 #include "ntm_common.h"
@@ -50,10 +52,13 @@ extern "C" int ntk_ntm_fwd_prof(unsigned long long* out16) {
 // deep the prefetch (16 or 24 rows per thread in flight: the same) and however lean the loop (a guard-free form with
 // scalar row bases: the same) -- only fewer bytes help: 912 -> 614 KB per step, forward 21.6 -> 20.3 ms at B32 x S1300.
 // LDS rows alone at 640 threads gave nothing (the other phases lose at 512 threads what 14 % fewer bytes win).
-template <int MAXT, int FIXT, int NTM_RES_REG = 0, int NTM_RES_LDS = 0>
+// SIM (NTM_SIM_*) is the similarity of the content addressing, a compile-time mode: the as-coded instantiations are the
+// kernels they were, the smooth-cosine ones differ in P2's normaliser (N row norms where the Md column norms were) and in the
+// head waves' key and similarity.
+template <int MAXT, int FIXT, int NTM_RES_REG = 0, int NTM_RES_LDS = 0, int SIM = NTM_SIM_AS_CODED>
 __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr bool FIX = FIXT != 0, RES = NTM_RES_REG + NTM_RES_LDS > 0;
+    constexpr bool FIX = FIXT != 0, RES = NTM_RES_REG + NTM_RES_LDS > 0, SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
     const int b = blockIdx.x, tid = threadIdx.x, T = FIX ? FIXT : blockDim.x;
     const int N = FIX ? 128 : a.d.N, Md = FIX ? 20 : a.d.Md, MP = Md | 1, R = FIX ? 4 : a.d.R, Wh = FIX ? 1 : a.d.Wh;
     const int H = R + Wh, hid = FIX ? 200 : a.d.hid, SS = FIX ? 3 : a.d.SS;
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
     float* sC = smem + L.C;
     float* sU = smem + L.U;
     float* sKs = smem + L.Ks;
-    float* sCn = smem + L.Cn;
+    float* sCn = smem + L.Cn;              // [Md] inverse column norms of M (as coded) / [N] row norms of M (smooth cosine)
     float* sPw = smem + L.Pw;              // [H][N] sharpened weights before normalisation
 
     // work decomposition (uniform per kernel)
@@ -204,6 +209,16 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
         }
         {   // waves not running the LSTM normalise the feature columns over the slot axis (tf.nn.l2_normalize, ops.py:150)
             const int w0 = (hid + 63) >> 6;
+            if constexpr (SMOOTH) {
+                // smooth cosine: the row norms |M[n]|, a lane per slot (rows are MP = Md | 1 floats apart: no bank conflict), no clamp
+                if (wave >= w0) {
+                    for (int n = (wave - w0) * 64 + lane; n < N; n += (nwaves - w0) * 64) {
+                        float s = 0.f;
+                        for (int m = 0; m < Md; ++m) { const float v = sM[n * MP + m]; s += v * v; }
+                        sCn[n] = sqrtf(s);
+                    }
+                }
+            } else
             if (wave >= w0) {
                 for (int m = wave - w0; m < Md; m += nwaves - w0) {
                     float s = 0.f;
@@ -248,9 +263,14 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
             const int h = wave;
             float kss = 0.f;
             for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; kss += kv * kv; }
-            const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
-            if (lane < Md) sKs[h * Md + lane] = sU[d.oK + h * Md + lane] * kinv * sCn[lane];
-            for (int m = lane + 64; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
+            const float kn = sqrtf(kss);                           // |k|, smooth cosine only
+            if constexpr (SMOOTH) {
+                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m];
+            } else {
+                const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
+                if (lane < Md) sKs[h * Md + lane] = sU[d.oK + h * Md + lane] * kinv * sCn[lane];
+                for (int m = lane + 64; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
+            }
             const float beta = sU[d.oB + h], g = sU[d.oG + h], gamma = sU[d.oY + h];
             constexpr int MAXSS = FIX ? 3 : NTM_MAX_SHIFT_TAPS;     // (a compile-time 3 taps at the benchmark shape)
             float swv[MAXSS];                                      // softmax of the shift logits (ntm_cell.py:161)
@@ -270,6 +290,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
             for (int n = lane; n < N; n += 64) {
                 float sim = 0.f;
                 for (int m = 0; m < Md; ++m) sim += sKs[h * Md + m] * sM[n * MP + m];
+                if constexpr (SMOOTH) sim = sim / (sCn[n] * kn + 1e-3f);
                 const float v = sim * beta;
                 sWg[h * N + n] = v;
                 mxv = fmaxf(mxv, v);
@@ -416,7 +437,7 @@ int ntm_fwd_plan(const NtmDims& d, NtmFwdPlan& p, const char* who) {
     // NTK_NTM_FWD_FORM=res selects round 2's resident-rows kernel below, for comparison)
     const char* form_env = getenv("NTK_NTM_FWD_FORM");               // read per call (development switch)
     const bool ws_off = form_env && form_env[0] == 'r';
-    if (!ws_off && ntm_seq_fwd_ws_takes(d)) {
+    if (!ws_off && d.similarity == NTM_SIM_AS_CODED && ntm_seq_fwd_ws_takes(d)) {      // (no wave-specialised smooth-cosine form)
         p.kernel = NTK_NTM_FWD_WS;
         p.T = ntm_seq_fwd_ws_plan(d, p.L, p.lds_bytes);
     } else {
@@ -450,8 +471,8 @@ extern "C" int ntk_ntm_padded_dims(int N, int Md, int R, int Wh, int hid, int sh
     return NTK_OK;
 }
 
-extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
-                               int write_first,
+extern "C" int ntk_ntm_seq_fwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                               int write_first, int similarity,
                                const float* xproj, const float* Wr, const float* Wa,
                                const float* M0, const float* w0, const float* read0, const float* cs0,
                                float* logits, float* outputs,
@@ -459,8 +480,9 @@ extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int h
                                float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
                                void* stream) {
+    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_fwd");
     NtmFwdArgs a;
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first);
+    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     NtmFwdPlan p;
     int rc = ntm_fwd_plan(a.d, p, "ntk_ntm_seq_fwd");
     if (rc != NTK_OK) return rc;
@@ -478,15 +500,39 @@ extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int h
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)ntm_seq_fwd_kernel<768, 0>, (const void*)ntm_seq_fwd_kernel<1024, 0>, (const void*)ntm_seq_fwd_kernel<768, 640>,
-                                  (const void*)ntm_seq_fwd_kernel<512, 512, 24, 20>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_ntm_seq_fwd");
+                                  (const void*)ntm_seq_fwd_kernel<512, 512, 24, 20>,
+                                  (const void*)ntm_seq_fwd_kernel<768, 0, 0, 0, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_fwd_kernel<1024, 0, 0, 0, NTM_SIM_SMOOTH_COSINE>,
+                                  (const void*)ntm_seq_fwd_kernel<512, 512, 24, 20, NTM_SIM_SMOOTH_COSINE>};
+        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 7, "ntk_ntm_seq_fwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
     const hipStream_t st = (hipStream_t)stream;
+    if (similarity == NTM_SIM_SMOOTH_COSINE) {
+        constexpr int SC = NTM_SIM_SMOOTH_COSINE;
+        if (p.kernel == NTK_NTM_FWD_FIX512) ntm_seq_fwd_kernel<512, 512, 24, 20, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+        else if (p.kernel == NTK_NTM_FWD_GENERIC768) ntm_seq_fwd_kernel<768, 0, 0, 0, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+        else if (p.kernel == NTK_NTM_FWD_GENERIC1024) ntm_seq_fwd_kernel<1024, 0, 0, 0, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
+        else NTK_REQUIRE(false, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_fwd: kernel %d has no smooth-cosine form", p.kernel);
+    } else
     if (p.kernel == NTK_NTM_FWD_FIX512) ntm_seq_fwd_kernel<512, 512, 24, 20><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
     else if (p.kernel == NTK_NTM_FWD_FIX640_DEV) ntm_seq_fwd_kernel<768, 640><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
     else if (p.kernel == NTK_NTM_FWD_GENERIC768) ntm_seq_fwd_kernel<768, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
     else ntm_seq_fwd_kernel<1024, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
     NTK_CHECK_LAUNCH("ntk_ntm_seq_fwd");
     return NTK_OK;
+}
+
+extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
+                               int write_first,
+                               const float* xproj, const float* Wr, const float* Wa,
+                               const float* M0, const float* w0, const float* read0, const float* cs0,
+                               float* logits, float* outputs,
+                               float* M_out, float* w_out, float* read_out, float* cs_out,
+                               float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                               float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                               void* stream) {
+    return ntk_ntm_seq_fwd_sim(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED, xproj, Wr, Wa, M0, w0, read0, cs0,
+                               logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w,
+                               st_M, st_read, stream);
 }

@@ -7,15 +7,42 @@
 // ---------------------------------------------------------------------------------------------------------
 // one NTM cell step = the persistent kernel with S = 1 (ntm_cell.py:53-253)
 // ---------------------------------------------------------------------------------------------------------
+extern "C" int ntk_ntm_step_fwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                                int similarity,
+                                const float* xproj, const float* Wr, const float* Wa,
+                                const float* M_prev, const float* w_prev, const float* read_prev, const float* cs_prev,
+                                float* logits, float* outputs, float* M, float* w, float* read, float* cs,
+                                float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                                float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read, void* stream) {
+    return ntk_ntm_seq_fwd_sim(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity, xproj, Wr, Wa, M_prev, w_prev, read_prev,
+                               cs_prev, logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M,
+                               st_read, stream);
+}
+
 extern "C" int ntk_ntm_step_fwd(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
                                 const float* xproj, const float* Wr, const float* Wa,
                                 const float* M_prev, const float* w_prev, const float* read_prev, const float* cs_prev,
                                 float* logits, float* outputs, float* M, float* w, float* read, float* cs,
                                 float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                 float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read, void* stream) {
-    return ntk_ntm_seq_fwd(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, xproj, Wr, Wa, M_prev, w_prev, read_prev, cs_prev,
-                           logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M, st_read,
-                           stream);
+    return ntk_ntm_step_fwd_sim(B, N, Md, R, Wh, hid, shift_range, O, write_first, 0, xproj, Wr, Wa, M_prev, w_prev, read_prev, cs_prev,
+                                logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M, st_read,
+                                stream);
+}
+
+extern "C" int ntk_ntm_step_bwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
+                                int similarity,
+                                const float* WrT, int ldkT, const float* WaT, int ldhT,
+                                const float* M_prev, const float* w_prev, const float* cs_prev,
+                                const float* st_gates, const float* st_c, const float* st_u,
+                                const float* st_wc, const float* st_wv, const float* st_w, const float* st_M,
+                                const float* dlogits,
+                                const float* dM, const float* dw, const float* dread, const float* dcs,
+                                float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
+                                void* stream) {
+    return ntk_ntm_seq_bwd_sim(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity, WrT, ldkT, WaT, ldhT, M_prev, w_prev,
+                               cs_prev, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
+                               dM_prev, dw_prev, dread_prev, dcs_prev, stream);
 }
 
 extern "C" int ntk_ntm_step_bwd(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
@@ -27,9 +54,9 @@ extern "C" int ntk_ntm_step_bwd(int B, int N, int Md, int R, int Wh, int hid, in
                                 const float* dM, const float* dw, const float* dread, const float* dcs,
                                 float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
                                 void* stream) {
-    return ntk_ntm_seq_bwd(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, WrT, ldkT, WaT, ldhT, M_prev, w_prev, cs_prev,
-                           st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
-                           dM_prev, dw_prev, dread_prev, dcs_prev, stream);
+    return ntk_ntm_step_bwd_sim(B, N, Md, R, Wh, hid, shift_range, O, write_first, 0, WrT, ldkT, WaT, ldhT, M_prev, w_prev, cs_prev,
+                                st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
+                                dM_prev, dw_prev, dread_prev, dcs_prev, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

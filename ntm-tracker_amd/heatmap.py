@@ -50,13 +50,13 @@ class NTMHeatmapTracker(_Checkpointing):
 
     def __init__(self, batch_size, sequence_length, num_features, feature_channels, mem_size=128, mem_dim=20, hidden_size=200,
                  read_head_size=4, write_head_size=1, init_scale=0.05, learning_rate=1e-4, decay=0.95, momentum=0.9,
-                 max_gradient_norm=5.0, device="cuda", seed=42):
+                 max_gradient_norm=5.0, device="cuda", seed=42, similarity="as_coded"):
         self.B, self.T, self.F, self.C = int(batch_size), int(sequence_length), int(num_features), int(feature_channels)
         self.S = sequential_steps(self.T, self.F)
         self.device = torch.device(device)
         self.cell = NTMCell(1, mem_size=mem_size, mem_dim=mem_dim, controller_hidden_size=hidden_size, controller_num_layers=1,
                             write_head_size=write_head_size, read_head_size=read_head_size, input_dim=self.C + 3,
-                            device=self.device, init_scale=init_scale, seed=seed)
+                            device=self.device, init_scale=init_scale, seed=seed, similarity=similarity)
         self.opt = RMSPropClip(self.cell.params, learning_rate, decay, momentum, 1e-10, max_gradient_norm)
 
     def _ckpt_params(self):

@@ -172,8 +172,23 @@ def gemm_tn(A, B, out, accumulate=False, splits=None, workspace=None):
     return out
 
 
+#: similarity modes of the content addressing -> the `similarity` argument of the C ABI's *_sim entry points
+SIMILARITY_MODES = {"as_coded": 0, "smooth_cosine": 1}
+
+
+def similarity_mode(similarity):
+    """The C ABI's mode value of a ``similarity=`` keyword; any other value raises."""
+    if similarity not in SIMILARITY_MODES:
+        raise _lib.NtkError("similarity=%r: expected one of %s" % (similarity, ", ".join(sorted(SIMILARITY_MODES))))
+    return SIMILARITY_MODES[similarity]
+
+
 class NTMCell(object):
     """The NTM recurrent cell (ntm_cell.py:17-315) on the HIP path.
+
+    ``similarity``: "as_coded" (default) is the reference's content addressing as its code computes it (quirk Q1: every
+    feature column of the memory l2-normalised over the slots); "smooth_cosine" is the row-wise k.M[n] / (|k||M[n]| + 1e-3)
+    the NTM was designed with and the reference's ops_test.py expects.  Both run forward and BPTT in the fused kernels.
 
     ``controller_num_layers == 1`` (what every reference script runs, direct_offset_output.py:24) is the fused
     persistent kernel with forward, BPTT and training.  A deeper MultiRNNCell controller (the constructor's default
@@ -189,9 +204,11 @@ class NTMCell(object):
     def __init__(self, output_dim, mem_size=128, mem_dim=20, shift_range=1,
                  controller_hidden_size=100, controller_num_layers=10,
                  write_head_size=3, read_head_size=3, write_first=False,
-                 input_dim=None, device="cuda", init_scale=0.1, seed=None):
+                 input_dim=None, device="cuda", init_scale=0.1, seed=None, similarity="as_coded"):
         if controller_num_layers != 1:
             raise _lib.NtkError("controller_num_layers=%d reached the single-layer cell" % controller_num_layers)
+        self._sim = similarity_mode(similarity)
+        self.similarity = similarity
         self.mem_size = mem_size
         self.mem_dim = mem_dim
         self.controller_hidden_size = controller_hidden_size
@@ -280,8 +297,8 @@ class NTMCell(object):
         if d is None:
             raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
         v = [ctypes.c_int() for _ in range(4)]
-        mask = _lib.lib().ntk_ntm_seq_plan(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
-                                           (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4, *[ctypes.byref(x) for x in v])
+        mask = _lib.lib().ntk_ntm_seq_plan_sim(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
+                                               self._sim, (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4, *[ctypes.byref(x) for x in v])
         msg = _lib.lib().ntk_last_error() if mask != 3 else b""
         return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.FWD_KERNELS[v[0].value],
                 "fwd_threads": v[1].value, "bwd_kernel": self.BWD_KERNELS[v[2].value], "bwd_threads": v[3].value,
@@ -328,10 +345,10 @@ class NTMCell(object):
             keep.append(t.contiguous())
             return _P(keep[-1])
         # a single step binds the step entry point of the C ABI (same kernel, S = 1)
-        fn, name, lead = ((_lib.lib().ntk_ntm_step_fwd, "ntk_ntm_step_fwd", (B,)) if S == 1 else
-                          (_lib.lib().ntk_ntm_seq_fwd, "ntk_ntm_seq_fwd", (B, S)))
+        fn, name, lead = ((_lib.lib().ntk_ntm_step_fwd_sim, "ntk_ntm_step_fwd", (B,)) if S == 1 else
+                          (_lib.lib().ntk_ntm_seq_fwd_sim, "ntk_ntm_seq_fwd", (B, S)))
         _lib.check(fn(
-            *lead, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
+            *lead, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
             _P(xproj), _P(self.params.view("Wr")), _P(self.params.view("Wa")),
             cp(state["M"]), cp(state["w"]), cp(state["read"]), cp(state["controller_state"]),
             _P(logits), _np(outputs), _P(new["M"]), _P(new["w"]), _P(new["read"]), _P(new["controller_state"]),
@@ -352,8 +369,8 @@ class NTMCell(object):
         P = self.params
         ldkT, ldhT = (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4
         # a shape that runs forward only (see include/ntmtrack.h) is refused here, before anything is launched
-        if not L.ntk_ntm_seq_plan(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, ldkT, ldhT,
-                                  None, None, None, None) & 2:
+        if not L.ntk_ntm_seq_plan_sim(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
+                                      ldkT, ldhT, None, None, None, None) & 2:
             _lib.check(-3, "ntk_ntm_seq_bwd")
         WrT = torch.empty((4 * d.hid, ldkT), device=dev)
         WaT = torch.empty((d.PP, ldhT), device=dev)
@@ -369,8 +386,8 @@ class NTMCell(object):
         def cp(t):
             keep.append(t.contiguous())
             return _P(keep[-1])
-        _lib.check(L.ntk_ntm_seq_bwd(
-            B, S, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
+        _lib.check(L.ntk_ntm_seq_bwd_sim(
+            B, S, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
             _P(WrT), ldkT, _P(WaT), ldhT,
             cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
             _P(rec["gates"]), _P(rec["c"]), _P(rec["u"]), _P(rec["wc"]), _P(rec["wv"]), _P(rec["w"]), _P(rec["M"]),
@@ -420,10 +437,11 @@ class NTMCell(object):
         w = rec["w"][:, 0]
         k = u[:, d.oK:d.oB].reshape(B, H, Md)
         # the six tensors the fused step keeps in registers, from HIP kernels on what the step recorded: the similarity is
-        # ops.batched_smooth_cosine_similarity as coded (ntm_cell.py:136, quirk Q1), the other four one elementwise kernel
+        # ops.batched_smooth_cosine_similarity in the cell's mode (as coded: ntm_cell.py:136, quirk Q1), the other four one
+        # elementwise kernel
         from . import ops as _ops
         Mp, wp = M_prev.contiguous().float(), w_prev.contiguous().float()
-        similarity = _ops.batched_smooth_cosine_similarity(Mp, k.contiguous(), device=self.device)
+        similarity = _ops.batched_smooth_cosine_similarity(Mp, k.contiguous(), device=self.device, similarity=self.similarity)
         wc, wv, wcur = rec["wc"][:, 0].contiguous(), rec["wv"][:, 0].contiguous(), w.contiguous()
         uc = u.contiguous()
         w_gated, powed = torch.empty_like(wcur), torch.empty_like(wcur)
@@ -496,14 +514,17 @@ class StackedNTMCell(NTMCell):
 
     def __init__(self, output_dim, mem_size=128, mem_dim=20, shift_range=1, controller_hidden_size=100,
                  controller_num_layers=10, write_head_size=3, read_head_size=3, write_first=False,
-                 input_dim=None, device="cuda", init_scale=0.1, seed=None):
+                 input_dim=None, device="cuda", init_scale=0.1, seed=None, similarity="as_coded"):
+        self._sim = similarity_mode(similarity)
+        self.similarity = similarity
         self.L = int(controller_num_layers)
         self.output_dim, self.mem_size, self.mem_dim, self.shift_range = output_dim, mem_size, mem_dim, shift_range
         self.controller_hidden_size, self.controller_num_layers = controller_hidden_size, self.L
         self.write_head_size, self.read_head_size, self.write_first = write_head_size, read_head_size, bool(write_first)
         self.device, self.init_scale, self.seed = torch.device(device), init_scale, seed
         self.top = NTMCell(output_dim, mem_size, mem_dim, shift_range, controller_hidden_size, 1, write_head_size,
-                           read_head_size, write_first, input_dim=None, device=device, init_scale=init_scale, seed=seed)
+                           read_head_size, write_first, input_dim=None, device=device, init_scale=init_scale, seed=seed,
+                           similarity=similarity)      # the step-wise form's addressing runs in the top cell: same mode
         self.D = None
         self.params = None
         self.lower = []
@@ -648,8 +669,8 @@ class StackedNTMCell(NTMCell):
             return False
         d = self.dims
         # the plan, not ntk_ntm_seq_deep_supported: that one answers for write_first = 0, and a write_first cell needs more LDS
-        return _lib.lib().ntk_ntm_seq_deep_plan(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
-                                                1 if self.write_first else 0, None, None, None, None) == 3
+        return _lib.lib().ntk_ntm_seq_deep_plan_sim(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
+                                                    1 if self.write_first else 0, self._sim, None, None, None, None) == 3
 
     DEEP_KERNELS = {0: None, 1: "deep-768", 2: "deep-1024"}
 
@@ -659,8 +680,8 @@ class StackedNTMCell(NTMCell):
         if d is None:
             raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
         v = [ctypes.c_int() for _ in range(4)]
-        mask = _lib.lib().ntk_ntm_seq_deep_plan(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
-                                                1 if self.write_first else 0, *[ctypes.byref(x) for x in v])
+        mask = _lib.lib().ntk_ntm_seq_deep_plan_sim(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
+                                                    1 if self.write_first else 0, self._sim, *[ctypes.byref(x) for x in v])
         msg = _lib.lib().ntk_last_error() if mask != 3 else b""
         return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.DEEP_KERNELS[v[0].value],
                 "fwd_threads": v[1].value, "bwd_kernel": self.DEEP_KERNELS[v[2].value], "bwd_threads": v[3].value,
@@ -716,8 +737,8 @@ class StackedNTMCell(NTMCell):
         def cp(t):
             keep.append(t.contiguous())
             return _P(keep[-1])
-        _lib.check(_lib.lib().ntk_ntm_seq_fwd_deep(
-            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self.D,
+        _lib.check(_lib.lib().ntk_ntm_seq_fwd_deep_sim(
+            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self._sim, self.D,
             _P(X), _P(xproj), _P(Wf), _P(self.top.params.view("Wa")),
             cp(state["M"]), cp(state["w"]), cp(state["read"]), cp(state["controller_state"]),
             _P(logits), _np(outputs), _P(new["M"]), _P(new["w"]), _P(new["read"]), _P(new["controller_state"]),
@@ -788,8 +809,8 @@ class StackedNTMCell(NTMCell):
             dgates, du = torch.empty((B, 4 * hid), device=dev), torch.empty((B, d.PP), device=dev)
             g0 = self.top.state_placeholder(B)
             dlt = dl[:, t].contiguous()
-            _lib.check(lib.ntk_ntm_step_bwd(
-                B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
+            _lib.check(lib.ntk_ntm_step_bwd_sim(
+                B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
                 _P(WrT), ldkT, _P(WaT), ldhT, _P(ts["M"].contiguous()), _P(ts["w"].contiguous()), _P(ts["controller_state"]),
                 _P(r["gates"]), _P(r["c"]), _P(r["u"]), _P(r["wc"]), _P(r["wv"]), _P(r["w"]), _P(r["M"]), _P(dlt),
                 _P(dM), _P(dw), _P(dread), _P(dcs_top),
@@ -845,8 +866,8 @@ class StackedNTMCell(NTMCell):
         def cp(t):
             keep.append(t.contiguous())
             return _P(keep[-1])
-        _lib.check(lib.ntk_ntm_seq_bwd_deep(
-            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0,
+        _lib.check(lib.ntk_ntm_seq_bwd_deep_sim(
+            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self._sim,
             _P(rec["Wb"]), _P(WaT), ldhT, cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
             _P(rec["gates"]), _P(rec["c"]), _P(rec["u"]), _P(rec["wc"]), _P(rec["wv"]), _P(rec["w"]), _P(rec["M"]),
             _P(rec["lgates"]), _P(rec["lc"]), cp(dlogits),

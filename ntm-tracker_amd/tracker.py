@@ -118,14 +118,22 @@ class _Checkpointing(object):
         P = self._ckpt_params()
         torch.save({"format": "ntmtrack-ckpt-1", "kind": type(self).__name__, "numel": P.numel,
                     "params": P.flat.detach().cpu(), "ms": self.opt.ms.detach().cpu(), "mom": self.opt.mom.detach().cpu(),
-                    "global_step": int(self.opt.global_step)}, path)
+                    "global_step": int(self.opt.global_step), "similarity": self._ckpt_similarity()}, path)
         return path
+
+    def _ckpt_similarity(self):
+        """The similarity mode of the tracker's NTM cell; "as_coded" for a core without the choice."""
+        return getattr(getattr(self, "cell", None), "similarity", "as_coded")
 
     def load_checkpoint(self, path):
         ck = torch.load(path, map_location="cpu", weights_only=True)
         P = self._ckpt_params()
         if ck.get("format") != "ntmtrack-ckpt-1" or ck.get("kind") != type(self).__name__ or ck.get("numel") != P.numel:
             raise _lib.NtkError("checkpoint %s does not match this tracker (%s, %d parameters)" % (path, type(self).__name__, P.numel))
+        # the two similarity modes are different models with the same parameter layout; a checkpoint from before the mode existed is as coded
+        if ck.get("similarity", "as_coded") != self._ckpt_similarity():
+            raise _lib.NtkError("checkpoint %s was trained with similarity=%r, this tracker runs %r"
+                                % (path, ck.get("similarity", "as_coded"), self._ckpt_similarity()))
         P.flat.copy_(ck["params"].to(P.flat.device))
         self.opt.ms.copy_(ck["ms"].to(P.flat.device))
         self.opt.mom.copy_(ck["mom"].to(P.flat.device))
@@ -255,7 +263,8 @@ class NTMOffsetTracker(_TwoStreamPipeline, _Checkpointing):
     def __init__(self, batch_size, sequence_length, vgg_weights=None, mem_size=128, mem_dim=20, hidden_size=200,
                  num_layers=1, read_head_size=4, write_head_size=1, write_first=False, init_scale=0.05,
                  learning_rate=1e-4, decay=0.95, momentum=0.9, max_gradient_norm=5.0, feature_channels=512,
-                 device="cuda", seed=42, vgg_chunk_frames=1024, conv_dtype="f32", conv_algo=None, features_roi=False):
+                 device="cuda", seed=42, vgg_chunk_frames=1024, conv_dtype="f32", conv_algo=None, features_roi=False,
+                 similarity="as_coded"):
         self.B, self.T = int(batch_size), int(sequence_length)
         self.S = self.T * (NUM_FEATURES + 1)
         self.device = torch.device(device)
@@ -268,7 +277,8 @@ class NTMOffsetTracker(_TwoStreamPipeline, _Checkpointing):
         self.cell = NTMCell(2, mem_size=mem_size, mem_dim=mem_dim, controller_hidden_size=hidden_size,
                             controller_num_layers=num_layers, write_head_size=write_head_size,
                             read_head_size=read_head_size, write_first=write_first,
-                            input_dim=feature_channels + 2, device=self.device, init_scale=init_scale, seed=seed)
+                            input_dim=feature_channels + 2, device=self.device, init_scale=init_scale, seed=seed,
+                            similarity=similarity)
         self.opt = RMSPropClip(self.cell.params, learning_rate, decay, momentum, 1e-10, max_gradient_norm)
         self.add_pipeline()
 

@@ -81,7 +81,7 @@ class NTMTwoStepTracker(_Checkpointing):
 
     def __init__(self, batch_size, sequence_length, num_features, feature_dim, mem_size=128, mem_dim=20, hidden_size=200,
                  read_head_size=4, write_head_size=1, write_first=False, init_scale=0.05, learning_rate=1e-4, decay=0.95,
-                 momentum=0.9, max_gradient_norm=5.0, device="cuda", seed=42, compressor=None):
+                 momentum=0.9, max_gradient_norm=5.0, device="cuda", seed=42, compressor=None, similarity="as_coded"):
         """compressor: optional InputCompressor applied to feature maps [B, T, F, C] -> the cell sees F * compress_dim values
         per frame (feature_dim must then equal F * compress_dim).  loss_and_grads leaves its weight gradient in
         ``compressor.grad``; train_step updates the CELL only (the reference clips the joint global norm of all variables
@@ -93,7 +93,7 @@ class NTMTwoStepTracker(_Checkpointing):
         self.cell = NTMCell(self.F + 1, mem_size=mem_size, mem_dim=mem_dim, controller_hidden_size=hidden_size,
                             controller_num_layers=1, write_head_size=write_head_size, read_head_size=read_head_size,
                             write_first=write_first, input_dim=1 + self.D + self.F, device=self.device, init_scale=init_scale,
-                            seed=seed)
+                            seed=seed, similarity=similarity)
         self.opt = RMSPropClip(self.cell.params, learning_rate, decay, momentum, 1e-10, max_gradient_norm)
 
     def _ckpt_params(self):

@@ -3,7 +3,11 @@
   * forward and BPTT per step at B 32, S 1300, the tracker's shape (mem 128x20, 4 read + 1 write head, hid 200, D 514), L = 2, 3
   * forward per step at the reference constructor's default controller (10 layers of 100; 3 read + 3 write heads)
   * NTMOffsetTracker(num_layers=2).loss_and_grads at B 32, T 20 (ms per call)
-The step-wise form runs the same cell with ``fused = False``."""
+The step-wise form runs the same cell with ``fused = False``.
+
+  dev_ntm_deep_timing.py [B] [--similarity as_coded|smooth_cosine] [--fused-only]
+--fused-only times the fused form of L = 2, 3 alone (profiles/ntm_smooth_cosine.txt: both similarity modes)."""
+import argparse
 import os
 import sys
 
@@ -12,8 +16,13 @@ import torch
 from ntmtrack import tracker
 from ntmtrack.ntm import NTMCell
 
+ap = argparse.ArgumentParser()
+ap.add_argument("B", nargs="?", type=int, default=32)
+ap.add_argument("--similarity", default="as_coded", choices=("as_coded", "smooth_cosine"))
+ap.add_argument("--fused-only", action="store_true")
+args = ap.parse_args()
 dev = torch.device("cuda:0")
-B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+B = args.B
 S = 1300
 
 
@@ -45,20 +54,24 @@ def time_cell(cell, D, S, bptt, iters):
 
 def cell_for(L, hid, R, Wh):
     return NTMCell(2, mem_size=128, mem_dim=20, shift_range=1, controller_hidden_size=hid, controller_num_layers=L,
-                   write_head_size=Wh, read_head_size=R, input_dim=514, device=dev, init_scale=0.05, seed=1)
+                   write_head_size=Wh, read_head_size=R, input_dim=514, device=dev, init_scale=0.05, seed=1, similarity=args.similarity)
 
 
+print("similarity = %s" % args.similarity)
 print("B = %d, S = %d; us per step (best of the timed passes); BPTT = backward_sequence incl. the weight-gradient GEMMs" % (B, S))
 print("%-44s %12s %12s %10s" % ("shape", "forward", "BPTT", "form"))
 for L in (2, 3):
     c = cell_for(L, 200, 4, 1)
     rows = {}
-    for fused in (None, False):
+    for fused in ((None,) if args.fused_only else (None, False)):
         c.fused = fused
         f, b, form = time_cell(c, 514, S, True, 3 if fused is None else 1)
         rows[form] = (f, b)
         print("%-44s %12.1f %12.1f %10s" % ("tracker shape, L=%d (hid 200, R4 W1)" % L, f, b, form), flush=True)
-    print("%-44s %11.1fx %11.1fx" % ("  step-wise / fused", rows["stepwise"][0] / rows["fused"][0], rows["stepwise"][1] / rows["fused"][1]))
+    if not args.fused_only:
+        print("%-44s %11.1fx %11.1fx" % ("  step-wise / fused", rows["stepwise"][0] / rows["fused"][0], rows["stepwise"][1] / rows["fused"][1]))
+if args.fused_only:
+    sys.exit(0)
 c = cell_for(10, 100, 3, 3)
 rows = {}
 for fused in (None, False):
@@ -69,7 +82,7 @@ for fused in (None, False):
 print("%-44s %11.1fx" % ("  step-wise / fused", rows["stepwise"] / rows["fused"]))
 
 T = 20
-trk = tracker.NTMOffsetTracker(B, T, vgg_weights=None, num_layers=2, device=dev, seed=1)
+trk = tracker.NTMOffsetTracker(B, T, vgg_weights=None, num_layers=2, device=dev, seed=1, similarity=args.similarity)
 g = torch.Generator().manual_seed(0)
 fmap = torch.relu(torch.randn((B * T, 28, 28, 512), generator=g)).to(dev)
 gts0 = torch.rand((B, 64), generator=g).to(dev)
