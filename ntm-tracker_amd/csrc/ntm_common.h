@@ -72,6 +72,19 @@ struct NtmLds {
     int part, M, W, Wg, Z, C, U, Ks, Cn, Pw, total;
 };
 
+// LDS carve-up of the BPTT kernels, single-layer and deep (offsets in floats)
+struct NtmBwdLds {
+    int part, dM, G, Mp, Mt, dW, Wp, Wt, Wc, Wv, Wg, Dwv, Dsim, U, DU, DG, dZ, dC, Gt, Ct, Cp,
+        Khat, Ks, Kinv, Kss, Cinv, Css, C2, Dkhat, Sw, Red, Dmh, total;
+};
+
+// BPTT: per-head reduction slots, record prefetch depth, resident rows
+constexpr int NQ = 1 + NTM_MAX_SHIFT_TAPS;   // max simultaneous per-head reductions in one stage (d gamma + one per shift tap)
+constexpr int QR1 = 0, QR2 = 2, QR3 = QR2 + NQ, QR4 = QR3 + 2;
+constexpr int NQT = QR4 + 1; // (smooth cosine: one more, QR4 + 1 = sum_n b |M[n]|) reduction slots per head; every stage owns its own slots (no read/write reuse inside a step)
+constexpr int MAXM = 8;      // max memory elements prefetched per thread
+constexpr int NTMB_RES_WA = 7;   // benchmark shape: rows of Wa^T per thread (of its 15) kept in the LDS the state leaves free
+
 static inline __host__ __device__ int ntm_imax(int a, int b) { return a > b ? a : b; }
 static inline __host__ __device__ int ntm_imin(int a, int b) { return a < b ? a : b; }
 static inline __host__ __device__ int ntm_align4(int x) { return (x + 3) & ~3; }

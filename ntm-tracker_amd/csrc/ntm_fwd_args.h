@@ -1,4 +1,4 @@
-// Arguments and LDS carve-up of the NTM forward sequence kernels (ntm_seq_fwd.hip, ntm_seq_fwd_ws.hip).
+// Arguments and LDS carve-up of the NTM forward sequence kernels (ntm_seq_fwd.hip, ntm_seq_fwd_ws.hip, ntm_seq_deep.hip).
 #pragma once
 #include "ntm_common.h"
 
@@ -63,3 +63,4 @@ struct NtmFwdPlan {
     size_t lds_bytes;
 };
 int ntm_fwd_plan(const NtmDims& d, NtmFwdPlan& p, const char* who);
+int ntm_pick_threads(const NtmDims& d);           // workgroup size of the generic forward kernels, single-layer and deep (ntm_seq_fwd.hip)

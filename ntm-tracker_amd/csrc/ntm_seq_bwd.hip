@@ -13,8 +13,13 @@
 // Gradient semantics: pow: d/dx = y*x^(y-1), d/dy = x^y*log(x)
 // with log(x) -> 0 for x <= 0; l2_normalize differentiates through
 // rsqrt(max(sum x^2, 1e-12)) (zero through the norm when clamped).
+//
+// The head / memory / unpack half of a step (phases X1 .. B9, ntm_bwd_heads_step), the record prefetch / commit, the per-head
+// reductions and the set-up of the carried dM / dw / dread are in ntm_phases.h, shared with ntm_seq_deep.hip; the step takes this
+// kernel's stamped barrier as a callable.  This file's own: the LSTM backward B10, the gate-weight product B11 with its
+// wave-specialised form (stream waves, resident rows), the LDS carve-up, the plan and the launcher.
 #include "ntm_common.h"
-#include "ntm_fwd_args.h"           // NtmFwdPlan: ntk_ntm_seq_plan answers for both directions
+#include "ntm_phases.h"           // (NtmFwdPlan: ntk_ntm_seq_plan answers for both directions)
 #include <stdlib.h>
 #include <type_traits>
 
@@ -50,17 +55,6 @@ struct NtmBwdArgs {
     float* du;             // [B,S,PP]
     float* dM0; float* dw0; float* dread0; float* dcs0;
 };
-
-struct NtmBwdLds {
-    int part, dM, G, Mp, Mt, dW, Wp, Wt, Wc, Wv, Wg, Dwv, Dsim, U, DU, DG, dZ, dC, Gt, Ct, Cp,
-        Khat, Ks, Kinv, Kss, Cinv, Css, C2, Dkhat, Sw, Red, Dmh, total;
-};
-
-constexpr int NQ = 1 + NTM_MAX_SHIFT_TAPS;   // max simultaneous per-head reductions in one stage (d gamma + one per shift tap)
-constexpr int QR1 = 0, QR2 = 2, QR3 = QR2 + NQ, QR4 = QR3 + 2;
-constexpr int NQT = QR4 + 1; // (smooth cosine: one more, QR4 + 1 = sum_n b |M[n]|) reduction slots per head; every stage owns its own slots (no read/write reuse inside a step)
-constexpr int MAXM = 8;      // max memory elements prefetched per thread
-constexpr int NTMB_RES_WA = 7;   // benchmark shape: rows of Wa^T per thread (of its 15) kept in the LDS the state leaves free
 
 static void ntm_bwd_lds(const NtmDims& d, int T, int ldkT, int ldhT, NtmBwdLds& L) {
     const int MP = d.Md | 1, NM = d.N * MP, HN = d.H * d.N;
@@ -116,34 +110,17 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     extern __shared__ __attribute__((aligned(16))) float smem[];
     static_assert(!WS || FIX, "the wave-specialised form exists for the benchmark shape only");
     constexpr bool SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
-    constexpr int NQS = NQT + (SMOOTH ? 1 : 0);         // reduction slots per head
     static_assert(!WS || !SMOOTH, "the wave-specialised form is as coded only");
     const int b = blockIdx.x, tid0 = threadIdx.x, T = FIX ? 640 : blockDim.x;
     const int N = FIX ? 128 : a.d.N, Md = FIX ? 20 : a.d.Md, MP = Md | 1, R = FIX ? 4 : a.d.R, Wh = FIX ? 1 : a.d.Wh;
     const int H = R + Wh, hid = FIX ? 200 : a.d.hid, SS = FIX ? 3 : a.d.SS;
-    const int S = a.d.S, RM = R * Md, K = RM + hid, NW = N >> 6, NMd = N * Md, HN = H * N;
-    struct {
-        int O, oK, oB, oG, oS, oY, oE, oA, P, PP;
-    } d;
-    d.O = FIX ? 2 : a.d.O;
-    d.oK = 0; d.oB = H * Md; d.oG = d.oB + H; d.oS = d.oG + H; d.oY = d.oS + H * SS; d.oE = d.oY + H;
-    d.oA = d.oE + Wh * Md; d.P = d.oA + Wh * Md;
-    d.PP = (d.P + d.O + 3) & ~3;
+    const int S = a.d.S, RM = R * Md, K = RM + hid, NMd = N * Md, HN = H * N;
+    const NtmCtl d = ntm_ctl(Md, R, Wh, hid, SS, FIX ? 2 : a.d.O, FIX ? 0 : a.d.write_first);
     const int PP = d.PP;
-    const bool wf = FIX ? false : (a.d.write_first != 0);
     const int ldkT = FIX ? 280 : a.ldkT, ldhT = FIX ? 200 : a.ldhT;
-    int tid = tid0, lane = tid0 & 63;
-
-    float* sPart = smem + L.part;
-    float* sdM = smem + L.dM;  float* sG = smem + L.G;  float* sMp = smem + L.Mp;  float* sMt = smem + L.Mt;
-    float* sdW = smem + L.dW;  float* sWp = smem + L.Wp; float* sWt = smem + L.Wt; float* sWc = smem + L.Wc;
-    float* sWv = smem + L.Wv;  float* sWg = smem + L.Wg; float* sDwv = smem + L.Dwv; float* sDsim = smem + L.Dsim;
-    float* sU = smem + L.U;    float* sDU = smem + L.DU; float* sDG = smem + L.DG; float* sdZ = smem + L.dZ;
-    float* sdC = smem + L.dC;  float* sGt = smem + L.Gt; float* sCt = smem + L.Ct; float* sCp = smem + L.Cp;
-    float* sKhat = smem + L.Khat; float* sKs = smem + L.Ks; float* sKinv = smem + L.Kinv; float* sKss = smem + L.Kss;
-    float* sCinv = smem + L.Cinv; float* sCss = smem + L.Css; float* sC2 = smem + L.C2; float* sDkhat = smem + L.Dkhat;
-    float* sSw = smem + L.Sw;  float* sRed = smem + L.Red;  float* sDmh = smem + L.Dmh;
-    float* sRn = sCinv; float* sRc = sC2;  // smooth cosine: [N] row norms |M_prev[n]| and the row-norm coefficients where the [Md] column terms are
+    const NtmBwdSt c = ntm_bwd_state(smem, L, b, S, T, N, Md, R, Wh, hid, SS, PP, ldhT);      // LDS pointers + decomposition of X1 .. B9
+    float* const sPart = c.sPart; float* const sdM = c.sdM; float* const sdW = c.sdW; float* const sDG = c.sDG;
+    float* const sdZ = c.sdZ; float* const sdC = c.sdC; float* const sGt = c.sGt; float* const sCt = c.sCt; float* const sCp = c.sCp;
     f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart);
     // WS: d h_{t-1} partials of the stream waves, [2 row halves][200] floats, behind the resident rows of Wa^T
     float* sPartH = smem + L.total + 32 + NTMB_RES_WA * 600 * 4;
@@ -211,98 +188,28 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
         }
     }
 
-    // thread roles
-    int hh = tid / N, nn = tid - hh * N;                // (head, slot) owner; active iff hh < H
-    bool hn = hh < H;
-    int wi = nn >> 6;
-    const int nout = H * Md + 2 * Wh * Md;
-    const int nslP = min(max(1, T / nout), N);
-    const int nperP = (N + nslP - 1) / nslP;
-    const int kg4 = ldkT >> 2, hg4 = ldhT >> 2;
+    const int kg4 = ldkT >> 2, hg4 = c.hg4;
     const int nslZ = max(1, T / kg4), nperZ = (4 * hid + nslZ - 1) / nslZ;
-    const int nslH = max(1, T / hg4), nperH = (PP + nslH - 1) / nslH;
-    const int nslC = max(1, T / Md), nperC = (N + nslC - 1) / nslC;
+    const int nslH = c.nslH, nperH = c.nperH;
 
-    // ---- prefetch registers for one step's records
-    float pM[MAXM], pMt[MAXM], pWp = 0.f, pWt = 0.f, pWc = 0.f, pWv = 0.f, pU = 0.f, pCt = 0.f, pCp = 0.f, pDl = 0.f;
-    f32x4 pG = {0.f, 0.f, 0.f, 0.f};
-    auto prefetch = [&](int t) {
-        const size_t bt = (size_t)b * S + t;
-        const float* Mp = (t > 0) ? a.st_M + (bt - 1) * NMd : a.M0 + (size_t)b * NMd;
-#pragma unroll
-        for (int q = 0; q < MAXM; ++q) {
-            const int idx = tid + q * T;
-            pM[q] = (idx < NMd) ? Mp[idx] : 0.f;
-            pMt[q] = (wf && idx < NMd) ? a.st_M[bt * NMd + idx] : 0.f;
-        }
-        if (hn) {
-            pWp = (t > 0) ? a.st_w[(bt - 1) * HN + tid] : a.w0[(size_t)b * HN + tid];
-            pWt = a.st_w[bt * HN + tid];
-            pWc = a.st_wc[bt * HN + tid];
-            pWv = a.st_wv[bt * HN + tid];
-        }
-        if (tid < PP) {
-            pU = a.st_u[bt * PP + tid];
-            pDl = (tid >= d.P && tid < d.P + d.O) ? a.dlogits[bt * d.O + (tid - d.P)] : 0.f;
-        }
-        if (tid < hid) {
-            pG = reinterpret_cast<const f32x4*>(a.st_gates)[bt * hid + tid];
-            pCt = a.st_c[bt * hid + tid];
-            pCp = (t > 0) ? a.st_c[(bt - 1) * hid + tid] : a.cs0[(size_t)b * 2 * hid + tid];
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int q = 0; q < MAXM; ++q) {
-            const int idx = tid + q * T;
-            if (idx < NMd) {
-                const int n = idx / Md, m = idx - n * Md;
-                sMp[n * MP + m] = pM[q];
-                if (wf) sMt[n * MP + m] = pMt[q];
-            }
-        }
-        if (hn) { sWp[tid] = pWp; sWt[tid] = pWt; sWc[tid] = pWc; sWv[tid] = pWv; }
-        if (tid < PP) { sU[tid] = pU; sDU[tid] = pDl; }
-        if (tid < hid) { reinterpret_cast<f32x4*>(sGt)[tid] = pG; sCt[tid] = pCt; sCp[tid] = pCp; }
-    };
-
-    // ---- carried gradients start from the (optional) gradient of the final state
-    for (int i = tid; i < NMd; i += T)
-        sdM[(i / Md) * MP + (i % Md)] = a.dM_fin ? a.dM_fin[(size_t)b * NMd + i] : 0.f;
-    for (int i = tid; i < HN; i += T) sdW[i] = a.dw_fin ? a.dw_fin[(size_t)b * HN + i] : 0.f;
-    for (int i = tid; i < ldkT; i += T) {
-        float v = 0.f;
-        if (i < RM) v = a.dread_fin ? a.dread_fin[(size_t)b * RM + i] : 0.f;
-        else if (i < K) v = a.dcs_fin ? a.dcs_fin[(size_t)b * 2 * hid + hid + (i - RM)] : 0.f;
-        sdZ[i] = v;
-    }
-    for (int i = tid; i < hid; i += T) sdC[i] = a.dcs_fin ? a.dcs_fin[(size_t)b * 2 * hid + i] : 0.f;
+    // ---- carried gradients start from the (optional) gradient of the final state; the records of the last step
+    ntm_bwd_init_carried(c, a, tid0);
+    for (int i = RM + tid0; i < ldkT; i += T) sdZ[i] = (i < K && a.dcs_fin) ? a.dcs_fin[(size_t)b * 2 * hid + hid + (i - RM)] : 0.f;
+    for (int i = tid0; i < hid; i += T) sdC[i] = a.dcs_fin ? a.dcs_fin[(size_t)b * 2 * hid + i] : 0.f;
     if constexpr (WS) {
-        for (int i = tid; i < 4 * hid; i += T) sDG[i] = 0.f;          // the stream waves' first (partial) lap multiplies these
+        for (int i = tid0; i < 4 * hid; i += T) sDG[i] = 0.f;         // the stream waves' first (partial) lap multiplies these
     }
-    prefetch(S - 1);
-    commit();
+    NtmBwdRecs rec = {};                                 // prefetch registers for one step's records
+    const float* const c_init = a.cs0 + (size_t)b * 2 * hid;
+    {
+        const NtmBwdWho w = ntm_bwd_who(tid0, N, H);
+        ntm_bwd_prefetch(c, d, a, w, rec, S - 1, c_init);
+        ntm_bwd_commit(c, d, w, rec);
+    }
     __syncthreads();
-
-    // per-head block reduction of nq values held by the (h, n) owner threads
-    auto red_write = [&](const float (&v)[NQ], int nq, int base) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            if (q < nq) {
-                const float s = wave_sum(hn ? v[q] : 0.f);
-                if (hn && lane == 0) sRed[(hh * NQS + base + q) * NW + wi] = s;
-            }
-        }
-    };
-    auto red_read = [&](int h, int q) -> float {
-        float s = 0.f;
-        for (int w = 0; w < NW; ++w) s += sRed[(h * NQS + q) * NW + w];
-        return s;
-    };
 
     // benchmark shape: 7 of the 15 rows of Wa^T a thread multiplies in B9 stay in LDS for the whole sequence (67 KB of the 74 KB
     // the state leaves free); B9's stream runs at ~67 GB/s, the worst of the kernel's three weight streams
-    const f32x4* sWaRes4 = reinterpret_cast<const f32x4*>(smem + L.total + 32);
     if constexpr (FIX) {
         if (tid0 < nslH * hg4) {
             const int cg = tid0 % hg4, sl = tid0 / hg4;
@@ -329,356 +236,15 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     for (int t = S - 1; t >= 0; --t) {
         // opaque thread id: keeps loop-invariant index/address expressions from being hoisted out of the
         // t-loop (they would be spilled to scratch and reloaded every step)
-        {
-            int tid_op = tid0;
-            asm volatile("" : "+v"(tid_op));
-            tid = tid_op; lane = tid & 63;
-            hh = tid / N; nn = tid - hh * N; hn = hh < H; wi = nn >> 6;
-        }
+        int tid_op = tid0;
+        asm volatile("" : "+v"(tid_op));
+        const NtmBwdWho w = ntm_bwd_who(tid_op, N, H);
+        const int tid = w.tid;
         const size_t bt = (size_t)b * S + t;
-        if (t > 0) prefetch(t - 1);
+        if (t > 0) ntm_bwd_prefetch(c, d, a, w, rec, t - 1, c_init);
 
-        // ------------------------------------------------ X1: memory-shaped elementwise + column norms + small vectors
-        if constexpr (FIX) {
-            // benchmark shape (write_first off): a thread = (slot n, four adjacent columns): the five head weights of the slot
-            // are read once for four elements and d(read) comes in 16-byte reads: 29 LDS operations per thread instead of 52
-            const int n = tid / 5, m0 = (tid - n * 5) * 4;
-            float wt[5];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) wt[i] = sWt[i * N + n];
-            f32x4 dmr = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) dmr += wt[i] * *reinterpret_cast<const f32x4*>(sdZ + i * Md + m0);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int ai = n * MP + m0 + e;
-                const float dMt = sdM[ai];
-                const float E = 1.0f - wt[4] * sU[d.oE + m0 + e];
-                sG[ai] = dMt;
-                sdM[ai] = dMt * E + dmr[e];
-            }
-        } else
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            float dMt = sdM[ai];
-            float dMr = 0.f;
-            for (int i = 0; i < R; ++i) dMr += sWt[i * N + n] * sdZ[i * Md + m];
-            if (wf) dMt += dMr;
-            float E = 1.f;
-            for (int j = 0; j < Wh; ++j) E *= (1.0f - sWt[(R + j) * N + n] * sU[d.oE + j * Md + m]);
-            sG[ai] = dMt;
-            sdM[ai] = dMt * E + (wf ? 0.f : dMr);
-        }
-        if constexpr (SMOOTH) {
-            if (tid < N) {         // row norms of M_prev, no clamp
-                float s = 0.f;
-                for (int m = 0; m < Md; ++m) { const float v = sMp[tid * MP + m]; s += v * v; }
-                sRn[tid] = sqrtf(s);
-            }
-        } else
-        if (tid < nslC * Md) {     // column sum of squares of M_prev (quirk Q1 normaliser)
-            const int m = tid % Md, sl = tid / Md;
-            const int n0 = sl * nperC, n1 = min(N, n0 + nperC);
-            float s = 0.f;
-            for (int n = n0; n < n1; ++n) { const float v = sMp[n * MP + m]; s += v * v; }
-            sPart[sl * Md + m] = s;
-        }
-        if (tid < H) {             // key norms and shift softmax
-            const int h = tid;
-            float ss = 0.f;
-            for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; ss += kv * kv; }
-            sKss[h] = ss;
-            sKinv[h] = SMOOTH ? sqrtf(ss) : 1.0f / sqrtf(fmaxf(ss, 1e-12f));        // smooth cosine: |k| itself
-            float mx = -INFINITY;
-            for (int j = 0; j < SS; ++j) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
-            float sum = 0.f;
-            for (int j = 0; j < SS; ++j) sum += expf(sU[d.oS + h * SS + j] - mx);
-            for (int j = 0; j < SS; ++j) sSw[h * SS + j] = expf(sU[d.oS + h * SS + j] - mx) / sum;
-        }
-        __syncthreads();
-        NTMB_STAMP(0);
-
-        // ------------------------------------------------ X2: d(w_t) for every head; R1 sums
-        float dwt = 0.f, pw = 0.f, wv = 0.f, wt = 0.f, wc = 0.f, wp = 0.f, gam = 1.f, gate = 0.f;
-        float rv[NQ];
-        if (!SMOOTH && tid < Md) {
-            float s = 0.f;
-            for (int sl = 0; sl < nslC; ++sl) s += sPart[sl * Md + tid];
-            sCss[tid] = s;
-            sCinv[tid] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-        }
-        if (hn) {
-            const int h = hh, n = nn;
-            float acc = sdW[tid];
-            if (h < R) {
-                const float* Mr = wf ? sMt : sMp;
-                for (int m = 0; m < Md; ++m) acc += sdZ[h * Md + m] * Mr[n * MP + m];
-            } else {
-                const int j = h - R;
-                for (int m = 0; m < Md; ++m) {
-                    float oth = 1.f;
-                    for (int j2 = 0; j2 < Wh; ++j2)
-                        if (j2 != j) oth *= (1.0f - sWt[(R + j2) * N + n] * sU[d.oE + j2 * Md + m]);
-                    const float g = sG[n * MP + m];
-                    const float Tj = g * sMp[n * MP + m] * oth;
-                    acc += -sU[d.oE + j * Md + m] * Tj + sU[d.oA + j * Md + m] * g;
-                }
-            }
-            dwt = acc;
-            wv = sWv[tid]; wt = sWt[tid]; wc = sWc[tid]; wp = sWp[tid];
-            gam = sU[d.oY + h]; gate = sU[d.oG + h];
-            pw = powf(wv, gam);
-            sWg[tid] = gate * wc + (1.0f - gate) * wp;
-            rv[0] = pw; rv[1] = dwt * wt;
-        }
-        red_write(rv, 2, QR1);
-        __syncthreads();
-        NTMB_STAMP(1);
-
-        // ------------------------------------------------ R2: sharpen backward, shift-weight sums
-        float dpw = 0.f, dwv = 0.f;
-        if (tid < H * Md) {        // normalised keys (needed from R4 on); smooth cosine: the keys as they are
-            const int h = tid / Md, m = tid - h * Md;
-            const float kh = SMOOTH ? sU[d.oK + tid] : sU[d.oK + tid] * sKinv[h];
-            sKhat[tid] = kh;
-            sKs[tid] = SMOOTH ? kh : kh * sCinv[m];
-        }
-        if (hn) {
-            const float den = red_read(hh, QR1) + 1e-3f;
-            const float s2 = red_read(hh, QR1 + 1);
-            dpw = (dwt - s2) / den;
-            dwv = (wv > 0.f) ? dpw * gam * pw / wv : 0.f;
-            sDwv[tid] = dwv;
-            rv[0] = (wv > 0.f) ? dpw * pw * logf(wv) : 0.f;        // d gamma
-            const int start = -((SS + 1) >> 1);
-#pragma unroll
-            for (int j = 0; j < NQ - 1; ++j) {
-                if (j < SS) {
-                    int src = nn + start + j; src = (src % N + N) % N;
-                    rv[1 + j] = dwv * sWg[hh * N + src];            // d shift_j
-                }
-            }
-        }
-        red_write(rv, 1 + SS, QR2);
-        __syncthreads();
-        NTMB_STAMP(2);
-
-        // ------------------------------------------------ R3: shift + gate backward
-        float dwg = 0.f, dwc = 0.f;
-        float Sgam = 0.f, Ssw[NQ - 1];
-        if (hn) {
-            Sgam = red_read(hh, QR2);
-#pragma unroll
-            for (int j = 0; j < NQ - 1; ++j) Ssw[j] = (j < SS) ? red_read(hh, QR2 + 1 + j) : 0.f;
-            const int start = -((SS + 1) >> 1);
-            for (int j = 0; j < SS; ++j) {
-                int src = nn - (start + j); src = (src % N + N) % N;
-                dwg += sSw[hh * SS + j] * sDwv[hh * N + src];
-            }
-            sdW[tid] = (1.0f - gate) * dwg;                         // carried d(w_{t-1})
-            dwc = gate * dwg;
-            rv[0] = dwg * (wc - wp);                                // d g
-            rv[1] = wc * dwc;                                       // softmax backward inner product
-        }
-        red_write(rv, 2, QR3);
-        __syncthreads();
-        NTMB_STAMP(3);
-
-        // ------------------------------------------------ R4: content softmax backward
-        float Sg = 0.f, dv = 0.f;
-        if (hn) {
-            Sg = red_read(hh, QR3);
-            const float Bs = red_read(hh, QR3 + 1);
-            dv = wc * (dwc - Bs);
-            float sim = 0.f;
-            for (int m = 0; m < Md; ++m) sim += sKs[hh * Md + m] * sMp[nn * MP + m];
-            if constexpr (SMOOTH) {
-                // sim = dot / den, den = |M[n]||k| + 1e-3:  d dot = a = dsim / den,  d den = b = -dsim sim / den.  sDsim keeps a
-                // (B7 and the key sums below read it where they read dsim as coded); b |k| goes to the row-norm term of d M_prev
-                // (sDwv is free: its readers passed R3's barrier) and b |M[n]|, summed over the slots, to the norm term of d k
-                const float rn = sRn[nn], kn = sKinv[hh], den = rn * kn + 1e-3f;
-                sim = sim / den;
-                const float da = dv * sU[d.oB + hh] / den, db = -da * sim;
-                rv[0] = dv * sim;                                   // d beta
-                sDsim[tid] = da;
-                sDwv[tid] = db * kn;
-                rv[1] = db * rn;
-            } else {
-                rv[0] = dv * sim;                                   // d beta
-                sDsim[tid] = dv * sU[d.oB + hh];
-            }
-        }
-        red_write(rv, SMOOTH ? 2 : 1, QR4);
-        __syncthreads();
-        NTMB_STAMP(4);
-        if constexpr (SMOOTH) {
-            if (tid < N) {         // row-norm term: d M_prev[n][:] += M_prev[n][:] * (sum_h b[h][n] |k_h|) / |M[n]|, 0 at a zero row
-                float s = 0.f;
-                for (int h = 0; h < H; ++h) s += sDwv[h * N + tid];
-                const float rn = sRn[tid];
-                sRc[tid] = (rn > 0.f) ? s / rn : 0.f;
-            }
-        }
-        if (hn && nn == 0) {       // per-head scalar controls -> raw gradients
-            const int h = hh;
-            const float beta = sU[d.oB + h];
-            sDU[d.oB + h] = red_read(h, QR4) * (1.0f - expf(-beta));                 // softplus' = 1 - exp(-softplus)
-            sDU[d.oG + h] = Sg * gate * (1.0f - gate);
-            sDU[d.oY + h] = Sgam * (1.0f - expf(-(gam - 1.0f)));
-            float dot = 0.f;
-#pragma unroll
-            for (int j = 0; j < NQ - 1; ++j) if (j < SS) dot += sSw[h * SS + j] * Ssw[j];
-#pragma unroll
-            for (int j = 0; j < NQ - 1; ++j) if (j < SS) sDU[d.oS + h * SS + j] = sSw[h * SS + j] * (Ssw[j] - dot);
-        }
-
-        NTMB_STAMP(12);
-        // ------------------------------------------------ B7: dMhat[n][m] = sum_h dsim[h][n] khat[h][m], computed ONCE
-        //                                                  (the column-norm sum and the d(M_prev) update both use it);
-        //                                                  reductions over slots (keys, erase, add)
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md;
-            float dmh = 0.f;
-            for (int h = 0; h < H; ++h) dmh += sDsim[h * N + n] * sKhat[h * Md + m];
-            sDmh[n * MP + m] = dmh;
-        }
-        NTMB_STAMP(13);
-        if constexpr (FIX) {
-            // benchmark shape (5 heads, 1 write head): a thread = (memory column m = tid >> 4, row class sl = tid & 15) reads
-            // M_prev[n][m], G[n][m], ww[n] and dsim[0..4][n] ONCE per row n = sl, sl + 16, ... and feeds seven sums; the sixteen
-            // row classes of a column are sixteen adjacent lanes, reduced on the DPP path: 20 K LDS reads per step instead of 41 K,
-            // no slot partials (the one-output-per-thread form below was 14 % of a BPTT step)
-            if (tid < 16 * Md) {
-                const int m = tid >> 4, sl = tid & 15;
-                float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f, ae = 0.f, aa = 0.f;
-#pragma unroll 4
-                for (int n = sl; n < N; n += 16) {
-                    const float mp = sMp[n * MP + m], g = sG[n * MP + m], ww = sWt[R * N + n];
-                    a0 += sDsim[0 * N + n] * mp; a1 += sDsim[1 * N + n] * mp; a2 += sDsim[2 * N + n] * mp;
-                    a3 += sDsim[3 * N + n] * mp; a4 += sDsim[4 * N + n] * mp;
-                    const float wg = ww * g;
-                    ae -= wg * mp;
-                    aa += wg;
-                }
-                auto r16 = [](float v) { v += ntk_dpp<0xB1>(v); v += ntk_dpp<0x4E>(v); v += ntk_dpp<0x141>(v); v += ntk_dpp<0x140>(v); return v; };
-                a0 = r16(a0); a1 = r16(a1); a2 = r16(a2); a3 = r16(a3); a4 = r16(a4); ae = r16(ae); aa = r16(aa);
-                if (sl == 0) {
-                    sPart[0 * Md + m] = a0; sPart[1 * Md + m] = a1; sPart[2 * Md + m] = a2; sPart[3 * Md + m] = a3; sPart[4 * Md + m] = a4;
-                    sPart[H * Md + m] = ae; sPart[H * Md + Wh * Md + m] = aa;
-                }
-            }
-        } else if (tid < nslP * nout) {
-            const int o = tid % nout, sl = tid / nout;
-            const int n0 = sl * nperP, n1 = min(N, n0 + nperP);
-            float s = 0.f;
-            if (o < H * Md) {                                  // sum_n dsim[h][n] * M_prev[n][m]
-                const int h = o / Md, m = o - h * Md;
-                // four independent chains, four rows per trip: the rolled single-chain loop paid an LDS round trip + the add
-                // latency per row (this phase was 18 % of a BPTT step)
-                float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-                int n = n0;
-                for (; n + 3 < n1; n += 4) {
-                    s += sDsim[h * N + n] * sMp[n * MP + m];
-                    s1 += sDsim[h * N + n + 1] * sMp[(n + 1) * MP + m];
-                    s2 += sDsim[h * N + n + 2] * sMp[(n + 2) * MP + m];
-                    s3 += sDsim[h * N + n + 3] * sMp[(n + 3) * MP + m];
-                }
-                for (; n < n1; ++n) s += sDsim[h * N + n] * sMp[n * MP + m];
-                s = (s + s1) + (s2 + s3);
-            } else {
-                const int o2 = o - H * Md;
-                const int which = o2 / (Wh * Md);              // 0: erase, 1: add
-                const int jm = o2 - which * Wh * Md;
-                const int j = jm / Md, m = jm - j * Md;
-                float sa = 0.f, sb = 0.f;                       // two chains (even / odd rows)
-                for (int n = n0; n < n1; ++n) {
-                    const float ww = sWt[(R + j) * N + n];
-                    const float g = sG[n * MP + m];
-                    float term;
-                    if (which == 0) {
-                        float oth = 1.f;
-                        for (int j2 = 0; j2 < Wh; ++j2)
-                            if (j2 != j) oth *= (1.0f - sWt[(R + j2) * N + n] * sU[d.oE + j2 * Md + m]);
-                        term = -ww * g * sMp[n * MP + m] * oth;
-                    } else {
-                        term = ww * g;
-                    }
-                    if ((n - n0) & 1) sb += term; else sa += term;
-                }
-                s = sa + sb;
-            }
-            sPart[sl * nout + o] = s;
-        }
-        __syncthreads();
-        NTMB_STAMP(5);
-        // column-norm term: s_m = sum_n dMhat[n][m] * M_prev[n][m], one wave_sum per column (waves stride over m)
-        if constexpr (!SMOOTH)
-        for (int m = (tid >> 6); m < Md; m += (T >> 6)) {
-            float s = 0.f;
-            for (int n = lane; n < N; n += 64) s += sDmh[n * MP + m] * sMp[n * MP + m];
-            s = wave_sum(s);
-            if (lane == 0) {
-                const float ci = sCinv[m];
-                sC2[m] = (sCss[m] > 1e-12f) ? -ci * ci * ci * s : 0.f;   // dM += M * C2 (2 * d css)
-            }
-        }
-        if (tid < nout) {
-            float s = 0.f;
-            for (int sl = 0; sl < (FIX ? 1 : nslP); ++sl) s += sPart[sl * nout + tid];
-            if (tid < H * Md) {
-                sDkhat[tid] = SMOOTH ? s : s * sCinv[tid % Md];
-            } else {
-                const int o2 = tid - H * Md;
-                const int which = o2 / (Wh * Md);
-                const int jm = o2 - which * Wh * Md;
-                if (which == 0) { const float e = sU[d.oE + jm]; sDU[d.oE + jm] = s * e * (1.0f - e); }
-                else { const float av = sU[d.oA + jm]; sDU[d.oA + jm] = s * (1.0f - av * av); }
-            }
-        }
-        __syncthreads();
-        NTMB_STAMP(6);
-        if (tid < H * Md) {
-            const int h = tid / Md;
-            if constexpr (SMOOTH) {                                 // d k = sum_n a M_prev[n] + k / |k| * sum_n b |M[n]|, 0 through |k| = 0
-                const float kn = sKinv[h], kv = sU[d.oK + tid];
-                const float dk = sDkhat[tid] + ((kn > 0.f) ? kv / kn * red_read(h, QR4 + 1) : 0.f);
-                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
-            } else {
-                float dot = 0.f;
-                for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
-                const float ki = sKinv[h];
-                const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
-                const float kv = sU[d.oK + tid];
-                const float dk = ki * sDkhat[tid] + kv * ck;
-                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
-            }
-        }
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            if constexpr (SMOOTH) sdM[ai] += sDmh[ai] + sMp[ai] * sRc[n];
-            else sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
-        }
-        __syncthreads();
-        NTMB_STAMP(7);
-        if (tid < PP) a.du[bt * PP + tid] = sDU[tid];
-
-        // ------------------------------------------------ B9: dh' = carried dh + dU . Wa^T
-        if (tid < nslH * hg4) {
-            const int cg = tid % hg4, sl = tid / hg4;
-            const int c0 = sl * nperH, c1 = min(PP, c0 + nperH);
-            if constexpr (FIX) {
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                const int cs = min(c1, c0 + NTMB_RES_WA);
-                const f32x4 str = ntk_stream_matvec_exact<4>(reinterpret_cast<const f32x4*>(a.WaT) + cg, hg4, sDU, cs, c1);
-#pragma unroll
-                for (int q = 0; q < NTMB_RES_WA; ++q) acc += ((c0 + q < c1) ? sDU[c0 + q] : 0.f) * sWaRes4[q * (nslH * hg4) + tid];
-                sPart4[sl * hg4 + cg] = acc + str;
-            } else {
-                sPart4[sl * hg4 + cg] = ntk_stream_matvec<(MAXT > 768 ? 2 : 4)>(reinterpret_cast<const f32x4*>(a.WaT) + cg, hg4, sDU, c0, c1, PP - 1);
-            }
-        }
-        __syncthreads();
-        NTMB_STAMP(8);
+        // ------------------------------------------------ X1 .. B9 (ntm_phases.h): heads, memory, unpack; nine barriers, stamps 0 .. 8
+        ntm_bwd_heads_step<MAXT, FIX, SMOOTH>(c, d, a, w, bt, [&](int i) { __syncthreads(); NTMB_STAMP(i); }, [&](int i) { NTMB_STAMP(i); });
         // ------------------------------------------------ B10: LSTM cell backward
         if (tid < hid) {
             float dh = WS ? sPartH[tid] + sPartH[hid + tid] : sdZ[RM + tid];
@@ -725,7 +291,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
             for (int sl = 0; sl < nslZ; ++sl) s += sPart[sl * ldkT + tid];
             sdZ[tid] = s;
         }
-        if (t > 0) commit();       // next (earlier) step's records: every reader of the old ones has passed a barrier
+        if (t > 0) ntm_bwd_commit(c, d, w, rec);       // next (earlier) step's records: every reader of the old ones has passed a barrier
         __syncthreads();
         NTMB_STAMP(11);
     }
@@ -734,15 +300,15 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     if (blockIdx.x == 0 && threadIdx.x == 0) for (int i = 0; i < 16; ++i) g_ntm_bwd_prof[i] = s_prof[i];
 #endif
     // ---- gradient of the initial state
-    for (int i = tid; i < NMd; i += T) a.dM0[(size_t)b * NMd + i] = sdM[(i / Md) * MP + (i % Md)];
-    for (int i = tid; i < HN; i += T) a.dw0[(size_t)b * HN + i] = sdW[i];
-    for (int i = tid; i < RM; i += T) a.dread0[(size_t)b * RM + i] = sdZ[i];
+    for (int i = tid0; i < NMd; i += T) a.dM0[(size_t)b * NMd + i] = sdM[(i / Md) * MP + (i % Md)];
+    for (int i = tid0; i < HN; i += T) a.dw0[(size_t)b * HN + i] = sdW[i];
+    for (int i = tid0; i < RM; i += T) a.dread0[(size_t)b * RM + i] = sdZ[i];
     if constexpr (WS) {
         // the stream waves finish the last lap (d h_{-1}) behind eight more barriers and one for the hand-over
 #pragma unroll
         for (int i = 0; i < 9; ++i) __syncthreads();
     }
-    for (int i = tid; i < hid; i += T) {
+    for (int i = tid0; i < hid; i += T) {
         a.dcs0[(size_t)b * 2 * hid + i] = sdC[i];
         a.dcs0[(size_t)b * 2 * hid + hid + i] = WS ? sPartH[i] + sPartH[hid + i] : sdZ[RM + i];
     }

@@ -10,9 +10,12 @@
 // layer k's is z[R*Md+(k-1)*hid .. R*Md+(k+1)*hid): updating h_k in place, layer by layer, hands layer k+1 the new h_k and
 // its own old h_{k+1}.  The BPTT keeps the carried gradients in the same layout.
 //
-// The single-layer kernels are not touched: these are kernels of their own, with argument structs of their own.
-#include "ntm_common.h"
-#include "ntm_fwd_args.h"
+// Shared with the single-layer kernels (ntm_phases.h): the control layout, P2's memory normaliser and P3 .. P8 of the forward step,
+// X1 .. B9 of the BPTT step with its record prefetch / commit, per-head reductions and carried-gradient set-up, the BPTT's LDS
+// carve-up struct and reduction slots (ntm_common.h) and the forward's workgroup size (ntm_pick_threads).  This file's own: the
+// layer loops (P1 / P2 per layer forward, B10 / B11 per layer in the BPTT), the records of the lower layers, the packed weight
+// layouts and their pack kernel, the argument structs (NtmDeepFwdArgs, NtmDeepBwdArgs), the plan and the launchers.
+#include "ntm_phases.h"
 #include <initializer_list>
 
 // ------------------------------------------------------------------------------------------------ packed layouts
@@ -137,35 +140,16 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
     const int H = R + Wh, hid = a.d.hid, SS = a.d.SS, NL = dp.s.L;
     const int S = a.d.S, RM = R * Md, K = RM + hid;
     const size_t BS = (size_t)a.d.B * S;
-    struct {
-        int O, oK, oB, oG, oS, oY, oE, oA, P, PP, ldz, ldh, write_first;
-    } d;
-    d.O = a.d.O;
-    d.oK = 0; d.oB = H * Md; d.oG = d.oB + H; d.oS = d.oG + H; d.oY = d.oS + H * SS; d.oE = d.oY + H;
-    d.oA = d.oE + Wh * Md; d.P = d.oA + Wh * Md;
-    d.PP = (d.P + d.O + 3) & ~3; d.ldz = (K + 1 + 3) & ~3; d.ldh = (hid + 1 + 3) & ~3;
-    d.write_first = a.d.write_first;
+    const NtmCtl d = ntm_ctl(Md, R, Wh, hid, SS, a.d.O, a.d.write_first);
     const int PP = d.PP;
     const NtmDeepShape& sh = dp.s;
-
-    float* sPart = smem + L.part;
-    float* sM = smem + L.M;
-    float* sW = smem + L.W;
-    float* sWg = smem + L.Wg;
-    float* sZ = smem + L.Z;                 // [read | h_0 | .. | h_{L-1}]
-    float* sC = smem + L.C;                 // [c_0 | .. | c_{L-1}]
-    float* sU = smem + L.U;
-    float* sKs = smem + L.Ks;
-    float* sCn = smem + L.Cn;
-    float* sPw = smem + L.Pw;
+    const NtmFwdSt c = ntm_fwd_state(smem, L, T, N, Md, R, Wh, hid, SS, PP, RM + (NL - 1) * hid);
+    float* const sPart = c.sPart; float* const sM = c.sM; float* const sW = c.sW;
+    float* const sZ = c.sZ;                 // [read | h_0 | .. | h_{L-1}]
+    float* const sC = smem + L.C;           // [c_0 | .. | c_{L-1}]
     float* sHtop = sZ + RM + (NL - 1) * hid;
 
     const int nsl = max(1, T / hid);        // K-slices of the gate products
-    const int ncg = PP >> 2;
-    const int nslB = min(max(1, T / ncg), hid);
-    const int kperB = (hid + nslB - 1) / nslB;
-    const int nslR = min(max(1, T / RM), N);
-    const int nperR = (N + nslR - 1) / nslR;
     const int cs_ld = 2 * hid * NL;
 
     for (int i = tid0; i < N * Md; i += T) sM[(i / Md) * MP + (i % Md)] = a.M0[(size_t)b * N * Md + i];
@@ -187,7 +171,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
         asm volatile("" : "+v"(tid_op));
         const int tid = tid_op;
         const int lane = tid & 63;
-        const int wave = tid >> 6, nwaves = T >> 6;
+        const int wave = tid >> 6;
         const size_t bt = (size_t)b * S + t;
         // ------------------------------------------------------------ P1 / P2 of ntm_seq_fwd.hip, once per layer
         for (int l = 0; l < NL; ++l) {
@@ -249,166 +233,22 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
             } else if (l == NL - 1 && a.st_h && tid < d.ldh) {
                 a.st_h[bt * d.ldh + tid] = (tid == hid) ? 1.f : 0.f;
             }
-            if (l == NL - 1) {  // waves not running the LSTM normalise the feature columns of M over the slots (ops.py:150)
-                const int w0 = (hid + 63) >> 6;
-                if constexpr (SMOOTH) {     // smooth cosine: the row norms |M[n]|, a lane per slot, no clamp
-                    if (wave >= w0) {
-                        for (int n = (wave - w0) * 64 + lane; n < N; n += (nwaves - w0) * 64) {
-                            float sq = 0.f;
-                            for (int m = 0; m < Md; ++m) { const float v = sM[n * MP + m]; sq += v * v; }
-                            sCn[n] = sqrtf(sq);
-                        }
-                    }
-                } else
-                if (wave >= w0) {
-                    for (int m = wave - w0; m < Md; m += nwaves - w0) {
-                        float sq = 0.f;
-                        for (int n = lane; n < N; n += 64) { const float v = sM[n * MP + m]; sq += v * v; }
-                        sq = wave_sum(sq);
-                        if (lane == 0) sCn[m] = 1.0f / sqrtf(fmaxf(sq, 1e-12f));
-                    }
-                }
-            }
+            if (l == NL - 1) ntm_fwd_mem_norms<SMOOTH>(c, tid);      // the waves not running the top LSTM
             __syncthreads();
         }
-        // ------------------------------------------------------------ P3: unpack / output partials on h_{L-1}
-        if (tid < nslB * ncg) {
-            const int cg = tid % ncg, ks = tid / ncg;
-            const int k0 = ks * kperB, k1 = min(hid, k0 + kperB);
-            sPart4[ks * ncg + cg] = ntk_stream_matvec<(MAXT > 768 ? 2 : 4)>(Wa4 + cg, ncg, sHtop, k0, k1, hid);
-        }
+        // ------------------------------------------------------------ P3 .. P8 of ntm_seq_fwd.hip on h_{L-1} (ntm_phases.h)
+        ntm_fwd_unpack_partials<(MAXT > 768 ? 2 : 4)>(c, d, Wa4, tid);
         __syncthreads();
-        // ------------------------------------------------------------ P4: control activations
-        if (tid < PP) {
-            float v = a.Wa[(size_t)hid * PP + tid];
-            for (int ks = 0; ks < nslB; ++ks) v += sPart[ks * PP + tid];
-            float r = v;
-            if (tid < d.oB) r = ntm_tanh(v);
-            else if (tid < d.oG) r = ntm_softplus(v);
-            else if (tid < d.oS) r = ntm_sigmoid(v);
-            else if (tid < d.oY) r = v;
-            else if (tid < d.oE) r = ntm_softplus(v) + 1.0f;
-            else if (tid < d.oA) r = ntm_sigmoid(v);
-            else if (tid < d.P) r = ntm_tanh(v);
-            sU[tid] = r;
-            if (a.st_u) a.st_u[bt * PP + tid] = r;
-            if (tid >= d.P && tid < d.P + d.O) a.logits[bt * d.O + (tid - d.P)] = v;
-        }
+        ntm_fwd_controls(c, d, a, tid, bt);
         __syncthreads();
-        // ------------------------------------------------------------ P5-P7: addressing, one wave per head (ntm_seq_fwd.hip)
-        if (wave < H) {
-            const int h = wave;
-            float kss = 0.f;
-            for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; kss += kv * kv; }
-            const float kn = sqrtf(kss);                           // |k|, smooth cosine only
-            if constexpr (SMOOTH) {
-                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m];
-            } else {
-                const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
-                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
-            }
-            const float beta = sU[d.oB + h], g = sU[d.oG + h], gamma = sU[d.oY + h];
-            float swv[NTM_MAX_SHIFT_TAPS];
-            {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < NTM_MAX_SHIFT_TAPS; ++j) if (j < SS) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < NTM_MAX_SHIFT_TAPS; ++j) { swv[j] = (j < SS) ? ntm_exp(sU[d.oS + h * SS + j] - mx) : 0.f; sum += swv[j]; }
-#pragma unroll
-                for (int j = 0; j < NTM_MAX_SHIFT_TAPS; ++j) swv[j] = swv[j] / sum;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            float mxv = -INFINITY;
-            for (int n = lane; n < N; n += 64) {
-                float sim = 0.f;
-                for (int m = 0; m < Md; ++m) sim += sKs[h * Md + m] * sM[n * MP + m];
-                if constexpr (SMOOTH) sim = sim / (sCn[n] * kn + 1e-3f);
-                const float v = sim * beta;
-                sWg[h * N + n] = v;
-                mxv = fmaxf(mxv, v);
-            }
-            mxv = wave_max(mxv);
-            float sum = 0.f;
-            for (int n = lane; n < N; n += 64) { const float e = ntm_exp(sWg[h * N + n] - mxv); sWg[h * N + n] = e; sum += e; }
-            sum = wave_sum(sum);
-            for (int n = lane; n < N; n += 64) {
-                const float wc = sWg[h * N + n] / sum;
-                if (a.st_wc) a.st_wc[(bt * H + h) * N + n] = wc;
-                sWg[h * N + n] = wc * g + sW[h * N + n] * (1.0f - g);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int start = -((SS + 1) >> 1);                    // Py2 floor of -SS/2 (Q2)
-            float psum = 0.f;
-            for (int n = lane; n < N; n += 64) {
-                float wv = 0.f;
-#pragma unroll
-                for (int j = 0; j < NTM_MAX_SHIFT_TAPS; ++j) {
-                    if (j < SS) {
-                        int src = n + start + j;
-                        src = (src % N + N) % N;
-                        wv += swv[j] * sWg[h * N + src];
-                    }
-                }
-                if (a.st_wv) a.st_wv[(bt * H + h) * N + n] = wv;
-                const float pw = ntm_pow(wv, gamma);
-                sPw[h * N + n] = pw;
-                psum += pw;
-            }
-            psum = wave_sum(psum);
-            for (int n = lane; n < N; n += 64) {
-                const float w = sPw[h * N + n] / (psum + 1e-3f);
-                sW[h * N + n] = w;
-                if (a.st_w) a.st_w[(bt * H + h) * N + n] = w;
-            }
-        } else if (wave == H && lane == 0 && a.outputs) {
-            float mx = -INFINITY;
-            for (int j = 0; j < d.O; ++j) mx = fmaxf(mx, sU[d.P + j]);
-            float sum = 0.f;
-            for (int j = 0; j < d.O; ++j) sum += expf(sU[d.P + j] - mx);
-            for (int j = 0; j < d.O; ++j) a.outputs[bt * d.O + j] = expf(sU[d.P + j] - mx) / sum;
-        }
+        if (wave < H) ntm_fwd_head_wave<SMOOTH, NTM_MAX_SHIFT_TAPS>(c, d, a, wave, lane, bt);
+        else if (wave == H && lane == 0 && a.outputs) ntm_fwd_output_softmax(c, d, a, bt);
         __syncthreads();
-        // ------------------------------------------------------------ P8: write + read
-        auto update_M = [&]() {
-            for (int idx = tid; idx < N * Md; idx += T) {
-                const int n = idx / Md, m = idx - n * Md;
-                float E = 1.f, A = 0.f;
-                for (int j = 0; j < Wh; ++j) {
-                    const float ww = sW[(R + j) * N + n];
-                    E *= (1.0f - ww * sU[d.oE + j * Md + m]);
-                    A += ww * sU[d.oA + j * Md + m];
-                }
-                const float nm = sM[n * MP + m] * E + A;
-                sM[n * MP + m] = nm;
-                if (a.st_M) a.st_M[bt * N * Md + idx] = nm;
-            }
-        };
-        if (d.write_first) { update_M(); __syncthreads(); }
-        if (tid < nslR * RM) {
-            const int o = tid % RM, sl = tid / RM;
-            const int i = o / Md, m = o - i * Md;
-            const int n0 = sl * nperR, n1 = min(N, n0 + nperR);
-            float s0 = 0.f, s1 = 0.f;
-            int n = n0;
-            for (; n + 1 < n1; n += 2) {
-                s0 += sW[i * N + n] * sM[n * MP + m];
-                s1 += sW[i * N + n + 1] * sM[(n + 1) * MP + m];
-            }
-            if (n < n1) s0 += sW[i * N + n] * sM[n * MP + m];
-            sPart[sl * RM + o] = s0 + s1;
-        }
+        if (d.write_first) { ntm_fwd_update_M(c, d, a, tid, bt); __syncthreads(); }
+        ntm_fwd_read_partials(c, tid);
         __syncthreads();
-        if (!d.write_first) update_M();
-        if (tid < RM) {
-            float sr = 0.f;
-            for (int sl = 0; sl < nslR; ++sl) sr += sPart[sl * RM + tid];
-            sZ[tid] = sr;
-            if (a.st_read) a.st_read[bt * RM + tid] = sr;
-        }
+        if (!d.write_first) ntm_fwd_update_M(c, d, a, tid, bt);
+        ntm_fwd_read_finish(c, a, tid, bt);
         __syncthreads();
     }
 
@@ -423,8 +263,8 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
 }
 
 // ------------------------------------------------------------------------------------------------ BPTT
-// The generic form of ntm_seq_bwd_kernel (phases X1 .. B9 unchanged: heads, memory, unpack), then the LSTM backward once per
-// layer, top first: B10 (cell backward; the top layer adds dU . Wa^T to its carried dh) and B11 (d[input ; h_prev] = dpre . W^T,
+// Phases X1 .. B9 (heads, memory, unpack) are ntm_bwd_heads_step of ntm_phases.h in its generic form; then the LSTM backward once
+// per layer, top first: B10 (cell backward; the top layer adds dU . Wa^T to its carried dh) and B11 (d[input ; h_prev] = dpre . W^T,
 // streamed).  Layer k's input gradient is added to the carried dh_{k-1} (which layer k-1 consumes next), its h_prev part replaces
 // the carried dh_k; layer 0's splits into the carried dread and dh_0.  Fixed summation order, no atomics: bitwise reproducible.
 struct NtmDeepBwdArgs {
@@ -446,18 +286,7 @@ struct NtmDeepBwdArgs {
     float* dM0; float* dw0; float* dread0; float* dcs0;                // dcs0 [B,2*hid*L]
 };
 
-struct NtmDeepBwdLds {
-    int part, dM, G, Mp, Mt, dW, Wp, Wt, Wc, Wv, Wg, Dwv, Dsim, U, DU, DG, dZ, dC, Gt, Ct, Cp,
-        Khat, Ks, Kinv, Kss, Cinv, Css, C2, Dkhat, Sw, Red, Dmh, total;
-};
-
-// per-head reduction slots and the record prefetch depth, as ntm_seq_bwd.hip
-constexpr int DNQ = 1 + NTM_MAX_SHIFT_TAPS;
-constexpr int DQR1 = 0, DQR2 = 2, DQR3 = DQR2 + DNQ, DQR4 = DQR3 + 2;
-constexpr int DNQT = DQR4 + 1;    // (smooth cosine: one more, DQR4 + 1 = sum_n b rn)
-constexpr int DMAXM = 8;
-
-static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int ldhT, NtmDeepBwdLds& L) {
+static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int ldhT, NtmBwdLds& L) {
     const int MP = d.Md | 1, NM = d.N * MP, HN = d.H * d.N;
     const int nout = d.H * d.Md + 2 * d.Wh * d.Md;
     const int nslP = ntm_imin(ntm_imax(1, T / nout), d.N);
@@ -478,424 +307,58 @@ static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int
     L.Khat = take(d.H * d.Md); L.Ks = take(d.H * d.Md); L.Kinv = take(d.H); L.Kss = take(d.H);
     L.Cinv = take(ntm_norm_floats(d)); L.Css = take(d.Md); L.C2 = take(ntm_norm_floats(d)); L.Dkhat = take(d.H * d.Md);
     L.Sw = take(d.H * d.SS);
-    L.Red = take(d.H * (DNQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
+    L.Red = take(d.H * (NQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
     L.Dmh = take(d.N * (d.Md | 1));
     L.total = o;
 }
 
 template <int MAXT, int SIM = NTM_SIM_AS_CODED>             // SIM: as ntm_seq_bwd.hip
-__global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a, NtmDeepBwdLds L) {
+__global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a, NtmBwdLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr bool SMOOTH = SIM == NTM_SIM_SMOOTH_COSINE;
-    constexpr int NQS = DNQT + (SMOOTH ? 1 : 0);         // reduction slots per head
     const int b = blockIdx.x, tid0 = threadIdx.x, T = blockDim.x;
     const int N = a.d.N, Md = a.d.Md, MP = Md | 1, R = a.d.R, Wh = a.d.Wh;
     const int H = R + Wh, hid = a.d.hid, SS = a.d.SS, NL = a.s.L;
-    const int S = a.d.S, RM = R * Md, NW = N >> 6, NMd = N * Md, HN = H * N;
+    const int S = a.d.S, RM = R * Md, NMd = N * Md, HN = H * N;
     const size_t BS = (size_t)a.d.B * S;
-    struct {
-        int O, oK, oB, oG, oS, oY, oE, oA, P, PP;
-    } d;
-    d.O = a.d.O;
-    d.oK = 0; d.oB = H * Md; d.oG = d.oB + H; d.oS = d.oG + H; d.oY = d.oS + H * SS; d.oE = d.oY + H;
-    d.oA = d.oE + Wh * Md; d.P = d.oA + Wh * Md;
-    d.PP = (d.P + d.O + 3) & ~3;
+    const NtmCtl d = ntm_ctl(Md, R, Wh, hid, SS, a.d.O, a.d.write_first);
     const int PP = d.PP;
-    const bool wf = a.d.write_first != 0;
     const int ldhT = a.ldhT, cs_ld = 2 * hid * NL;
-    int tid = tid0, lane = tid0 & 63;
-
-    float* sPart = smem + L.part;
-    float* sdM = smem + L.dM;  float* sG = smem + L.G;  float* sMp = smem + L.Mp;  float* sMt = smem + L.Mt;
-    float* sdW = smem + L.dW;  float* sWp = smem + L.Wp; float* sWt = smem + L.Wt; float* sWc = smem + L.Wc;
-    float* sWv = smem + L.Wv;  float* sWg = smem + L.Wg; float* sDwv = smem + L.Dwv; float* sDsim = smem + L.Dsim;
-    float* sU = smem + L.U;    float* sDU = smem + L.DU; float* sDG = smem + L.DG;
-    float* sdZ = smem + L.dZ;  // carried [dread | dh_0 | .. | dh_{L-1}]
-    float* sdC = smem + L.dC;  // carried [dc_0 | .. | dc_{L-1}]
-    float* sGt = smem + L.Gt;  float* sCt = smem + L.Ct; float* sCp = smem + L.Cp;
-    float* sKhat = smem + L.Khat; float* sKs = smem + L.Ks; float* sKinv = smem + L.Kinv; float* sKss = smem + L.Kss;
-    float* sCinv = smem + L.Cinv; float* sCss = smem + L.Css; float* sC2 = smem + L.C2; float* sDkhat = smem + L.Dkhat;
-    float* sSw = smem + L.Sw;  float* sRed = smem + L.Red;  float* sDmh = smem + L.Dmh;
-    float* sRn = sCinv; float* sRc = sC2;  // smooth cosine: [N] row norms |M_prev[n]| and the row-norm coefficients where the [Md] column terms are
+    const NtmBwdSt c = ntm_bwd_state(smem, L, b, S, T, N, Md, R, Wh, hid, SS, PP, ldhT);
+    float* const sPart = c.sPart; float* const sdM = c.sdM; float* const sdW = c.sdW; float* const sDG = c.sDG;
+    float* const sdZ = c.sdZ;  // carried [dread | dh_0 | .. | dh_{L-1}]
+    float* const sdC = c.sdC;  // carried [dc_0 | .. | dc_{L-1}]
+    float* const sGt = c.sGt; float* const sCt = c.sCt; float* const sCp = c.sCp;
     f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart);
     const f32x4* Wb4 = reinterpret_cast<const f32x4*>(a.Wb);
+    const int nslH = c.nslH;
 
-    // thread roles
-    int hh = tid / N, nn = tid - hh * N;                // (head, slot) owner; active iff hh < H
-    bool hn = hh < H;
-    int wi = nn >> 6;
-    const int nout = H * Md + 2 * Wh * Md;
-    const int nslP = min(max(1, T / nout), N);
-    const int nperP = (N + nslP - 1) / nslP;
-    const int hg4 = ldhT >> 2;
-    const int nslH = max(1, T / hg4), nperH = (PP + nslH - 1) / nslH;
-    const int nslC = max(1, T / Md), nperC = (N + nslC - 1) / nslC;
-
-    // ---- prefetch registers for one step's records (the top layer's and the heads')
-    float pM[DMAXM], pMt[DMAXM], pWp = 0.f, pWt = 0.f, pWc = 0.f, pWv = 0.f, pU = 0.f, pCt = 0.f, pCp = 0.f, pDl = 0.f;
-    f32x4 pG = {0.f, 0.f, 0.f, 0.f};
-    auto prefetch = [&](int t) {
-        const size_t bt = (size_t)b * S + t;
-        const float* Mp = (t > 0) ? a.st_M + (bt - 1) * NMd : a.M0 + (size_t)b * NMd;
-#pragma unroll
-        for (int q = 0; q < DMAXM; ++q) {
-            const int idx = tid + q * T;
-            pM[q] = (idx < NMd) ? Mp[idx] : 0.f;
-            pMt[q] = (wf && idx < NMd) ? a.st_M[bt * NMd + idx] : 0.f;
-        }
-        if (hn) {
-            pWp = (t > 0) ? a.st_w[(bt - 1) * HN + tid] : a.w0[(size_t)b * HN + tid];
-            pWt = a.st_w[bt * HN + tid];
-            pWc = a.st_wc[bt * HN + tid];
-            pWv = a.st_wv[bt * HN + tid];
-        }
-        if (tid < PP) {
-            pU = a.st_u[bt * PP + tid];
-            pDl = (tid >= d.P && tid < d.P + d.O) ? a.dlogits[bt * d.O + (tid - d.P)] : 0.f;
-        }
-        if (tid < hid) {
-            pG = reinterpret_cast<const f32x4*>(a.st_gates)[bt * hid + tid];
-            pCt = a.st_c[bt * hid + tid];
-            pCp = (t > 0) ? a.st_c[(bt - 1) * hid + tid] : a.cs0[(size_t)b * cs_ld + 2 * hid * (NL - 1) + tid];
-        }
-    };
-    auto commit = [&]() {
-#pragma unroll
-        for (int q = 0; q < DMAXM; ++q) {
-            const int idx = tid + q * T;
-            if (idx < NMd) {
-                const int n = idx / Md, m = idx - n * Md;
-                sMp[n * MP + m] = pM[q];
-                if (wf) sMt[n * MP + m] = pMt[q];
-            }
-        }
-        if (hn) { sWp[tid] = pWp; sWt[tid] = pWt; sWc[tid] = pWc; sWv[tid] = pWv; }
-        if (tid < PP) { sU[tid] = pU; sDU[tid] = pDl; }
-        if (tid < hid) { reinterpret_cast<f32x4*>(sGt)[tid] = pG; sCt[tid] = pCt; sCp[tid] = pCp; }
-    };
-
-    // ---- carried gradients start from the (optional) gradient of the final state
-    for (int i = tid; i < NMd; i += T)
-        sdM[(i / Md) * MP + (i % Md)] = a.dM_fin ? a.dM_fin[(size_t)b * NMd + i] : 0.f;
-    for (int i = tid; i < HN; i += T) sdW[i] = a.dw_fin ? a.dw_fin[(size_t)b * HN + i] : 0.f;
-    for (int i = tid; i < RM + NL * hid; i += T) {
-        float v = 0.f;
-        if (i < RM) {
-            v = a.dread_fin ? a.dread_fin[(size_t)b * RM + i] : 0.f;
-        } else if (a.dcs_fin) {
-            const int l = (i - RM) / hid, j = (i - RM) - l * hid;
-            v = a.dcs_fin[(size_t)b * cs_ld + 2 * hid * l + hid + j];
-        }
-        sdZ[i] = v;
-    }
-    for (int i = tid; i < NL * hid; i += T) {
+    // ---- carried gradients start from the (optional) gradient of the final state; the records of the last step
+    ntm_bwd_init_carried(c, a, tid0);
+    for (int i = tid0; i < NL * hid; i += T) {
         const int l = i / hid, j = i - l * hid;
+        sdZ[RM + i] = a.dcs_fin ? a.dcs_fin[(size_t)b * cs_ld + 2 * hid * l + hid + j] : 0.f;
         sdC[i] = a.dcs_fin ? a.dcs_fin[(size_t)b * cs_ld + 2 * hid * l + j] : 0.f;
     }
-    prefetch(S - 1);
-    commit();
+    NtmBwdRecs rec = {};                                 // prefetch registers for one step's records (the top layer's and the heads')
+    const float* const c_init = a.cs0 + (size_t)b * cs_ld + 2 * hid * (NL - 1);
+    {
+        const NtmBwdWho w = ntm_bwd_who(tid0, N, H);
+        ntm_bwd_prefetch(c, d, a, w, rec, S - 1, c_init);
+        ntm_bwd_commit(c, d, w, rec);
+    }
     __syncthreads();
 
-    // per-head block reduction of nq values held by the (h, n) owner threads
-    auto red_write = [&](const float (&v)[DNQ], int nq, int base) {
-#pragma unroll
-        for (int q = 0; q < DNQ; ++q) {
-            if (q < nq) {
-                const float s = wave_sum(hn ? v[q] : 0.f);
-                if (hn && lane == 0) sRed[(hh * NQS + base + q) * NW + wi] = s;
-            }
-        }
-    };
-    auto red_read = [&](int h, int q) -> float {
-        float s = 0.f;
-        for (int w = 0; w < NW; ++w) s += sRed[(h * NQS + q) * NW + w];
-        return s;
-    };
-
     for (int t = S - 1; t >= 0; --t) {
-        {   // opaque thread id (see ntm_seq_bwd.hip)
-            int tid_op = tid0;
-            asm volatile("" : "+v"(tid_op));
-            tid = tid_op; lane = tid & 63;
-            hh = tid / N; nn = tid - hh * N; hn = hh < H; wi = nn >> 6;
-        }
+        int tid_op = tid0;                  // opaque thread id (see ntm_seq_bwd.hip)
+        asm volatile("" : "+v"(tid_op));
+        const NtmBwdWho w = ntm_bwd_who(tid_op, N, H);
+        const int tid = w.tid;
         const size_t bt = (size_t)b * S + t;
-        if (t > 0) prefetch(t - 1);
+        if (t > 0) ntm_bwd_prefetch(c, d, a, w, rec, t - 1, c_init);
 
-        // ------------------------------------------------ X1: memory-shaped elementwise + column norms + small vectors
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            float dMt = sdM[ai];
-            float dMr = 0.f;
-            for (int i = 0; i < R; ++i) dMr += sWt[i * N + n] * sdZ[i * Md + m];
-            if (wf) dMt += dMr;
-            float E = 1.f;
-            for (int j = 0; j < Wh; ++j) E *= (1.0f - sWt[(R + j) * N + n] * sU[d.oE + j * Md + m]);
-            sG[ai] = dMt;
-            sdM[ai] = dMt * E + (wf ? 0.f : dMr);
-        }
-        if constexpr (SMOOTH) {
-            if (tid < N) {         // row norms of M_prev, no clamp
-                float s = 0.f;
-                for (int m = 0; m < Md; ++m) { const float v = sMp[tid * MP + m]; s += v * v; }
-                sRn[tid] = sqrtf(s);
-            }
-        } else
-        if (tid < nslC * Md) {     // column sum of squares of M_prev (quirk Q1 normaliser)
-            const int m = tid % Md, sl = tid / Md;
-            const int n0 = sl * nperC, n1 = min(N, n0 + nperC);
-            float s = 0.f;
-            for (int n = n0; n < n1; ++n) { const float v = sMp[n * MP + m]; s += v * v; }
-            sPart[sl * Md + m] = s;
-        }
-        if (tid < H) {             // key norms and shift softmax
-            const int h = tid;
-            float ss = 0.f;
-            for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; ss += kv * kv; }
-            sKss[h] = ss;
-            sKinv[h] = SMOOTH ? sqrtf(ss) : 1.0f / sqrtf(fmaxf(ss, 1e-12f));        // smooth cosine: |k| itself
-            float mx = -INFINITY;
-            for (int j = 0; j < SS; ++j) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
-            float sum = 0.f;
-            for (int j = 0; j < SS; ++j) sum += expf(sU[d.oS + h * SS + j] - mx);
-            for (int j = 0; j < SS; ++j) sSw[h * SS + j] = expf(sU[d.oS + h * SS + j] - mx) / sum;
-        }
-        __syncthreads();
-
-        // ------------------------------------------------ X2: d(w_t) for every head; R1 sums
-        float dwt = 0.f, pw = 0.f, wv = 0.f, wt = 0.f, wc = 0.f, wp = 0.f, gam = 1.f, gate = 0.f;
-        float rv[DNQ];
-        if (!SMOOTH && tid < Md) {
-            float s = 0.f;
-            for (int sl = 0; sl < nslC; ++sl) s += sPart[sl * Md + tid];
-            sCss[tid] = s;
-            sCinv[tid] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-        }
-        if (hn) {
-            const int h = hh, n = nn;
-            float acc = sdW[tid];
-            if (h < R) {
-                const float* Mr = wf ? sMt : sMp;
-                for (int m = 0; m < Md; ++m) acc += sdZ[h * Md + m] * Mr[n * MP + m];
-            } else {
-                const int j = h - R;
-                for (int m = 0; m < Md; ++m) {
-                    float oth = 1.f;
-                    for (int j2 = 0; j2 < Wh; ++j2)
-                        if (j2 != j) oth *= (1.0f - sWt[(R + j2) * N + n] * sU[d.oE + j2 * Md + m]);
-                    const float g = sG[n * MP + m];
-                    const float Tj = g * sMp[n * MP + m] * oth;
-                    acc += -sU[d.oE + j * Md + m] * Tj + sU[d.oA + j * Md + m] * g;
-                }
-            }
-            dwt = acc;
-            wv = sWv[tid]; wt = sWt[tid]; wc = sWc[tid]; wp = sWp[tid];
-            gam = sU[d.oY + h]; gate = sU[d.oG + h];
-            pw = powf(wv, gam);
-            sWg[tid] = gate * wc + (1.0f - gate) * wp;
-            rv[0] = pw; rv[1] = dwt * wt;
-        }
-        red_write(rv, 2, DQR1);
-        __syncthreads();
-
-        // ------------------------------------------------ R2: sharpen backward, shift-weight sums
-        float dpw = 0.f, dwv = 0.f;
-        if (tid < H * Md) {        // normalised keys (needed from R4 on); smooth cosine: the keys as they are
-            const int h = tid / Md, m = tid - h * Md;
-            const float kh = SMOOTH ? sU[d.oK + tid] : sU[d.oK + tid] * sKinv[h];
-            sKhat[tid] = kh;
-            sKs[tid] = SMOOTH ? kh : kh * sCinv[m];
-        }
-        if (hn) {
-            const float den = red_read(hh, DQR1) + 1e-3f;
-            const float s2 = red_read(hh, DQR1 + 1);
-            dpw = (dwt - s2) / den;
-            dwv = (wv > 0.f) ? dpw * gam * pw / wv : 0.f;
-            sDwv[tid] = dwv;
-            rv[0] = (wv > 0.f) ? dpw * pw * logf(wv) : 0.f;        // d gamma
-            const int start = -((SS + 1) >> 1);
-#pragma unroll
-            for (int j = 0; j < DNQ - 1; ++j) {
-                if (j < SS) {
-                    int src = nn + start + j; src = (src % N + N) % N;
-                    rv[1 + j] = dwv * sWg[hh * N + src];            // d shift_j
-                }
-            }
-        }
-        red_write(rv, 1 + SS, DQR2);
-        __syncthreads();
-
-        // ------------------------------------------------ R3: shift + gate backward
-        float dwg = 0.f, dwc = 0.f;
-        float Sgam = 0.f, Ssw[DNQ - 1];
-        if (hn) {
-            Sgam = red_read(hh, DQR2);
-#pragma unroll
-            for (int j = 0; j < DNQ - 1; ++j) Ssw[j] = (j < SS) ? red_read(hh, DQR2 + 1 + j) : 0.f;
-            const int start = -((SS + 1) >> 1);
-            for (int j = 0; j < SS; ++j) {
-                int src = nn - (start + j); src = (src % N + N) % N;
-                dwg += sSw[hh * SS + j] * sDwv[hh * N + src];
-            }
-            sdW[tid] = (1.0f - gate) * dwg;                         // carried d(w_{t-1})
-            dwc = gate * dwg;
-            rv[0] = dwg * (wc - wp);                                // d g
-            rv[1] = wc * dwc;                                       // softmax backward inner product
-        }
-        red_write(rv, 2, DQR3);
-        __syncthreads();
-
-        // ------------------------------------------------ R4: content softmax backward
-        float Sg = 0.f, dv = 0.f;
-        if (hn) {
-            Sg = red_read(hh, DQR3);
-            const float Bs = red_read(hh, DQR3 + 1);
-            dv = wc * (dwc - Bs);
-            float sim = 0.f;
-            for (int m = 0; m < Md; ++m) sim += sKs[hh * Md + m] * sMp[nn * MP + m];
-            if constexpr (SMOOTH) {
-                // sim = dot / den, den = |M[n]||k| + 1e-3:  d dot = a = dsim / den,  d den = b = -dsim sim / den.  sDsim keeps a
-                // (B7 and the key sums below read it where they read dsim as coded); b |k| goes to the row-norm term of d M_prev
-                // (sDwv is free: its readers passed R3's barrier) and b |M[n]|, summed over the slots, to the norm term of d k
-                const float rn = sRn[nn], kn = sKinv[hh], den = rn * kn + 1e-3f;
-                sim = sim / den;
-                const float da = dv * sU[d.oB + hh] / den, db = -da * sim;
-                rv[0] = dv * sim;                                   // d beta
-                sDsim[tid] = da;
-                sDwv[tid] = db * kn;
-                rv[1] = db * rn;
-            } else {
-                rv[0] = dv * sim;                                   // d beta
-                sDsim[tid] = dv * sU[d.oB + hh];
-            }
-        }
-        red_write(rv, SMOOTH ? 2 : 1, DQR4);
-        __syncthreads();
-        if constexpr (SMOOTH) {
-            if (tid < N) {         // row-norm term: d M_prev[n][:] += M_prev[n][:] * (sum_h b[h][n] |k_h|) / |M[n]|, 0 at a zero row
-                float s = 0.f;
-                for (int h = 0; h < H; ++h) s += sDwv[h * N + tid];
-                const float rn = sRn[tid];
-                sRc[tid] = (rn > 0.f) ? s / rn : 0.f;
-            }
-        }
-        if (hn && nn == 0) {       // per-head scalar controls -> raw gradients
-            const int h = hh;
-            const float beta = sU[d.oB + h];
-            sDU[d.oB + h] = red_read(h, DQR4) * (1.0f - expf(-beta));                 // softplus' = 1 - exp(-softplus)
-            sDU[d.oG + h] = Sg * gate * (1.0f - gate);
-            sDU[d.oY + h] = Sgam * (1.0f - expf(-(gam - 1.0f)));
-            float dot = 0.f;
-#pragma unroll
-            for (int j = 0; j < DNQ - 1; ++j) if (j < SS) dot += sSw[h * SS + j] * Ssw[j];
-#pragma unroll
-            for (int j = 0; j < DNQ - 1; ++j) if (j < SS) sDU[d.oS + h * SS + j] = sSw[h * SS + j] * (Ssw[j] - dot);
-        }
-
-        // ------------------------------------------------ B7: dMhat = sum_h dsim khat; reductions over slots (keys, erase, add)
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md;
-            float dmh = 0.f;
-            for (int h = 0; h < H; ++h) dmh += sDsim[h * N + n] * sKhat[h * Md + m];
-            sDmh[n * MP + m] = dmh;
-        }
-        if (tid < nslP * nout) {
-            const int o = tid % nout, sl = tid / nout;
-            const int n0 = sl * nperP, n1 = min(N, n0 + nperP);
-            float s = 0.f;
-            if (o < H * Md) {                                  // sum_n dsim[h][n] * M_prev[n][m]
-                const int h = o / Md, m = o - h * Md;
-                float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-                int n = n0;
-                for (; n + 3 < n1; n += 4) {
-                    s += sDsim[h * N + n] * sMp[n * MP + m];
-                    s1 += sDsim[h * N + n + 1] * sMp[(n + 1) * MP + m];
-                    s2 += sDsim[h * N + n + 2] * sMp[(n + 2) * MP + m];
-                    s3 += sDsim[h * N + n + 3] * sMp[(n + 3) * MP + m];
-                }
-                for (; n < n1; ++n) s += sDsim[h * N + n] * sMp[n * MP + m];
-                s = (s + s1) + (s2 + s3);
-            } else {
-                const int o2 = o - H * Md;
-                const int which = o2 / (Wh * Md);              // 0: erase, 1: add
-                const int jm = o2 - which * Wh * Md;
-                const int j = jm / Md, m = jm - j * Md;
-                float sa = 0.f, sb = 0.f;
-                for (int n = n0; n < n1; ++n) {
-                    const float ww = sWt[(R + j) * N + n];
-                    const float g = sG[n * MP + m];
-                    float term;
-                    if (which == 0) {
-                        float oth = 1.f;
-                        for (int j2 = 0; j2 < Wh; ++j2)
-                            if (j2 != j) oth *= (1.0f - sWt[(R + j2) * N + n] * sU[d.oE + j2 * Md + m]);
-                        term = -ww * g * sMp[n * MP + m] * oth;
-                    } else {
-                        term = ww * g;
-                    }
-                    if ((n - n0) & 1) sb += term; else sa += term;
-                }
-                s = sa + sb;
-            }
-            sPart[sl * nout + o] = s;
-        }
-        __syncthreads();
-        // column-norm term: s_m = sum_n dMhat[n][m] * M_prev[n][m], one wave_sum per column (waves stride over m)
-        if constexpr (!SMOOTH)
-        for (int m = (tid >> 6); m < Md; m += (T >> 6)) {
-            float s = 0.f;
-            for (int n = lane; n < N; n += 64) s += sDmh[n * MP + m] * sMp[n * MP + m];
-            s = wave_sum(s);
-            if (lane == 0) {
-                const float ci = sCinv[m];
-                sC2[m] = (sCss[m] > 1e-12f) ? -ci * ci * ci * s : 0.f;
-            }
-        }
-        if (tid < nout) {
-            float s = 0.f;
-            for (int sl = 0; sl < nslP; ++sl) s += sPart[sl * nout + tid];
-            if (tid < H * Md) {
-                sDkhat[tid] = SMOOTH ? s : s * sCinv[tid % Md];
-            } else {
-                const int o2 = tid - H * Md;
-                const int which = o2 / (Wh * Md);
-                const int jm = o2 - which * Wh * Md;
-                if (which == 0) { const float e = sU[d.oE + jm]; sDU[d.oE + jm] = s * e * (1.0f - e); }
-                else { const float av = sU[d.oA + jm]; sDU[d.oA + jm] = s * (1.0f - av * av); }
-            }
-        }
-        __syncthreads();
-        if (tid < H * Md) {
-            const int h = tid / Md;
-            if constexpr (SMOOTH) {                                 // d k = sum_n a M_prev[n] + k / |k| * sum_n b |M[n]|, 0 through |k| = 0
-                const float kn = sKinv[h], kv = sU[d.oK + tid];
-                const float dk = sDkhat[tid] + ((kn > 0.f) ? kv / kn * red_read(h, DQR4 + 1) : 0.f);
-                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
-            } else {
-                float dot = 0.f;
-                for (int m = 0; m < Md; ++m) dot += sDkhat[h * Md + m] * sU[d.oK + h * Md + m];
-                const float ki = sKinv[h];
-                const float ck = (sKss[h] > 1e-12f) ? -ki * ki * ki * dot : 0.f;
-                const float kv = sU[d.oK + tid];
-                const float dk = ki * sDkhat[tid] + kv * ck;
-                sDU[d.oK + tid] = dk * (1.0f - kv * kv);
-            }
-        }
-        for (int idx = tid; idx < NMd; idx += T) {
-            const int n = idx / Md, m = idx - n * Md, ai = n * MP + m;
-            if constexpr (SMOOTH) sdM[ai] += sDmh[ai] + sMp[ai] * sRc[n];
-            else sdM[ai] += sCinv[m] * sDmh[ai] + sMp[ai] * sC2[m];
-        }
-        __syncthreads();
-        if (tid < PP) a.du[bt * PP + tid] = sDU[tid];
-
-        // ------------------------------------------------ B9: dU . Wa^T (partials; the top layer's B10 adds its carried dh)
-        if (tid < nslH * hg4) {
-            const int cg = tid % hg4, sl = tid / hg4;
-            const int c0 = sl * nperH, c1 = min(PP, c0 + nperH);
-            sPart4[sl * hg4 + cg] = ntk_stream_matvec<(MAXT > 768 ? 2 : 4)>(reinterpret_cast<const f32x4*>(a.WaT) + cg, hg4, sDU, c0, c1, PP - 1);
-        }
-        __syncthreads();
+        // ------------------------------------------------ X1 .. B9 (the B9 partials are left for the top layer's B10)
+        ntm_bwd_heads_step<MAXT, false, SMOOTH>(c, d, a, w, bt, [](int) { __syncthreads(); }, [](int) {});
 
         // ------------------------------------------------ B10 / B11 once per layer, top first
         for (int l = NL - 1; l >= 0; --l) {
@@ -947,16 +410,16 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
                 if (l > 0 && tid < hid) sdZ[base + tid] += s;     // d h_{l-1}(t): added to what step t+1 carried
                 else sdZ[base + tid] = s;                           // d h_l(t-1) (layer 0: d read_{t-1} and d h_0(t-1))
             }
-            if (l == NL - 1 && t > 0) commit();  // next (earlier) step's records: every reader of the old ones has passed a barrier
+            if (l == NL - 1 && t > 0) ntm_bwd_commit(c, d, w, rec);  // next (earlier) step's records: every reader of the old ones has passed a barrier
             __syncthreads();
         }
     }
 
     // ---- gradient of the initial state
-    for (int i = tid; i < NMd; i += T) a.dM0[(size_t)b * NMd + i] = sdM[(i / Md) * MP + (i % Md)];
-    for (int i = tid; i < HN; i += T) a.dw0[(size_t)b * HN + i] = sdW[i];
-    for (int i = tid; i < RM; i += T) a.dread0[(size_t)b * RM + i] = sdZ[i];
-    for (int i = tid; i < NL * hid; i += T) {
+    for (int i = tid0; i < NMd; i += T) a.dM0[(size_t)b * NMd + i] = sdM[(i / Md) * MP + (i % Md)];
+    for (int i = tid0; i < HN; i += T) a.dw0[(size_t)b * HN + i] = sdW[i];
+    for (int i = tid0; i < RM; i += T) a.dread0[(size_t)b * RM + i] = sdZ[i];
+    for (int i = tid0; i < NL * hid; i += T) {
         const int l = i / hid, j = i - l * hid;
         a.dcs0[(size_t)b * cs_ld + 2 * hid * l + j] = sdC[i];
         a.dcs0[(size_t)b * cs_ld + 2 * hid * l + hid + j] = sdZ[RM + i];
@@ -966,18 +429,8 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
 // ------------------------------------------------------------------------------------------------ host side
 int ntm_validate_dims(const NtmDims& d, const char* who);          // ntm_seq_fwd.hip
 
-// workgroup sizes: the single-layer kernels' rules (ntm_pick_threads / ntk_ntm_seq_bwd); the BPTT also covers the 2*hid
-// columns of a layer's input gradient
-static int ntm_deep_fwd_threads(const NtmDims& d) {
-    int want = ntm_imax(d.H * d.N, 3 * d.hid);
-    want = ntm_imax(want, d.hid + ntm_imax(d.Md, 4));
-    want = ntm_imax(want, d.PP + d.Md);
-    want = ntm_imax(want, d.H * d.Md + d.H + 1);
-    want = ntm_imax(want, ((d.hid + 63) / 64 + 1) * 64);
-    want = ntm_imax(want, (d.H + 1) * 64);
-    want = ((want + 63) / 64) * 64;
-    return want > 1024 ? 1024 : want;
-}
+// workgroup sizes: the forward takes the single-layer kernels' (ntm_pick_threads); the BPTT's rule is ntk_ntm_seq_bwd's and also
+// covers the 2*hid columns of a layer's input gradient
 
 static int ntm_deep_bwd_threads(const NtmDims& d) {
     int T = ntm_imax(d.H * d.N, 3 * d.hid);
@@ -991,7 +444,7 @@ static int ntm_deep_bwd_threads(const NtmDims& d) {
 struct NtmDeepPlan {
     int Tf, Tb;
     NtmLds Lf;
-    NtmDeepBwdLds Lb;
+    NtmBwdLds Lb;
     size_t lds_f, lds_b;
 };
 
@@ -1004,11 +457,11 @@ static int ntm_deep_plan(const NtmDims& d, const NtmDeepShape& s, NtmDeepPlan& p
     int rc = ntm_validate_dims(d, who);
     if (rc != NTK_OK) return rc;
     NTK_REQUIRE((d.hid % 4) == 0, NTK_ERR_UNSUPPORTED, "%s: hidden=%d must be a multiple of 4", who, d.hid);
-    NTK_REQUIRE(d.SS + 1 <= DNQ, NTK_ERR_UNSUPPORTED, "%s: shift space %d too wide", who, d.SS);
-    p.Tf = ntm_deep_fwd_threads(d);
+    NTK_REQUIRE(d.SS + 1 <= NQ, NTK_ERR_UNSUPPORTED, "%s: shift space %d too wide", who, d.SS);
+    p.Tf = ntm_pick_threads(d);
     NTK_REQUIRE(p.Tf >= d.N, NTK_ERR_UNSUPPORTED, "%s: mem_size %d exceeds the workgroup", who, d.N);
     p.Tb = ntm_deep_bwd_threads(d);
-    NTK_REQUIRE(p.Tb <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= DMAXM * p.Tb, NTK_ERR_UNSUPPORTED,
+    NTK_REQUIRE(p.Tb <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= MAXM * p.Tb, NTK_ERR_UNSUPPORTED,
                 "%s: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d exceed one workgroup", who, d.H * d.N, d.N * d.Md);
     ntm_deep_fwd_lds(d, s.L, p.Tf, p.Lf);
     ntm_deep_bwd_lds(d, s, p.Tb, ntm_align4(d.hid), p.Lb);

@@ -17,6 +17,10 @@
 //      content addressing of the reference's ops_test.py), beta, softmax over N, gate (:136-156),
 //      circular shift with taps -(r+1)..r-1 (Q2), sharpen with +1e-3 (Q4)   (ops.py:204-213, ntm_cell.py:173-176)
 //   P8 erase/add write and read (reads see the pre-write memory unless write_first, Q6) (:202-215)
+//
+// P2's normaliser and P3 .. P8 are the phase functions of ntm_phases.h, shared with ntm_seq_fwd_ws.hip and ntm_seq_deep.hip; the
+// barriers between them stay here.  This file's own: the gate product P1 with its resident rows and rolling prefetch, the LSTM
+// cell of P2, the initial / final state, the plan (ntm_fwd_plan, ntm_pick_threads, ntm_validate_dims) and the launcher.
 #include "ntm_common.h"
 
 // Diagnostic build only (-DNTK_CL_PROF): s_memtime shares per phase, accumulated in LDS by thread 0 of workgroup 0
@@ -37,7 +41,7 @@ extern "C" int ntk_ntm_fwd_prof(unsigned long long* out16) {
 #define NTM_STAMP(i) do { } while (0)
 #endif
 
-#include "ntm_fwd_args.h"
+#include "ntm_phases.h"
 #include <stdlib.h>
 
 // FIX = true specialises every dimension to the reference defaults the benchmark configs run
@@ -63,35 +67,15 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
     const int N = FIX ? 128 : a.d.N, Md = FIX ? 20 : a.d.Md, MP = Md | 1, R = FIX ? 4 : a.d.R, Wh = FIX ? 1 : a.d.Wh;
     const int H = R + Wh, hid = FIX ? 200 : a.d.hid, SS = FIX ? 3 : a.d.SS;
     const int S = a.d.S, RM = R * Md, K = RM + hid;
-    struct {
-        int O, oK, oB, oG, oS, oY, oE, oA, P, PP, ldz, ldh, write_first;
-    } d;
-    d.O = FIX ? 2 : a.d.O;
-    d.oK = 0; d.oB = H * Md; d.oG = d.oB + H; d.oS = d.oG + H; d.oY = d.oS + H * SS; d.oE = d.oY + H;
-    d.oA = d.oE + Wh * Md; d.P = d.oA + Wh * Md;
-    d.PP = (d.P + d.O + 3) & ~3; d.ldz = (K + 1 + 3) & ~3; d.ldh = (hid + 1 + 3) & ~3;
-    d.write_first = a.d.write_first;
+    const NtmCtl d = ntm_ctl(Md, R, Wh, hid, SS, FIX ? 2 : a.d.O, a.d.write_first);
     const int PP = d.PP;
+    const NtmFwdSt c = ntm_fwd_state(smem, L, T, N, Md, R, Wh, hid, SS, PP, RM);      // LDS pointers + decomposition of P3 .. P8
+    float* const sPart = c.sPart; float* const sM = c.sM; float* const sW = c.sW; float* const sZ = c.sZ;
+    float* const sC = smem + L.C;
 
-    float* sPart = smem + L.part;
-    float* sM = smem + L.M;
-    float* sW = smem + L.W;
-    float* sWg = smem + L.Wg;
-    float* sZ = smem + L.Z;
-    float* sC = smem + L.C;
-    float* sU = smem + L.U;
-    float* sKs = smem + L.Ks;
-    float* sCn = smem + L.Cn;              // [Md] inverse column norms of M (as coded) / [N] row norms of M (smooth cosine)
-    float* sPw = smem + L.Pw;              // [H][N] sharpened weights before normalisation
-
-    // work decomposition (uniform per kernel)
-    const int nsl = max(1, T / hid);                 // K-slices of the gate product
+    // K-slices of the gate product (uniform per kernel)
+    const int nsl = max(1, T / hid);
     const int kper = (K + nsl - 1) / nsl;
-    const int ncg = PP >> 2;                          // float4 column groups of the unpack product
-    const int nslB = min(max(1, T / ncg), hid);
-    const int kperB = (hid + nslB - 1) / nslB;
-    const int nslR = min(max(1, T / RM), N);          // N-slices of the read product
-    const int nperR = (N + nslR - 1) / nslR;
 
     // ---- load the initial state
     for (int i = tid; i < N * Md; i += T) sM[(i / Md) * MP + (i % Md)] = a.M0[(size_t)b * N * Md + i];
@@ -186,7 +170,7 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
         __syncthreads();
         NTM_STAMP(0);
         // ------------------------------------------------------------ P2: LSTM cell  ||  column norms of M (Q1)
-        const int wave = tid >> 6, nwaves = T >> 6;
+        const int wave = tid >> 6;
         if (tid < hid) {
             f32x4 g = xg;
             for (int ks = 0; ks < nsl; ++ks) g += sPart4[ks * hid + tid];
@@ -207,175 +191,31 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
         } else if (a.st_h && tid < d.ldh) {
             a.st_h[bt * d.ldh + tid] = (tid == hid) ? 1.f : 0.f;
         }
-        {   // waves not running the LSTM normalise the feature columns over the slot axis (tf.nn.l2_normalize, ops.py:150)
-            const int w0 = (hid + 63) >> 6;
-            if constexpr (SMOOTH) {
-                // smooth cosine: the row norms |M[n]|, a lane per slot (rows are MP = Md | 1 floats apart: no bank conflict), no clamp
-                if (wave >= w0) {
-                    for (int n = (wave - w0) * 64 + lane; n < N; n += (nwaves - w0) * 64) {
-                        float s = 0.f;
-                        for (int m = 0; m < Md; ++m) { const float v = sM[n * MP + m]; s += v * v; }
-                        sCn[n] = sqrtf(s);
-                    }
-                }
-            } else
-            if (wave >= w0) {
-                for (int m = wave - w0; m < Md; m += nwaves - w0) {
-                    float s = 0.f;
-                    for (int n = lane; n < N; n += 64) { const float v = sM[n * MP + m]; s += v * v; }
-                    s = wave_sum(s);
-                    if (lane == 0) sCn[m] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-                }
-            }
-        }
+        ntm_fwd_mem_norms<SMOOTH>(c, tid);       // the waves not running the LSTM
         __syncthreads();
         NTM_STAMP(1);
         // ------------------------------------------------------------ P3: unpack / output partials
-        if (tid < nslB * ncg) {
-            const int cg = tid % ncg, ks = tid / ncg;
-            const int k0 = ks * kperB, k1 = min(hid, k0 + kperB);
-            // explicit two-batch stream (the compiler otherwise keeps ONE load in flight, see common.h)
-            sPart4[ks * ncg + cg] = ntk_stream_matvec<(MAXT > 768 ? 2 : 4)>(Wa4 + cg, ncg, sZ + RM, k0, k1, hid);
-        }
+        ntm_fwd_unpack_partials<(MAXT > 768 ? 2 : 4)>(c, d, Wa4, tid);
         __syncthreads();
         NTM_STAMP(2);
         // ------------------------------------------------------------ P4: control activations
-        if (tid < PP) {
-            float v = a.Wa[(size_t)hid * PP + tid];
-            for (int ks = 0; ks < nslB; ++ks) v += sPart[ks * PP + tid];
-            float r = v;
-            if (tid < d.oB) r = ntm_tanh(v);                       // k      :133
-            else if (tid < d.oG) r = ntm_softplus(v);              // beta   :140
-            else if (tid < d.oS) r = ntm_sigmoid(v);               // g      :151
-            else if (tid < d.oY) r = v;                            // shift logits (softmax per head below)
-            else if (tid < d.oE) r = ntm_softplus(v) + 1.0f;       // gamma  :169-170
-            else if (tid < d.oA) r = ntm_sigmoid(v);               // erase  :193
-            else if (tid < d.P) r = ntm_tanh(v);                   // add    :195
-            sU[tid] = r;
-            if (a.st_u) a.st_u[bt * PP + tid] = r;
-            if (tid >= d.P && tid < d.P + d.O) a.logits[bt * d.O + (tid - d.P)] = v;
-        }
+        ntm_fwd_controls(c, d, a, tid, bt);
         __syncthreads();
         NTM_STAMP(3);
-        // ------------------------------------------------------------ P5-P7: one WAVE per head, no workgroup barrier inside:
-        // key scaling, similarity (Q1), beta, softmax over N, gate, circular shift (Q2), sharpen (Q4)
-        if (wave < H) {
-            const int h = wave;
-            float kss = 0.f;
-            for (int m = 0; m < Md; ++m) { const float kv = sU[d.oK + h * Md + m]; kss += kv * kv; }
-            const float kn = sqrtf(kss);                           // |k|, smooth cosine only
-            if constexpr (SMOOTH) {
-                for (int m = lane; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m];
-            } else {
-                const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
-                if (lane < Md) sKs[h * Md + lane] = sU[d.oK + h * Md + lane] * kinv * sCn[lane];
-                for (int m = lane + 64; m < Md; m += 64) sKs[h * Md + m] = sU[d.oK + h * Md + m] * kinv * sCn[m];
-            }
-            const float beta = sU[d.oB + h], g = sU[d.oG + h], gamma = sU[d.oY + h];
-            constexpr int MAXSS = FIX ? 3 : NTM_MAX_SHIFT_TAPS;     // (a compile-time 3 taps at the benchmark shape)
-            float swv[MAXSS];                                      // softmax of the shift logits (ntm_cell.py:161)
-            {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int j = 0; j < MAXSS; ++j) if (j < SS) mx = fmaxf(mx, sU[d.oS + h * SS + j]);
-                float sum = 0.f;
-#pragma unroll
-                for (int j = 0; j < MAXSS; ++j) { swv[j] = (j < SS) ? ntm_exp(sU[d.oS + h * SS + j] - mx) : 0.f; sum += swv[j]; }
-#pragma unroll
-                for (int j = 0; j < MAXSS; ++j) swv[j] = swv[j] / sum;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            float mxv = -INFINITY;
-            for (int n = lane; n < N; n += 64) {
-                float sim = 0.f;
-                for (int m = 0; m < Md; ++m) sim += sKs[h * Md + m] * sM[n * MP + m];
-                if constexpr (SMOOTH) sim = sim / (sCn[n] * kn + 1e-3f);
-                const float v = sim * beta;
-                sWg[h * N + n] = v;
-                mxv = fmaxf(mxv, v);
-            }
-            mxv = wave_max(mxv);
-            float sum = 0.f;
-            for (int n = lane; n < N; n += 64) { const float e = ntm_exp(sWg[h * N + n] - mxv); sWg[h * N + n] = e; sum += e; }
-            sum = wave_sum(sum);
-            for (int n = lane; n < N; n += 64) {
-                const float wc = sWg[h * N + n] / sum;
-                if (a.st_wc) a.st_wc[(bt * H + h) * N + n] = wc;
-                sWg[h * N + n] = wc * g + sW[h * N + n] * (1.0f - g);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int start = -((SS + 1) >> 1);                    // Py2 floor of -SS/2 (Q2): 3 -> -2
-            float psum = 0.f;
-            for (int n = lane; n < N; n += 64) {
-                float wv = 0.f;
-#pragma unroll
-                for (int j = 0; j < MAXSS; ++j) {
-                    if (j < SS) {
-                        int src = n + start + j;
-                        src = (src % N + N) % N;
-                        wv += swv[j] * sWg[h * N + src];
-                    }
-                }
-                if (a.st_wv) a.st_wv[(bt * H + h) * N + n] = wv;
-                const float pw = ntm_pow(wv, gamma);
-                sPw[h * N + n] = pw;
-                psum += pw;
-            }
-            psum = wave_sum(psum);
-            for (int n = lane; n < N; n += 64) {
-                const float w = sPw[h * N + n] / (psum + 1e-3f);
-                sW[h * N + n] = w;
-                if (a.st_w) a.st_w[(bt * H + h) * N + n] = w;
-            }
-        } else if (wave == H && lane == 0 && a.outputs) {
-            float mx = -INFINITY;
-            for (int j = 0; j < d.O; ++j) mx = fmaxf(mx, sU[d.P + j]);
-            float sum = 0.f;
-            for (int j = 0; j < d.O; ++j) sum += expf(sU[d.P + j] - mx);
-            for (int j = 0; j < d.O; ++j) a.outputs[bt * d.O + j] = expf(sU[d.P + j] - mx) / sum;
-        }
+        // ------------------------------------------------------------ P5-P7: one WAVE per head, no workgroup barrier inside;
+        // the wave behind them takes the softmax of the output logits
+        constexpr int MAXSS = FIX ? 3 : NTM_MAX_SHIFT_TAPS;         // (a compile-time 3 taps at the benchmark shape)
+        if (wave < H) ntm_fwd_head_wave<SMOOTH, MAXSS>(c, d, a, wave, lane, bt);
+        else if (wave == H && lane == 0 && a.outputs) ntm_fwd_output_softmax(c, d, a, bt);
         __syncthreads();
         NTM_STAMP(4);
         // ------------------------------------------------------------ P8: write + read
-        auto update_M = [&]() {
-            for (int idx = tid; idx < N * Md; idx += T) {
-                const int n = idx / Md, m = idx - n * Md;
-                float E = 1.f, A = 0.f;
-                for (int j = 0; j < Wh; ++j) {
-                    const float ww = sW[(R + j) * N + n];
-                    E *= (1.0f - ww * sU[d.oE + j * Md + m]);
-                    A += ww * sU[d.oA + j * Md + m];
-                }
-                const float nm = sM[n * MP + m] * E + A;
-                sM[n * MP + m] = nm;
-                if (a.st_M) a.st_M[bt * N * Md + idx] = nm;
-            }
-        };
-        if (d.write_first) { update_M(); __syncthreads(); }
-        if (tid < nslR * RM) {
-            const int o = tid % RM, sl = tid / RM;
-            const int i = o / Md, m = o - i * Md;
-            const int n0 = sl * nperR, n1 = min(N, n0 + nperR);
-            float s0 = 0.f, s1 = 0.f;                 // two chains: the loop is bound by the add latency, not by LDS
-            int n = n0;
-            for (; n + 1 < n1; n += 2) {
-                s0 += sW[i * N + n] * sM[n * MP + m];
-                s1 += sW[i * N + n + 1] * sM[(n + 1) * MP + m];
-            }
-            if (n < n1) s0 += sW[i * N + n] * sM[n * MP + m];
-            sPart[sl * RM + o] = s0 + s1;
-        }
+        if (d.write_first) { ntm_fwd_update_M(c, d, a, tid, bt); __syncthreads(); }
+        ntm_fwd_read_partials(c, tid);
         __syncthreads();
         NTM_STAMP(5);
-        if (!d.write_first) update_M();
-        if (tid < RM) {
-            float s = 0.f;
-            for (int sl = 0; sl < nslR; ++sl) s += sPart[sl * RM + tid];
-            sZ[tid] = s;
-            if (a.st_read) a.st_read[bt * RM + tid] = s;
-        }
+        if (!d.write_first) ntm_fwd_update_M(c, d, a, tid, bt);
+        ntm_fwd_read_finish(c, a, tid, bt);
         __syncthreads();
         NTM_STAMP(6);
     }
@@ -394,7 +234,8 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_kernel(NtmFwdArgs a, NtmLds 
 }
 
 // pick the workgroup size: whole waves, enough threads for N slots x >=1 head, hid units + Md columns
-static int ntm_pick_threads(const NtmDims& d) {
+// (the deep kernels' forward takes the same size, ntm_seq_deep.hip)
+int ntm_pick_threads(const NtmDims& d) {
     int want = ntm_imax(d.H * d.N, 3 * d.hid);
     want = ntm_imax(want, d.hid + ntm_imax(d.Md, 4));
     want = ntm_imax(want, d.PP + d.Md);

@@ -19,8 +19,10 @@
 // run beside), and their loads stay in flight across the barriers (__syncthreads() waits for LDS traffic only on gfx950).
 // One workgroup per sequence, one CU per workgroup, no communication between workgroups: the summation ORDER of a gate
 // differs from ntm_seq_fwd_kernel's (read rows in two slices + h rows in one chain), the arithmetic does not.
+// The compute waves take P2's normaliser, P3 .. P7 and the read from ntm_phases.h with this kernel's compile-time dimensions; the
+// gate product, the LSTM cell, the memory write, the stream waves and the barriers (WS_BARRIER) are this file's own.
 // Reference: ntm_cell.py:45-50, :101-105 (controller), ops.py / ntm_cell.py lines as cited in ntm_seq_fwd.hip.
-#include "ntm_fwd_args.h"
+#include "ntm_phases.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -47,7 +49,6 @@ extern "C" int ntk_ntm_ws_prof(unsigned long long* out32) {
 namespace {
 
 constexpr int WN = 128, WMd = 20, WMP = 21, WR = 4, WH = 5, Whid = 200, WSS = 3, WRM = 80, WK = 280, WO = 2;
-constexpr int WoB = 100, WoG = 105, WoS = 110, WoY = 125, WoE = 130, WoA = 150, WP = 170, WPP = 172, Wldz = 284, Wldh = 204;
 constexpr int TC = 512, TA = 768;          // compute threads, all threads
 constexpr int RESQ = 20, RESL = 20;        // read rows per compute thread resident in registers / in LDS (2 slices x 40 rows)
 constexpr int NG = Whid / 4;               // groups of four h rows per lap (50)
@@ -67,18 +68,13 @@ __global__ __launch_bounds__(TA) void ntm_seq_fwd_ws_kernel(NtmFwdArgs a, NtmLds
     static_assert(PFIN >= 0 && PFIN <= NG && Whid % RING == 0, "groups per lap; the ring's phase is static when it divides the lap");
     const int b = blockIdx.x, tid0 = threadIdx.x;
     const int S = a.d.S;
-    constexpr int N = WN, Md = WMd, MP = WMP, R = WR, H = WH, hid = Whid, SS = WSS, RM = WRM, K = WK, PP = WPP;
+    constexpr int N = WN, Md = WMd, MP = WMP, R = WR, Wh = 1, H = WH, hid = Whid, SS = WSS, RM = WRM, K = WK;
 
     float* sPart = smem + L.part;
     float* sM = smem + L.M;
     float* sW = smem + L.W;
-    float* sWg = smem + L.Wg;
     float* sZ = smem + L.Z;
     float* sC = smem + L.C;
-    float* sU = smem + L.U;
-    float* sKs = smem + L.Ks;
-    float* sCn = smem + L.Cn;
-    float* sPw = smem + L.Pw;
     f32x4* sWres4 = reinterpret_cast<f32x4*>(smem + L.total + 32);                           // [RESL][400]
     f32x4* sPartH4 = reinterpret_cast<f32x4*>(smem + L.total + 32 + RESL * 400 * 4);        // [200]: h rows . Wr for the coming step
     f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart);
@@ -170,10 +166,9 @@ __global__ __launch_bounds__(TA) void ntm_seq_fwd_ws_kernel(NtmFwdArgs a, NtmLds
 
     // =============================================================== compute waves (512 threads)
     constexpr int T = TC;
-    constexpr int ncg = PP >> 2;                                     // 43 float4 column groups of the unpack product
-    constexpr int nslB = 11, kperB = (hid + nslB - 1) / nslB;        // T / ncg slices of the hidden units
-    constexpr int nslR = 6, nperR = (N + nslR - 1) / nslR;           // T / RM slices of the slots in the read product
-    static_assert(nslB * ncg <= T && nslR * RM <= T, "decomposition");
+    // the shared phases (ntm_phases.h) over the compute threads: every dimension is a compile-time constant and folds
+    const NtmCtl d = ntm_ctl(Md, R, Wh, hid, SS, WO, 0);
+    const NtmFwdSt c = ntm_fwd_state(smem, L, T, N, Md, R, Wh, hid, SS, d.PP, RM);
     f32x4 wres[RESQ];
     if (tid0 < 2 * hid) {
         const int j = tid0 % hid, k0 = (tid0 / hid) * (RESQ + RESL);
@@ -196,7 +191,7 @@ __global__ __launch_bounds__(TA) void ntm_seq_fwd_ws_kernel(NtmFwdArgs a, NtmLds
             xg += Wr4[(size_t)K * hid + tid];
         }
         if (a.st_z) {
-            for (int i = tid; i < Wldz; i += T) a.st_z[bt * Wldz + i] = (i < K) ? sZ[i] : (i == K ? 1.f : 0.f);
+            for (int i = tid; i < d.ldz; i += T) a.st_z[bt * d.ldz + i] = (i < K) ? sZ[i] : (i == K ? 1.f : 0.f);
         }
         if (tid < 2 * hid) {
             const int k0 = (tid / hid) * (RESQ + RESL);
@@ -224,139 +219,36 @@ __global__ __launch_bounds__(TA) void ntm_seq_fwd_ws_kernel(NtmFwdArgs a, NtmLds
                 reinterpret_cast<f32x4*>(a.st_gates)[bt * hid + tid] = ga;
                 a.st_c[bt * hid + tid] = c2;
             }
-            if (a.st_h) a.st_h[bt * Wldh + tid] = h2;
-        } else if (a.st_h && tid < Wldh) {
-            a.st_h[bt * Wldh + tid] = (tid == hid) ? 1.f : 0.f;
+            if (a.st_h) a.st_h[bt * d.ldh + tid] = h2;
+        } else if (a.st_h && tid < d.ldh) {
+            a.st_h[bt * d.ldh + tid] = (tid == hid) ? 1.f : 0.f;
         }
-        {   // waves 4..7 normalise the feature columns over the slot axis (tf.nn.l2_normalize, ops.py:150)
-            constexpr int w0 = (hid + 63) >> 6, nwaves = T >> 6;
-            if (wave >= w0) {
-                for (int m = wave - w0; m < Md; m += nwaves - w0) {
-                    float s = 0.f;
-                    for (int n = lane; n < N; n += 64) { const float v = sM[n * MP + m]; s += v * v; }
-                    s = wave_sum(s);
-                    if (lane == 0) sCn[m] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-                }
-            }
-        }
+        ntm_fwd_mem_norms<false>(c, tid);            // waves 4..7
         WS_BARRIER(0, 1);                                            // B2
         // ------------------------------------------------------------ P3: unpack / output partials (Wa streams: 137 KB)
-        if (tid < nslB * ncg) {
-            const int cg = tid % ncg, ks = tid / ncg;
-            const int k0 = ks * kperB, k1 = min(hid, k0 + kperB);
-            sPart4[ks * ncg + cg] = ntk_stream_matvec<4>(Wa4 + cg, ncg, sZ + RM, k0, k1, hid);
-        }
+        ntm_fwd_unpack_partials<4>(c, d, Wa4, tid);
         WS_BARRIER(0, 2);                                            // B3
         // ------------------------------------------------------------ P4: control activations
-        if (tid < PP) {
-            float v = a.Wa[(size_t)hid * PP + tid];
-            for (int ks = 0; ks < nslB; ++ks) v += sPart[ks * PP + tid];
-            float r = v;
-            if (tid < WoB) r = ntm_tanh(v);                       // k      :133
-            else if (tid < WoG) r = ntm_softplus(v);              // beta   :140
-            else if (tid < WoS) r = ntm_sigmoid(v);               // g      :151
-            else if (tid < WoY) r = v;                            // shift logits (softmax per head below)
-            else if (tid < WoE) r = ntm_softplus(v) + 1.0f;       // gamma  :169-170
-            else if (tid < WoA) r = ntm_sigmoid(v);               // erase  :193
-            else if (tid < WP) r = ntm_tanh(v);                   // add    :195
-            sU[tid] = r;
-            if (a.st_u) a.st_u[bt * PP + tid] = r;
-            if (tid >= WP && tid < WP + WO) a.logits[bt * WO + (tid - WP)] = v;
-        }
+        ntm_fwd_controls(c, d, a, tid, bt);
         WS_BARRIER(0, 3);                                            // B4
         // ------------------------------------------------------------ P5-P7: one WAVE per head, no workgroup barrier inside
-        if (wave < H) {
-            const int h = wave;
-            float kss = 0.f;
-            for (int m = 0; m < Md; ++m) { const float kv = sU[h * Md + m]; kss += kv * kv; }
-            const float kinv = 1.0f / sqrtf(fmaxf(kss, 1e-12f));
-            if (lane < Md) sKs[h * Md + lane] = sU[h * Md + lane] * kinv * sCn[lane];
-            const float beta = sU[WoB + h], g = sU[WoG + h], gamma = sU[WoY + h];
-            float swv[SS];                                         // softmax of the shift logits (ntm_cell.py:161)
-            {
-                float mx = -INFINITY;
-#pragma unroll
-                for (int jj = 0; jj < SS; ++jj) mx = fmaxf(mx, sU[WoS + h * SS + jj]);
-                float sum = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < SS; ++jj) { swv[jj] = ntm_exp(sU[WoS + h * SS + jj] - mx); sum += swv[jj]; }
-#pragma unroll
-                for (int jj = 0; jj < SS; ++jj) swv[jj] = swv[jj] / sum;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            float mxv = -INFINITY;
-            for (int n = lane; n < N; n += 64) {
-                float sim = 0.f;
-                for (int m = 0; m < Md; ++m) sim += sKs[h * Md + m] * sM[n * MP + m];
-                const float v = sim * beta;
-                sWg[h * N + n] = v;
-                mxv = fmaxf(mxv, v);
-            }
-            mxv = wave_max(mxv);
-            float sum = 0.f;
-            for (int n = lane; n < N; n += 64) { const float e = ntm_exp(sWg[h * N + n] - mxv); sWg[h * N + n] = e; sum += e; }
-            sum = wave_sum(sum);
-            for (int n = lane; n < N; n += 64) {
-                const float wc = sWg[h * N + n] / sum;
-                if (a.st_wc) a.st_wc[(bt * H + h) * N + n] = wc;
-                sWg[h * N + n] = wc * g + sW[h * N + n] * (1.0f - g);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            constexpr int start = -((SS + 1) >> 1);                // Py2 floor of -SS/2 (Q2): 3 -> -2
-            float psum = 0.f;
-            for (int n = lane; n < N; n += 64) {
-                float wv = 0.f;
-#pragma unroll
-                for (int jj = 0; jj < SS; ++jj) wv += swv[jj] * sWg[h * N + ((n + start + jj + N) & (N - 1))];
-                if (a.st_wv) a.st_wv[(bt * H + h) * N + n] = wv;
-                const float pw = ntm_pow(wv, gamma);
-                sPw[h * N + n] = pw;
-                psum += pw;
-            }
-            psum = wave_sum(psum);
-            for (int n = lane; n < N; n += 64) {
-                const float w = sPw[h * N + n] / (psum + 1e-3f);
-                sW[h * N + n] = w;
-                if (a.st_w) a.st_w[(bt * H + h) * N + n] = w;
-            }
-        } else if (wave == H && lane == 0 && a.outputs) {
-            const float l0 = sU[WP], l1 = sU[WP + 1], mx = fmaxf(l0, l1);
-            const float e0 = expf(l0 - mx), e1 = expf(l1 - mx);
-            a.outputs[bt * WO] = e0 / (e0 + e1);
-            a.outputs[bt * WO + 1] = e1 / (e0 + e1);
-        }
+        if (wave < H) ntm_fwd_head_wave<false, SS>(c, d, a, wave, lane, bt);
+        else if (wave == H && lane == 0 && a.outputs) ntm_fwd_output_softmax(c, d, a, bt);
         WS_BARRIER(0, 4);                                            // B5
         // ------------------------------------------------------------ P8: read (of the PRE-write memory, Q6), then write
-        if (tid < nslR * RM) {
-            const int o = tid % RM, sl = tid / RM;
-            const int i = o / Md, m = o - i * Md;
-            const int n0 = sl * nperR, n1 = min(N, n0 + nperR);
-            float s0 = 0.f, s1 = 0.f;                 // two chains: the loop is bound by the add latency, not by LDS
-            int n = n0;
-            for (; n + 1 < n1; n += 2) {
-                s0 += sW[i * N + n] * sM[n * MP + m];
-                s1 += sW[i * N + n + 1] * sM[(n + 1) * MP + m];
-            }
-            if (n < n1) s0 += sW[i * N + n] * sM[n * MP + m];
-            sPart[sl * RM + o] = s0 + s1;
-        }
+        ntm_fwd_read_partials(c, tid);
         WS_BARRIER(0, 5);                                            // B6
+        // the write keeps this kernel's own one-write-head expression: the shared ntm_fwd_update_M accumulates over the write heads
+        // from E = 1, A = 0, which the compiler contracts as fma(M, E, ww a) where this form gives fma(ww, a, M E) -- one rounding
+        // apart, and this kernel's results stay the bits they were
         for (int idx = tid; idx < N * Md; idx += T) {
             const int n = idx / Md, m = idx - n * Md;
             const float ww = sW[R * N + n];
-            const float nm = sM[n * MP + m] * (1.0f - ww * sU[WoE + m]) + ww * sU[WoA + m];
+            const float nm = sM[n * MP + m] * (1.0f - ww * c.sU[d.oE + m]) + ww * c.sU[d.oA + m];
             sM[n * MP + m] = nm;
             if (a.st_M) a.st_M[bt * N * Md + idx] = nm;
         }
-        if (tid < RM) {
-            float s = 0.f;
-#pragma unroll
-            for (int sl = 0; sl < nslR; ++sl) s += sPart[sl * RM + tid];
-            sZ[tid] = s;
-            if (a.st_read) a.st_read[bt * RM + tid] = s;
-        }
+        ntm_fwd_read_finish(c, a, tid, bt);
         WS_BARRIER(0, 6);                                            // B7
     }
 
