@@ -142,6 +142,19 @@ __device__ __forceinline__ float group_sum_rt(float v, int G) {
     }
 }
 
+__device__ __forceinline__ float cl_dot4(const f32x4& x, const f32x4& y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]; }
+
+// softmax of one row of length N held in LDS
+__device__ __forceinline__ void cl_softmax_row(float* r, int N, int lane) {      // one wave, in place
+    float mx = -INFINITY;
+    for (int n = lane; n < N; n += 64) mx = fmaxf(mx, r[n]);
+    mx = wave_max(mx);
+    float s = 0.f;
+    for (int n = lane; n < N; n += 64) { const float e = expf(r[n] - mx); r[n] = e; s += e; }
+    s = wave_sum(s);
+    for (int n = lane; n < N; n += 64) r[n] = r[n] / s;
+}
+
 // Reciprocal / square root on the hardware transcendental units (v_rcp_f32, v_sqrt_f32: ~1 ulp).  The per-row score and
 // norm terms of the memory passes are computed by every lane of a row's group: with IEEE division (a ~10-instruction
 // Newton sequence each) they were a third of the backward memory passes' instructions.

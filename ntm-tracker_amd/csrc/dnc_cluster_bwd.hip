@@ -118,7 +118,6 @@ struct DncClBwdArgs {
     unsigned* xcc;         // [B][k] handshake words of cl_same_xcd (control block)
 };
 
-__device__ __forceinline__ float cl_dot4(const f32x4& x, const f32x4& y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]; }
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MAXQ = 8;       // memory rows per 16-lane group (N <= 256)

@@ -92,17 +92,6 @@ struct DncClFwdArgs {
     unsigned* xcc;         // [B][k] handshake words of cl_same_xcd (control block)
 };
 
-__device__ __forceinline__ void cl_softmax_row(float* r, int N, int lane) {      // one wave, in place
-    float mx = -INFINITY;
-    for (int n = lane; n < N; n += 64) mx = fmaxf(mx, r[n]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int n = lane; n < N; n += 64) { const float e = expf(r[n] - mx); r[n] = e; s += e; }
-    s = wave_sum(s);
-    for (int n = lane; n < N; n += 64) r[n] = r[n] / s;
-}
-
-__device__ __forceinline__ float cl_dot4(const f32x4& x, const f32x4& y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]; }
 __device__ __forceinline__ float cl_pair_sum(float v) { return v + ntk_dpp<0xB1>(v); }      // lanes 2p, 2p+1
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));

@@ -122,7 +122,6 @@ struct DncMpBwdArgs {
     float* mbox; unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
 };
 
-__device__ __forceinline__ float mpb_dot4(const f32x4& x, const f32x4& y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]; }
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 // sum over the lane groups of a wave (groups of LPR consecutive lanes; lanes with equal index inside their group are added):
@@ -378,13 +377,13 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                     const int nl = grp + NG * q;
                     const bool rok = nl < NR;
                     const f32x4 m = Mt[q];
-                    const float nm = cl_sqrt(group_sum_rt(mpb_dot4(m, m), LPR) + EPS);
+                    const float nm = cl_sqrt(group_sum_rt(cl_dot4(m, m), LPR) + EPS);
                     if (gl == 0 && rok) sNMr[nl] = nm;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         if (i < R) {
-                            const float t1 = group_sum_rt(mpb_dot4(dr[i], m), LPR);
-                            const float dot = group_sum_rt(mpb_dot4(kr[i], m), LPR);
+                            const float t1 = group_sum_rt(cl_dot4(dr[i], m), LPR);
+                            const float dot = group_sum_rt(cl_dot4(kr[i], m), LPR);
                             if (gl == 0 && rok) {
                                 cl_store(slot1 + i * NR + nl, sgRW[i * N + row0 + nl] + t1, plain);
                                 cl_store(slot1 + (R + i) * NR + nl, dot * cl_rcp(sSC[i] * nm + EPS), plain);
@@ -569,8 +568,8 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                     }
                     gMr[q] = gq;                                   // now d(M_{t-1}) (content part added in B10b)
                     t1 = group_sum_rt(t1, LPR);
-                    const float dot = group_sum_rt(mpb_dot4(kp, mp), LPR);
-                    const float nm = cl_sqrt(group_sum_rt(mpb_dot4(mp, mp), LPR) + EPS);
+                    const float dot = group_sum_rt(cl_dot4(kp, mp), LPR);
+                    const float nm = cl_sqrt(group_sum_rt(cl_dot4(mp, mp), LPR) + EPS);
                     if (gl == 0 && rok) {
                         sNMw[nl] = nm;
                         cl_store(slot2 + Q.oT1 + nl, t1, plain);
@@ -644,7 +643,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                                 if (i < R) {
                                     const float dfa = rm1[i] * sG[i * N + ra], rwpa = sRWp[i * N + ra];
                                     gq += dfa * rwpb[i] + rwpa * dbb[i];
-                                    rowRW[i] = mpb_dot4(dbb[i], lt);
+                                    rowRW[i] = cl_dot4(dbb[i], lt);
                                     colRW[i] += dfa * lt;
                                 }
                             }
@@ -981,9 +980,9 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                     const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wi) + (size_t)(u0 + ju) * C.icg;
                     const int c1 = kw1 + ((l8 - kw1) & 7);             // first column >= kw1 of this lane's residue class
 #pragma unroll 8
-                    for (int c = l8; c < kw0; c += 8) dh_acc[p2] += mpb_dot4(dx4[c], wp[c]);
+                    for (int c = l8; c < kw0; c += 8) dh_acc[p2] += cl_dot4(dx4[c], wp[c]);
 #pragma unroll 8
-                    for (int c = c1; c < C.icg; c += 8) dh_acc[p2] += mpb_dot4(dx4[c], wp[c]);
+                    for (int c = c1; c < C.icg; c += 8) dh_acc[p2] += cl_dot4(dx4[c], wp[c]);
                 }
             }
         }
@@ -1011,7 +1010,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                 const int ju = (tid >> 3) + 64 * p2;
                 if (ju < nU) {
                     const f32x4* wp = reinterpret_cast<const f32x4*>(a.Wi) + (size_t)(u0 + ju) * C.icg;
-                    for (int c = kw0 + l8; c < kw1; c += 8) dh_acc[p2] += mpb_dot4(dx4[c], wp[c]);
+                    for (int c = kw0 + l8; c < kw1; c += 8) dh_acc[p2] += cl_dot4(dx4[c], wp[c]);
                 }
                 const float tot = group_sum<8>(dh_acc[p2]);
                 if (ju < nU && l8 == 0) sPart[ju] = tot;

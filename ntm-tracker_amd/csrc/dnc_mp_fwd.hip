@@ -81,18 +81,6 @@ struct DncMpFwdArgs {
     float* mbox; unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
 };
 
-__device__ __forceinline__ void mp_softmax_row(float* r, int N, int lane) {      // one wave, in place
-    float mx = -INFINITY;
-    for (int n = lane; n < N; n += 64) mx = fmaxf(mx, r[n]);
-    mx = wave_max(mx);
-    float s = 0.f;
-    for (int n = lane; n < N; n += 64) { const float e = expf(r[n] - mx); r[n] = e; s += e; }
-    s = wave_sum(s);
-    for (int n = lane; n < N; n += 64) r[n] = r[n] / s;
-}
-
-__device__ __forceinline__ float mp_dot4(const f32x4& x, const f32x4& y) { return x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3]; }
-
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 
@@ -375,7 +363,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_fwd_kernel(DncMpFwdArgs a0) {
                 const f32x4* mr = sM4 + r * WS4;
                 for (int jj = 0; jj < FPT; ++jj) {
                     const int j = h + jj * TPR;
-                    if (j < W4) { const f32x4 m = mr[j]; nsq += mp_dot4(m, m); dot += mp_dot4(sK4[j], m); }
+                    if (j < W4) { const f32x4 m = mr[j]; nsq += cl_dot4(m, m); dot += cl_dot4(sK4[j], m); }
                 }
                 nsq = group_sum_rt(nsq, TPR);
                 dot = group_sum_rt(dot, TPR);
@@ -418,7 +406,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_fwd_kernel(DncMpFwdArgs a0) {
                 for (int e = 0; e < 4; ++e) sT[rk[e]] = 1.0f - sNU[n + e];      // sorted_usage = 1 - sorted_nonusage (addressing.py:398)
             }
             __syncthreads();
-            if (wave == CW - 1) mp_softmax_row(sCW, N, lane);
+            if (wave == CW - 1) cl_softmax_row(sCW, N, lane);
             // P5c: exclusive cumulative product in rank order (tf.cumprod(exclusive=True), addressing.py:399) by wave 0
             if (wave == 0) {
                 const int PER = N >> 6, bs = lane * PER;
@@ -476,9 +464,9 @@ __global__ __launch_bounds__(CT) void dnc_mp_fwd_kernel(DncMpFwdArgs a0) {
                         for (int e = 0; e < 4; ++e) m[e] = m[e] * (1.0f - wwn * ev[e]) + wwn * vv[e];
                         mr[j] = m;
                         if (rec) reinterpret_cast<f32x4*>(a.rec_M + (bt * N + row0 + r) * W)[j] = m;
-                        nsq += mp_dot4(m, m);
+                        nsq += cl_dot4(m, m);
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) if (i < R) dot[i] += mp_dot4(sK4[(1 + i) * W4 + j], m);
+                        for (int i = 0; i < 4; ++i) if (i < R) dot[i] += cl_dot4(sK4[(1 + i) * W4 + j], m);
                     }
                 }
                 nsq = group_sum_rt(nsq, TPR);
@@ -558,7 +546,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_fwd_kernel(DncMpFwdArgs a0) {
 #pragma unroll
                                 for (int i = 0; i < 4; ++i) {
                                     if (i < R) {
-                                        f[i] += mp_dot4(rwb[i][h], v);
+                                        f[i] += cl_dot4(rwb[i][h], v);
                                         accB[i][h] += rwa[i] * v;
                                     }
                                 }
@@ -622,7 +610,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_fwd_kernel(DncMpFwdArgs a0) {
                 for (int gg = 0; gg < 8; ++gg) if (gg < k) bw_ += pv[gg];
             }
             __syncthreads();
-            if (wave < R) mp_softmax_row(sCR + wave * N, N, lane);                      // read content weights
+            if (wave < R) cl_softmax_row(sCR + wave * N, N, lane);                      // read content weights
             __syncthreads();
             if (qok) {
                 const int idx = 4 * q4;

@@ -190,8 +190,9 @@ BWD_CASES = [
     ("tight_clip", 10, 2, 16, 8, 2, 1, 16, 0.4, 4, 2, False),
     ("c3_shape", 514, 2, 256, 64, 4, 1, 200, 20.0, 4, 1, False),
     ("c5_shape", 514, 2, 512, 128, 4, 1, 200, 20.0, 3, 1, False),
-    # several write heads (dnc_seq_bwd_mw.hip): the reference's own DNC test shape (memory 20, word 6 -> padded to 8,
-    # 2 reads, 3 writes; dnc/access_test.py:28-34), two heads, four heads on a wider memory
+    # several write heads (the MW = 4 instantiation of dnc_seq_bwd.hip's kernel): the reference's own DNC test shape
+    # (memory 20, word 6 -> padded to 8, 2 reads, 3 writes; dnc/access_test.py:28-34), two heads, four heads on a wider
+    # memory
     ("reference_test_shape_3_writes", 10, 3, 20, 6, 2, 3, 16, 20.0, 6, 2, False),
     ("two_writes_zero_state", 12, 2, 32, 12, 3, 2, 24, 20.0, 6, 2, True),
     ("four_writes", 9, 2, 64, 16, 4, 4, 32, 20.0, 5, 2, False),
