@@ -24,6 +24,9 @@
 // grid at one workgroup per CU.
 #pragma once
 #include "dnc_common.h"
+#include <initializer_list>
+
+typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 void dnc_cluster_latch(const unsigned* err, unsigned* sticky, void* stream);      // dnc_cluster_fwd.hip
 
@@ -91,10 +94,10 @@ __device__ __forceinline__ int cl_same_xcd(unsigned* xw, int g, int k, unsigned*
 }
 
 // wait until all k flags of the cluster have reached `epoch`; returns false (uniformly over the workgroup) when the
-// launch was aborted.  s_abort: one int in LDS, zero-initialised before the first call.
-__device__ __forceinline__ bool cl_wait(const unsigned* flags, unsigned epoch, int k, unsigned* err, int* s_abort,
-                                        unsigned long long t_start, int tid) {
-    (void)t_start;      // the bound is on ONE stalled exchange, not on the kernel's run time: the time base is taken inside the wait
+// launch was aborted.  The bound is on ONE stalled exchange, not on the kernel's run time: the time base is taken inside
+// the wait.  s_abort: one int in LDS, zero-initialised before the first call.  sticky: the workspace's sticky error word,
+// set together with the launch's (memory-partitioned form), or null where a latch kernel behind the launch sets it (LDS form).
+__device__ __forceinline__ bool cl_wait(const unsigned* flags, unsigned epoch, int k, unsigned* err, unsigned* sticky, int* s_abort, int tid) {
     if (tid < 64) {
         unsigned spins = 0;
         unsigned long long t0 = 0;
@@ -106,7 +109,11 @@ __device__ __forceinline__ bool cl_wait(const unsigned* flags, unsigned epoch, i
                 if (t0 == 0) t0 = now;
                 const bool dead = __hip_atomic_load(err, NTK_RLX, NTK_AGENT) != 0 || (now - t0) > 300000000ull;      // 3 s at 100 MHz
                 if (dead) {
-                    if (tid == 0) { __hip_atomic_store(err, 1u, NTK_RLX, NTK_AGENT); *s_abort = 1; }
+                    if (tid == 0) {
+                        __hip_atomic_store(err, 1u, NTK_RLX, NTK_AGENT);
+                        if (sticky) __hip_atomic_store(sticky, 1u, NTK_RLX, NTK_AGENT);
+                        *s_abort = 1;
+                    }
                     break;
                 }
             }
@@ -205,33 +212,41 @@ static constexpr __host__ __device__ unsigned dnc_cluster_magic(int dv) {
 }
 __device__ __forceinline__ int cl_div(int x, unsigned mg) { return mg ? (int)__umulhi((unsigned)x, mg) : x; }
 
-static constexpr __host__ __device__ DncClusterCfg dnc_cluster_cfg(int N, int W, int R, int hid, int O, int k) {
-    DncClusterCfg c = {};
+// the fields DncClusterCfg and DncMpCfg (dnc_mp.h) share: the interface layout and padded widths (num_writes = 1) as
+// dnc_fill_dims lays them out, the split of the hidden units and the decomposition of the two controller products
+template <class Cfg>
+static constexpr __host__ __device__ void dnc_cluster_fill_shared(Cfg& c, int N, int W, int R, int hid, int O, int k) {
+    DncDims d = {};
+    dnc_fill_dims(d, 1, 1, N, W, R, 1, hid, O, 0.f);
     c.N = N; c.W = W; c.R = R; c.hid = hid; c.O = O; c.k = k;
-    // interface layout and padded widths (num_writes = 1): as dnc_fill_dims (dnc_common.h)
-    c.oV = 0; c.oE = W; c.oF = 2 * W; c.oAg = c.oF + R; c.oWg = c.oAg + 1; c.oRm = c.oWg + 1; c.oKw = c.oRm + 3 * R;
-    c.oBw = c.oKw + W; c.oKr = c.oBw + 1; c.oBr = c.oKr + R * W; c.I = c.oBr + R; c.IP = (c.I + 3) & ~3;
-    c.K = R * W + hid; c.ldz = (c.K + 1 + 3) & ~3; c.ldh = (hid + 1 + 3) & ~3;
-    c.Ky = hid + R * W; c.ldy = (c.Ky + 1 + 3) & ~3; c.OP = (O + 3) & ~3;
+    c.oV = d.oV; c.oE = d.oE; c.oF = d.oF; c.oAg = d.oAg; c.oWg = d.oWg; c.oRm = d.oRm; c.oKw = d.oKw; c.oBw = d.oBw;
+    c.oKr = d.oKr; c.oBr = d.oBr; c.I = d.I; c.IP = d.IP;
+    c.K = d.K; c.ldz = d.ldz; c.ldh = d.ldh; c.Ky = d.Ky; c.ldy = d.ldy; c.OP = d.OP;
     c.NR = N / k;
     c.upk = (hid + k - 1) / k;
     c.upkp = dnc_cluster_align4(c.upk);
-    c.slot0 = dnc_cluster_align4(c.upkp + c.IP);
-    c.slot1 = dnc_cluster_align4(R * c.NR + R * N);
     c.ksl = dnc_cluster_max(1, CLT / dnc_cluster_max(1, c.upk));
     if (c.ksl > c.K) c.ksl = c.K;
     c.kperG = (c.K + c.ksl - 1) / c.ksl;
     c.icg = c.IP / 4;
     c.nslI = dnc_cluster_max(1, CLT / c.icg);
     c.uperI = (c.upk + c.nslI - 1) / c.nslI;
+    c.mg_upk = dnc_cluster_magic(c.upk); c.mg_icg = dnc_cluster_magic(c.icg); c.mg_NR = dnc_cluster_magic(c.NR);
+    c.mg_N = dnc_cluster_magic(N); c.mg_W4 = dnc_cluster_magic(W / 4);
+}
+
+static constexpr __host__ __device__ DncClusterCfg dnc_cluster_cfg(int N, int W, int R, int hid, int O, int k) {
+    DncClusterCfg c = {};
+    dnc_cluster_fill_shared(c, N, W, R, hid, O, k);
+    c.slot0 = dnc_cluster_align4(c.upkp + c.IP);
+    c.slot1 = dnc_cluster_align4(R * c.NR + R * N);
     c.nslA = dnc_cluster_max(1, CLT / N);
     c.mperA = N / c.nslA;
     c.strips = N / 64;
     c.NRp = ((c.NR + 31) / 32) * 32;
     c.HW4 = (W / 4 + 1) / 2;
     c.nperW = N / (CLT / 64);
-    c.mg_upk = dnc_cluster_magic(c.upk); c.mg_icg = dnc_cluster_magic(c.icg); c.mg_NR = dnc_cluster_magic(c.NR);
-    c.mg_N = dnc_cluster_magic(N); c.mg_N4 = dnc_cluster_magic(N / 4); c.mg_W4 = dnc_cluster_magic(W / 4);
+    c.mg_N4 = dnc_cluster_magic(N / 4);
     return c;
 }
 
@@ -252,4 +267,23 @@ static inline size_t dnc_cluster_ctrl_bytes(int B, int k) { return dnc_cluster_c
 // mailbox layout (floats): per sequence [exchange][parity][g][slot]; flags (unsigned): per sequence [exchange][g]
 static inline size_t dnc_cluster_mbox_floats(int B, int k, int slot0, int slot1) {
     return (size_t)B * 2 * k * ((size_t)slot0 + slot1);
+}
+
+// the first test of every forward planner: the shapes the k-workgroup forward kernels of either form can run at all
+static inline bool dnc_cluster_shape_ok(int B, int N, int W, int R, int Wn, int hid, int O) {
+    return Wn == 1 && R >= 1 && R <= 4 && N >= 64 && (N % 64) == 0 && N <= CT && W >= 4 && (W % 4) == 0 && W <= 256 && hid >= 4 &&
+           hid <= 1024 && O >= 1 && O <= CW - 1 && B >= 1;
+}
+
+// pointer checks of the launchers: `required` non-null, `records` all given or none, `aligned16` 16-byte aligned (a null
+// pointer passes: absent records).  NTK_OK, or the error with its message set.
+static inline int dnc_cluster_check_ptrs(const char* who, std::initializer_list<const void*> required,
+                                         std::initializer_list<const void*> records, std::initializer_list<const void*> aligned16) {
+    for (const void* p : required) NTK_REQUIRE(p != nullptr, NTK_ERR_BAD_PTR, "%s: null pointer", who);
+    int nn = 0;
+    for (const void* p : records) nn += (p != nullptr);
+    NTK_REQUIRE(nn == 0 || nn == (int)records.size(), NTK_ERR_BAD_PTR, "%s: record pointers are all-or-none (%d of %d given)", who, nn,
+                (int)records.size());
+    for (const void* p : aligned16) NTK_REQUIRE(ntk_aligned16(p), NTK_ERR_BAD_PTR, "%s: 16-byte alignment", who);
+    return NTK_OK;
 }

@@ -20,7 +20,7 @@
 // bitwise reproducible (the one-workgroup kernel used LDS float atomics).
 // The allocation gradient uses the usage ORDER of the forward pass: it is re-derived from the recorded usages with
 // the forward kernel's op-by-op rounding (fp contract off) and compared on stored values, never recomputed inline.
-#include "dnc_cluster.h"
+#include "dnc_cluster_phases.h"
 #include <stdlib.h>
 
 // Diagnostic build only (-DNTK_CL_PROF): see dnc_cluster_fwd.hip
@@ -118,33 +118,27 @@ struct DncClBwdArgs {
     unsigned* xcc;         // [B][k] handshake words of cl_same_xcd (control block)
 };
 
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
 constexpr int MAXQ = 8;       // memory rows per 16-lane group (N <= 256)
 
 #define CL_BWD_VIEWS()                                                                                                        \
     const int k = C.k, NR = C.NR, upk = C.upk;                                                                                \
     const int N = C.N, W = C.W, R = C.R, RN = R * N;                                                                          \
-    const int hid = C.hid, K = C.K, IP = C.IP, RWd = R * W, N4 = N >> 2, W4 = W >> 2;                                         \
-    const int row0 = g * NR, u0 = min(hid, g * upk), u1 = min(hid, u0 + upk), nU = u1 - u0;                                   \
-    float* sPart = smem + L.part; float* sCS = smem + L.CS; float* sGL = smem + L.GL; float* sLt = smem + L.LT;               \
+    const int hid = C.hid, K = C.K, IP = C.IP, N4 = N >> 2, W4 = W >> 2;                                                      \
+    const int row0 = g * NR, u0 = min(hid, g * upk), nU = min(hid, u0 + upk) - u0;                                            \
+    float* sPart = smem + L.part; float* sCS = smem + L.CS; float* sLt = smem + L.LT;                                         \
     float* sI = smem + L.I; float* sDX = smem + L.DX;                                                                         \
-    float* sWW = smem + L.WW; float* sWWp = smem + L.WWp; float* sU = smem + L.U; float* sUp = smem + L.Up;                   \
-    float* sPp = smem + L.Pp; float* sCW = smem + L.CW; float* sAL = smem + L.AL; float* sSIMw = smem + L.SIMw;               \
-    float* sDWW = smem + L.DWW; float* sDCW = smem + L.DCW; float* sDA = smem + L.DA; float* sgP = smem + L.gP;               \
-    float* sDPp = smem + L.DPp; float* sgU = smem + L.gU; float* sgUn = smem + L.gUn; float* sNU = smem + L.NU;               \
-    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                          \
+    float* sWW = smem + L.WW; float* sPp = smem + L.Pp; float* sSIMw = smem + L.SIMw;                                         \
+    float* sDWW = smem + L.DWW; float* sDCW = smem + L.DCW; float* sDPp = smem + L.DPp;                                       \
+    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                           \
     int* sRank = reinterpret_cast<int*>(smem + L.RANK);                                                                       \
-    float* sRWp = smem + L.RWp; float* sRWt = smem + L.RWt; float* sgRW = smem + L.gRW; float* sG = smem + L.G; float* sDRWp = smem + L.DRWp;             \
-    float* sDSIM = smem + L.DSIM; float* sSIMr = smem + L.SIMr;                                                               \
-    float* sGZ = smem + L.GZ; float* sDR = smem + L.DR; float* sDHC = smem + L.DHC; float* sDG = smem + L.DG;                 \
-    float* sgC = smem + L.gC; float* sSC = smem + L.SC; int* sAbort = reinterpret_cast<int*>(sSC + 120);                       \
-    f32x4* sGL4 = reinterpret_cast<f32x4*>(sGL); f32x4* sLt4 = reinterpret_cast<f32x4*>(sLt);                                 \
-    (void)k; (void)K; (void)IP; (void)RWd; (void)N4; (void)W4; (void)u1; (void)nU; (void)RN; (void)sPart; (void)sCS; (void)sGL;\
-    (void)sLt; (void)sI; (void)sDX; (void)sWW; (void)sWWp; (void)sU; (void)sUp; (void)sPp; (void)sCW; (void)sAL; (void)sSIMw; \
-    (void)sDWW; (void)sDCW; (void)sDA; (void)sgP; (void)sDPp; (void)sgU; (void)sgUn; (void)sNU; (void)sKEY; (void)sRank;      \
-    (void)sRWp; (void)sRWt; (void)sgRW; (void)sG; (void)sDRWp; (void)sDSIM; (void)sSIMr; (void)sGZ; (void)sDR; (void)sDHC; (void)sDG;     \
-    (void)sgC; (void)sAbort; (void)sGL4; (void)sLt4; (void)row0; (void)u0
+    float* sRWp = smem + L.RWp; float* sRWt = smem + L.RWt; float* sgRW = smem + L.gRW; float* sG = smem + L.G; float* sDRWp = smem + L.DRWp;\
+    float* sDSIM = smem + L.DSIM; float* sSIMr = smem + L.SIMr; float* sDR = smem + L.DR; float* sDHC = smem + L.DHC;         \
+    float* sSC = smem + L.SC; int* sAbort = reinterpret_cast<int*>(sSC + 120);                                                \
+    f32x4* sGL4 = reinterpret_cast<f32x4*>(smem + L.GL); f32x4* sLt4 = reinterpret_cast<f32x4*>(sLt);                         \
+    (void)k; (void)K; (void)IP; (void)N4; (void)W4; (void)nU; (void)RN; (void)sPart; (void)sCS; (void)upk; (void)hid; (void)W; (void)R;\
+    (void)sLt; (void)sI; (void)sDX; (void)sWW; (void)sPp; (void)sSIMw; (void)sDWW; (void)sDCW; (void)sDPp; (void)sKEY; (void)sRank;\
+    (void)sRWp; (void)sRWt; (void)sgRW; (void)sG; (void)sDRWp; (void)sDSIM; (void)sSIMr; (void)sDR; (void)sDHC; (void)sSC;    \
+    (void)sAbort; (void)sGL4; (void)sLt4; (void)row0; (void)u0
 
 template <bool FIX>
 __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
@@ -154,14 +148,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
     const int tid0 = threadIdx.x;
     const int kk0 = FIX ? kDncClusterFixCfg.k : a0.c.k;
     int b, g;
-    if (a0.xcd_local) {
-        const int x = blockIdx.x & 7, s = blockIdx.x >> 3;
-        b = x + 8 * (s / kk0);
-        g = s % kk0;
-    } else {
-        b = blockIdx.x / kk0;
-        g = blockIdx.x % kk0;
-    }
+    dncc_block_to_bg(a0.xcd_local, kk0, b, g);
     const float EPS = 1e-6f;
     const int S = a0.S;
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -179,12 +166,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         const DncClBwdLds L = FIX ? kDncClFixBwdLds : a.lds;
         CL_BWD_VIEWS();
         if (tid0 == 0) *sAbort = 0;
-        float* cy = a.gcarry ? a.gcarry + (size_t)b * (2 * N + RN + Q.ldkT + hid) : nullptr;
-        const bool cin = cy && a.carry_in;
-        for (int i = tid0; i < N; i += CT) { sgP[i] = cin ? cy[i] : 0.f; sgU[i] = cin ? cy[N + i] : 0.f; }
-        for (int i = tid0; i < RN; i += CT) sgRW[i] = cin ? cy[2 * N + i] : 0.f;
-        for (int i = tid0; i < Q.ldkT; i += CT) sGZ[i] = (cin && i < K) ? cy[2 * N + RN + i] : 0.f;
-        for (int i = tid0; i < nU; i += CT) sgC[i] = cin ? cy[2 * N + RN + Q.ldkT + u0 + i] : 0.f;
+        dncc_bwd_carry_in(C, a, dncc_bwd_state(smem, L, C, g, tid0), b, Q.ldkT);
         const f32x4* gG4 = reinterpret_cast<const f32x4*>(a.gL + ((size_t)b * N + row0) * N);
         for (int i = tid0; i < NR * N4; i += CT) {
             const int r = i / N4, qq = i - r * N4;
@@ -203,13 +185,10 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         }
     }
     __syncthreads();
-    // same-XCD fast form of the hand-offs (dnc_cluster.h): decided per cluster by a handshake, never assumed
-    bool plain = false;
-    if (a0.xcd_local) {
+    bool plain;
+    {
         int* const sw = reinterpret_cast<int*>(smem + (FIX ? kDncClFixBwdLds.SC : a0.lds.SC)) + 121;
-        const int same = cl_same_xcd(a0.xcc + (size_t)b * kk0, g, kk0, a0.err, sw - 1, sw, t_start, tid0);
-        if (same < 0) return;
-        plain = __builtin_amdgcn_readfirstlane(same) != 0;
+        if (!dncc_same_xcd_prologue(a0.xcd_local, a0.xcc, b, g, kk0, a0.err, nullptr, sw, t_start, tid0, plain)) return;
     }
 #ifdef NTK_CL_PROF
     if (blockIdx.x == 0 && tid0 == 0) for (int i = 0; i < 20; ++i) g_clb_prof[i] = 0;
@@ -297,6 +276,8 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         const int par = t & 1;
         const float* Ltg = a.rec_L + (bt * N + row0) * N;
         const float* Lpg = (t > 0) ? a.rec_L + ((bt - 1) * N + row0) * N : a.link0 + ((size_t)b * N + row0) * N;
+        DncClBwdSt st = dncc_bwd_state(smem, L, C, g, tid);
+        st.bt = bt; st.plain = plain; st.clipv = clipv;
 
         CLB_STAMP(0);
         // ------------------------------------------------------------ this step's records: registers -> LDS; next step's requested
@@ -307,58 +288,16 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
                 const int i = tid + u * CT;
                 if (i < RN) { sRWp[i] = pf_rwp[u]; sRWt[i] = pf_rwt[u]; }
             }
-            {
-#pragma clang fp contract(off)
-                if (tid < N) {
-                    const float u = pf_u;
-                    sWW[tid] = pf_ww;
-                    sU[tid] = u;
-                    sCW[tid] = pf_cw;
-                    sAL[tid] = pf_al;
-                    sWWp[tid] = pf_wwp;
-                    sUp[tid] = pf_up;
-                    sPp[tid] = pf_pp;
-                    const float nu = 1.0f - (EPS + (1.0f - EPS) * u);             // exactly the forward kernel's expression
-                    sNU[tid] = nu;
-                    sKEY[tid] = ((unsigned long long)__float_as_uint(nu) << 32) | (unsigned)(0xFFFF - tid);
-                }
-            }
+            if (tid < N) dncc_bwd_slot_records(st, tid, pf_ww, pf_u, pf_cw, pf_al, pf_wwp, pf_up, pf_pp);
         }
-        if (tid < 64) sSC[tid] = 0.f;
-        if (tid < C.OP) {                         // B1: output clip + linear
-            float gy = 0.f;
-            if (tid < C.O) gy = (clipv <= 0.f || fabsf(pf_ypre) < clipv) ? pf_dout : 0.f;
-            sSC[32 + tid] = gy;
-            if (g == 0) a.dypre[bt * C.OP + tid] = gy;
-        }
+        dncc_bwd_output_clip(C, a, st, pf_ypre, pf_dout);      // B1
         __syncthreads();
         CLB_STAMP(1);
-        for (int kk = tid; kk < C.Ky; kk += CT) {
-            float s = 0.f;
-            for (int o = 0; o < C.O; ++o) s += a.Wy[(size_t)kk * C.OP + o] * sSC[32 + o];
-            if (kk < hid) sDHC[kk] = sGZ[RWd + kk] + s;       // carried d(clipped h) + this step's output path
-            else sDR[kk - hid] = sGZ[kk - hid] + s;           // carried d(reads) + output path
-        }
-        if (wave <= R) {                                      // key norms: sSC[0..R-1] = |kr_i|, sSC[R] = |kw|
-            const float* kp = (wave < R) ? sI + C.oKr + wave * W : sI + C.oKw;
-            float ss = 0.f;
-            for (int w = lane; w < W; w += 64) ss += kp[w] * kp[w];
-            ss = wave_sum(ss);
-            if (lane == 0) sSC[wave] = sqrtf(ss + EPS);
-        }
+        dncc_bwd_output_path_key_norms(C, a, st);
         // rank of every slot in the usage order (independent of the gradients: done here, used in B9)
         if (tid < C.nslA * N) {
             const int sl = FIX ? tid / N : cl_div(tid, C.mg_N), n = tid - sl * N;
-            const unsigned long long mine = sKEY[n];
-            const u64x2* kp = reinterpret_cast<const u64x2*>(sKEY + sl * C.mperA);
-            int cnt = 0;
-#pragma unroll 2
-            for (int m = 0; m < C.mperA; m += 8) {
-                const u64x2 k0 = kp[(m >> 1)], k1 = kp[(m >> 1) + 1], k2 = kp[(m >> 1) + 2], k3 = kp[(m >> 1) + 3];
-                cnt += (k0[0] > mine) + (k0[1] > mine) + (k1[0] > mine) + (k1[1] > mine) + (k2[0] > mine) + (k2[1] > mine) +
-                       (k3[0] > mine) + (k3[1] > mine);
-            }
-            reinterpret_cast<int*>(sPart)[sl * N + n] = cnt;
+            reinterpret_cast<int*>(sPart)[sl * N + n] = dncc_rank_count<2>(sKEY + sl * C.mperA, C.mperA, sKEY[n]);
         }
         __syncthreads();
         for (int n = tid; n < N; n += CT) {
@@ -410,41 +349,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         __syncthreads();
         CLB_STAMP(3);
         // ------------------------------------------------------------ B3: read-weight mix, read-content softmax (wave i = head i)
-        if (wave < R) {
-            const int i = wave;
-            const float* rm = sI + C.oRm + i * 3;              // [backward, forward, content] (access.py:283-289)
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = lane + 64 * j;
-                if (n < N) {
-                    const float gg = sG[i * N + n], cr = pf_cr[j];
-                    p0 += gg * pf_bv[j]; p1 += gg * pf_fv[j]; p2 += gg * cr;
-                    s1 += cr * (rm[2] * gg);
-                }
-            }
-            p0 = wave_sum(p0); p1 = wave_sum(p1); p2 = wave_sum(p2); s1 = wave_sum(s1);
-            const float br = sI[C.oBr + i];
-            float dbeta = 0.f;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int n = lane + 64 * j;
-                if (n < N) {
-                    const float gg = sG[i * N + n];
-                    const float dscore = pf_cr[j] * (rm[2] * gg - s1);
-                    dbeta += dscore * sSIMr[i * N + n];
-                    sDSIM[i * N + n] = dscore * br;
-                }
-            }
-            dbeta = wave_sum(dbeta);
-            if (lane == 0) {
-                const float dotp = rm[0] * p0 + rm[1] * p1 + rm[2] * p2;
-                sDX[C.oRm + i * 3 + 0] = rm[0] * (p0 - dotp);
-                sDX[C.oRm + i * 3 + 1] = rm[1] * (p1 - dotp);
-                sDX[C.oRm + i * 3 + 2] = rm[2] * (p2 - dotp);
-                sDX[C.oBr + i] = dbeta * (1.0f - expf(-br));   // strengths pass through softplus
-            }
-        }
+        dncc_bwd_read_mix(C, st, pf_cr, pf_fv, pf_bv);
         __syncthreads();
         CLB_STAMP(4);
         // ------------------------------------------------------------ B4: pass 2 over M_t: d(M_t) (registers) and d(read keys)
@@ -670,7 +575,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
             cl_publish(fl0 + g, epoch, tid, plain);
         }
         CLB_STAMP(7);
-        if (!cl_wait(fl0, epoch, k, a.err, sAbort, t_start, tid)) return;
+        if (!cl_wait(fl0, epoch, k, a.err, nullptr, sAbort, tid)) return;
         CLB_STAMP(8);
         {   // consume exchange 0: d(rw_{t-1}) (link part), d(ww_t) (link part), d(precedence_{t-1}) (link part)
             const float* base = mb0 + (size_t)par * k * slot0;
@@ -705,18 +610,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         // while B6..B11 run from registers and LDS, and the drain of the second publish finds them complete
         if (t > 0) prefetch_records(ak, t - 1, N, RN, IP);
         // ------------------------------------------------------------ B6: precedence (wave 0 computes the two scalars)
-        if (wave == 0) {
-            float sw = 0.f, t1 = 0.f;
-            for (int n = lane; n < N; n += 64) { sw += sWW[n]; t1 += sgP[n] * sPp[n]; }
-            sw = wave_sum(sw); t1 = wave_sum(t1);
-            if (lane == 0) { sSC[16] = sw; sSC[17] = t1; }
-        }
-        __syncthreads();
-        for (int n = tid; n < N; n += CT) {
-            sDPp[n] += (1.0f - sSC[16]) * sgP[n];
-            sDWW[n] += sgP[n] - sSC[17];
-        }
-        __syncthreads();
+        dncc_bwd_precedence(C, st);
         CLB_STAMP(10);
         // ------------------------------------------------------------ B7: write backward over (dM, M_{t-1}); write-key scores
         f32x4 accE = {0.f, 0.f, 0.f, 0.f}, accV = accE;
@@ -761,76 +655,8 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         }
         __syncthreads();
         CLB_STAMP(11);
-        // ------------------------------------------------------------ B8: write-weight mix (access.py:252-257)
-        {
-            const float ga = sI[C.oAg], gw = sI[C.oWg];
-            float* sT = sPart + C.nslA * N;                        // rank-ordered usages
-            float* sS = sT + N;                                    // rank-ordered dA * a
-            for (int n = tid; n < N; n += CT) {
-                const float dww = sDWW[n];
-                const float dA = gw * ga * dww;
-                sDA[n] = dA;
-                sDCW[n] = gw * (1.0f - ga) * dww;
-                const int rk = sRank[n];
-                sT[rk] = 1.0f - sNU[n];
-                sS[rk] = dA * sAL[n];
-            }
-            if (wave == CW - 1) {
-                float dgw = 0.f, dga = 0.f, s18 = 0.f;
-                for (int n = lane; n < N; n += 64) {
-                    const float dww = sDWW[n];
-                    dgw += dww * (ga * sAL[n] + (1.0f - ga) * sCW[n]);
-                    dga += gw * dww * (sAL[n] - sCW[n]);
-                    s18 += sCW[n] * (gw * (1.0f - ga) * dww);
-                }
-                dgw = wave_sum(dgw); dga = wave_sum(dga); s18 = wave_sum(s18);
-                if (lane == 0) { sDX[C.oWg] = dgw * gw * (1.0f - gw); sDX[C.oAg] = dga * ga * (1.0f - ga); sSC[18] = s18; }
-            }
-            __syncthreads();
-            // ------------------------------------------------------------ B9: allocation backward in rank order
-            //   a[n] = nonusage[n] * prod_{before n} usage  ->  d usage[n] = -dA[n] * prod[n] + (sum_{after n} dA a) / usage[n]
-            if (wave == 0) {                                       // exclusive prefix product (as the forward pass)
-                const int PER = N >> 6, bs = lane * PER;
-                float ex[8], run = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) { ex[j] = run; run *= sT[bs + j]; }
-                float inc = run;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const float o = __shfl_up(inc, dd, 64); if (lane >= dd) inc *= o; }
-                float excl = __shfl_up(inc, 1, 64);
-                if (lane == 0) excl = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) sT[bs + j] = excl * ex[j];
-            } else if (wave == 1) {                                // exclusive SUFFIX sum: S[r] = sum_{r' > r} dA a
-                const int PER = N >> 6, bs = lane * PER;
-                float ex[8], run = 0.f;
-#pragma unroll
-                for (int j = 7; j >= 0; --j) if (j < PER) { ex[j] = run; run += sS[bs + j]; }
-                float inc = run;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const float o = __shfl_down(inc, dd, 64); if (lane + dd < 64) inc += o; }
-                float excl = __shfl_down(inc, 1, 64);
-                if (lane == 63) excl = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) sS[bs + j] = excl + ex[j];
-            }
-            __syncthreads();
-            for (int n = tid; n < N; n += CT) {
-                const int rk = sRank[n];
-                const float ut = 1.0f - sNU[n];                    // sorted_usage = 1 - sorted_nonusage
-                const float dut = -sDA[n] * sT[rk] + sS[rk] / ut;
-                sgUn[n] = sgU[n] + (1.0f - EPS) * dut;             // total d(usage_t)
-                sDCW[n] = sCW[n] * (sDCW[n] - sSC[18]);            // d(score) of the write-content softmax
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float dbeta = 0.f;
-            for (int n = lane; n < N; n += 64) dbeta += sDCW[n] * sSIMw[n];
-            dbeta = wave_sum(dbeta);
-            const float bw = sI[C.oBw];
-            if (lane == 0) sDX[C.oBw] = dbeta * (1.0f - expf(-bw));
-        }
+        // ------------------------------------------------------------ B8 | B9: write-weight mix, allocation backward, d(write strength)
+        dncc_bwd_write_mix_alloc(C, st, sPart + C.nslA * N);
         CLB_STAMP(12);
         // ------------------------------------------------------------ B10b: content part of d(M_{t-1}) (registers), d(write key)
         f32x4 accKw = {0.f, 0.f, 0.f, 0.f};
@@ -859,31 +685,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
             }
         }
         // ------------------------------------------------------------ B11: usage backward (addressing.py:342-374)
-        {
-            float fgv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fgv[i] = (i < R) ? sI[C.oF + i] : 0.f;
-            for (int n = tid; n < N; n += CT) {
-                const float gq = sgUn[n];
-                const float wwp = sWWp[n];
-                const float u1v = sUp[n] + (1.0f - sUp[n]) * wwp;                // write weights: stop_gradient
-                float rwp[4], phi = 1.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { rwp[i] = (i < R) ? sRWp[i * N + n] : 0.f; phi *= (1.0f - fgv[i] * rwp[i]); }
-                const float dphi = gq * u1v;
-                sgU[n] = gq * phi * (1.0f - wwp);                                // carried d(usage_{t-1})
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i < R) {
-                        float oth = 1.f;
-#pragma unroll
-                        for (int i2 = 0; i2 < 4; ++i2) if (i2 != i) oth *= (1.0f - fgv[i2] * rwp[i2]);
-                        sDRWp[i * N + n] += dphi * (-fgv[i]) * oth;
-                        sDSIM[i * N + n] = dphi * (-rwp[i]) * oth;               // reuse: per-slot term of d(free_gate_i)
-                    }
-                }
-            }
-        }
+        dncc_bwd_usage(C, st);
         // column sums of B7 / B10b: fold the wave's groups, park per wave
         {
 #pragma unroll
@@ -901,14 +703,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
             if (lane == 0) sSC[20 + wave] = v;                                   // sSC[20 .. 28): d|kw| per wave
         }
         __syncthreads();
-        if (wave < R) {
-            const int i = wave;
-            float s = 0.f;
-            for (int n = lane; n < N; n += 64) s += sDSIM[i * N + n];
-            s = wave_sum(s);
-            const float fg = sI[C.oF + i];
-            if (lane == 0) sDX[C.oF + i] = s * fg * (1.0f - fg);
-        }
+        dncc_bwd_free_gates(C, st);
         for (int idx = tid; idx < 7 * W; idx += CT) {                            // remaining interface gradients
             const int which = idx / W, w = idx - which * W;
             float s = 0.f;
@@ -933,8 +728,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
                 sDX[C.oKw + w] = s + dn * sI[C.oKw + w] / sSC[R];
             }
         }
-        for (int i = tid; i < RN; i += CT) sgRW[i] = sDRWp[i];                  // carried d(read weights_{t-1})
-        for (int n = tid; n < N; n += CT) sgP[n] = sDPp[n];                     // carried d(precedence_{t-1})
+        dncc_bwd_carry_vectors(C, st);
         __syncthreads();
         if (g == 0) for (int c = tid; c < IP; c += CT) a.dxi[bt * IP + c] = sDX[c];
 
@@ -955,64 +749,22 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         }
         __syncthreads();
         // ------------------------------------------------------------ B15: clip + snt.LSTM backward of the own units
-        if (tid < nU) {
-            const int u = u0 + tid;
-            float dh = sDHC[u];
-            for (int sl = 0; sl < Q.nslH; ++sl) dh += sPart[sl * upk + tid];
-            const f32x4 gg = pf_gates;
-            const float gi = gg[0], gj = gg[1], gf = gg[2], go = gg[3];
-            const float c2 = pf_c;
-            const float cprev = dnc_clip(pf_cprev, clipv);        // the recorded cell is pre-clip; the carried state was clipped
-            const float tc = cl_tanh(c2);
-            const float h2 = tc * go;
-            const float dh2 = (clipv <= 0.f || fabsf(h2) < clipv) ? dh : 0.f;
-            const float dcc = (clipv <= 0.f || fabsf(c2) < clipv) ? sgC[tid] : 0.f;
-            const float dc2 = dcc + dh2 * go * (1.0f - tc * tc);
-            f32x4 dg;
-            dg[0] = dc2 * gj * gi * (1.0f - gi);
-            dg[1] = dc2 * gi * (1.0f - gj * gj);
-            dg[2] = dc2 * cprev * gf * (1.0f - gf);
-            dg[3] = dh2 * tc * go * (1.0f - go);
-            sgC[tid] = dc2 * gf;
-            reinterpret_cast<f32x4*>(sDG)[tid] = dg;
-            reinterpret_cast<f32x4*>(a.dgates)[bt * hid + u] = dg;
+        {
+            float dh = 0.f;
+            if (tid < nU) {
+                dh = sDHC[u0 + tid];
+                for (int sl = 0; sl < Q.nslH; ++sl) dh += sPart[sl * upk + tid];
+            }
+            dncc_bwd_lstm(C, a, st, dh, pf_gates, pf_c, pf_cprev);
         }
         __syncthreads();
         CLB_STAMP(14);
         // ------------------------------------------------------------ B16: partial d[reads_prev ; h_prev] over the own gate columns
-        {
-            const int kg4 = Q.kg4, nrow = 4 * nU;
-            if (tid < Q.nslZ * kg4) {
-                const int sl = cl_div(tid, Q.mg_kg4), cg = tid - sl * kg4;
-                const int r0 = sl * Q.nperZ, r1 = min(nrow, r0 + Q.nperZ);
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (r0 < r1) acc = ntk_stream_matvec<4>(reinterpret_cast<const f32x4*>(a.WrT) + (size_t)(4 * u0) * kg4 + cg, kg4, sDG, r0, r1, nrow - 1);
-                *reinterpret_cast<f32x4*>(sPart + sl * Q.ldkT + cg * 4) = acc;
-            }
-            __syncthreads();
-            float* slot = mb1 + ((size_t)par * k + g) * slot1;
-            for (int kk = tid; kk < Q.ldkT; kk += CT) {
-                float s = 0.f;
-                for (int sl = 0; sl < Q.nslZ; ++sl) s += sPart[sl * Q.ldkT + kk];
-                cl_store(slot + kk, s, plain);
-            }
-            cl_publish(fl1 + g, epoch, tid, plain);
-        }
+        dncc_bwd_zprev_publish<4>(Q, a, st, mb1 + ((size_t)par * k + g) * slot1, fl1 + g, epoch);
         CLB_STAMP(15);
-        if (!cl_wait(fl1, epoch, k, a.err, sAbort, t_start, tid)) return;
+        if (!cl_wait(fl1, epoch, k, a.err, nullptr, sAbort, tid)) return;
         CLB_STAMP(16);
-        {
-            const float* base = mb1 + (size_t)par * k * slot1;
-            for (int kk = tid; kk < K; kk += CT) {
-                float pv[8];
-#pragma unroll
-                for (int gg = 0; gg < 8; ++gg) pv[gg] = (gg < k) ? cl_load(base + (size_t)gg * slot1 + kk) : 0.f;
-                float s = 0.f;
-#pragma unroll
-                for (int gg = 0; gg < 8; ++gg) if (gg < k) s += pv[gg];
-                sGZ[kk] = s;
-            }
-        }
+        dncc_bwd_zprev_consume(st, mb1 + (size_t)par * k * slot1, slot1, k, K);
         __syncthreads();
         CLB_STAMP(17);
     }
@@ -1027,15 +779,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
         const DncClBwdGeo Q = FIX ? kDncClFixBwdGeo : a.q;
         const DncClBwdLds L = FIX ? kDncClFixBwdLds : a.lds;
         CL_BWD_VIEWS();
-        float* cy = a.gcarry ? a.gcarry + (size_t)b * (2 * N + RN + Q.ldkT + hid) : nullptr;
-        if (cy) {
-            if (g == 0) {
-                for (int i = tid0; i < N; i += CT) { cy[i] = sgP[i]; cy[N + i] = sgU[i]; }
-                for (int i = tid0; i < RN; i += CT) cy[2 * N + i] = sgRW[i];
-                for (int i = tid0; i < Q.ldkT; i += CT) cy[2 * N + RN + i] = sGZ[i];
-            }
-            for (int i = tid0; i < nU; i += CT) cy[2 * N + RN + Q.ldkT + u0 + i] = sgC[i];
-        }
+        dncc_bwd_carry_out(C, a, dncc_bwd_state(smem, L, C, g, tid0), b, Q.ldkT);
         f32x4* gG4 = reinterpret_cast<f32x4*>(a.gL + ((size_t)b * N + row0) * N);
         for (int i = tid0; i < NR * N4; i += CT) {
             const int r = i / N4, qq = i - r * N4;
@@ -1118,14 +862,11 @@ extern "C" int ntk_dnc_cluster_bwd(int B, int S, int N, int W, int R, int Wn, in
     NTK_REQUIRE(ldkT == a.q.ldkT, NTK_ERR_BAD_SHAPE, "ntk_dnc_cluster_bwd: ldkT=%d (expected %d = K rounded up to 4)", ldkT, a.q.ldkT);
     a.lds = dnc_cl_bwd_lds(a.c, a.q);
     a.B = B; a.S = S; a.clip = clip_value; a.carry_in = carry_in;
-    NTK_REQUIRE(WrT && Wi && Wy && mem0 && link0 && usage0 && rw0 && ww0 && prec0 && hc0 && rec_gates && rec_c && rec_ifc &&
-                    rec_u && rec_ww && rec_rw && rec_cw && rec_cr && rec_al && rec_p && rec_fwd && rec_bwd && rec_M && rec_L &&
-                    rec_ypre && dout && gM && gL && dgates && dxi && dypre && workspace,
-                NTK_ERR_BAD_PTR, "ntk_dnc_cluster_bwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(WrT) && ntk_aligned16(Wi) && ntk_aligned16(rec_gates) && ntk_aligned16(rec_M) && ntk_aligned16(rec_L) &&
-                    ntk_aligned16(gM) && ntk_aligned16(gL) && ntk_aligned16(dgates) && ntk_aligned16(mem0) && ntk_aligned16(link0) &&
-                    ntk_aligned16(workspace),
-                NTK_ERR_BAD_PTR, "ntk_dnc_cluster_bwd: 16-byte alignment");
+    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_cluster_bwd", {WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0, rec_gates, rec_c, rec_ifc,
+                                               rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
+                                               dout, gM, gL, dgates, dxi, dypre, workspace}, {},
+                                              {WrT, Wi, rec_gates, rec_M, rec_L, gM, gL, dgates, mem0, link0, workspace});
+    if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
     a.WrT = WrT; a.Wi = Wi; a.Wy = Wy;
     a.mem0 = mem0; a.link0 = link0; a.usage0 = usage0; a.rw0 = rw0; a.ww0 = ww0; a.prec0 = prec0; a.hc0 = hc0;

@@ -19,7 +19,7 @@
 //   backward  D[head][col]  += rw_prev[head][row] * L[row][col]      block = 4 columns, one link row per instruction
 //   forward   D[row][head]  += L[row][col] * rw_prev[head][col]      block = 4 rows,    one link column per block
 // (exact fp32 FMA chains, k-ordered: same numerics as a scalar loop).
-#include "dnc_cluster.h"
+#include "dnc_cluster_phases.h"
 #include <vector>
 
 // Diagnostic build only (-DNTK_CL_PROF): workgroup 0 accumulates s_memtime deltas per phase (its wave 0, lane 0) into
@@ -94,26 +94,23 @@ struct DncClFwdArgs {
 
 __device__ __forceinline__ float cl_pair_sum(float v) { return v + ntk_dpp<0xB1>(v); }      // lanes 2p, 2p+1
 
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
 // LDS views and launch constants derived from the shape configuration C and the LDS layout L in scope
 #define CL_FWD_VIEWS()                                                                                                        \
     const int k = C.k, NR = C.NR, upk = C.upk, upkp = C.upkp;                                                                 \
     const int N = C.N, W = C.W, R = C.R;                                                                                      \
     const int hid = C.hid, K = C.K, IP = C.IP, RWd = R * W, N4 = N >> 2, W4 = W >> 2, WS = W + 4, WS4 = W4 + 1;               \
-    const int row0 = g * NR, u0 = min(hid, g * upk), u1 = min(hid, u0 + upk), nU = u1 - u0;                                   \
+    const int row0 = g * NR, u0 = min(hid, g * upk), nU = min(hid, u0 + upk) - u0;                                            \
     float* sPart = smem + L.part; float* sM = smem + L.M; float* sL = smem + L.L;                                             \
-    float* sZ = smem + L.Z; float* sC = smem + L.C; float* sHP = smem + L.HP; float* sI = smem + L.I; float* sK = smem + L.K;                            \
-    float* sU = smem + L.U; float* sNU = smem + L.NU;                                                                         \
-    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                          \
+    float* sZ = smem + L.Z; float* sI = smem + L.I; float* sNU = smem + L.NU;                                                 \
+    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                           \
     int* sRank = reinterpret_cast<int*>(smem + L.RANK);                                                                       \
     float* sRW = smem + L.RW; float* sRWT = smem + L.RWT; float* sWW = smem + L.WW;                                           \
     float* sP = smem + L.P; float* sCW = smem + L.CW; float* sCR = smem + L.CR;                                               \
     float* sSC = smem + L.SC; int* sAbort = reinterpret_cast<int*>(sSC + 32);                                                 \
-    f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart); f32x4* sM4 = reinterpret_cast<f32x4*>(sM);                              \
-    f32x4* sL4 = reinterpret_cast<f32x4*>(sL); const f32x4* sK4 = reinterpret_cast<const f32x4*>(sK);                        \
-    (void)upkp; (void)K; (void)IP; (void)RWd; (void)N4; (void)WS; (void)WS4; (void)u1; (void)nU; (void)sPart4; (void)sK4;    \
-    (void)sKEY; (void)sRank; (void)sNU; (void)sCW; (void)sCR; (void)sK; (void)sAbort; (void)sL; (void)sM; (void)sRWT; (void)sI; (void)sC; (void)sHP; (void)k
+    f32x4* sPart4 = reinterpret_cast<f32x4*>(sPart); f32x4* sM4 = reinterpret_cast<f32x4*>(sM);                               \
+    f32x4* sL4 = reinterpret_cast<f32x4*>(sL); const f32x4* sK4 = reinterpret_cast<const f32x4*>(smem + L.K);                 \
+    (void)upkp; (void)K; (void)IP; (void)RWd; (void)N4; (void)WS; (void)WS4; (void)u0; (void)nU; (void)sPart4; (void)sK4;     \
+    (void)sKEY; (void)sRank; (void)sNU; (void)sCW; (void)sCR; (void)sAbort; (void)sL; (void)sM; (void)sRWT; (void)sI; (void)sZ; (void)sRW; (void)sWW; (void)sP; (void)k
 
 // FIX: the benchmark shape (kDncClusterFixCfg) with every dimension, offset and LDS address a compile-time constant:
 // the short per-row and per-slot loops unroll, their LDS loads are issued in batches instead of one dependent load
@@ -128,14 +125,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
     const int tid0 = threadIdx.x;
     const int kk0 = FIX ? kDncClusterFixCfg.k : a0.c.k;
     int b, g;
-    if (a0.xcd_local) {                     // the k members of a sequence share blockIdx % 8 (speed only, never correctness)
-        const int x = blockIdx.x & 7, s = blockIdx.x >> 3;
-        b = x + 8 * (s / kk0);
-        g = s % kk0;
-    } else {
-        b = blockIdx.x / kk0;
-        g = blockIdx.x % kk0;
-    }
+    dncc_block_to_bg(a0.xcd_local, kk0, b, g);
     const float EPS = 1e-6f;
     const int S = a0.S;
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -154,26 +144,14 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
             const int r = i / N4, q = i - r * N4;
             sL4[r * N4 + (q ^ (r & 7))] = gL4[i];
         }
-        for (int i = tid0; i < N; i += CT) {
-            sU[i] = a.usage[(size_t)b * N + i];
-            sWW[i] = a.ww[(size_t)b * N + i];
-            sP[i] = a.prec[(size_t)b * N + i];
-        }
         for (int i = tid0; i < 4 * N; i += CT) sRWT[i] = 0.f;
-        for (int i = tid0; i < R * N; i += CT) sRW[i] = a.rw[(size_t)b * R * N + i];
-        for (int i = tid0; i < RWd; i += CT) sZ[i] = a.reads[(size_t)b * RWd + i];
-        for (int i = tid0; i < hid; i += CT) sZ[RWd + i] = a.hc[(size_t)b * 2 * hid + i];
-        for (int i = tid0; i < nU; i += CT) sC[i] = a.hc[(size_t)b * 2 * hid + hid + u0 + i];
-        for (int i = tid0; i < (1 + R) * W; i += CT) sK[i] = 0.f;
+        dncc_fwd_load_state(C, a, dncc_fwd_state(smem, L, C, g, tid0), b);
     }
     __syncthreads();
-    // same-XCD fast form of the hand-offs (dnc_cluster.h): decided per cluster by a handshake, never assumed
-    bool plain = false;
-    if (a0.xcd_local) {
+    bool plain;
+    {
         int* const sw = reinterpret_cast<int*>(smem + (FIX ? kDncClFixFwdLds.SC : a0.lds.SC)) + 33;
-        const int same = cl_same_xcd(a0.xcc + (size_t)b * kk0, g, kk0, a0.err, sw - 1, sw, t_start, tid0);
-        if (same < 0) return;
-        plain = __builtin_amdgcn_readfirstlane(same) != 0;
+        if (!dncc_same_xcd_prologue(a0.xcd_local, a0.xcc, b, g, kk0, a0.err, nullptr, sw, t_start, tid0, plain)) return;
     }
 
     // FIX: the slice of Wr a thread multiplies in P1 (own unit j x K-slice ks: kperG rows of one float4 gate column) never
@@ -212,15 +190,12 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         }
         CL_FWD_VIEWS();
         const float clipv = a.clip;
-        const int ksl = C.ksl, kperG = C.kperG, icg = C.icg, nslI = C.nslI, uperI = C.uperI;
         const int nslA = C.nslA, mperA = C.mperA, strips = C.strips, NRp = C.NRp, HW4 = C.HW4, nperW = C.nperW;
         const int slot0 = C.slot0, slot1 = C.slot1;
         float* mb0 = a.mbox + (size_t)b * 2 * k * ((size_t)slot0 + slot1);        // [parity][g][slot0]
         float* mb1 = mb0 + (size_t)2 * k * slot0;                                 // [parity][g][slot1]
         unsigned* fl0 = a.flags + (size_t)b * 2 * k;
         unsigned* fl1 = fl0 + k;
-        const f32x4* Wr4 = reinterpret_cast<const f32x4*>(a.Wr);
-        const f32x4* Wi4 = reinterpret_cast<const f32x4*>(a.Wi);
         const bool rec = a.rec_z != nullptr;
         int tid_op = tid0;
         asm volatile("" : "+v"(tid_op));       // keep per-thread index math inside the step (no hoist + spill)
@@ -228,93 +203,45 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         const size_t bt = (size_t)b * S + t;
         const unsigned epoch = (unsigned)t + 1u;
         const int par = t & 1;
+        DncClFwdSt st = dncc_fwd_state(smem, L, C, g, tid);
+        st.bt = bt; st.rec = rec; st.plain = plain; st.clipv = clipv;
         CL_STAMP(15);
 
         // ------------------------------------------------------------ P1: LSTM gates of the own hidden units
-        f32x4 xg = {0.f, 0.f, 0.f, 0.f};
+        f32x4 xg;
         if constexpr (FIX) xg = xp_next + xg_bias;
-        else if (tid < nU) xg = reinterpret_cast<const f32x4*>(a.xproj)[bt * hid + u0 + tid] + Wr4[(size_t)K * hid + u0 + tid];
-        if (rec && g == 0) for (int i = tid; i < C.ldz; i += CT) a.rec_z[bt * C.ldz + i] = (i < K) ? sZ[i] : (i == K ? 1.f : 0.f);
-        if (tid < ksl * upk) {
-            const int ks = cl_div(tid, C.mg_upk), j = tid - ks * upk;
-            const int k0 = ks * kperG, k1 = min(K, k0 + kperG);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (FIX) {
+        else xg = dncc_fwd_gate_input(C, a, st);
+        dncc_fwd_rec_z(C, a, st);
+        if constexpr (FIX) {
+            if (tid < C.ksl * upk) {
+                const int ks = cl_div(tid, C.mg_upk), j = tid - ks * upk;
+                const int k0 = ks * C.kperG, k1 = min(K, k0 + C.kperG);
+                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int q = 0; q < KPG; ++q) acc += ((k0 + q < k1) ? sZ[k0 + q] : 0.f) * wres[q];
-            } else {
-                if (j < nU && k0 < k1) acc = ntk_stream_matvec<4>(Wr4 + u0 + j, hid, sZ, k0, k1, K - 1);
+                sPart4[ks * upk + j] = acc;
             }
-            sPart4[ks * upk + j] = acc;
+        } else {
+            dncc_fwd_gate_partials(C, st, reinterpret_cast<const f32x4*>(a.Wr));
         }
         __syncthreads();
-        if (tid < nU) {
-            f32x4 gsum = xg;
-            for (int ks = 0; ks < ksl; ++ks) gsum += sPart4[ks * upk + tid];
-            const float gi = cl_sigmoid(gsum[0]), gj = cl_tanh(gsum[1]);
-            const float gf = cl_sigmoid(gsum[2] + 1.0f);             // snt.LSTM forget_bias = 1.0
-            const float go = cl_sigmoid(gsum[3]);
-            const float c2 = gf * sC[tid] + gi * gj;
-            const float h2 = cl_tanh(c2) * go;
-            sC[tid] = dnc_clip(c2, clipv);                           // dnc.py:112-113
-            sHP[tid] = sZ[RWd + u0 + tid];                           // h_{t-1}: still needed by the deferred output of step t-1
-            sZ[RWd + u0 + tid] = dnc_clip(h2, clipv);
-            if (rec) {
-                f32x4 ga = {gi, gj, gf, go};
-                reinterpret_cast<f32x4*>(a.rec_gates)[bt * hid + u0 + tid] = ga;
-                a.rec_c[bt * hid + u0 + tid] = c2;
-            }
-        }
+        dncc_fwd_lstm(C, a, st, xg);
         __syncthreads();
         CL_STAMP(0);
         // ------------------------------------------------------------ P2: interface partial sums over the own units
-        if (tid < nslI * icg) {
-            const int us = cl_div(tid, C.mg_icg), cg = tid - us * icg;
-            const int ua = u0 + us * uperI, ub = min(u1, ua + uperI);
-            f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            const f32x4* wp = Wi4 + (size_t)ua * icg + cg;
-#pragma unroll 8
-            for (int u = ua; u < ub; ++u, wp += icg) acc += sZ[RWd + u] * (*wp);
-            sPart4[us * icg + cg] = acc;
-        }
+        dncc_fwd_ifc_partials(C, st, reinterpret_cast<const f32x4*>(a.Wi));
         __syncthreads();
         CL_STAMP(1);
-        {   // publish exchange 0: [h of the own units | interface partial]
-            float* slot = mb0 + ((size_t)par * k + g) * slot0;
-            if (tid < nU) cl_store(slot + tid, sZ[RWd + u0 + tid], plain);
-            for (int c = tid; c < IP; c += CT) {
-                float v = 0.f;
-                for (int us = 0; us < nslI; ++us) v += sPart[us * IP + c];
-                cl_store(slot + upkp + c, v, plain);
-            }
-            cl_publish(fl0 + g, epoch, tid, plain);
-        }
-        // y_{t-1} = clip([h_{t-1} ; reads_{t-1}] Wy + by) (dnc.py:118-122) does not feed the recurrence: workgroup 0 computes it
-        // HERE, in the shadow of the hand-off (its wave 0 polls, waves 1.. have nothing else to do), not on the step's
-        // critical path.  h_{t-1}: sHP for the own units (already overwritten in sZ), sZ for the others (overwritten after the wait).
-        if (g == 0 && t > 0 && wave >= 1 && wave <= C.O) {
-            const int o = wave - 1;
-            float s = 0.f;
-            for (int kk = lane; kk < C.Ky; kk += 64) {
-                const float zv = (kk < hid) ? ((kk >= u0 && kk < u1) ? sHP[kk - u0] : sZ[RWd + kk]) : sZ[kk - hid];
-                s += zv * a.Wy[(size_t)kk * C.OP + o];
-            }
-            s = wave_sum(s);
-            if (lane == 0) {
-                const float pre = s + a.Wy[(size_t)C.Ky * C.OP + o];
-                a.out[(bt - 1) * C.O + o] = dnc_clip(pre, clipv);
-                if (rec) a.rec_ypre[(bt - 1) * C.O + o] = pre;
-            }
-        }
+        dncc_fwd_publish0(C, st, mb0 + ((size_t)par * k + g) * slot0, fl0 + g, epoch);      // [h of the own units | interface partial]
+        // y_{t-1} does not feed the recurrence: workgroup 0 computes it HERE, in the shadow of the hand-off (its wave 0 polls,
+        // waves 1.. have nothing else to do), not on the step's critical path
+        if (g == 0 && t > 0 && wave >= 1 && wave <= C.O) dncc_fwd_output<true>(C, a, st, bt - 1, wave - 1, lane);
         CL_STAMP(2);
-        if (!cl_wait(fl0, epoch, k, a.err, sAbort, t_start, tid)) return;
+        if (!cl_wait(fl0, epoch, k, a.err, nullptr, sAbort, tid)) return;
         CL_STAMP(3);
         {   // consume exchange 0: full h, activated interface (+ aligned copies of the keys)
             const float* base = mb0 + (size_t)par * k * slot0;
-            for (int u = tid; u < hid; u += CT) {
-                const int gg = cl_div(u, C.mg_upk);
-                sZ[RWd + u] = cl_load(base + (size_t)gg * slot0 + (u - gg * upk));
-            }
+            dncc_fwd_gather_h(C, st, base, slot0);
             for (int c = tid; c < IP; c += CT) {
                 float pv[8];
 #pragma unroll
@@ -322,12 +249,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
                 float v = a.Wi[(size_t)hid * IP + c];
 #pragma unroll
                 for (int gg = 0; gg < 8; ++gg) if (gg < k) v += pv[gg];
-                float r = v;
-                if (c >= C.oE && c < C.oRm) r = dnc_sigmoid(v);                      // erase, free, alloc, write gates
-                else if ((c >= C.oBw && c < C.oKr) || (c >= C.oBr && c < C.I)) r = dnc_softplus(v);   // strengths
-                sI[c] = r;
-                if (c >= C.oKw && c < C.oBw) sK[c - C.oKw] = r;
-                else if (c >= C.oKr && c < C.oBr) sK[W + (c - C.oKr)] = r;
+                dncc_fwd_ifc_column(C, st, c, v);
             }
         }
         if constexpr (FIX) {   // the next step's input projection row (HBM): requested here, used at the top of the next step
@@ -335,62 +257,12 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         }
         __syncthreads();
         CL_STAMP(4);
-        if (rec && g == 0) {
-            for (int i = tid; i < C.ldh; i += CT) {
-                const float v = (i < hid) ? sZ[RWd + i] : (i == hid ? 1.f : 0.f);
-                a.rec_hc[bt * C.ldh + i] = v;
-                if (i < hid) a.rec_yin[bt * C.ldy + i] = v;
-            }
-            for (int c = tid; c < IP; c += CT) {
-                float v = sI[c];
-                if (c >= C.oRm && c < C.oKw) {             // the read modes are recorded after their softmax (computed below)
-                    const float* rm = sI + C.oRm + ((c - C.oRm) / 3) * 3;
-                    const float mx = fmaxf(rm[0], fmaxf(rm[1], rm[2]));
-                    const float e0 = expf(rm[0] - mx), e1 = expf(rm[1] - mx), e2 = expf(rm[2] - mx);
-                    v = expf(v - mx) / (e0 + e1 + e2);
-                }
-                a.rec_ifc[bt * IP + c] = v;
-            }
-        }
-        // key norms: wave i < 1 + R  ->  sSC[8 + i] = sqrt(|key_i|^2 + eps)
-        if (wave < 1 + R) {
-            float ss = 0.f;
-            for (int w = lane; w < W; w += 64) { const float kv = sK[wave * W + w]; ss += kv * kv; }
-            ss = wave_sum(ss);
-            if (lane == 0) sSC[8 + wave] = sqrtf(ss + EPS);
-        }
-        // ------------------------------------------------------------ P3: usage (addressing.py:342-374), op by op
-        {
-#pragma clang fp contract(off)
-            float fg[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fg[i] = (i < R) ? sI[C.oF + i] : 0.f;
-            for (int n = tid; n < N; n += CT) {
-                float pw = 1.f;
-                pw *= (1.0f - sWW[n]);
-                float u = sU[n];
-                u = u + (1.0f - u) * (1.0f - pw);
-                float phi = 1.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) if (i < R) phi *= (1.0f - fg[i] * sRW[i * N + n]);
-                u *= phi;
-                sU[n] = u;
-                const float nu = 1.0f - (EPS + (1.0f - EPS) * u);
-                sNU[n] = nu;
-                // sort key of the allocation: larger nonusage first, ties to the lower slot (tf.nn.top_k); nonusage >= +0,
-                // so its bit pattern orders like its value
-                sKEY[n] = ((unsigned long long)__float_as_uint(nu) << 32) | (unsigned)(0xFFFF - n);
-                if (rec && n >= row0 && n < row0 + NR) a.rec_u[bt * N + n] = u;
-            }
-        }
+        dncc_fwd_rec_hc_ifc(C, a, st);
+        dncc_fwd_key_norms(C, st);
+        // ------------------------------------------------------------ P3: usage, sort key of the allocation; read modes
+        dncc_fwd_usage(C, a, st);
         __syncthreads();
-        if (tid < R) {                                                               // read_mode softmax (access.py:186-187)
-            float* rm = sI + C.oRm + tid * 3;
-            const float mx = fmaxf(rm[0], fmaxf(rm[1], rm[2]));
-            const float e0 = expf(rm[0] - mx), e1 = expf(rm[1] - mx), e2 = expf(rm[2] - mx);
-            const float s = e0 + e1 + e2;
-            rm[0] = e0 / s; rm[1] = e1 / s; rm[2] = e2 / s;
-        }
+        dncc_fwd_read_modes(C, st);
         CL_STAMP(5);
         // ------------------------------------------------------------ P4: write content scores on M_{t-1}: a thread PAIR per row
         {
@@ -409,15 +281,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         // ------------------------------------------------------------ P5a: rank of every slot in the usage order
         if (tid < nslA * N) {
             const int sl = (FIX ? tid / N : cl_div(tid, C.mg_N)), n = tid - sl * N;
-            const unsigned long long mine = sKEY[n];
-            const u64x2* kp = reinterpret_cast<const u64x2*>(sKEY + sl * mperA);
-            int cnt = 0;
-            for (int m = 0; m < mperA; m += 8) {
-                const u64x2 k0 = kp[(m >> 1)], k1 = kp[(m >> 1) + 1], k2 = kp[(m >> 1) + 2], k3 = kp[(m >> 1) + 3];
-                cnt += (k0[0] > mine) + (k0[1] > mine) + (k1[0] > mine) + (k1[1] > mine) + (k2[0] > mine) + (k2[1] > mine) +
-                       (k3[0] > mine) + (k3[1] > mine);
-            }
-            reinterpret_cast<int*>(sPart)[sl * N + n] = cnt;
+            reinterpret_cast<int*>(sPart)[sl * N + n] = dncc_rank_count(sKEY + sl * mperA, mperA, sKEY[n]);
         }
         __syncthreads();
         CL_STAMP(6);
@@ -432,32 +296,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
             }
             if (wave == CW - 1) cl_softmax_row(sCW, N, lane);
             __syncthreads();
-            // P5c: exclusive cumulative product in rank order (tf.cumprod(exclusive=True), addressing.py:399) by wave 0
-            if (wave == 0) {
-                const int PER = N >> 6, base = lane * PER;
-                float ex[8], run = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) { ex[j] = run; run *= sT[base + j]; }
-                float inc = run;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const float o = __shfl_up(inc, dd, 64); if (lane >= dd) inc *= o; }
-                float excl = __shfl_up(inc, 1, 64);
-                if (lane == 0) excl = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) sT[base + j] = excl * ex[j];
-            }
-            __syncthreads();
-            // P5d: allocation and write weights (access.py:220-257), op by op
-            {
-#pragma clang fp contract(off)
-                const float ag = sI[C.oAg], wg = sI[C.oWg];
-                for (int n = tid; n < N; n += CT) {
-                    const float al = sNU[n] * sT[sRank[n]];
-                    const float cw = sCW[n];
-                    sWW[n] = wg * (ag * al + (1.0f - ag) * cw);
-                    if (rec && n >= row0 && n < row0 + NR) { a.rec_al[bt * N + n] = al; a.rec_cw[bt * N + n] = cw; }
-                }
-            }
+            dncc_fwd_alloc_write_weights(C, a, st, sT);                            // P5c | P5d
         }
         __syncthreads();
         CL_STAMP(7);
@@ -585,15 +424,10 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
             cl_store(slot1p + idx, f, plain);
         }
         if (wave >= CW - R) cl_softmax_row(sCR + (wave - (CW - R)) * N, N, lane);     // read content weights
-        if (wave == CW - R - 1) {                                                     // sum of the write weights (precedence)
-            float s = 0.f;
-            for (int n = lane; n < N; n += 64) s += sWW[n];
-            s = wave_sum(s);
-            if (lane == 0) sSC[0] = s;
-        }
+        if (wave == CW - R - 1) dncc_fwd_ww_sum(st, N, lane);                         // sum of the write weights (precedence)
         cl_publish(fl1 + g, epoch, tid, plain);
         CL_STAMP(11);
-        if (!cl_wait(fl1, epoch, k, a.err, sAbort, t_start, tid)) return;
+        if (!cl_wait(fl1, epoch, k, a.err, nullptr, sAbort, tid)) return;
         CL_STAMP(12);
         // ------------------------------------------------------------ P8: read weights, precedence, reads, output
         {
@@ -620,12 +454,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
                     a.rec_bwd[bt * R * N + idx] = bwd;
                 }
             }
-            const float sww = sSC[0];
-            for (int n = tid; n < N; n += CT) {
-                const float pn = (1.0f - sww) * sP[n] + sWW[n];                         // addressing.py:238-240
-                sP[n] = pn;
-                if (rec && n >= row0 && n < row0 + NR) { a.rec_p[bt * N + n] = pn; a.rec_ww[bt * N + n] = sWW[n]; }
-            }
+            dncc_fwd_precedence(C, a, st);
         }
         __syncthreads();
         CL_STAMP(13);
@@ -680,23 +509,10 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         const DncClusterCfg C = FIX ? kDncClusterFixCfg : a.c;
         const DncClFwdLds L = FIX ? kDncClFixFwdLds : a.lds;
         CL_FWD_VIEWS();
-        if (g == 0) {                                            // output of the last step (the loop defers each step's by one)
-            const int wave = tid0 >> 6, lane = tid0 & 63;
-            const size_t bt = (size_t)b * S + (S - 1);
-            for (int o = wave; o < C.O; o += CW) {
-                float s = 0.f;
-                for (int kk = lane; kk < C.Ky; kk += 64) {
-                    const float zv = (kk < hid) ? sZ[RWd + kk] : sZ[kk - hid];
-                    s += zv * a.Wy[(size_t)kk * C.OP + o];
-                }
-                s = wave_sum(s);
-                if (lane == 0) {
-                    const float pre = s + a.Wy[(size_t)C.Ky * C.OP + o];
-                    a.out[bt * C.O + o] = dnc_clip(pre, a.clip);
-                    if (a.rec_z != nullptr) a.rec_ypre[bt * C.O + o] = pre;
-                }
-            }
-        }
+        DncClFwdSt st = dncc_fwd_state(smem, L, C, g, tid0);
+        st.rec = a.rec_z != nullptr; st.clipv = a.clip;
+        if (g == 0)                                              // output of the last step (the loop defers each step's by one)
+            for (int o = tid0 >> 6; o < C.O; o += CW) dncc_fwd_output<false>(C, a, st, (size_t)b * S + (S - 1), o, tid0 & 63);
         f32x4* gM4 = reinterpret_cast<f32x4*>(a.mem + ((size_t)b * N + row0) * W);
         for (int i = tid0; i < NR * W4; i += CT) { const int n = i / W4, j = i - n * W4; gM4[i] = sM4[(row0 + n) * WS4 + j]; }
         f32x4* gL4 = reinterpret_cast<f32x4*>(a.link + ((size_t)b * N + row0) * N);
@@ -704,17 +520,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
             const int r = i / N4, q = i - r * N4;
             gL4[i] = sL4[r * N4 + (q ^ (r & 7))];
         }
-        for (int i = tid0; i < nU; i += CT) a.hc[(size_t)b * 2 * hid + hid + u0 + i] = sC[i];
-        if (g == 0) {
-            for (int i = tid0; i < N; i += CT) {
-                a.usage[(size_t)b * N + i] = sU[i];
-                a.ww[(size_t)b * N + i] = sWW[i];
-                a.prec[(size_t)b * N + i] = sP[i];
-            }
-            for (int i = tid0; i < R * N; i += CT) a.rw[(size_t)b * R * N + i] = sRW[i];
-            for (int i = tid0; i < RWd; i += CT) a.reads[(size_t)b * RWd + i] = sZ[i];
-            for (int i = tid0; i < hid; i += CT) a.hc[(size_t)b * 2 * hid + i] = sZ[RWd + i];
-        }
+        dncc_fwd_store_state(C, a, st, b);
     }
 }
 
@@ -774,9 +580,7 @@ extern "C" int ntk_dnc_cluster_inject_abort(void* workspace, size_t workspace_by
 
 // the cluster size (0 = none) and configuration of a shape; k_req 0 = the largest k that fits
 static int dnc_cluster_pick(int B, int N, int W, int R, int Wn, int hid, int O, int k_req, DncClusterCfg& c, size_t* lds_bytes) {
-    if (Wn != 1 || R < 1 || R > 4 || N < 64 || (N % 64) != 0 || N > CT || W < 4 || (W % 4) != 0 || W > 256 || hid < 4 ||
-        hid > 1024 || O < 1 || O > CW - 1 || B < 1)
-        return 0;
+    if (!dnc_cluster_shape_ok(B, N, W, R, Wn, hid, O)) return 0;
     for (int k = 8; k >= 1; k >>= 1) {
         if (k_req > 0 && k != k_req) continue;
         if ((long)B * k > ntk_device_cu_count()) continue;     // one workgroup per CU, all co-resident (api.cpp)
@@ -858,19 +662,11 @@ extern "C" int ntk_dnc_cluster_fwd(int B, int S, int N, int W, int R, int Wn, in
                 "(ask ntk_dnc_cluster_plan)", k, B, N, W, R, Wn, hid);
     a.lds = dnc_cl_fwd_lds(a.c);
     a.B = B; a.S = S; a.clip = clip_value;
-    NTK_REQUIRE(xproj && Wr && Wi && Wy && mem && link && usage && rw && ww && prec && reads && hc && out && workspace, NTK_ERR_BAD_PTR,
-                "ntk_dnc_cluster_fwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(xproj) && ntk_aligned16(Wr) && ntk_aligned16(Wi) && ntk_aligned16(mem) && ntk_aligned16(link) &&
-                    ntk_aligned16(workspace), NTK_ERR_BAD_PTR, "ntk_dnc_cluster_fwd: xproj/Wr/Wi/mem/link/workspace must be 16-byte aligned");
-    {
-        float* recs[] = {rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al,
-                         rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre};
-        int nn = 0;
-        for (float* r : recs) nn += (r != nullptr);
-        NTK_REQUIRE(nn == 0 || nn == 18, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_fwd: record pointers are all-or-none (%d of 18 given)", nn);
-        NTK_REQUIRE(nn == 0 || (ntk_aligned16(rec_gates) && ntk_aligned16(rec_M) && ntk_aligned16(rec_L)), NTK_ERR_BAD_PTR,
-                    "ntk_dnc_cluster_fwd: rec_gates/rec_M/rec_L must be 16-byte aligned");
-    }
+    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_cluster_fwd", {xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out, workspace},
+                                              {rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al,
+                                               rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre},
+                                              {xproj, Wr, Wi, mem, link, workspace, rec_gates, rec_M, rec_L});
+    if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
     a.xproj = xproj; a.Wr = Wr; a.Wi = Wi; a.Wy = Wy; a.mem = mem; a.link = link; a.usage = usage; a.rw = rw; a.ww = ww;
     a.prec = prec; a.reads = reads; a.hc = hc; a.out = out;

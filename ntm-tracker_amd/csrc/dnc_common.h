@@ -14,7 +14,7 @@ struct DncDims {
     int oV, oE, oF, oAg, oWg, oRm, oKw, oBw, oKr, oBr;
 };
 
-static void dnc_fill_dims(DncDims& d, int B, int S, int N, int W, int R, int Wn, int hid, int O, float clip) {
+static constexpr __host__ __device__ void dnc_fill_dims(DncDims& d, int B, int S, int N, int W, int R, int Wn, int hid, int O, float clip) {
     d.B = B; d.S = S; d.N = N; d.W = W; d.R = R; d.Wn = Wn; d.hid = hid; d.O = O; d.clip = clip;
     d.oV = 0;
     d.oE = d.oV + Wn * W;

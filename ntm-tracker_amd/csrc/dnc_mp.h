@@ -43,24 +43,11 @@ static constexpr __host__ __device__ int dnc_mp_pow2floor(int x) { int p = 1; wh
 
 static constexpr __host__ __device__ DncMpCfg dnc_mp_cfg(int N, int W, int R, int hid, int O, int k) {
     DncMpCfg c = {};
-    c.N = N; c.W = W; c.R = R; c.hid = hid; c.O = O; c.k = k;
-    c.oV = 0; c.oE = W; c.oF = 2 * W; c.oAg = c.oF + R; c.oWg = c.oAg + 1; c.oRm = c.oWg + 1; c.oKw = c.oRm + 3 * R;
-    c.oBw = c.oKw + W; c.oKr = c.oBw + 1; c.oBr = c.oKr + R * W; c.I = c.oBr + R; c.IP = (c.I + 3) & ~3;
-    c.K = R * W + hid; c.ldz = (c.K + 1 + 3) & ~3; c.ldh = (hid + 1 + 3) & ~3;
-    c.Ky = hid + R * W; c.ldy = (c.Ky + 1 + 3) & ~3; c.OP = (O + 3) & ~3;
-    c.NR = N / k;
-    c.upk = (hid + k - 1) / k;
-    c.upkp = dnc_cluster_align4(c.upk);
+    dnc_cluster_fill_shared(c, N, W, R, hid, O, k);
     c.slot[0] = dnc_cluster_align4(c.upkp + c.IP);
     c.slot[1] = dnc_cluster_align4(c.NR + N);
     c.slot[2] = dnc_cluster_align4(2 * R * c.NR + R * N);
     c.slot[3] = dnc_cluster_align4(R * W);
-    c.ksl = dnc_cluster_max(1, CLT / dnc_cluster_max(1, c.upk));
-    if (c.ksl > c.K) c.ksl = c.K;
-    c.kperG = (c.K + c.ksl - 1) / c.ksl;
-    c.icg = c.IP / 4;
-    c.nslI = dnc_cluster_max(1, CLT / c.icg);
-    c.uperI = (c.upk + c.nslI - 1) / c.nslI;
     c.mperA = N / k;
     c.N4 = N / 4; c.W4 = W / 4;
     c.NH = (c.N4 + 63) / 64;
@@ -75,8 +62,7 @@ static constexpr __host__ __device__ DncMpCfg dnc_mp_cfg(int N, int W, int R, in
     if (c.nslR > c.NR) c.nslR = c.NR;
     c.nperR = (c.NR + c.nslR - 1) / c.nslR;
     c.RNP = (R * N + CLT - 1) / CLT;
-    c.mg_upk = dnc_cluster_magic(c.upk); c.mg_icg = dnc_cluster_magic(c.icg); c.mg_NR = dnc_cluster_magic(c.NR);
-    c.mg_N = dnc_cluster_magic(N); c.mg_W4 = dnc_cluster_magic(c.W4); c.mg_RW4 = dnc_cluster_magic(c.RW4);
+    c.mg_RW4 = dnc_cluster_magic(c.RW4);
     return c;
 }
 
@@ -126,33 +112,4 @@ __device__ __forceinline__ f32x4 mp_load4(__amdgpu_buffer_rsrc_t rs, int float_o
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ i32x4 mp_load4i(__amdgpu_buffer_rsrc_t rs, int float_off) {
     return __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, float_off * 4, 0, 16));
-}
-
-// wait with its OWN time base (a bound on one stalled exchange, not on the kernel's run time) and a sticky error word
-__device__ __forceinline__ bool mp_wait(const unsigned* flags, unsigned epoch, int k, unsigned* err, unsigned* sticky, int* s_abort, int tid) {
-    if (tid < 64) {
-        unsigned spins = 0;
-        unsigned long long t0 = 0;
-        for (;;) {
-            const unsigned v = (tid < k) ? __hip_atomic_load(flags + tid, NTK_RLX, NTK_AGENT) : epoch;
-            if (__all((int)(v - epoch) >= 0)) break;
-            if ((++spins & 127u) == 0) {
-                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                if (t0 == 0) t0 = now;
-                const bool dead = __hip_atomic_load(err, NTK_RLX, NTK_AGENT) != 0 || (now - t0) > 300000000ull;      // 3 s at 100 MHz
-                if (dead) {
-                    if (tid == 0) {
-                        __hip_atomic_store(err, 1u, NTK_RLX, NTK_AGENT);
-                        __hip_atomic_store(sticky, 1u, NTK_RLX, NTK_AGENT);
-                        *s_abort = 1;
-                    }
-                    break;
-                }
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __syncthreads();
-    return *s_abort == 0;
 }

@@ -15,6 +15,7 @@
 // partial d(write key); (4) the partial d[reads ; h]_{t-1}.  Every sum over workgroups, waves and lanes has a fixed order:
 // gradients are bitwise reproducible.
 #include "dnc_mp.h"
+#include "dnc_cluster_phases.h"
 #include <stdlib.h>
 
 // Diagnostic build only (-DNTK_CL_PROF): workgroup 0's thread 0 adds s_memtime deltas per phase to g_mpb_prof (global atomics: no
@@ -122,8 +123,6 @@ struct DncMpBwdArgs {
     float* mbox; unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
 };
 
-typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
-
 // sum over the lane groups of a wave (groups of LPR consecutive lanes; lanes with equal index inside their group are added):
 // afterwards lanes < LPR hold the wave's totals
 __device__ __forceinline__ float mpb_fold(float v, int LPR) {
@@ -140,24 +139,20 @@ __device__ __forceinline__ f32x4 mpb_fold4(f32x4 v, int LPR) {
     const int k = C.k, NR = C.NR, upk = C.upk;                                                                                \
     const int N = C.N, W = C.W, R = C.R, RN = R * N;                                                                          \
     const int hid = C.hid, K = C.K, IP = C.IP, RWd = R * W, N4 = C.N4, W4 = C.W4;                                             \
-    const int row0 = g * NR, u0 = min(hid, g * upk), u1 = min(hid, u0 + upk), nU = u1 - u0;                                   \
+    const int row0 = g * NR, u0 = min(hid, g * upk), nU = min(hid, u0 + upk) - u0;                                            \
     float* sPart = smem + L.part; float* sRP = smem + L.RP; float* sNMr = smem + L.NMr; float* sNMw = smem + L.NMw;           \
     float* sI = smem + L.I; float* sDX = smem + L.DX;                                                                         \
-    float* sWW = smem + L.WW; float* sWWp = smem + L.WWp; float* sU = smem + L.U; float* sUp = smem + L.Up;                   \
-    float* sPp = smem + L.Pp; float* sCW = smem + L.CW; float* sAL = smem + L.AL; float* sSIMw = smem + L.SIMw;               \
-    float* sDWW = smem + L.DWW; float* sDCW = smem + L.DCW; float* sDA = smem + L.DA; float* sgP = smem + L.gP;               \
-    float* sDPp = smem + L.DPp; float* sgU = smem + L.gU; float* sgUn = smem + L.gUn; float* sNU = smem + L.NU;               \
-    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                          \
+    float* sWW = smem + L.WW; float* sPp = smem + L.Pp; float* sSIMw = smem + L.SIMw;                                         \
+    float* sDWW = smem + L.DWW; float* sDCW = smem + L.DCW; float* sDPp = smem + L.DPp;                                       \
+    unsigned long long* sKEY = reinterpret_cast<unsigned long long*>(smem + L.KEY);                                           \
     int* sRank = reinterpret_cast<int*>(smem + L.RANK);                                                                       \
-    float* sRWp = smem + L.RWp; float* sRWt = smem + L.RWt; float* sgRW = smem + L.gRW; float* sG = smem + L.G; float* sDRWp = smem + L.DRWp;             \
-    float* sDSIM = smem + L.DSIM; float* sSIMr = smem + L.SIMr;                                                               \
-    float* sGZ = smem + L.GZ; float* sDR = smem + L.DR; float* sDHC = smem + L.DHC; float* sDG = smem + L.DG;                 \
-    float* sgC = smem + L.gC; float* sSC = smem + L.SC; int* sAbort = reinterpret_cast<int*>(sSC + 120);                       \
-    (void)k; (void)K; (void)IP; (void)RWd; (void)N4; (void)W4; (void)u1; (void)nU; (void)RN; (void)sPart; (void)sRP; (void)sNMr; (void)sNMw; \
-    (void)sI; (void)sDX; (void)sWW; (void)sWWp; (void)sU; (void)sUp; (void)sPp; (void)sCW; (void)sAL; (void)sSIMw;            \
-    (void)sDWW; (void)sDCW; (void)sDA; (void)sgP; (void)sDPp; (void)sgU; (void)sgUn; (void)sNU; (void)sKEY; (void)sRank;      \
-    (void)sRWp; (void)sRWt; (void)sgRW; (void)sG; (void)sDRWp; (void)sDSIM; (void)sSIMr; (void)sGZ; (void)sDR; (void)sDHC; (void)sDG;     \
-    (void)sgC; (void)sAbort; (void)row0; (void)u0
+    float* sRWp = smem + L.RWp; float* sRWt = smem + L.RWt; float* sgRW = smem + L.gRW; float* sG = smem + L.G; float* sDRWp = smem + L.DRWp;\
+    float* sDSIM = smem + L.DSIM; float* sSIMr = smem + L.SIMr; float* sDR = smem + L.DR; float* sDHC = smem + L.DHC;         \
+    float* sSC = smem + L.SC; int* sAbort = reinterpret_cast<int*>(sSC + 120);                                                \
+    (void)k; (void)K; (void)IP; (void)RWd; (void)N4; (void)W4; (void)nU; (void)RN; (void)sPart; (void)sRP; (void)sNMr; (void)sNMw; (void)upk; (void)hid; (void)W; (void)R;\
+    (void)sI; (void)sDX; (void)sWW; (void)sPp; (void)sSIMw; (void)sDWW; (void)sDCW; (void)sDPp; (void)sKEY; (void)sRank;      \
+    (void)sRWp; (void)sRWt; (void)sgRW; (void)sG; (void)sDRWp; (void)sDSIM; (void)sSIMr; (void)sDR; (void)sDHC; (void)sSC;    \
+    (void)sAbort; (void)row0; (void)u0
 
 template <int SH>
 __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
@@ -174,14 +169,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
     const int tid0 = threadIdx.x;
     const int kk0 = FIX ? kDncMpFixCfg.k : a0.c.k;
     int b, g;
-    if (a0.xcd_local) {
-        const int x = blockIdx.x & 7, s = blockIdx.x >> 3;
-        b = x + 8 * (s / kk0);
-        g = s % kk0;
-    } else {
-        b = blockIdx.x / kk0;
-        g = blockIdx.x % kk0;
-    }
+    dncc_block_to_bg(a0.xcd_local, kk0, b, g);
     const float EPS = 1e-6f;
     const int S = a0.S;
     const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
@@ -200,12 +188,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         const DncMpBwdLds L = FIX ? kDncMpFixBwdLds : a.lds;
         MP_BWD_VIEWS();
         if (tid0 == 0) *sAbort = 0;
-        float* cy = a.gcarry ? a.gcarry + (size_t)b * (2 * N + RN + Q.ldkT + hid) : nullptr;
-        const bool cin = cy && a.carry_in;
-        for (int i = tid0; i < N; i += CT) { sgP[i] = cin ? cy[i] : 0.f; sgU[i] = cin ? cy[N + i] : 0.f; }
-        for (int i = tid0; i < RN; i += CT) sgRW[i] = cin ? cy[2 * N + i] : 0.f;
-        for (int i = tid0; i < Q.ldkT; i += CT) sGZ[i] = (cin && i < K) ? cy[2 * N + RN + i] : 0.f;
-        for (int i = tid0; i < nU; i += CT) sgC[i] = cin ? cy[2 * N + RN + Q.ldkT + u0 + i] : 0.f;
+        dncc_bwd_carry_in(C, a, dncc_bwd_state(smem, L, C, g, tid0), b, Q.ldkT);
         const int gl0 = tid0 & (Q.LPR - 1), grp0 = tid0 / Q.LPR;
 #pragma unroll
         for (int q = 0; q < MPQ; ++q) {
@@ -216,12 +199,10 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         }
     }
     __syncthreads();
-    bool plain = false;
-    if (a0.xcd_local) {
+    bool plain;
+    {
         int* const sw = reinterpret_cast<int*>(smem + (FIX ? kDncMpFixBwdLds.SC : a0.lds.SC)) + 121;
-        const int same = cl_same_xcd(a0.xcc + (size_t)b * kk0, g, kk0, a0.err, sw - 1, sw, t_start, tid0);
-        if (same < 0) { if (tid0 == 0) __hip_atomic_store(a0.sticky, 1u, NTK_RLX, NTK_AGENT); return; }
-        plain = __builtin_amdgcn_readfirstlane(same) != 0;
+        if (!dncc_same_xcd_prologue(a0.xcd_local, a0.xcc, b, g, kk0, a0.err, a0.sticky, sw, t_start, tid0, plain)) return;
     }
 
 #ifdef NTK_CL_PROF
@@ -266,6 +247,8 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         float* slot2 = mb2 + ((size_t)par * k + g) * sl2;
         float* slot3 = mb3 + ((size_t)par * k + g) * sl3;
         float* slot4 = mb4 + ((size_t)par * k + g) * sl4;
+        DncClBwdSt st = dncc_bwd_state(smem, L, C, g, tid);
+        st.bt = bt; st.plain = plain; st.clipv = clipv;
 
         MP_STAMP(0);       // loop top
         // Memory rows in registers: Mt = own rows of M_t (B2, B4), Mp = own rows of M_{t-1} (B7; requested again behind hand-off 2
@@ -294,22 +277,9 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
             const float* p_rwp = (t > 0) ? a.rec_rw + (bt - 1) * RN : a.rw0 + (size_t)b * RN;
             for (int c = tid; c < IP; c += CT) { sI[c] = a.rec_ifc[bt * IP + c]; sDX[c] = 0.f; }
             for (int i = tid; i < RN; i += CT) { sRWp[i] = p_rwp[i]; sRWt[i] = a.rec_rw[bt * RN + i]; }
-            {
-#pragma clang fp contract(off)
-                for (int n = tid; n < N; n += CT) {
-                    const float u = a.rec_u[bt * N + n];
-                    sWW[n] = a.rec_ww[bt * N + n];
-                    sU[n] = u;
-                    sCW[n] = a.rec_cw[bt * N + n];
-                    sAL[n] = a.rec_al[bt * N + n];
-                    sWWp[n] = p_wwp[n];
-                    sUp[n] = p_up[n];
-                    sPp[n] = p_pp[n];
-                    const float nu = 1.0f - (EPS + (1.0f - EPS) * u);             // exactly the forward kernel's expression
-                    sNU[n] = nu;
-                    sKEY[n] = ((unsigned long long)__float_as_uint(nu) << 32) | (unsigned)(0xFFFF - n);
-                }
-            }
+            for (int n = tid; n < N; n += CT)
+                dncc_bwd_slot_records(st, n, a.rec_ww[bt * N + n], a.rec_u[bt * N + n], a.rec_cw[bt * N + n], a.rec_al[bt * N + n], p_wwp[n], p_up[n],
+                                      p_pp[n]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 pf_cr[j] = 0.f; pf_fv[j] = 0.f; pf_bv[j] = 0.f;
@@ -321,42 +291,16 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                 }
             }
         }
-        if (tid < 64) sSC[tid] = 0.f;
-        if (tid < C.OP) {                         // B1: output clip + linear
-            float gy = 0.f;
-            if (tid < C.O) {
-                const float ypre = a.rec_ypre[bt * C.O + tid];
-                gy = (clipv <= 0.f || fabsf(ypre) < clipv) ? a.dout[bt * C.O + tid] : 0.f;
-            }
-            sSC[32 + tid] = gy;
-            if (g == 0) a.dypre[bt * C.OP + tid] = gy;
+        {                                         // B1: output clip + linear
+            float ypre = 0.f, dout = 0.f;
+            if (tid < C.O) { ypre = a.rec_ypre[bt * C.O + tid]; dout = a.dout[bt * C.O + tid]; }
+            dncc_bwd_output_clip(C, a, st, ypre, dout);
         }
         __syncthreads();
-        for (int kk = tid; kk < C.Ky; kk += CT) {
-            float s = 0.f;
-            for (int o = 0; o < C.O; ++o) s += a.Wy[(size_t)kk * C.OP + o] * sSC[32 + o];
-            if (kk < hid) sDHC[kk] = sGZ[RWd + kk] + s;       // carried d(clipped h) + this step's output path
-            else sDR[kk - hid] = sGZ[kk - hid] + s;           // carried d(reads) + output path
-        }
-        if (wave <= R) {                                      // key norms: sSC[0..R-1] = |kr_i|, sSC[R] = |kw|
-            const float* kp = (wave < R) ? sI + C.oKr + wave * W : sI + C.oKw;
-            float ss = 0.f;
-            for (int w = lane; w < W; w += 64) ss += kp[w] * kp[w];
-            ss = wave_sum(ss);
-            if (lane == 0) sSC[wave] = sqrtf(ss + EPS);
-        }
+        dncc_bwd_output_path_key_norms(C, a, st);
         // rank of every slot among the own N/k keys (partial count; summed after hand-off 1)
-        for (int n = tid; n < N; n += CT) {
-            const unsigned long long mine = sKEY[n];
-            const u64x2* kp = reinterpret_cast<const u64x2*>(sKEY + g * C.mperA);
-            int cnt = 0;
-            for (int m = 0; m < C.mperA; m += 8) {
-                const u64x2 k0 = kp[(m >> 1)], k1 = kp[(m >> 1) + 1], k2 = kp[(m >> 1) + 2], k3 = kp[(m >> 1) + 3];
-                cnt += (k0[0] > mine) + (k0[1] > mine) + (k1[0] > mine) + (k1[1] > mine) + (k2[0] > mine) + (k2[1] > mine) +
-                       (k3[0] > mine) + (k3[1] > mine);
-            }
-            cl_store(slot1 + 2 * R * NR + n, __int_as_float(cnt), plain);
-        }
+        for (int n = tid; n < N; n += CT)
+            cl_store(slot1 + 2 * R * NR + n, __int_as_float(dncc_rank_count(sKEY + g * C.mperA, C.mperA, sKEY[n])), plain);
         __syncthreads();
         MP_STAMP(1);       // records -> LDS, B1, key norms, rank partial
         // ------------------------------------------------------------ B2: pass 1 over M_t (registers): d(rw) through the reads, read-key scores
@@ -406,7 +350,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
             pf_cprev = p_cprev[u];
         }
         MP_STAMP(3);       // publish 1 + gate record requests
-        if (!mp_wait(fl1, epoch, k, a.err, a.sticky, sAbort, tid)) return;
+        if (!cl_wait(fl1, epoch, k, a.err, a.sticky, sAbort, tid)) return;
         MP_STAMP(4);       // wait 1
         {   // consume hand-off 1: G and the read-key scores of every slot; ranks (16-byte loads: four consecutive slots per thread)
             const __amdgpu_buffer_rsrc_t rs = mp_rsrc(mb1 + (size_t)par * k * sl1, (size_t)k * sl1);
@@ -430,41 +374,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         __syncthreads();
         MP_STAMP(5);       // consume 1
         // ------------------------------------------------------------ B3: read-weight mix, read-content softmax (wave i = head i)
-        if (wave < R) {
-            const int i = wave;
-            const float* rm = sI + C.oRm + i * 3;              // [backward, forward, content] (access.py:283-289)
-            float p0 = 0.f, p1 = 0.f, p2 = 0.f, s1 = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int n = lane + 64 * j;
-                if (n < N) {
-                    const float gg = sG[i * N + n], cr = pf_cr[j];
-                    p0 += gg * pf_bv[j]; p1 += gg * pf_fv[j]; p2 += gg * cr;
-                    s1 += cr * (rm[2] * gg);
-                }
-            }
-            p0 = wave_sum(p0); p1 = wave_sum(p1); p2 = wave_sum(p2); s1 = wave_sum(s1);
-            const float br = sI[C.oBr + i];
-            float dbeta = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int n = lane + 64 * j;
-                if (n < N) {
-                    const float gg = sG[i * N + n];
-                    const float dscore = pf_cr[j] * (rm[2] * gg - s1);
-                    dbeta += dscore * sSIMr[i * N + n];
-                    sDSIM[i * N + n] = dscore * br;
-                }
-            }
-            dbeta = wave_sum(dbeta);
-            if (lane == 0) {
-                const float dotp = rm[0] * p0 + rm[1] * p1 + rm[2] * p2;
-                sDX[C.oRm + i * 3 + 0] = rm[0] * (p0 - dotp);
-                sDX[C.oRm + i * 3 + 1] = rm[1] * (p1 - dotp);
-                sDX[C.oRm + i * 3 + 2] = rm[2] * (p2 - dotp);
-                sDX[C.oBr + i] = dbeta * (1.0f - expf(-br));   // strengths pass through softplus
-            }
-        }
+        dncc_bwd_read_mix(C, st, pf_cr, pf_fv, pf_bv);
         __syncthreads();
         MP_STAMP(6);       // B3
         // ------------------------------------------------------------ B4: pass 2 over M_t: d(M_t) (registers) and d(read keys) of the own rows
@@ -714,7 +624,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
             Mp[q] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (q < NQ && nl < NR && gl < W4) Mp[q] = reinterpret_cast<const f32x4*>(Mpg + (size_t)nl * W)[gl];
         }
-        if (!mp_wait(fl2, epoch, k, a.err, a.sticky, sAbort, tid)) return;
+        if (!cl_wait(fl2, epoch, k, a.err, a.sticky, sAbort, tid)) return;
         MP_STAMP(12);      // publish 2 + wait 2
         {   // consume hand-off 2 (16-byte loads; the order of every sum is fixed: owner's row sum, then workgroups 0..k-1)
             const __amdgpu_buffer_rsrc_t rs = mp_rsrc(mb2 + (size_t)par * k * sl2, (size_t)k * sl2);
@@ -783,88 +693,9 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         }
         MP_STAMP(13);      // consume 2
         // ------------------------------------------------------------ B6: precedence (wave 0 computes the two scalars)
-        if (wave == 0) {
-            float sw = 0.f, t1 = 0.f;
-            for (int n = lane; n < N; n += 64) { sw += sWW[n]; t1 += sgP[n] * sPp[n]; }
-            sw = wave_sum(sw); t1 = wave_sum(t1);
-            if (lane == 0) { sSC[16] = sw; sSC[17] = t1; }
-        }
-        __syncthreads();
-        for (int n = tid; n < N; n += CT) {
-            sDPp[n] += (1.0f - sSC[16]) * sgP[n];
-            sDWW[n] += sgP[n] - sSC[17];
-        }
-        __syncthreads();
-        // ------------------------------------------------------------ B8: write-weight mix (access.py:252-257)
-        {
-            const float ga = sI[C.oAg], gw = sI[C.oWg];
-            float* sT = sPart;                                     // rank-ordered usages
-            float* sS = sT + N;                                    // rank-ordered dA * a
-            for (int n = tid; n < N; n += CT) {
-                const float dww = sDWW[n];
-                const float dA = gw * ga * dww;
-                sDA[n] = dA;
-                sDCW[n] = gw * (1.0f - ga) * dww;
-                const int rk = sRank[n];
-                sT[rk] = 1.0f - sNU[n];
-                sS[rk] = dA * sAL[n];
-            }
-            if (wave == CW - 1) {
-                float dgw = 0.f, dga = 0.f, s18 = 0.f;
-                for (int n = lane; n < N; n += 64) {
-                    const float dww = sDWW[n];
-                    dgw += dww * (ga * sAL[n] + (1.0f - ga) * sCW[n]);
-                    dga += gw * dww * (sAL[n] - sCW[n]);
-                    s18 += sCW[n] * (gw * (1.0f - ga) * dww);
-                }
-                dgw = wave_sum(dgw); dga = wave_sum(dga); s18 = wave_sum(s18);
-                if (lane == 0) { sDX[C.oWg] = dgw * gw * (1.0f - gw); sDX[C.oAg] = dga * ga * (1.0f - ga); sSC[18] = s18; }
-            }
-            __syncthreads();
-            // ------------------------------------------------------------ B9: allocation backward in rank order
-            //   a[n] = nonusage[n] * prod_{before n} usage  ->  d usage[n] = -dA[n] * prod[n] + (sum_{after n} dA a) / usage[n]
-            if (wave == 0) {                                       // exclusive prefix product (as the forward pass)
-                const int PER = N >> 6, bs = lane * PER;
-                float ex[8], run = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) { ex[j] = run; run *= sT[bs + j]; }
-                float inc = run;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const float o = __shfl_up(inc, dd, 64); if (lane >= dd) inc *= o; }
-                float excl = __shfl_up(inc, 1, 64);
-                if (lane == 0) excl = 1.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) sT[bs + j] = excl * ex[j];
-            } else if (wave == 1) {                                // exclusive SUFFIX sum: S[r] = sum_{r' > r} dA a
-                const int PER = N >> 6, bs = lane * PER;
-                float ex[8], run = 0.f;
-#pragma unroll
-                for (int j = 7; j >= 0; --j) if (j < PER) { ex[j] = run; run += sS[bs + j]; }
-                float inc = run;
-#pragma unroll
-                for (int dd = 1; dd < 64; dd <<= 1) { const float o = __shfl_down(inc, dd, 64); if (lane + dd < 64) inc += o; }
-                float excl = __shfl_down(inc, 1, 64);
-                if (lane == 63) excl = 0.f;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if (j < PER) sS[bs + j] = excl + ex[j];
-            }
-            __syncthreads();
-            for (int n = tid; n < N; n += CT) {
-                const int rk = sRank[n];
-                const float ut = 1.0f - sNU[n];                    // sorted_usage = 1 - sorted_nonusage
-                const float dut = -sDA[n] * sT[rk] + sS[rk] / ut;
-                sgUn[n] = sgU[n] + (1.0f - EPS) * dut;             // total d(usage_t)
-                sDCW[n] = sCW[n] * (sDCW[n] - sSC[18]);            // d(score) of the write-content softmax
-            }
-        }
-        __syncthreads();
-        if (wave == 0) {
-            float dbeta = 0.f;
-            for (int n = lane; n < N; n += 64) dbeta += sDCW[n] * sSIMw[n];
-            dbeta = wave_sum(dbeta);
-            const float bw = sI[C.oBw];
-            if (lane == 0) sDX[C.oBw] = dbeta * (1.0f - expf(-bw));
-        }
+        dncc_bwd_precedence(C, st);
+        // ------------------------------------------------------------ B8 | B9: write-weight mix, allocation backward, d(write strength)
+        dncc_bwd_write_mix_alloc(C, st, sPart);
         MP_STAMP(14);      // B6, B8, B9
         // ------------------------------------------------------------ B10b: content part of d(M_{t-1}) (registers), d(write key) of the own rows
         {
@@ -910,31 +741,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         }
         MP_STAMP(23);      // B10b park
         // ------------------------------------------------------------ B11: usage backward (addressing.py:342-374)
-        {
-            float fgv[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) fgv[i] = (i < R) ? sI[C.oF + i] : 0.f;
-            for (int n = tid; n < N; n += CT) {
-                const float gq = sgUn[n];
-                const float wwp = sWWp[n];
-                const float u1v = sUp[n] + (1.0f - sUp[n]) * wwp;                // write weights: stop_gradient
-                float rwp[4], phi = 1.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { rwp[i] = (i < R) ? sRWp[i * N + n] : 0.f; phi *= (1.0f - fgv[i] * rwp[i]); }
-                const float dphi = gq * u1v;
-                sgU[n] = gq * phi * (1.0f - wwp);                                // carried d(usage_{t-1})
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (i < R) {
-                        float oth = 1.f;
-#pragma unroll
-                        for (int i2 = 0; i2 < 4; ++i2) if (i2 != i) oth *= (1.0f - fgv[i2] * rwp[i2]);
-                        sDRWp[i * N + n] += dphi * (-fgv[i]) * oth;
-                        sDSIM[i * N + n] = dphi * (-rwp[i]) * oth;               // reuse: per-slot term of d(free_gate_i)
-                    }
-                }
-            }
-        }
+        dncc_bwd_usage(C, st);
         __syncthreads();
         MP_STAMP(15);      // B10b, B11
         {   // publish hand-off 3: partial d(write key) column sums + partial d|kw|
@@ -952,16 +759,8 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
             }
             cl_publish(fl3 + g, epoch, tid, plain);
         }
-        if (wave < R) {                                                          // d(free gates)
-            const int i = wave;
-            float s = 0.f;
-            for (int n = lane; n < N; n += 64) s += sDSIM[i * N + n];
-            s = wave_sum(s);
-            const float fg = sI[C.oF + i];
-            if (lane == 0) sDX[C.oF + i] = s * fg * (1.0f - fg);
-        }
-        for (int i = tid; i < RN; i += CT) sgRW[i] = sDRWp[i];                  // carried d(read weights_{t-1})
-        for (int n = tid; n < N; n += CT) sgP[n] = sDPp[n];                     // carried d(precedence_{t-1})
+        dncc_bwd_free_gates(C, st);
+        dncc_bwd_carry_vectors(C, st);
         __syncthreads();
         MP_STAMP(16);      // publish 3, free gates, carried vectors
         // ------------------------------------------------------------ B14: d(clipped h) of the own units += d(interface) . Wi^T
@@ -986,7 +785,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
                 }
             }
         }
-        if (!mp_wait(fl3, epoch, k, a.err, a.sticky, sAbort, tid)) return;
+        if (!cl_wait(fl3, epoch, k, a.err, a.sticky, sAbort, tid)) return;
         {
             const float* base = mb3 + (size_t)par * k * sl3;
             float dn = 0.f;
@@ -1018,61 +817,14 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         }
         __syncthreads();
         // ------------------------------------------------------------ B15: clip + snt.LSTM backward of the own units
-        if (tid < nU) {
-            const int u = u0 + tid;
-            const float dh = sDHC[u] + sPart[tid];
-            const f32x4 gg = pf_gates;
-            const float gi = gg[0], gj = gg[1], gf = gg[2], go = gg[3];
-            const float c2 = pf_c;
-            const float cprev = dnc_clip(pf_cprev, clipv);        // the recorded cell is pre-clip; the carried state was clipped
-            const float tc = cl_tanh(c2);
-            const float h2 = tc * go;
-            const float dh2 = (clipv <= 0.f || fabsf(h2) < clipv) ? dh : 0.f;
-            const float dcc = (clipv <= 0.f || fabsf(c2) < clipv) ? sgC[tid] : 0.f;
-            const float dc2 = dcc + dh2 * go * (1.0f - tc * tc);
-            f32x4 dg;
-            dg[0] = dc2 * gj * gi * (1.0f - gi);
-            dg[1] = dc2 * gi * (1.0f - gj * gj);
-            dg[2] = dc2 * cprev * gf * (1.0f - gf);
-            dg[3] = dh2 * tc * go * (1.0f - go);
-            sgC[tid] = dc2 * gf;
-            reinterpret_cast<f32x4*>(sDG)[tid] = dg;
-            reinterpret_cast<f32x4*>(a.dgates)[bt * hid + u] = dg;
-        }
+        dncc_bwd_lstm(C, a, st, (tid < nU) ? sDHC[u0 + tid] + sPart[tid] : 0.f, pf_gates, pf_c, pf_cprev);
         __syncthreads();
         MP_STAMP(18);      // B14, B15
         // ------------------------------------------------------------ B16: partial d[reads_prev ; h_prev] over the own gate columns
-        {
-            const int kg4 = Q.kg4, nrow = 4 * nU;
-            if (tid < Q.nslZ * kg4) {
-                const int sl = cl_div(tid, Q.mg_kg4), cg = tid - sl * kg4;
-                const int r0 = sl * Q.nperZ, r1 = min(nrow, r0 + Q.nperZ);
-                f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-                if (r0 < r1) acc = ntk_stream_matvec<FIX ? 8 : 4>(reinterpret_cast<const f32x4*>(a.WrT) + (size_t)(4 * u0) * kg4 + cg, kg4, sDG, r0, r1, nrow - 1);
-                *reinterpret_cast<f32x4*>(sPart + sl * Q.ldkT + cg * 4) = acc;
-            }
-            __syncthreads();
-            for (int kk = tid; kk < Q.ldkT; kk += CT) {
-                float s = 0.f;
-                for (int sl = 0; sl < Q.nslZ; ++sl) s += sPart[sl * Q.ldkT + kk];
-                cl_store(slot4 + kk, s, plain);
-            }
-            cl_publish(fl4 + g, epoch, tid, plain);
-        }
+        dncc_bwd_zprev_publish<FIX ? 8 : 4>(Q, a, st, slot4, fl4 + g, epoch);
         MP_STAMP(19);      // B16 + publish 4
-        if (!mp_wait(fl4, epoch, k, a.err, a.sticky, sAbort, tid)) return;
-        {
-            const float* base = mb4 + (size_t)par * k * sl4;
-            for (int kk = tid; kk < K; kk += CT) {
-                float pv[8];
-#pragma unroll
-                for (int gg = 0; gg < 8; ++gg) pv[gg] = (gg < k) ? cl_load(base + (size_t)gg * sl4 + kk) : 0.f;
-                float s = 0.f;
-#pragma unroll
-                for (int gg = 0; gg < 8; ++gg) if (gg < k) s += pv[gg];
-                sGZ[kk] = s;
-            }
-        }
+        if (!cl_wait(fl4, epoch, k, a.err, a.sticky, sAbort, tid)) return;
+        dncc_bwd_zprev_consume(st, mb4 + (size_t)par * k * sl4, sl4, k, K);
         MP_STAMP(20);      // wait 4 + consume
         __syncthreads();
     }
@@ -1087,15 +839,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         const DncMpBwdGeo Q = FIX ? kDncMpFixBwdGeo : a.q;
         const DncMpBwdLds L = FIX ? kDncMpFixBwdLds : a.lds;
         MP_BWD_VIEWS();
-        float* cy = a.gcarry ? a.gcarry + (size_t)b * (2 * N + RN + Q.ldkT + hid) : nullptr;
-        if (cy) {
-            if (g == 0) {
-                for (int i = tid0; i < N; i += CT) { cy[i] = sgP[i]; cy[N + i] = sgU[i]; }
-                for (int i = tid0; i < RN; i += CT) cy[2 * N + i] = sgRW[i];
-                for (int i = tid0; i < Q.ldkT; i += CT) cy[2 * N + RN + i] = sGZ[i];
-            }
-            for (int i = tid0; i < nU; i += CT) cy[2 * N + RN + Q.ldkT + u0 + i] = sgC[i];
-        }
+        dncc_bwd_carry_out(C, a, dncc_bwd_state(smem, L, C, g, tid0), b, Q.ldkT);
         const int gl0 = tid0 & (Q.LPR - 1), grp0 = tid0 / Q.LPR;
 #pragma unroll
         for (int q = 0; q < MPQ; ++q) {
@@ -1174,14 +918,11 @@ extern "C" int ntk_dnc_mp_bwd(int B, int S, int N, int W, int R, int Wn, int hid
     NTK_REQUIRE(ldkT == a.q.ldkT, NTK_ERR_BAD_SHAPE, "ntk_dnc_mp_bwd: ldkT=%d (expected %d = K rounded up to 4)", ldkT, a.q.ldkT);
     a.lds = dnc_mp_bwd_lds(a.c, a.q);
     a.B = B; a.S = S; a.clip = clip_value; a.carry_in = carry_in;
-    NTK_REQUIRE(WrT && Wi && Wy && mem0 && link0 && usage0 && rw0 && ww0 && prec0 && hc0 && rec_gates && rec_c && rec_ifc &&
-                    rec_u && rec_ww && rec_rw && rec_cw && rec_cr && rec_al && rec_p && rec_fwd && rec_bwd && rec_M && rec_L &&
-                    rec_ypre && dout && gM && gL && dgates && dxi && dypre && workspace,
-                NTK_ERR_BAD_PTR, "ntk_dnc_mp_bwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(WrT) && ntk_aligned16(Wi) && ntk_aligned16(rec_gates) && ntk_aligned16(rec_M) && ntk_aligned16(rec_L) &&
-                    ntk_aligned16(gM) && ntk_aligned16(gL) && ntk_aligned16(dgates) && ntk_aligned16(mem0) && ntk_aligned16(link0) &&
-                    ntk_aligned16(workspace),
-                NTK_ERR_BAD_PTR, "ntk_dnc_mp_bwd: 16-byte alignment");
+    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_mp_bwd", {WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0, rec_gates, rec_c, rec_ifc,
+                                               rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
+                                               dout, gM, gL, dgates, dxi, dypre, workspace}, {},
+                                              {WrT, Wi, rec_gates, rec_M, rec_L, gM, gL, dgates, mem0, link0, workspace});
+    if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
     a.WrT = WrT; a.Wi = Wi; a.Wy = Wy;
     a.mem0 = mem0; a.link0 = link0; a.usage0 = usage0; a.rw0 = rw0; a.ww0 = ww0; a.prec0 = prec0; a.hc0 = hc0;
