@@ -104,8 +104,9 @@ int ntk_vgg_conv3x3_relu_split3(const void* in_split, const void* w_packed, cons
  * ntk_vgg_conv3x3_relu_f32 up to rounding, ~1e-6 relative per layer).  Weights: U = G g G^T for the 16 transform
  * planes, packed lane-major for the MFMA B operand (ntk_vgg_wino_packed_floats(cin, cout) = 16*cin*cout floats).
  * cin a multiple of 16 and at most 1024, cout a multiple of 64 (64, 128, 256 or a multiple of 512); H and W multiples
- * of 4. */
+ * of 4.  ntk_vgg_wino_supported: 1 for a layer shape the entry takes (the entry's own decision, from shapes alone). */
 size_t ntk_vgg_wino_packed_floats(int cin, int cout);
+int ntk_vgg_wino_supported(int frames, int H, int W, int cin, int cout);
 int ntk_vgg_pack_weights_wino(const float* w_hwio, float* u_packed, int cin, int cout, void* stream);
 int ntk_vgg_conv3x3_relu_wino_f32(const float* in, const float* u_packed, const float* bias, float* out,
                                   int frames, int H, int W, int cin, int cout, int fuse_pool, void* stream);
@@ -113,8 +114,14 @@ int ntk_vgg_conv3x3_relu_wino_f32(const float* in, const float* u_packed, const 
 /* The same operator by fused Winograd F(4x4,3x3) (csrc/conv_wino43.hip): 36 transform planes, 4x fewer multiplies
  * than the direct form; fp32 rounding error ~16x that of F(2x2,3x3) (4e-6 .. 9e-6 of the activation scale per layer),
  * inside the 1e-4 bound of the path.  cin multiple of 16, cout multiple of 64 (cout/64 dividing or a multiple of 8),
- * H and W multiples of 4.  ntk_vgg_wino43_packed_floats(cin, cout) = 36*cin*cout floats. */
+ * H and W multiples of 4.  ntk_vgg_wino43_packed_floats(cin, cout) = 36*cin*cout floats.
+ * ntk_vgg_wino43_supported: 1 for a whole-frame layer shape the entries below take (on four or eight waves);
+ * ntk_vgg_wino43_blocked_supported: 1 where the eight-wave kernel takes it, which is what the channel-blocked entry
+ * ntk_vgg_conv3x3_relu_wino43_layout_f32 needs (a layer cut into single tiles only while a block of 32 tiles spans less than
+ * 16 MB of input).  Both are the launcher's own decision, from shapes alone. */
 size_t ntk_vgg_wino43_packed_floats(int cin, int cout);
+int ntk_vgg_wino43_supported(int frames, int H, int W, int cin, int cout);
+int ntk_vgg_wino43_blocked_supported(int frames, int H, int W, int cin, int cout);
 int ntk_vgg_pack_weights_wino43(const float* w_hwio, float* u_packed, int cin, int cout, void* stream);
 int ntk_vgg_conv3x3_relu_wino43_f32(const float* in, const float* u_packed, const float* bias, float* out,
                                     int frames, int H, int W, int cin, int cout, int fuse_pool, void* stream);

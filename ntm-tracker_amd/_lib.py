@@ -102,9 +102,12 @@ def _sig(lib):
         "ntk_lstm_step_fwd": (c_int, [P, P, ctypes.c_float, P, P, P, c_int, c_int, P]),
         "ntk_lstm_step_bwd": (c_int, [P] * 7 + [c_int, c_int, P]),
         "ntk_vgg_wino_packed_floats": (ctypes.c_size_t, [c_int, c_int]),
+        "ntk_vgg_wino_supported": (c_int, [c_int] * 5),
         "ntk_vgg_pack_weights_wino": (c_int, [P, P, c_int, c_int, P]),
         "ntk_vgg_conv3x3_relu_wino_f32": (c_int, [P] * 4 + [c_int] * 6 + [P]),
         "ntk_vgg_wino43_packed_floats": (ctypes.c_size_t, [c_int, c_int]),
+        "ntk_vgg_wino43_supported": (c_int, [c_int] * 5),
+        "ntk_vgg_wino43_blocked_supported": (c_int, [c_int] * 5),
         "ntk_vgg_pack_weights_wino43": (c_int, [P, P, c_int, c_int, P]),
         "ntk_vgg_conv3x3_relu_wino43_f32": (c_int, [P] * 4 + [c_int] * 6 + [P]),
         "ntk_vgg_conv3x3_relu_wino43_window_f32": (c_int, [P] * 4 + [c_int] * 10 + [P]),

@@ -345,37 +345,51 @@ extern "C" int ntk_vgg_pack_weights_wino(const float* w_hwio, float* u_packed, i
     return NTK_OK;
 }
 
+// What the launcher decides from a layer's shape alone: tile-block shape (see the table at the top: 0 = 8x4x1, 1 = 4x4x2, 3 = 2x2x8),
+// block counts and grid.  Returns 0 for a shape the kernel does not take.  One copy for the entry and for ntk_vgg_wino_supported.
+struct WinoForm { int shape, nCB, bxN, byN, NS, NQ; long long grid; };
+
+static int wino_form(int frames, int H, int W, int cin, int cout, WinoForm* f) {
+    if (frames <= 0 || H < 4 || (H % 4) || W < 4 || (W % 4)) return 0;
+    if (cin < KC || (cin % KC) || cin > WINO_MAX_CIN || cout < BNW || (cout % BNW)) return 0;      // WINO_MAX_CIN: the zero page padding pixels read from
+    if ((unsigned long long)frames * H * W * cin >= 0xffffffffull) return 0;                       // 32-bit element offsets
+    f->shape = ((W % 16) == 0 && (H % 8) == 0) ? 0 : (((W % 8) == 0 && (H % 8) == 0) ? 1 : 3);
+    f->nCB = cout / BNW;
+    f->bxN = f->shape == 0 ? W / 16 : (f->shape == 1 ? W / 8 : W / 4);
+    f->byN = f->shape == 3 ? H / 4 : H / 8;
+    const long long NQ = (long long)frames * f->byN * f->bxN;
+    const long long NS = f->shape == 1 ? (NQ + 1) / 2 : (f->shape == 3 ? (NQ + 7) / 8 : NQ);
+    if (NS >= (1ll << 30) || !(f->nCB <= 8 ? (8 % f->nCB) == 0 : (f->nCB % 8) == 0)) return 0;
+    f->NS = (int)NS;
+    f->NQ = (int)NQ;
+    long long slots;                                  // workgroup ids = slots * 8
+    if (f->nCB >= 8) slots = NS * (f->nCB / 8);
+    else { const int per = 8 / f->nCB; slots = (NS + per - 1) / per; }
+    f->grid = slots * 8;
+    return f->grid < (1ll << 31);
+}
+
+// 1 when ntk_vgg_conv3x3_relu_wino_f32 takes the layer shape
+extern "C" int ntk_vgg_wino_supported(int frames, int H, int W, int cin, int cout) {
+    WinoForm f;
+    return wino_form(frames, H, W, cin, cout, &f);
+}
+
 extern "C" int ntk_vgg_conv3x3_relu_wino_f32(const float* in, const float* u_packed, const float* bias, float* out,
                                              int frames, int H, int W, int cin, int cout, int fuse_pool, void* stream) {
     NTK_REQUIRE(in && u_packed && bias && out, NTK_ERR_BAD_PTR, "ntk_vgg_conv3x3_relu_wino_f32: null pointer");
     NTK_REQUIRE(ntk_aligned16(in) && ntk_aligned16(u_packed) && ntk_aligned16(out), NTK_ERR_BAD_PTR,
                 "ntk_vgg_conv3x3_relu_wino_f32: 16-byte alignment");
-    NTK_REQUIRE(frames > 0 && H >= 4 && (H % 4) == 0 && W >= 4 && (W % 4) == 0, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino_f32: frames=%d H=%d W=%d (H, W multiples of 4)", frames, H, W);
-    NTK_REQUIRE(cin >= KC && (cin % KC) == 0 && cin <= WINO_MAX_CIN && cout >= BNW && (cout % BNW) == 0, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino_f32: cin=%d (multiple of 16, at most %d: the zero page padding pixels read from) "
-                "cout=%d (multiple of 64)", cin, WINO_MAX_CIN, cout);
-    NTK_REQUIRE((unsigned long long)frames * H * W * cin < 0xffffffffull, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino_f32: input of %d x %d x %d x %d floats exceeds the 32-bit offset range", frames, H, W, cin);
+    WinoForm f;
+    NTK_REQUIRE(wino_form(frames, H, W, cin, cout, &f), NTK_ERR_UNSUPPORTED,
+                "ntk_vgg_conv3x3_relu_wino_f32: frames=%d H=%d W=%d (multiples of 4) cin=%d (multiple of 16, at most %d) cout=%d (multiple of 64, "
+                "cout/64 dividing or a multiple of 8); input and grid within 32-bit offsets", frames, H, W, cin, WINO_MAX_CIN, cout);
     WinoArgs a;
     a.in = in; a.U = u_packed; a.bias = bias; a.out = out;
     a.frames = frames; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout;
-    // tile-block shape (see the table at the top): 0 = 8x4x1, 1 = 4x4x2, 3 = 2x2x8
-    int shape = ((W % 16) == 0 && (H % 8) == 0) ? 0 : (((W % 8) == 0 && (H % 8) == 0) ? 1 : 3);
-    a.nCB = cout / BNW;
-    a.bxN = shape == 0 ? W / 16 : (shape == 1 ? W / 8 : W / 4);
-    a.byN = shape == 3 ? H / 4 : H / 8;
-    const long long NQ = (long long)frames * a.byN * a.bxN;
-    const long long NS = shape == 1 ? (NQ + 1) / 2 : (shape == 3 ? (NQ + 7) / 8 : NQ);
-    NTK_REQUIRE(NS < (1ll << 30) && (a.nCB <= 8 ? (8 % a.nCB) == 0 : (a.nCB % 8) == 0), NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino_f32: cout/64=%d must divide or be a multiple of 8", a.nCB);
-    a.NS = (int)NS;
-    a.NQ = (int)NQ;
-    long long slots;                                  // workgroup ids = slots * 8
-    if (a.nCB >= 8) slots = NS * (a.nCB / 8);
-    else { const int per = 8 / a.nCB; slots = (NS + per - 1) / per; }
-    const long long grid = slots * 8;
-    NTK_REQUIRE(grid < (1ll << 31), NTK_ERR_UNSUPPORTED, "ntk_vgg_conv3x3_relu_wino_f32: grid too large");
+    a.nCB = f.nCB; a.bxN = f.bxN; a.byN = f.byN; a.NS = f.NS; a.NQ = f.NQ;
+    const int shape = f.shape;
+    const long long grid = f.grid;
 #define WINO_LAUNCH(POOL_, TW_, TH_, NSUB_) conv3x3_wino_kernel<POOL_, TW_, TH_, NSUB_><<<(unsigned)grid, WT, 0, (hipStream_t)stream>>>(a)
     if (shape == 0) {
         if (fuse_pool) WINO_LAUNCH(true, 8, 4, 1); else WINO_LAUNCH(false, 8, 4, 1);

@@ -1107,6 +1107,59 @@ extern "C" int ntk_vgg_pack_weights_wino43(const float* w_hwio, float* u_packed,
     return NTK_OK;
 }
 
+// What the launcher decides from a layer's shape and window alone: tile-block shape, block counts, grid, and whether the eight-wave
+// kernel takes the layer.  Returns NTK_OK, or the code the entries refuse the shape with.  One copy for wino43_launch and for the
+// ntk_vgg_wino43*_supported predicates.
+struct Wino43Form { int shape, nCB, bxN, byN, bx0, by0, NS, NQ; long long grid, span; bool dual8; };
+
+static int wino43_form(int frames, int H, int W, int cin, int cout, int y0, int x0, int y1, int x1, Wino43Form* f) {
+    if (frames <= 0 || H < 4 || (H % 4) || W < 4 || (W % 4)) return NTK_ERR_UNSUPPORTED;
+    if (cin < 16 || (cin % 16) || cout < 64 || (cout % 64)) return NTK_ERR_UNSUPPORTED;       // the K loop takes two 8-channel steps per trip
+    // two frames within the 1 GiB window of the staging buffer resource
+    if ((unsigned long long)2 * H * W * cin * sizeof(float) > 0x40000000ull) return NTK_ERR_UNSUPPORTED;
+    // the computed window [y0, y1) x [x0, x1) in output pixels before the pool (whole frame: 0, 0, H, W), multiples of 4
+    if (!(y0 >= 0 && x0 >= 0 && y1 <= H && x1 <= W && y0 < y1 && x0 < x1 && ((y0 | x0 | y1 | x1) & 3) == 0)) return NTK_ERR_BAD_SHAPE;
+    // tile-block shape: 0 = 8x4x1 (tile grid multiple of 8 x 4), 1 = 4x4x2, 2 = 2x2x8, 3 = 1x1x32 (any grid)
+    const int gw = (x1 - x0) / 4, gh = (y1 - y0) / 4, gx0 = x0 / 4, gy0 = y0 / 4;
+    auto fits = [&](int tw, int th) { return (gw % tw) == 0 && (gh % th) == 0 && (gx0 % tw) == 0 && (gy0 % th) == 0; };
+    const int shape = fits(8, 4) ? 0 : (fits(4, 4) ? 1 : (fits(2, 2) ? 2 : 3));
+    static const int TWs[4] = {8, 4, 2, 1}, THs[4] = {4, 4, 2, 1}, NSUBs[4] = {1, 2, 8, 32};
+    f->shape = shape;
+    f->nCB = cout / 64;
+    f->bxN = gw / TWs[shape];
+    f->byN = gh / THs[shape];
+    f->bx0 = gx0 / TWs[shape];
+    f->by0 = gy0 / THs[shape];
+    const long long NQ = (long long)frames * f->byN * f->bxN;
+    const long long NS = (NQ + NSUBs[shape] - 1) / NSUBs[shape];
+    if (NS >= (1ll << 30) || !(f->nCB <= 8 ? (8 % f->nCB) == 0 : (f->nCB % 8) == 0)) return NTK_ERR_UNSUPPORTED;
+    f->NS = (int)NS;
+    f->NQ = (int)NQ;
+    long long slots;
+    if (f->nCB >= 8) slots = NS * (f->nCB / 8);
+    else { const int per = 8 / f->nCB; slots = (NS + per - 1) / per; }
+    f->grid = slots * 8;
+    if (f->grid >= (1ll << 31)) return NTK_ERR_UNSUPPORTED;
+    // the eight-wave kernel packs a staging slot into one register on the 1x1x32 shape: a block's input span (the frames its 32
+    // tiles touch) must stay below 16 MB there
+    const long long tpf = (long long)f->bxN * f->byN;
+    f->span = ((32 + tpf - 1) / tpf + 1) * (long long)H * W * cin * (long long)sizeof(float);
+    f->dual8 = shape != 3 || f->span <= 0xfffff0ll;
+    return NTK_OK;
+}
+
+// 1 when the F(4x4) entries take the whole-frame layer (on four or on eight waves)
+extern "C" int ntk_vgg_wino43_supported(int frames, int H, int W, int cin, int cout) {
+    Wino43Form f;
+    return wino43_form(frames, H, W, cin, cout, 0, 0, H, W, &f) == NTK_OK;
+}
+
+// 1 when the EIGHT-WAVE kernel takes the whole-frame layer: what ntk_vgg_conv3x3_relu_wino43_layout_f32 (channel-blocked maps) needs
+extern "C" int ntk_vgg_wino43_blocked_supported(int frames, int H, int W, int cin, int cout) {
+    Wino43Form f;
+    return wino43_form(frames, H, W, cin, cout, 0, 0, H, W, &f) == NTK_OK && f.dual8;
+}
+
 static int wino43_launch(const float* in, const float* u_packed, const float* bias, float* out,
                          int frames, int H, int W, int cin, int cout, int fuse_pool, int y0, int x0, int y1, int x1, int waves, void* stream,
                          int in_blocked = 0, int out_blocked = 0) {
@@ -1114,49 +1167,22 @@ static int wino43_launch(const float* in, const float* u_packed, const float* bi
     NTK_REQUIRE(in && u_packed && bias && out, NTK_ERR_BAD_PTR, "ntk_vgg_conv3x3_relu_wino43_f32: null pointer");
     NTK_REQUIRE(ntk_aligned16(in) && ntk_aligned16(u_packed) && ntk_aligned16(out), NTK_ERR_BAD_PTR,
                 "ntk_vgg_conv3x3_relu_wino43_f32: 16-byte alignment");
-    NTK_REQUIRE(frames > 0 && H >= 4 && (H % 4) == 0 && W >= 4 && (W % 4) == 0, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino43_f32: frames=%d H=%d W=%d (H, W multiples of 4)", frames, H, W);
-    NTK_REQUIRE(cin >= 16 && (cin % 16) == 0 && cout >= 64 && (cout % 64) == 0, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino43_f32: cin=%d (multiple of 16: the K loop takes two 8-channel steps per trip) "
-                "cout=%d (multiple of 64)", cin, cout);
-    NTK_REQUIRE((unsigned long long)2 * H * W * cin * sizeof(float) <= 0x40000000ull, NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino43_f32: two frames of %d x %d x %d floats exceed the 1 GiB window of the staging buffer resource",
-                H, W, cin);
+    Wino43Form f;
+    const int rc = wino43_form(frames, H, W, cin, cout, y0, x0, y1, x1, &f);
+    NTK_REQUIRE(rc == NTK_OK, rc,
+                "ntk_vgg_conv3x3_relu_wino43_f32: frames=%d H=%d W=%d (multiples of 4) cin=%d (multiple of 16) cout=%d (multiple of 64, cout/64 "
+                "dividing or a multiple of 8), window [%d,%d) x [%d,%d) (multiples of 4 inside the frame); two frames within 1 GiB, grid within "
+                "32 bits", frames, H, W, cin, cout, y0, y1, x0, x1);
     Wino43Args a;
     a.in = in; a.U = u_packed; a.bias = bias; a.out = out;
     a.frames = frames; a.H = H; a.W = W; a.Cin = cin; a.Cout = cout;
-    // tile-block shape: 0 = 8x4x1 (tile grid multiple of 8 x 4), 1 = 4x4x2, 2 = 2x2x8, 3 = 1x1x32 (any grid)
-    // the computed window [y0, y1) x [x0, x1) in output pixels before the pool (whole frame: 0, 0, H, W), multiples of 4
-    NTK_REQUIRE(y0 >= 0 && x0 >= 0 && y1 <= H && x1 <= W && y0 < y1 && x0 < x1 && ((y0 | x0 | y1 | x1) & 3) == 0, NTK_ERR_BAD_SHAPE,
-                "ntk_vgg_conv3x3_relu_wino43: window [%d,%d) x [%d,%d) of a %d x %d frame (multiples of 4 inside the frame)", y0, y1, x0, x1, H, W);
-    const int gw = (x1 - x0) / 4, gh = (y1 - y0) / 4, gx0 = x0 / 4, gy0 = y0 / 4;
-    auto fits = [&](int tw, int th) { return (gw % tw) == 0 && (gh % th) == 0 && (gx0 % tw) == 0 && (gy0 % th) == 0; };
-    const int shape = fits(8, 4) ? 0 : (fits(4, 4) ? 1 : (fits(2, 2) ? 2 : 3));
-    static const int TWs[4] = {8, 4, 2, 1}, THs[4] = {4, 4, 2, 1}, NSUBs[4] = {1, 2, 8, 32};
-    a.nCB = cout / 64;
-    a.bxN = gw / TWs[shape];
-    a.byN = gh / THs[shape];
-    a.bx0 = gx0 / TWs[shape];
-    a.by0 = gy0 / THs[shape];
-    const long long NQ = (long long)frames * a.byN * a.bxN;
-    const long long NS = (NQ + NSUBs[shape] - 1) / NSUBs[shape];
-    NTK_REQUIRE(NS < (1ll << 30) && (a.nCB <= 8 ? (8 % a.nCB) == 0 : (a.nCB % 8) == 0), NTK_ERR_UNSUPPORTED,
-                "ntk_vgg_conv3x3_relu_wino43_f32: cout/64=%d must divide or be a multiple of 8", a.nCB);
-    a.NS = (int)NS;
-    a.NQ = (int)NQ;
-    long long slots;
-    if (a.nCB >= 8) slots = NS * (a.nCB / 8);
-    else { const int per = 8 / a.nCB; slots = (NS + per - 1) / per; }
-    const long long grid = slots * 8;
-    NTK_REQUIRE(grid < (1ll << 31), NTK_ERR_UNSUPPORTED, "ntk_vgg_conv3x3_relu_wino43_f32: grid too large");
-    // the eight-wave kernel packs a staging slot into one register on the 1x1x32 shape: a block's input span (the frames its 32
-    // tiles touch) must stay below 16 MB there
-    const long long tpf = (long long)a.bxN * a.byN;
-    const long long span = ((32 + tpf - 1) / tpf + 1) * (long long)H * W * cin * (long long)sizeof(float);
-    const bool dual = waves == 8 && (shape != 3 || span <= 0xfffff0ll);
+    a.nCB = f.nCB; a.bxN = f.bxN; a.byN = f.byN; a.bx0 = f.bx0; a.by0 = f.by0; a.NS = f.NS; a.NQ = f.NQ;
+    const int shape = f.shape;
+    const long long grid = f.grid;
+    const bool dual = waves == 8 && f.dual8;
     NTK_REQUIRE(!(in_blocked || out_blocked) || dual, NTK_ERR_UNSUPPORTED,
                 "ntk_vgg_conv3x3_relu_wino43_layout_f32: channel-blocked maps need the eight-wave kernel "
-                "(in_blocked=%d out_blocked=%d waves=%d, input span of a block %lld B)", in_blocked, out_blocked, waves, span);
+                "(in_blocked=%d out_blocked=%d waves=%d, input span of a block %lld B)", in_blocked, out_blocked, waves, f.span);
 #define W43_LAUNCH(POOL_, TW_, TH_, NSUB_, PWS_, SPXS_)                                                                       \
     do {                                                                                                                      \
         if (dual && in_blocked && out_blocked)                                                                                \

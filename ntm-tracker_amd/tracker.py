@@ -45,6 +45,17 @@ def offset_loss(logits, offsets, T, want_grad=True):
     return loss, pred, dlogits
 
 
+def _window_features(vgg, features_roi, conv_dtype):
+    """features_roi on an fp32 Winograd trunk: conv4_3 only where extract_features reads it (GRID_START .. GRID_START +
+    (GRID_N - 1) * GRID_STEP), in whole 4x4 tiles.  Returns whether the window was set."""
+    if not (features_roi and vgg is not None and conv_dtype == "f32" and vgg.algo == "winograd"):
+        return False
+    lo = (GRID_START // 4) * 4
+    hi = ((GRID_START + (GRID_N - 1) * GRID_STEP) // 4 + 1) * 4
+    vgg.features_window = (lo, lo, hi, hi)
+    return True
+
+
 class RMSPropClip(object):
     """tf.clip_by_global_norm + tf.train.RMSPropOptimizer on one flat buffer
     (direct_offset_output.py:620-626): ms slot starts at 1, epsilon inside the sqrt."""
@@ -203,12 +214,9 @@ class _TwoStreamPipeline(object):
         if slot["free"] is not None:
             s_vgg.wait_event(slot["free"])                               # core pass that last read this buffer is done
         with torch.cuda.stream(s_vgg):
-            keep = getattr(self.vgg, "split3", False)
-            self.vgg.split3 = keep and (beside != "train" or getattr(self, "pipeline_trunk_split3", True))    # (DNCOffsetTracker.__init__)
-            try:
-                self.vgg(frames, out=slot["buf"])
-            finally:
-                self.vgg.split3 = keep
+            # a split trunk beside a training pass runs the Winograd form unless its tracker says otherwise (DNCOffsetTracker.__init__)
+            wino = self.vgg.split3 and beside == "train" and not getattr(self, "pipeline_trunk_split3", True)
+            self.vgg(frames, out=slot["buf"], form="winograd" if wino else None)
             done = torch.cuda.Event()
             done.record(s_vgg)
         self._pending.append((slot, done))
@@ -269,11 +277,7 @@ class NTMOffsetTracker(_TwoStreamPipeline, _Checkpointing):
         self.S = self.T * (NUM_FEATURES + 1)
         self.device = torch.device(device)
         self.vgg = VGG16Conv43(vgg_weights, device=self.device, chunk_frames=vgg_chunk_frames, dtype=conv_dtype, algo=conv_algo) if vgg_weights else None
-        self.features_roi = bool(features_roi) and self.vgg is not None and conv_dtype == "f32" and self.vgg.algo == "winograd"
-        if self.features_roi:          # conv4_3 only where extract_features reads it (GRID_START .. GRID_START + (GRID_N - 1) * GRID_STEP), whole 4x4 tiles
-            lo = (GRID_START // 4) * 4
-            hi = ((GRID_START + (GRID_N - 1) * GRID_STEP) // 4 + 1) * 4
-            self.vgg.features_window = (lo, lo, hi, hi)
+        self.features_roi = _window_features(self.vgg, features_roi, conv_dtype)
         self.cell = NTMCell(2, mem_size=mem_size, mem_dim=mem_dim, controller_hidden_size=hidden_size,
                             controller_num_layers=num_layers, write_head_size=write_head_size,
                             read_head_size=read_head_size, write_first=write_first,
@@ -353,11 +357,7 @@ class DNCOffsetTracker(_TwoStreamPipeline, _Checkpointing):
         # beside a TRAINING pass.
         self.pipeline_trunk_split3 = not (conv_algo is None and "NTK_TRUNK_ALGO" not in os.environ)
         self.vgg = VGG16Conv43(vgg_weights, device=self.device, chunk_frames=vgg_chunk_frames, dtype=conv_dtype, algo=conv_algo) if vgg_weights else None
-        self.features_roi = bool(features_roi) and self.vgg is not None and conv_dtype == "f32" and self.vgg.algo == "winograd"
-        if self.features_roi:          # conv4_3 only where extract_features reads it (GRID_START .. GRID_START + (GRID_N - 1) * GRID_STEP), whole 4x4 tiles
-            lo = (GRID_START // 4) * 4
-            hi = ((GRID_START + (GRID_N - 1) * GRID_STEP) // 4 + 1) * 4
-            self.vgg.features_window = (lo, lo, hi, hi)
+        self.features_roi = _window_features(self.vgg, features_roi, conv_dtype)
         self.core = DNC({"memory_size": mem_size, "word_size": mem_dim, "num_reads": read_head_size,
                          "num_writes": write_head_size}, {"hidden_size": hidden_size}, 2, clip_value,
                         input_dim=feature_channels + 2, device=self.device, seed=seed)

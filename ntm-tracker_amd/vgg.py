@@ -7,7 +7,10 @@ conv2_2 and conv3_3 (fused into the producing conv's epilogue), NHWC fp32,
 TF HWIO weights.  The extractor is frozen (constants in the reference), so it
 is inference-only.
 """
+import math
 import os
+from collections import namedtuple
+
 import torch
 
 from . import _lib
@@ -31,19 +34,49 @@ def conv_flops_per_frame(h=224, w=224):
     return total
 
 
+# activation maps by layout: fp32 "nhwc" [F,H,W,C], fp32 channel-"blocked" [F,H,C/8,W,8], fp16 "split" [F,H,W,C/16,2,16] (hi | lo parts),
+# "bf16" [F,H,W,C]
+_MAP_DTYPE = {"nhwc": torch.float32, "blocked": torch.float32, "split": torch.float16, "bf16": torch.bfloat16}
+
+
+def _map_shape(layout, F, H, W, C):
+    if layout == "blocked":
+        return (F, H, C // 8, W, 8)
+    if layout == "split":
+        return (F, H, W, C // 16, 2, 16)
+    return (F, H, W, C)
+
+
+def _conv(entry, x, src, dst, w_packed, bias, cin, cout, fuse_pool, out, tail, err, *err_args):
+    """What the conv3x3_relu* wrappers share: `x` must be a `src` map of cin channels (else NtkError(err % err_args)); the output
+    map, in the `dst` layout, is allocated unless given; one checked call of the library's `entry` with the common arguments and
+    `tail`.  fuse_pool None: the entry has no pool argument."""
+    F, H, W = (x.shape[0], x.shape[1], x.shape[3 if src == "blocked" else 2]) if x.dim() >= 4 else (0, 0, 0)
+    if x.dtype != _MAP_DTYPE[src] or tuple(x.shape) != _map_shape(src, F, H, W, cin):
+        raise _lib.NtkError(err % err_args)
+    if out is None:
+        oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
+        out = torch.empty(_map_shape(dst, F, oh, ow, cout), device=x.device, dtype=_MAP_DTYPE[dst])
+    pool = () if fuse_pool is None else (1 if fuse_pool else 0,)
+    _lib.check(getattr(_lib.lib(), entry)(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(out), F, H, W, cin, cout,
+                                          *pool, *tail, _lib.stream()), entry)
+    return out
+
+
+def _channels(x):
+    return x.shape[3] if x.dim() == 4 else -1
+
+
 def conv3x3_relu(x, w_packed, bias, cin, cout, fuse_pool=False, out=None):
     """x [F,H,W,Cin] fp32 NHWC device tensor -> relu(conv3x3_same(x)+b), optionally 2x2 max-pooled."""
-    F, H, W, C = x.shape
-    if C != cin:
-        raise _lib.NtkError("conv3x3_relu: input has %d channels, layer expects %d" % (C, cin))
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32)
-    L = _lib.lib()
-    _lib.check(L.ntk_vgg_conv3x3_relu_f32(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(out),
-                                          F, H, W, cin, cout, 1 if fuse_pool else 0, _lib.stream()),
-               "ntk_vgg_conv3x3_relu_f32")
-    return out
+    return _conv("ntk_vgg_conv3x3_relu_f32", x, "nhwc", "nhwc", w_packed, bias, cin, cout, fuse_pool, out, (),
+                 "conv3x3_relu: input has %d channels, layer expects %d", _channels(x), cin)
+
+
+def conv3x3_relu_f32_to_bf16(x, w_packed, bias, cin, cout, out=None):
+    """conv3x3_relu of fp32 NHWC frames written as a bf16 map (where the bf16 trunk starts: conv1_1)."""
+    return _conv("ntk_vgg_conv3x3_relu_f32_to_bf16", x, "nhwc", "bf16", w_packed, bias, cin, cout, None, out, (),
+                 "conv3x3_relu_f32_to_bf16: input has %d channels, layer expects %d", _channels(x), cin)
 
 
 def pack_weights(w_hwio):
@@ -59,12 +92,8 @@ def pack_weights(w_hwio):
 
 
 def wino_supported(cin, cout, H, W, frames=1):
-    """Shapes the fused Winograd kernel takes (otherwise the direct kernel runs): channel multiples, at most 1024 input
-    channels (WINO_MAX_CIN: the zero page padding pixels read from), H and W multiples of 4, and an input small enough for
-    its 32-bit element offsets."""
-    nCB = cout // 64
-    return (cin % 16 == 0 and 0 < cin <= 1024 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
-            and H > 0 and W > 0 and H % 4 == 0 and W % 4 == 0 and frames * H * W * cin < 0xffffffff)
+    """Shapes the fused Winograd kernel takes (otherwise the direct kernel runs): the entry's own answer (csrc/conv_wino.hip, wino_form)."""
+    return bool(_lib.lib().ntk_vgg_wino_supported(frames, H, W, cin, cout))
 
 
 def pack_weights_wino(w_hwio):
@@ -80,23 +109,13 @@ def pack_weights_wino(w_hwio):
 
 def conv3x3_relu_wino(x, u_packed, bias, cin, cout, fuse_pool=False, out=None):
     """Same operator as conv3x3_relu by fused Winograd F(2x2,3x3) (csrc/conv_wino.hip)."""
-    F, H, W, C = x.shape
-    if C != cin:
-        raise _lib.NtkError("conv3x3_relu_wino: input has %d channels, layer expects %d" % (C, cin))
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_wino_f32(_lib.ptr(x), _lib.ptr(u_packed), _lib.ptr(bias), _lib.ptr(out),
-                                                        F, H, W, cin, cout, 1 if fuse_pool else 0, _lib.stream()),
-               "ntk_vgg_conv3x3_relu_wino_f32")
-    return out
+    return _conv("ntk_vgg_conv3x3_relu_wino_f32", x, "nhwc", "nhwc", u_packed, bias, cin, cout, fuse_pool, out, (),
+                 "conv3x3_relu_wino: input has %d channels, layer expects %d", _channels(x), cin)
 
 
 def wino43_supported(cin, cout, H, W, frames=1):
-    """Shapes the fused Winograd F(4x4,3x3) kernel takes."""
-    nCB = cout // 64
-    return (cin % 16 == 0 and cin > 0 and cout % 64 == 0 and nCB >= 1 and (8 % nCB == 0 if nCB <= 8 else nCB % 8 == 0)
-            and H > 0 and W > 0 and H % 4 == 0 and W % 4 == 0 and 2 * H * W * cin * 4 <= 0x40000000)
+    """Shapes the fused Winograd F(4x4,3x3) kernel takes: the launcher's own answer (csrc/conv_wino43.hip, wino43_form)."""
+    return bool(_lib.lib().ntk_vgg_wino43_supported(frames, H, W, cin, cout))
 
 
 def pack_weights_wino43(w_hwio):
@@ -114,53 +133,25 @@ def conv3x3_relu_wino43(x, u_packed, bias, cin, cout, fuse_pool=False, out=None,
     """Same operator as conv3x3_relu by fused Winograd F(4x4,3x3) (csrc/conv_wino43.hip).
     window = (y0, x0, y1, x1), multiples of 4: compute only that part of the un-pooled output (the rest of `out` is not touched).
     waves = 4 / 8: the one- / two-waves-per-SIMD form of the kernel (default: 8; same bits)."""
-    F, H, W, C = x.shape
-    if C != cin:
-        raise _lib.NtkError("conv3x3_relu_wino43: input has %d channels, layer expects %d" % (C, cin))
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32)
+    win = tuple(int(v) for v in window) if window is not None else None
     if waves is not None:
-        y0, x0, y1, x1 = [int(v) for v in window] if window is not None else (0, 0, H, W)
-        _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_wino43_form_f32(_lib.ptr(x), _lib.ptr(u_packed), _lib.ptr(bias), _lib.ptr(out),
-                                                                   F, H, W, cin, cout, 1 if fuse_pool else 0, y0, x0, y1, x1,
-                                                                   int(waves), _lib.stream()), "ntk_vgg_conv3x3_relu_wino43_form_f32")
-        return out
-    if window is not None:
-        y0, x0, y1, x1 = [int(v) for v in window]
-        _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_wino43_window_f32(_lib.ptr(x), _lib.ptr(u_packed), _lib.ptr(bias), _lib.ptr(out),
-                                                                     F, H, W, cin, cout, 1 if fuse_pool else 0, y0, x0, y1, x1,
-                                                                     _lib.stream()), "ntk_vgg_conv3x3_relu_wino43_window_f32")
-        return out
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_wino43_f32(_lib.ptr(x), _lib.ptr(u_packed), _lib.ptr(bias), _lib.ptr(out),
-                                                          F, H, W, cin, cout, 1 if fuse_pool else 0, _lib.stream()),
-               "ntk_vgg_conv3x3_relu_wino43_f32")
-    return out
-
-
-def _wino43_shape(H, W):
-    """Tile-block shape the F(4x4) kernel picks for a frame (csrc/conv_wino43.hip, wino43_launch): 0 = 8x4x1, 1 = 4x4x2, 2 = 2x2x8, 3 = 1x1x32."""
-    gw, gh = W // 4, H // 4
-    for i, (tw, th) in enumerate(((8, 4), (4, 4), (2, 2))):
-        if gw % tw == 0 and gh % th == 0:
-            return i
-    return 3
+        entry, tail = "ntk_vgg_conv3x3_relu_wino43_form_f32", (win or (0, 0, x.shape[1], x.shape[2])) + (int(waves),)
+    elif win is not None:
+        entry, tail = "ntk_vgg_conv3x3_relu_wino43_window_f32", win
+    else:
+        entry, tail = "ntk_vgg_conv3x3_relu_wino43_f32", ()
+    return _conv(entry, x, "nhwc", "nhwc", u_packed, bias, cin, cout, fuse_pool, out, tail,
+                 "conv3x3_relu_wino43: input has %d channels, layer expects %d", _channels(x), cin)
 
 
 def blocked_trunk_supported(frames, H, W):
     """Can conv1_2 .. conv4_3 of a [frames,H,W,3] batch hand channel-blocked maps [H][C/8][W][8] to each other?  Every one of them
-    must be a shape of the eight-wave F(4x4) kernel (a 1x1x32-block layer only while its blocks span less than 16 MB of input:
-    there the slot words are packed)."""
-    if H % 32 or W % 32 or H < 32 or W < 32:
-        return False
+    must be a shape of the eight-wave F(4x4) kernel (ntk_vgg_wino43_blocked_supported), which holds only for H and W that are multiples of 32."""
+    L = _lib.lib()
     h, w = H, W
     for _name, cin, cout, pool in VGG_LAYERS[1:]:
-        if not wino43_supported(cin, cout, h, w, frames):
+        if not L.ntk_vgg_wino43_blocked_supported(frames, h, w, cin, cout):
             return False
-        if _wino43_shape(h, w) == 3:
-            tpf = (w // 4) * (h // 4)
-            if ((32 + tpf - 1) // tpf + 1) * h * w * cin * 4 > 0xfffff0:
-                return False
         if pool:
             h //= 2
             w //= 2
@@ -171,22 +162,10 @@ def conv3x3_relu_wino43_blocked(x, u_packed, bias, cin, cout, fuse_pool=False, o
     """conv3x3_relu_wino43 with channel-blocked maps: the input is blocked [F,H,cin/8,W,8] (5-D) or NHWC [F,H,W,cin] (4-D); the
     output blocked [F,Ho,cout/8,Wo,8] or NHWC [F,Ho,Wo,cout].  Same arithmetic and bits as the NHWC call (csrc/conv_wino43.hip)."""
     in_blocked = x.dim() == 5
-    if in_blocked:
-        F, H, CB, W, E = x.shape
-        if CB * 8 != cin or E != 8:
-            raise _lib.NtkError("conv3x3_relu_wino43_blocked: input is %s, layer expects %d channels in blocks of 8" % (tuple(x.shape), cin))
-    else:
-        F, H, W, C = x.shape
-        if C != cin:
-            raise _lib.NtkError("conv3x3_relu_wino43_blocked: input has %d channels, layer expects %d" % (C, cin))
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, cout // 8, ow, 8) if out_blocked else (F, oh, ow, cout), device=x.device, dtype=torch.float32)
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_wino43_layout_f32(_lib.ptr(x), _lib.ptr(u_packed), _lib.ptr(bias), _lib.ptr(out),
-                                                                 F, H, W, cin, cout, 1 if fuse_pool else 0, 1 if in_blocked else 0,
-                                                                 1 if out_blocked else 0,
-                                                                 _lib.stream()), "ntk_vgg_conv3x3_relu_wino43_layout_f32")
-    return out
+    err = (("conv3x3_relu_wino43_blocked: input is %s, layer expects %d channels in blocks of 8", tuple(x.shape), cin) if in_blocked
+           else ("conv3x3_relu_wino43_blocked: input has %d channels, layer expects %d", _channels(x), cin))
+    return _conv("ntk_vgg_conv3x3_relu_wino43_layout_f32", x, "blocked" if in_blocked else "nhwc", "blocked" if out_blocked else "nhwc",
+                 u_packed, bias, cin, cout, fuse_pool, out, (1 if in_blocked else 0, 1 if out_blocked else 0), *err)
 
 
 def nhwc_to_blocked(x):
@@ -202,30 +181,14 @@ def blocked_to_nhwc(x):
 
 def conv3x3_relu_bf16(x, w_packed, bias, cin, cout, fuse_pool=False, out_f32=False, out=None):
     """bf16 NHWC activations [F,H,W,Cin] -> relu(conv3x3_same(x)+b) in bf16 (or fp32 when out_f32)."""
-    F, H, W, C = x.shape
-    if C != cin or x.dtype != torch.bfloat16:
-        raise _lib.NtkError("conv3x3_relu_bf16: expected bf16 input with %d channels" % cin)
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_bf16(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(out), F, H, W,
-                                                    cin, cout, 1 if fuse_pool else 0, 1 if out_f32 else 0, _lib.stream()),
-               "ntk_vgg_conv3x3_relu_bf16")
-    return out
+    return _conv("ntk_vgg_conv3x3_relu_bf16", x, "bf16", "nhwc" if out_f32 else "bf16", w_packed, bias, cin, cout, fuse_pool, out,
+                 (1 if out_f32 else 0,), "conv3x3_relu_bf16: expected bf16 input with %d channels", cin)
 
 
 def conv3x3_relu_bf16p(x, w_packed, bias, cin, cout, fuse_pool=False, out_f32=False, out=None):
     """conv3x3_relu_bf16 in patch form (csrc/conv_bf16p.hip); w_packed from pack_weights_bf16p for THIS frame shape."""
-    F, H, W, C = x.shape
-    if C != cin or x.dtype != torch.bfloat16:
-        raise _lib.NtkError("conv3x3_relu_bf16p: expected bf16 input with %d channels" % cin)
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32 if out_f32 else torch.bfloat16)
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_bf16p(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(out), F, H, W,
-                                                     cin, cout, 1 if fuse_pool else 0, 1 if out_f32 else 0, _lib.stream()),
-               "ntk_vgg_conv3x3_relu_bf16p")
-    return out
+    return _conv("ntk_vgg_conv3x3_relu_bf16p", x, "bf16", "nhwc" if out_f32 else "bf16", w_packed, bias, cin, cout, fuse_pool, out,
+                 (1 if out_f32 else 0,), "conv3x3_relu_bf16p: expected bf16 input with %d channels", cin)
 
 
 def pack_weights_bf16p(w_hwio, H, W):
@@ -272,21 +235,10 @@ def conv3x3_relu_split3(x, w_packed, bias, cin, cout, fuse_pool=False, out_f32=F
     """split map [F,H,W,Cin/16,2,16] (or an fp32 NHWC map [F,H,W,Cin]: the kernel's staging splits it; cin <= 64 and cout == 64 only)
     -> relu(conv3x3_same(x) + b) as a split map (or fp32 NHWC when out_f32): the fp32 product x w accumulated as
     xh wh + xh wl + xl wh on the 16-bit matrix pipe (fp16 parts, fp32 accumulators)."""
-    F, H, W = x.shape[:3]
     in_f32 = x.dtype == torch.float32
-    if in_f32:
-        if x.dim() != 4 or x.shape[3] != cin:
-            raise _lib.NtkError("conv3x3_relu_split3: expected an fp32 NHWC map of %d channels" % cin)
-    elif x.dim() != 6 or x.shape[3] * 16 != cin or x.dtype != torch.float16 or tuple(x.shape[4:]) != (2, 16):
-        raise _lib.NtkError("conv3x3_relu_split3: expected a split map of %d channels" % cin)
-    oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
-    if out is None:
-        out = (torch.empty((F, oh, ow, cout), device=x.device, dtype=torch.float32) if out_f32
-               else torch.empty((F, oh, ow, cout // 16, 2, 16), device=x.device, dtype=torch.float16))
-    _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_split3(_lib.ptr(x), _lib.ptr(w_packed), _lib.ptr(bias), _lib.ptr(out), F, H, W,
-                                                      cin, cout, 1 if fuse_pool else 0, 1 if in_f32 else 0, 1 if out_f32 else 0,
-                                                      _lib.stream()), "ntk_vgg_conv3x3_relu_split3")
-    return out
+    return _conv("ntk_vgg_conv3x3_relu_split3", x, "nhwc" if in_f32 else "split", "nhwc" if out_f32 else "split", w_packed, bias,
+                 cin, cout, fuse_pool, out, (1 if in_f32 else 0, 1 if out_f32 else 0),
+                 "conv3x3_relu_split3: expected %s of %d channels", "an fp32 NHWC map" if in_f32 else "a split map", cin)
 
 
 def pack_weights_bf16(w_hwio):
@@ -295,6 +247,80 @@ def pack_weights_bf16(w_hwio):
     _lib.check(_lib.lib().ntk_vgg_pack_weights_bf16(_lib.ptr(w_hwio.contiguous()), _lib.ptr(wp), cin, cout, _lib.stream()),
                "ntk_vgg_pack_weights_bf16")
     return wp
+
+
+# ---- which kernel runs which layer in which activation layout: decided once per frame shape
+TrunkStep = namedtuple("TrunkStep", "layer kernel src dst pool window waves")
+# TrunkStep.kernel -> the module-level function that launches it (looked up by name when a step runs)
+_STEP_FN = {"direct": "conv3x3_relu", "direct_to_bf16": "conv3x3_relu_f32_to_bf16", "wino": "conv3x3_relu_wino",
+            "wino43": "conv3x3_relu_wino43", "wino43_blocked": "conv3x3_relu_wino43_blocked", "split3": "conv3x3_relu_split3",
+            "bf16": "conv3x3_relu_bf16", "bf16p": "conv3x3_relu_bf16p"}
+
+
+def trunk_plan(frames_shape, dtype, form, upto="conv4_3", *, layout, wino_waves, features_window, split3_upto, bf16_form):
+    """The layers conv1_1 .. `upto` of a [F,H,W,3] chunk as TrunkSteps.  A pure host function: it asks the library's shape
+    predicates and touches no device and no weights.  dtype "bf16": the patch form where it takes the layer (bf16_form "patch"), the
+    tile form otherwise.  dtype "f32", by `form`:
+      "split3"    where the whole trunk can (the eight-wave F(4x4) kernel takes every layer, no window, conv1_2 fits the split form):
+                  conv1_1 direct, conv1_2 .. split3_upto in the split form for as long as it takes the layer, the rest on the F(4x4)
+                  kernel with channel-blocked maps; elsewhere as "winograd";
+      "winograd"  with layout "blocked" where the whole trunk can: F(4x4) with channel-blocked maps between the layers; elsewhere
+                  NHWC maps and per layer F(4x4) (carrying wino_waves; features_window on a final conv4_3), F(2x2), direct;
+      "winograd2" NHWC, per layer F(2x2), direct;  "direct": NHWC, direct.
+    The last step writes fp32 NHWC and is un-pooled when `upto` comes before conv4_3."""
+    F, H, W = frames_shape[:3]
+    names = [l[0] for l in VGG_LAYERS]
+    layers = VGG_LAYERS[:names.index(upto) + 1]
+    steps = []
+    if dtype == "bf16":
+        if upto != "conv4_3":
+            raise _lib.NtkError("bf16 trunk runs to conv4_3 only")
+        h, w = H, W
+        for name, cin, cout, pool in layers:
+            if not steps:
+                kernel, src = "direct_to_bf16", "nhwc"
+            else:
+                patch = bf16_form == "patch" and _lib.lib().ntk_vgg_bf16p_supported(h, w, cin, cout, 1 if pool else 0)
+                kernel, src = "bf16p" if patch else "bf16", "bf16"
+            steps.append(TrunkStep(name, kernel, src, "nhwc" if name == upto else "bf16", pool, None, None))
+            h, w = (h // 2, w // 2) if pool else (h, w)
+        return tuple(steps)
+    # the whole-trunk routes first: maps between the layers in the workspaces' own layouts, no NHWC layer after conv1_1's output
+    whole = upto == "conv4_3" and wino_waves in (None, 8) and features_window is None and blocked_trunk_supported(F, H, W)
+    n_split = None                                   # layers after conv1_1 that may run in the split form; None: the NHWC fall-back
+    if form == "split3":
+        if whole and split3_supported(H, W, 64, 64, True):
+            n_split = names.index(split3_upto) if split3_upto in names else 0
+        form = "winograd"                            # everything else as the Winograd trunk
+    if n_split is None and whole and form == "winograd" and layout == "blocked":
+        n_split = 0
+    h, w = H, W
+    for li, (name, cin, cout, pool) in enumerate(layers):
+        last = name == upto
+        src = steps[-1].dst if steps else "nhwc"
+        pool = pool and not last
+        oh, ow = (h // 2, w // 2) if pool else (h, w)
+        dst, window, waves = "nhwc", None, None
+        if li == 0:
+            kernel = "direct"                        # conv1_1: three input channels
+        elif n_split is not None:
+            if (li <= n_split and src != "blocked" and split3_supported(h, w, cin, cout, pool)
+                    and (src == "split" or (cin <= 64 and cout == 64))):     # an fp32 map is read by the four-wave form only (conv1_2)
+                kernel = "split3"                    # writes fp32 NHWC when the next layer cannot read a split map
+                nxt = None if last else VGG_LAYERS[li + 1]
+                if nxt is not None and li + 1 <= n_split and split3_supported(oh, ow, nxt[1], nxt[2], nxt[3]):
+                    dst = "split"
+            else:
+                kernel, dst = "wino43_blocked", "nhwc" if last else "blocked"
+        elif form == "winograd" and wino43_supported(cin, cout, h, w, F):
+            kernel, waves, window = "wino43", wino_waves, features_window if name == "conv4_3" else None
+        elif form in ("winograd", "winograd2") and wino_supported(cin, cout, h, w, F):
+            kernel = "wino"
+        else:
+            kernel = "direct"
+        steps.append(TrunkStep(name, kernel, src, dst, pool, window, waves))
+        h, w = oh, ow
+    return tuple(steps)
 
 
 class VGG16Conv43(object):
@@ -345,8 +371,9 @@ class VGG16Conv43(object):
         # Without the flag every call runs the same form, so a frame's features do not depend on the size of the batch it is in
         # (bit for bit: tests/test_fullsize_gpu.py).
         self.split3_latency_frames = 12
-        self._call_split3 = True
         self._packed_split3 = {}
+        self._plans = {}
+        self.last_plan = None                                   # the plan of the chunk that ran last
         if self.split3:
             algo = "winograd"                                # everything else (weights packed, layouts, fallbacks) as the Winograd trunk
         self.algo = algo
@@ -383,133 +410,101 @@ class VGG16Conv43(object):
                     if algo == "winograd":
                         self.packed_wino43[name] = pack_weights_wino43(w)
 
-    def _forward_chunk_bf16(self, frames, out=None):
-        F, H, W, _ = frames.shape
-        L = _lib.lib()
-        wp, b = self.packed["conv1_1"]
-        x = torch.empty((F, H, W, 64), device=frames.device, dtype=torch.bfloat16)
-        _lib.check(L.ntk_vgg_conv3x3_relu_f32_to_bf16(_lib.ptr(frames), _lib.ptr(wp), _lib.ptr(b), _lib.ptr(x), F, H, W, 3, 64,
-                                                      _lib.stream()), "ntk_vgg_conv3x3_relu_f32_to_bf16")
-        for name, cin, cout, pool in VGG_LAYERS[1:]:
-            wp, b = self.packed[name]
-            last = (name == "conv4_3")
-            h, w = x.shape[1], x.shape[2]
-            if self.bf16_form == "patch" and L.ntk_vgg_bf16p_supported(h, w, cin, cout, 1 if pool else 0):
-                key = (name, h % 8 == 0 and w % 8 == 0)
-                if key not in self._packed_bf16p:
-                    self._packed_bf16p[key] = pack_weights_bf16p(self._w_hwio[name], h, w)
-                    torch.cuda.current_stream(frames.device).synchronize()    # packed once, read from every stream a pass runs on
-                x = conv3x3_relu_bf16p(x, self._packed_bf16p[key], b, cin, cout, fuse_pool=pool, out_f32=last, out=out if last else None)
-            else:
-                x = conv3x3_relu_bf16(x, wp, b, cin, cout, fuse_pool=pool, out_f32=last, out=out if last else None)
-        return x
-
-    def _trunk_ws(self, frames):
-        """two ping-pong workspaces per (stream, chunk shape) for the maps between the layers, allocated once: a training loop then
-        makes no allocator calls in its trunk passes (the largest map, conv1_1's, is 12.8 MB per frame)"""
+    def _trunk_ws(self, frames, plan):
+        """Where every step of `plan` but the last writes: two ping-pong workspaces per (stream, chunk shape) for the maps between the
+        layers, allocated once -- a training loop then makes no allocator calls in its trunk passes -- and viewed once per plan in each
+        step's layout.  The largest map, conv1_1's, is 12.8 MB per frame; a split or bf16 map has at most the bytes of its layer's
+        fp32 map."""
         F, H, W, _ = frames.shape
         key = (torch.cuda.current_stream(frames.device).cuda_stream, F, H, W)
-        ws = self._blocked_ws.get(key)
-        if ws is None:
+        if key not in self._blocked_ws:
             if len(self._blocked_ws) >= 8:                        # shapes come and go (tests, online tracking): keep the table small
                 self._blocked_ws.clear()
             ws = (torch.empty(F * H * W * 64, device=frames.device), torch.empty(F * (H // 2) * (W // 2) * 64, device=frames.device))
-            self._blocked_ws[key] = ws
-        return ws
+            self._blocked_ws[key] = (ws, {})
+        ws, views = self._blocked_ws[key]
+        if plan not in views:
+            if len(views) >= 8:
+                views.clear()
+            dsts, h, w = [], H, W
+            for i, (step, (_name, _cin, cout, _pool)) in enumerate(zip(plan[:-1], VGG_LAYERS)):
+                h, w = (h // 2, w // 2) if step.pool else (h, w)
+                shape = _map_shape(step.dst, F, h, w, cout)
+                dsts.append(ws[i & 1].view(_MAP_DTYPE[step.dst])[:math.prod(shape)].view(shape))
+            views[plan] = dsts
+        return views[plan]
 
     def split3_trunk_supported(self, frames_shape):
         F, H, W = frames_shape[:3]
         return (self.wino_waves in (None, 8) and self.features_window is None and blocked_trunk_supported(F, H, W)
                 and split3_supported(H, W, 64, 64, True))
 
-    def _forward_chunk_split3(self, frames, out):
-        """conv1_1 (fp32 kernel) -> conv1_2 .. split3_upto in the split form -> the rest on the F(4x4) kernel with blocked maps."""
-        F, H, W, _ = frames.shape
-        ws = self._trunk_ws(frames)
-        wp, b = self.packed["conv1_1"]
-        x = conv3x3_relu(frames, wp, b, 3, 64, out=ws[0][:F * H * W * 64].view(F, H, W, 64))
-        names = [l[0] for l in VGG_LAYERS]
-        n_split = names.index(self.split3_upto) if self.split3_upto in names else 0
-        mode = "nhwc"                                            # what x is: fp32 "nhwc", a "split" map, or a "blocked" fp32 map
-        h, w = H, W
-        for li, (name, cin, cout, pool) in enumerate(VGG_LAYERS[1:]):
-            last = (name == "conv4_3")
-            oh, ow = (h // 2, w // 2) if pool else (h, w)
-            buf = ws[(li + 1) & 1][:F * oh * ow * cout]
-            use_split = (li + 1 <= n_split and mode != "blocked" and split3_supported(h, w, cin, cout, pool)
-                         and (mode == "split" or (cin <= 64 and cout == 64)))
-            if use_split:
-                nxt = VGG_LAYERS[li + 2] if not last else None
-                nh, nw_ = oh, ow
-                stay = (nxt is not None and li + 2 <= n_split and split3_supported(nh, nw_, nxt[1], nxt[2], nxt[3]))
-                key = (name, h, w)
-                if key not in self._packed_split3:
-                    self._packed_split3[key] = pack_weights_split3(self._w_hwio[name], h, w)
-                    torch.cuda.current_stream(frames.device).synchronize()    # packed once, read from every stream a pass runs on
-                dst = out if last else (buf.view(torch.float16).view(F, oh, ow, cout // 16, 2, 16) if stay else buf.view(F, oh, ow, cout))
-                x = conv3x3_relu_split3(x, self._packed_split3[key], self.packed[name][1], cin, cout, fuse_pool=pool,
-                                        out_f32=(last or not stay), out=dst)
-                mode = "split" if stay else "nhwc"
-            else:
-                if mode == "split":
-                    raise _lib.NtkError("split3 trunk: %s cannot read a split map" % name)
-                dst = out if last else buf.view(F, oh, cout // 8, ow, 8)
-                x = conv3x3_relu_wino43_blocked(x, self.packed_wino43[name], self.packed[name][1], cin, cout, fuse_pool=pool,
-                                                out_blocked=not last, out=dst)
-                mode = "blocked"
-            h, w = oh, ow
-        return x
+    def plan(self, frames_shape, upto="conv4_3", form=None):
+        """trunk_plan of this trunk as it is configured NOW (layout, wino_waves, features_window, ... may be assigned at any time), cached
+        per argument set.  form: None = the trunk's own ("split3" while self.split3, else self.algo); a split trunk also runs "winograd"."""
+        own = "split3" if self.split3 else self.algo
+        if form is None:
+            form = own
+        elif form != own and not (form == "winograd" and self.algo == "winograd"):
+            raise _lib.NtkError("VGG16Conv43: this %s trunk has no weights packed for form=%r" % (own, form))
+        win = self.features_window
+        key = (tuple(frames_shape[:3]), self.dtype, form, upto, self.layout, self.wino_waves, None if win is None else tuple(win),
+               self.split3_upto, self.bf16_form)
+        plan = self._plans.get(key)
+        if plan is None:
+            if len(self._plans) >= 8:
+                self._plans.clear()
+            plan = self._plans[key] = trunk_plan(key[0], *key[1:4], layout=key[4], wino_waves=key[5], features_window=key[6],
+                                                 split3_upto=key[7], bf16_form=key[8])
+        return plan
 
-    def forward_chunk(self, frames, upto="conv4_3", out=None):
-        if self.dtype == "bf16":
-            if upto != "conv4_3":
-                raise _lib.NtkError("bf16 trunk runs to conv4_3 only")
-            return self._forward_chunk_bf16(frames.contiguous(), out=out)
+    def _step_weights(self, step, h, w, device):
+        name = step.layer
+        if step.kernel in ("split3", "bf16p"):                   # packed per frame shape, on first use
+            cache, pack, key = ((self._packed_split3, pack_weights_split3, (name, h, w)) if step.kernel == "split3"
+                                else (self._packed_bf16p, pack_weights_bf16p, (name, h % 8 == 0 and w % 8 == 0)))
+            if key not in cache:
+                cache[key] = pack(self._w_hwio[name], h, w)
+                torch.cuda.current_stream(device).synchronize()    # packed once, read from every stream a pass runs on
+            return cache[key]
+        if step.kernel in ("wino43", "wino43_blocked"):
+            return self.packed_wino43[name]
+        return self.packed_wino[name] if step.kernel == "wino" else self.packed[name][0]
+
+    def forward_chunk(self, frames, upto="conv4_3", out=None, form=None):
+        """Plan and run one chunk: one loop for every form.  The last step writes `out` (allocated when None: zeroed under a window,
+        which leaves the rest untouched); every other map lives in one of the two ping-pong workspaces, viewed in the step's layout."""
+        frames = frames.contiguous()
+        F, h, w, _ = frames.shape
+        plan = self.last_plan = self.plan(frames.shape, upto, form)
+        launch = globals()                         # the conv functions by name at call time: tests count launches by patching them
+        dsts = self._trunk_ws(frames, plan) if len(plan) > 1 else []
         x = frames
-        if self.split3 and self._call_split3 and upto == "conv4_3" and self.split3_trunk_supported(frames.shape):
-            if out is None:
-                out = torch.empty((frames.shape[0], frames.shape[1] // 8, frames.shape[2] // 8, 512), device=frames.device)
-            return self._forward_chunk_split3(frames.contiguous(), out)
-        if (self.layout == "blocked" and self.algo == "winograd" and self.wino_waves in (None, 8) and self.features_window is None
-                and upto == "conv4_3" and blocked_trunk_supported(*frames.shape[:3])):
-            # the maps between the layers live in two ping-pong workspaces per (stream, chunk shape), allocated once: a training
-            # loop then makes no allocator calls in its trunk passes (the largest map, conv1_1's, is 12.8 MB per frame)
-            F, H, W, _ = frames.shape
-            ws = self._trunk_ws(frames)
-            wp, b = self.packed["conv1_1"]
-            x = conv3x3_relu(frames, wp, b, 3, 64, out=ws[0][:F * H * W * 64].view(F, H, W, 64))   # NHWC: conv1_2 reads it as it is
-            h, w = H, W
-            for li, (name, cin, cout, pool) in enumerate(VGG_LAYERS[1:]):
-                last = (name == "conv4_3")
-                oh, ow = (h // 2, w // 2) if pool else (h, w)
-                dst = out if last else ws[(li + 1) & 1][:F * oh * ow * cout].view(F, oh, cout // 8, ow, 8)
-                x = conv3x3_relu_wino43_blocked(x, self.packed_wino43[name], self.packed[name][1], cin, cout, fuse_pool=pool,
-                                                out_blocked=not last, out=dst)
-                h, w = oh, ow
-            return x
-        for name, cin, cout, pool in VGG_LAYERS:
-            wp, b = self.packed[name]
-            last = (name == upto)
-            if name in self.packed_wino43 and wino43_supported(cin, cout, x.shape[1], x.shape[2], x.shape[0]):
-                win = self.features_window if (last and name == "conv4_3") else None
-                if win is not None and out is None:
-                    out = torch.zeros((x.shape[0], x.shape[1], x.shape[2], cout), device=x.device, dtype=torch.float32)
-                x = conv3x3_relu_wino43(x, self.packed_wino43[name], b, cin, cout, fuse_pool=(pool and not last),
-                                        out=out if last else None, window=win, waves=self.wino_waves)
-            elif name in self.packed_wino and wino_supported(cin, cout, x.shape[1], x.shape[2], x.shape[0]):
-                x = conv3x3_relu_wino(x, self.packed_wino[name], b, cin, cout, fuse_pool=(pool and not last),
-                                      out=out if last else None)
+        for i, (step, (name, cin, cout, _pool)) in enumerate(zip(plan, VGG_LAYERS)):
+            if i < len(dsts):
+                dst = dsts[i]
+            elif out is None and step.window is not None:
+                dst = torch.zeros((F, h, w, cout), device=frames.device, dtype=torch.float32)
             else:
-                x = conv3x3_relu(x, wp, b, cin, cout, fuse_pool=(pool and not last), out=out if last else None)
-            if last:
-                break
+                dst = out
+            kw = {} if step.kernel == "direct_to_bf16" else {"fuse_pool": step.pool}
+            if step.kernel == "wino43":
+                kw.update(window=step.window, waves=step.waves)
+            elif step.kernel == "wino43_blocked":
+                kw["out_blocked"] = step.dst == "blocked"
+            elif step.kernel in ("split3", "bf16", "bf16p"):
+                kw["out_f32"] = step.dst == "nhwc"
+            x = launch[_STEP_FN[step.kernel]](x, self._step_weights(step, h, w, frames.device), self.packed[name][1], cin, cout,
+                                              out=dst, **kw)
+            h, w = (h // 2, w // 2) if step.pool else (h, w)
         return x
 
-    def __call__(self, frames, out=None, latency=False):
+    def __call__(self, frames, out=None, latency=False, form=None):
         """frames [F,H,W,3] mean-subtracted fp32 NHWC, H and W multiples of 32 (the reference's frames: 224 x 224) -> [F,H/8,W/8,512].
         Frames with other sides are refused before anything is launched: conv4_x runs on H/8 x W/8 maps, and every conv form needs
-        sides that are multiples of 4.  latency=True: a call of a few frames may run the form with the shorter critical path
-        (split3_latency_frames) -- same operator, results equal to fp32 rounding, not bit for bit."""
+        sides that are multiples of 4.  form: run THIS call in that form instead of the trunk's own (see plan()).  latency=True: a call
+        of a few frames may run the form with the shorter critical path (split3_latency_frames) -- same operator, results equal to fp32
+        rounding, not bit for bit."""
         if frames.dim() != 4 or frames.shape[3] != 3:
             raise _lib.NtkError("frames must be [F,H,W,3] NHWC")
         F, H, W, _ = frames.shape
@@ -521,19 +516,17 @@ class VGG16Conv43(object):
             # gets back must be zero there, not uninitialised memory
             alloc = torch.zeros if getattr(self, "features_window", None) is not None else torch.empty
             out = alloc((F, H // 8, W // 8, 512), device=frames.device, dtype=torch.float32)
-        self._call_split3 = not (latency and F < self.split3_latency_frames)
-        try:
-            return self._run_chunks(frames, out)
-        finally:
-            self._call_split3 = True
+        if form is None and latency and F < self.split3_latency_frames and self.split3:
+            form = "winograd"
+        return self._run_chunks(frames, out, form)
 
-    def _run_chunks(self, frames, out):
+    def _run_chunks(self, frames, out, form=None):
         F = frames.shape[0]
         for f0 in range(0, F, self.chunk_frames):
             f1 = min(F, f0 + self.chunk_frames)
             n = self.split_streams if (f1 - f0) >= 32 * self.split_streams else 1
             if n <= 1:
-                self.forward_chunk(frames[f0:f1], out=out[f0:f1])
+                self.forward_chunk(frames[f0:f1], out=out[f0:f1], form=form)
                 continue
             # the chunk in n parts on n streams: the kernels of the parts fill each other's launch tails (a layer's last
             # workgroups leave CUs idle until the next launch; frames are independent, the layers of one frame are not).
@@ -545,8 +538,8 @@ class VGG16Conv43(object):
             for i in range(1, n):
                 self._side[i - 1].wait_stream(cur)
                 with torch.cuda.stream(self._side[i - 1]):
-                    self.forward_chunk(frames[cuts[i]:cuts[i + 1]], out=out[cuts[i]:cuts[i + 1]])
-            self.forward_chunk(frames[cuts[0]:cuts[1]], out=out[cuts[0]:cuts[1]])
+                    self.forward_chunk(frames[cuts[i]:cuts[i + 1]], out=out[cuts[i]:cuts[i + 1]], form=form)
+            self.forward_chunk(frames[cuts[0]:cuts[1]], out=out[cuts[0]:cuts[1]], form=form)
             for i in range(1, n):
                 cur.wait_stream(self._side[i - 1])
         return out

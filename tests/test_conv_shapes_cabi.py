@@ -1,7 +1,8 @@
 """CPU: every conv form's shape predicate agrees with its launcher, over a grid of layer shapes.
 
-The trunk picks a conv kernel per layer by asking a predicate (ntk_vgg_split3_supported, ntk_vgg_bf16p_supported, vgg.wino_supported,
-vgg.wino43_supported); the entry then picks an instantiation by its own logic.  Here every entry is called with fake pointers
+The trunk picks a conv kernel per layer by asking a predicate (ntk_vgg_split3_supported, ntk_vgg_bf16p_supported, and through
+vgg.wino_supported / vgg.wino43_supported ntk_vgg_wino_supported / ntk_vgg_wino43_supported; ntk_vgg_wino43_blocked_supported for
+channel-blocked maps); the entry then picks an instantiation by its own logic.  Here every entry is called with fake pointers
 (non-null, 16-byte aligned, never dereferenced): a shape its predicate accepts must pass every host-side check and reach the launch,
 which fails without a device (NTK_ERR_HIP); a shape the predicate refuses must be refused before that (NTK_ERR_BAD_SHAPE /
 NTK_ERR_UNSUPPORTED).  With a device present a wrongly accepted shape would launch against the fake pointers, so the file runs only
@@ -101,21 +102,28 @@ def test_winograd_f2_entry_agrees_with_its_predicate():
 
 def test_winograd_f4_entries_agree_with_their_predicate():
     """ntk_vgg_conv3x3_relu_wino43_form_f32 on four and on eight waves over the whole frame, and the channel-blocked entry
-    ntk_vgg_conv3x3_relu_wino43_layout_f32 (eight waves).  Every layer of the grid is within the eight-wave kernel's reach (where it
-    cuts a frame into single tiles, a block's input spans less than 16 MB), so the blocked entry must take what the predicate takes."""
+    ntk_vgg_conv3x3_relu_wino43_layout_f32 (eight waves) against its own predicate ntk_vgg_wino43_blocked_supported.  Every layer
+    of the grid is within the eight-wave kernel's reach (where it cuts a frame into single tiles, a block's input spans less than
+    16 MB), so the blocked predicate and entry must take what the whole-frame predicate takes."""
     from ntmtrack import vgg
     L = _lib()
     form, layout = _Sweep("ntk_vgg_conv3x3_relu_wino43_form_f32"), _Sweep("ntk_vgg_conv3x3_relu_wino43_layout_f32")
     for (H, W), (cin, cout), pool in _layers():
         ok = vgg.wino43_supported(cin, cout, H, W, FRAMES)
+        blocked = bool(L.ntk_vgg_wino43_blocked_supported(FRAMES, H, W, cin, cout))
+        assert blocked == ok, (H, W, cin, cout)
         for waves in (4, 8):
             rc = L.ntk_vgg_conv3x3_relu_wino43_form_f32(P, P, P, P, FRAMES, H, W, cin, cout, pool, 0, 0, H, W, waves, None)
             form.check(ok, rc, H=H, W=W, cin=cin, cout=cout, pool=pool, waves=waves)
         for in_blocked, out_blocked in ((1, 1), (1, 0), (0, 1)):
             rc = L.ntk_vgg_conv3x3_relu_wino43_layout_f32(P, P, P, P, FRAMES, H, W, cin, cout, pool, in_blocked, out_blocked, None)
-            layout.check(ok, rc, H=H, W=W, cin=cin, cout=cout, pool=pool, in_blocked=in_blocked, out_blocked=out_blocked)
+            layout.check(blocked, rc, H=H, W=W, cin=cin, cout=cout, pool=pool, in_blocked=in_blocked, out_blocked=out_blocked)
     form.verdict()
     layout.verdict()
+    # beyond the grid: a frame the kernel cuts into single tiles whose blocks of 32 span more than 16 MB (conv4_2 of a 480 x 640 frame)
+    assert L.ntk_vgg_wino43_supported(1, 60, 80, 512, 512) and not L.ntk_vgg_wino43_blocked_supported(1, 60, 80, 512, 512)
+    for in_blocked, out_blocked, want in ((1, 1, NTK_ERR_UNSUPPORTED), (0, 1, NTK_ERR_UNSUPPORTED), (0, 0, NTK_ERR_HIP)):
+        assert L.ntk_vgg_conv3x3_relu_wino43_layout_f32(P, P, P, P, 1, 60, 80, 512, 512, 0, in_blocked, out_blocked, None) == want
 
 
 def test_packed_weight_sizes_are_pinned():

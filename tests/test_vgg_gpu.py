@@ -426,11 +426,16 @@ def test_trackers_pick_the_trunk_form_per_pass(cuda):
     gts0 = torch.from_numpy(rng.uniform(0, 1, size=(B, 64)).astype(np.float32)).to(cuda)
 
     def forms_seen(trk, fn):
+        """per chunk that ran, from the plan it ran (VGG16Conv43.last_plan): True = conv1_2 .. conv4_3 in the split form, False = all
+        of them on the F(4x4) kernel with blocked maps (anything else: the kernels, which equal neither)"""
         seen = []
         orig = trk.vgg.forward_chunk
-        def spy(fr, upto="conv4_3", out=None):
-            seen.append(bool(trk.vgg.split3) and trk.vgg._call_split3 and trk.vgg.split3_trunk_supported(fr.shape))
-            return orig(fr, upto=upto, out=out)
+        def spy(fr, **kw):
+            y = orig(fr, **kw)
+            ran = [s.kernel for s in trk.vgg.last_plan]
+            assert ran[0] == "direct" and len(ran) == 10
+            seen.append({("split3",): True, ("wino43_blocked",): False}.get(tuple(set(ran[1:])), ran))
+            return y
         trk.vgg.forward_chunk = spy
         try:
             fn()
