@@ -718,6 +718,43 @@ int ntk_crop_and_resize(const float* image, int H, int W, int C, const float* me
                         float y2, float x2, float* out, int crop_h, int crop_w, float extrapolation,
                         void* stream);
 
+/* The same crop for B boxes in one launch, with boxes and frame indices read from DEVICE memory (the batched online tracker:
+ * nothing comes back to the host between frames).  images [F,H,W,C], fp32 (dtype NTK_IMAGE_F32) or uint8 (NTK_IMAGE_U8, every
+ * pixel converted to fp32 exactly); frame_of int32 [B]: tracker b reads frame frame_of[b] (several objects in one video share
+ * an image, F = 1; separate clips of equal size have F = B) -- an index outside [0, F) is never dereferenced, that tracker's
+ * crop is the extrapolation value everywhere; boxes fp32 [B,4] (y1,x1,y2,x2, normalised); mean [C] (nullable);
+ * out [B,crop_h,crop_w,C].  Same box and same image give the same bits as ntk_crop_and_resize (one shared device function).
+ * B <= 65535. */
+#define NTK_IMAGE_F32 0
+#define NTK_IMAGE_U8  1
+int ntk_crop_and_resize_batch(const void* images, int dtype, int F, int H, int W, int C, const int* frame_of,
+                              const float* boxes, const float* mean, float* out, int B, int crop_h, int crop_w,
+                              float extrapolation, void* stream);
+
+/* Per-frame box bookkeeping of the online tracker (test_tracker.py:274-329) for B trackers on the device, one thread per
+ * tracker; the offsets are the fp32 tanh the single tracker takes and the shifted box is the fp32 sum it forms, everything after that is double precision.  Box state: double [B, NTK_TRACK_STATE_DOUBLES], per tracker
+ *   [0] image width w   [1] image height h   [2..5] normalised object box (y1,x1,y2,x2)   [6..9] crop box (y1,x1,y2,x2)
+ * logits fp32 [B,S,2]: the step read is the LAST one (quirk Q8).  Per active tracker: offsets (dy,dx) = tanh(logits[b,S-1,:]);
+ * the centred box 0.5 -+ bbox_grid / (2 cropbox_grid) shifted by them; decoded through the inverse of the crop transformation
+ * of the crop box in the state; scaled by (w, h) (not (w-1, h-1): the reference's asymmetry is kept); the region
+ * (x, y, width, height) -> regions double [B,4]; then the state for the next frame: a region whose four numbers are all < 1 is
+ * taken as already normalised (test_tracker.py:306-309), else divided by (h-1, w-1); crop box = that box scaled about its
+ * centre by cropbox_grid / bbox_grid.  Writes regions, offsets fp32 [B,2], state[2..9], the crop box a second time as
+ * cropbox32 fp32 [B,4] (what ntk_crop_and_resize_batch reads) and frame[b] += 1 (int32 [B], nullable).
+ * active uint8 [B] (nullable = all active): NOTHING of an inactive tracker is written. */
+#define NTK_TRACK_STATE_DOUBLES 10
+#define NTK_TRACK_STATE_W        0
+#define NTK_TRACK_STATE_H        1
+#define NTK_TRACK_STATE_BBOX     2
+#define NTK_TRACK_STATE_CROPBOX  6
+int ntk_track_boxes_update(const float* logits, int B, int S, double cropbox_grid, double bbox_grid,
+                           const unsigned char* active, double* state, float* cropbox32, double* regions,
+                           float* offsets, int* frame, void* stream);
+
+/* out[b,:] = mask[b] ? a[b,:] : b[b,:] for fp32 [B,n] rows, mask uint8 [B] on the device (out may alias a or b): keeps the
+ * recurrent state of a tracker that sat a frame out. */
+int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);
+
 /* tf.image.resize_images(img, [out_h, out_w]) (bilinear, TF-1 defaults) -- direct_offset_output.py:193 */
 int ntk_resize_bilinear(const float* image, int H, int W, int C, float* out, int out_h, int out_w, void* stream);
 

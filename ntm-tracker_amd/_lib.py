@@ -120,6 +120,9 @@ def _sig(lib):
         "ntk_gather_serialize": (c_int, [P, P, P] + [c_int] * 9 + [P]),
         "ntk_gather_serialize_online": (c_int, [P, P, P] + [c_int] * 9 + [P]),
         "ntk_crop_and_resize": (c_int, [P, c_int, c_int, c_int, P] + [ctypes.c_float] * 4 + [P, c_int, c_int, ctypes.c_float, P]),
+        "ntk_crop_and_resize_batch": (c_int, [P] + [c_int] * 5 + [P, P, P, P] + [c_int] * 3 + [ctypes.c_float, P]),
+        "ntk_track_boxes_update": (c_int, [P, c_int, c_int, ctypes.c_double, ctypes.c_double] + [P] * 6 + [P]),
+        "ntk_select_rows": (c_int, [P, P, P, P, c_int, c_int, P]),
         "ntk_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
         "ntk_offset_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
         "ntk_log_loss": (c_int, [P, P, P, P, c_int, P]),

@@ -390,13 +390,13 @@ extern "C" int ntk_gather_serialize_online(const float* fmap, const float* gts0,
     return gather_serialize_impl(fmap, gts0, X, B, T, Hf, Wf, C, ldx, grid_start, grid_step, grid_n, 1, stream);
 }
 
-// tf.image.crop_and_resize (bilinear, one box) of (image - mean): out[y][x][c], extrapolation outside the image
-__global__ void crop_resize_kernel(const float* __restrict__ img, int H, int W, int C, const float* __restrict__ mean,
-                                   float y1, float x1, float y2, float x2, float* __restrict__ out, int ch, int cw,
-                                   float extrapolation) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= ch * cw * C) return;
-    const int c = idx % C, x = (idx / C) % cw, y = idx / (C * cw);
+// One output element of tf.image.crop_and_resize (bilinear, normalised box y1,x1,y2,x2) of (image - mean): the ONE copy of the
+// per-pixel arithmetic, shared by the one-box and the batched kernel, so that the same box on the same image gives the same
+// bits from either entry.  PixelT: float, or unsigned char (converted to fp32 exactly).
+template <typename PixelT>
+__device__ __forceinline__ float crop_resize_pixel(const PixelT* __restrict__ img, int H, int W, int C, const float* __restrict__ mean,
+                                                   float y1, float x1, float y2, float x2, int ch, int cw, float extrapolation,
+                                                   int y, int x, int c) {
     const float hs = (ch > 1) ? (y2 - y1) * (float)(H - 1) / (float)(ch - 1) : 0.f;
     const float wsc = (cw > 1) ? (x2 - x1) * (float)(W - 1) / (float)(cw - 1) : 0.f;
     const float in_y = (ch > 1) ? y1 * (float)(H - 1) + (float)y * hs : 0.5f * (y1 + y2) * (float)(H - 1);
@@ -407,12 +407,98 @@ __global__ void crop_resize_kernel(const float* __restrict__ img, int H, int W, 
         const int lx = (int)floorf(in_x), rx = (int)ceilf(in_x);
         const float yl = in_y - (float)ty, xl = in_x - (float)lx;
         const float m = mean ? mean[c] : 0.f;
-        const float tl = img[((size_t)ty * W + lx) * C + c] - m, tr = img[((size_t)ty * W + rx) * C + c] - m;
-        const float bl = img[((size_t)by * W + lx) * C + c] - m, br = img[((size_t)by * W + rx) * C + c] - m;
+        const float tl = (float)img[((size_t)ty * W + lx) * C + c] - m, tr = (float)img[((size_t)ty * W + rx) * C + c] - m;
+        const float bl = (float)img[((size_t)by * W + lx) * C + c] - m, br = (float)img[((size_t)by * W + rx) * C + c] - m;
         const float top = tl + (tr - tl) * xl, bot = bl + (br - bl) * xl;
         v = top + (bot - top) * yl;
     }
-    out[idx] = v;
+    return v;
+}
+
+// tf.image.crop_and_resize (bilinear, one box) of (image - mean): out[y][x][c], extrapolation outside the image
+__global__ void crop_resize_kernel(const float* __restrict__ img, int H, int W, int C, const float* __restrict__ mean,
+                                   float y1, float x1, float y2, float x2, float* __restrict__ out, int ch, int cw,
+                                   float extrapolation) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= ch * cw * C) return;
+    const int c = idx % C, x = (idx / C) % cw, y = idx / (C * cw);
+    out[idx] = crop_resize_pixel(img, H, W, C, mean, y1, x1, y2, x2, ch, cw, extrapolation, y, x, c);
+}
+
+// The same for B boxes in one launch (blockIdx.y = tracker b): tracker b crops frame frame_of[b] of images [F,H,W,C] to boxes[b]
+// (both read from device memory).  A frame index outside [0, F) is never dereferenced: that tracker's crop is the extrapolation value.
+template <typename PixelT>
+__global__ void crop_resize_batch_kernel(const PixelT* __restrict__ images, int F, int H, int W, int C,
+                                         const int* __restrict__ frame_of, const float* __restrict__ boxes,
+                                         const float* __restrict__ mean, float* __restrict__ out, int ch, int cw,
+                                         float extrapolation) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int total = ch * cw * C;
+    if (idx >= total) return;
+    const int b = blockIdx.y;
+    const int f = frame_of[b];
+    float v = extrapolation;
+    if (f >= 0 && f < F) {
+        const int c = idx % C, x = (idx / C) % cw, y = idx / (C * cw);
+        const float* box = boxes + 4 * (size_t)b;
+        v = crop_resize_pixel(images + (size_t)f * H * W * C, H, W, C, mean, box[0], box[1], box[2], box[3], ch, cw, extrapolation,
+                              y, x, c);
+    }
+    out[(size_t)b * total + idx] = v;
+}
+
+// Per-frame box bookkeeping of the online tracker for B trackers, one thread each, the geometry in double precision throughout
+// (state layout: include/ntmtrack.h, NTK_TRACK_STATE_*).  offsets = fp32 tanh(logits[b, S-1, :]) ordered (dy, dx); the centred box
+// 0.5 -+ bbox_grid / (2 cropbox_grid) shifted by them; back through the inverse of the crop transformation (the crop box was mapped
+// onto the unit square, so the inverse is X * (x2 - x1) + x1); scaled by (w, h) -- NOT (w - 1, h - 1): the decode and
+// normalize_bbox are asymmetric in the reference and here; the region (x, y, width, height); then the next frame's box state:
+// a region whose four numbers are all < 1 is taken as already normalised (test_tracker.py:306-309), else divided by
+// (h - 1, w - 1); the crop box is that box scaled about its centre by cropbox_grid / bbox_grid.
+__global__ void track_boxes_update_kernel(const float* __restrict__ logits, int B, int S, double cropbox_grid, double bbox_grid,
+                                          const unsigned char* __restrict__ active, double* __restrict__ state,
+                                          float* __restrict__ cropbox32, double* __restrict__ regions, float* __restrict__ offsets,
+                                          int* __restrict__ frame) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (active && !active[b]) return;
+    double* st = state + (size_t)b * NTK_TRACK_STATE_DOUBLES;
+    const float* lg = logits + ((size_t)b * S + (S - 1)) * 2;
+    const float fy = tanhf(lg[0]), fx = tanhf(lg[1]);       // fp32 tanh, as the single tracker takes it (torch.tanh of fp32 logits)
+    const double w = st[NTK_TRACK_STATE_W], h = st[NTK_TRACK_STATE_H];
+    const double* cb = st + NTK_TRACK_STATE_CROPBOX;
+    const double width = bbox_grid / cropbox_grid;
+    const double lo = .5 - width / 2, hi = .5 + width / 2;
+    const double sy = cb[2] - cb[0], sx = cb[3] - cb[1];
+    // the shifted box is an fp32 sum, as in the single tracker: there a Python float plus an fp32 offset is an fp32 number
+    const double oy1 = (float)lo + fy, ox1 = (float)lo + fx, oy2 = (float)hi + fy, ox2 = (float)hi + fx;
+    const double y1 = (oy1 * sy + cb[0]) * h, x1 = (ox1 * sx + cb[1]) * w;
+    const double y2 = (oy2 * sy + cb[0]) * h, x2 = (ox2 * sx + cb[1]) * w;
+    const double rw = x2 - x1, rh = y2 - y1;
+    const bool normalized = x1 < 1 && y1 < 1 && rw < 1 && rh < 1;
+    const double by = normalized ? 1.0 : h - 1, bx = normalized ? 1.0 : w - 1;
+    const double n0 = y1 / by, n1 = x1 / bx, n2 = (y1 + rh) / by, n3 = (x1 + rw) / bx;
+    const double scale = cropbox_grid / bbox_grid;
+    const double cy = (n0 + n2) / 2, cx = (n1 + n3) / 2, hy = (n2 - n0) * scale / 2, hx = (n3 - n1) * scale / 2;
+    const double c0 = cy - hy, c1 = cx - hx, c2 = cy + hy, c3 = cx + hx;
+    double* nb = st + NTK_TRACK_STATE_BBOX;
+    double* ncb = st + NTK_TRACK_STATE_CROPBOX;
+    nb[0] = n0; nb[1] = n1; nb[2] = n2; nb[3] = n3;
+    ncb[0] = c0; ncb[1] = c1; ncb[2] = c2; ncb[3] = c3;
+    float* c32 = cropbox32 + 4 * (size_t)b;
+    c32[0] = (float)c0; c32[1] = (float)c1; c32[2] = (float)c2; c32[3] = (float)c3;
+    double* rg = regions + 4 * (size_t)b;
+    rg[0] = x1; rg[1] = y1; rg[2] = rw; rg[3] = rh;
+    offsets[2 * (size_t)b] = fy;
+    offsets[2 * (size_t)b + 1] = fx;
+    if (frame) frame[b] += 1;
+}
+
+// out[b, :] = mask[b] ? a[b, :] : b_[b, :]   (out may be a or b_: every element is read and written by the same thread)
+__global__ void select_rows_kernel(const unsigned char* __restrict__ mask, const float* a, const float* b_, float* out,
+                                   size_t total, int n) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    out[idx] = mask[idx / (size_t)n] ? a[idx] : b_[idx];
 }
 
 // tf.image.resize_images(..., BILINEAR) with TF-1 defaults (align_corners=False, no half-pixel centres):
@@ -451,6 +537,50 @@ extern "C" int ntk_crop_and_resize(const float* image, int H, int W, int C, cons
     crop_resize_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(image, H, W, C, mean, y1, x1, y2, x2, out,
                                                                              crop_h, crop_w, extrapolation);
     NTK_CHECK_LAUNCH("ntk_crop_and_resize");
+    return NTK_OK;
+}
+
+extern "C" int ntk_crop_and_resize_batch(const void* images, int dtype, int F, int H, int W, int C, const int* frame_of,
+                                         const float* boxes, const float* mean, float* out, int B, int crop_h, int crop_w,
+                                         float extrapolation, void* stream) {
+    NTK_REQUIRE(images && frame_of && boxes && out, NTK_ERR_BAD_PTR, "ntk_crop_and_resize_batch: null pointer");
+    NTK_REQUIRE(dtype == NTK_IMAGE_F32 || dtype == NTK_IMAGE_U8, NTK_ERR_BAD_SHAPE,
+                "ntk_crop_and_resize_batch: dtype=%d (NTK_IMAGE_F32 or NTK_IMAGE_U8)", dtype);
+    NTK_REQUIRE(B > 0 && B <= 65535 && F > 0 && H > 0 && W > 0 && C > 0 && crop_h > 0 && crop_w > 0, NTK_ERR_BAD_SHAPE,
+                "ntk_crop_and_resize_batch: B=%d (1..65535) F=%d H=%d W=%d C=%d crop=%dx%d", B, F, H, W, C, crop_h, crop_w);
+    const long total = (long)crop_h * crop_w * C;
+    NTK_REQUIRE(total < 2147483647L - 256, NTK_ERR_BAD_SHAPE, "ntk_crop_and_resize_batch: crop=%dx%d C=%d: too many elements per box",
+                crop_h, crop_w, C);
+    const dim3 grid((unsigned)((total + 255) / 256), (unsigned)B);
+    if (dtype == NTK_IMAGE_U8)
+        crop_resize_batch_kernel<unsigned char><<<grid, 256, 0, (hipStream_t)stream>>>(
+            (const unsigned char*)images, F, H, W, C, frame_of, boxes, mean, out, crop_h, crop_w, extrapolation);
+    else
+        crop_resize_batch_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)images, F, H, W, C, frame_of, boxes, mean,
+                                                                               out, crop_h, crop_w, extrapolation);
+    NTK_CHECK_LAUNCH("ntk_crop_and_resize_batch");
+    return NTK_OK;
+}
+
+extern "C" int ntk_track_boxes_update(const float* logits, int B, int S, double cropbox_grid, double bbox_grid,
+                                      const unsigned char* active, double* state, float* cropbox32, double* regions,
+                                      float* offsets, int* frame, void* stream) {
+    NTK_REQUIRE(logits && state && cropbox32 && regions && offsets, NTK_ERR_BAD_PTR, "ntk_track_boxes_update: null pointer");
+    NTK_REQUIRE(B > 0 && S > 0 && cropbox_grid > 0 && bbox_grid > 0, NTK_ERR_BAD_SHAPE,
+                "ntk_track_boxes_update: B=%d S=%d cropbox_grid=%g bbox_grid=%g", B, S, cropbox_grid, bbox_grid);
+    track_boxes_update_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(logits, B, S, cropbox_grid, bbox_grid, active, state,
+                                                                            cropbox32, regions, offsets, frame);
+    NTK_CHECK_LAUNCH("ntk_track_boxes_update");
+    return NTK_OK;
+}
+
+extern "C" int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream) {
+    NTK_REQUIRE(mask && a && b && out, NTK_ERR_BAD_PTR, "ntk_select_rows: null pointer");
+    NTK_REQUIRE(B > 0 && n > 0, NTK_ERR_BAD_SHAPE, "ntk_select_rows: B=%d n=%d", B, n);
+    const size_t total = (size_t)B * n;
+    NTK_REQUIRE((total + 255) / 256 < 2147483647UL, NTK_ERR_BAD_SHAPE, "ntk_select_rows: B=%d n=%d: too many elements", B, n);
+    select_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(mask, a, b, out, total, n);
+    NTK_CHECK_LAUNCH("ntk_select_rows");
     return NTK_OK;
 }
 

@@ -9,6 +9,7 @@ Quirk Q8 is kept: inference puts the delimiter row FIRST and reads the output of
 Box geometry (preprocess.py:73-149, :205-240 for behaviour) lives in ntmtrack.geometry.
 """
 import collections
+import inspect
 
 import numpy as np
 import torch
@@ -115,3 +116,219 @@ class NTMTracker(object):
         region = self._decode_bbox(self.output_bbox)
         self._update_bbox(self.image_size, region)
         return region
+
+
+# ---- batched online tracker: boxes, crops and state stay on the device ---------------------------------------------------
+
+STATE_DOUBLES = 10           # include/ntmtrack.h NTK_TRACK_STATE_*: [w, h, object box y1 x1 y2 x2, crop box y1 x1 y2 x2]
+
+
+def _upload(array, dtype, device):
+    """Host array -> device tensor without a synchronising call: through a pinned staging tensor and an asynchronous copy
+    on the current stream (the pinned block is not reused before that copy has run)."""
+    t = torch.as_tensor(np.ascontiguousarray(array)).to(dtype)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def crop_and_resize_batch(images, frame_of, boxes, crop=224, mean=None, out=None):
+    """images [F,H,W,C] fp32 or uint8 device tensor; frame_of int32 [B] and boxes fp32 [B,4] (normalised y1,x1,y2,x2) on the
+    device; mean fp32 [C] device tensor or None -> (images[frame_of[b]] - mean) cropped to boxes[b], [B,crop,crop,C] fp32.
+    One launch; a frame index outside [0,F) gives the extrapolation value (0) for that tracker."""
+    F, H, W, C = images.shape
+    B = boxes.shape[0]
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise _lib.NtkError("crop_and_resize_batch: images must be fp32 or uint8, not %s" % images.dtype)
+    if frame_of.dtype != torch.int32 or boxes.dtype != torch.float32 or frame_of.shape[0] != B:
+        raise _lib.NtkError("crop_and_resize_batch: frame_of must be int32 [B] and boxes fp32 [B,4]")
+    if out is None:
+        out = torch.empty((B, crop, crop, C), device=images.device, dtype=torch.float32)
+    _lib.check(_lib.lib().ntk_crop_and_resize_batch(_P(images.contiguous()), 1 if images.dtype == torch.uint8 else 0, F, H, W, C,
+                                                    _P(frame_of), _P(boxes), _np(mean), _P(out), B, crop, crop, 0.0, _lib.stream()),
+               "ntk_crop_and_resize_batch")
+    return out
+
+
+def select_rows(mask, a, b, out=None):
+    """out[i] = mask[i] ? a[i] : b[i] over the leading dimension (mask uint8 [B] on the device; out may be a or b)."""
+    B = a.shape[0]
+    out = torch.empty_like(a) if out is None else out
+    _lib.check(_lib.lib().ntk_select_rows(_P(mask), _P(a), _P(b), _P(out), B, a.numel() // B, _lib.stream()), "ntk_select_rows")
+    return out
+
+
+class BatchNTMTracker(object):
+    """B online trackers in one pass per frame, with nothing read back to the host: NTMTracker's contract (same first-frame
+    pass, same per-frame arithmetic) for several objects in one video (``images`` [1,H,W,3]) or one object in each of several
+    clips of equal size (``images`` [B,H,W,3]); ``frame_of`` [B] says which image a tracker reads, in general.
+
+    ``images``: [F,H,W,3], uint8 (kept as uint8 on the device) or float; host array or device tensor.  ``regions``: [B,4]
+    (x, y, w, h) in pixels (normalised if all four < 1).  ``cell``: an NTMCell / StackedNTMCell with output_dim 2.
+    ``track`` returns the regions as a [B,4] float64 DEVICE tensor; ``offsets`` [B,2], ``frame`` [B] (frames tracked since
+    the slot was started) and ``state`` (the cell's state dict at batch B) live on the device too.  A host synchronisation
+    happens only when the caller reads one of them."""
+
+    def __init__(self, images, regions, cell, vgg, frame_of=None, cropbox_grid=8, bbox_grid=6, device="cuda"):
+        if cell.dims is None or cell.dims.O != 2:
+            raise _lib.NtkError("BatchNTMTracker: the cell must have parameters and output_dim 2 (dy, dx), not %s"
+                                % (None if cell.dims is None else cell.dims.O))
+        self.cell, self.vgg = cell, vgg
+        self.device = torch.device(device)
+        self.cropbox_grid, self.bbox_grid = cropbox_grid, bbox_grid
+        self.crop = 224
+        # asked once, not with a try/except around every frame's trunk pass: a caller's own trunk object may not know the flag
+        try:
+            takes_latency = "latency" in inspect.signature(vgg).parameters
+        except (TypeError, ValueError):
+            takes_latency = False
+        self._vgg_kw = {"latency": True} if takes_latency else {}
+        regions = np.asarray(regions, dtype=np.float64).reshape(-1, 4)
+        B = self.B = regions.shape[0]
+        if B < 1:
+            raise _lib.NtkError("BatchNTMTracker: no regions")
+        self.mean = torch.tensor(VGG_MEAN, device=self.device, dtype=torch.float32)
+        imgs = self._images(images)
+        self.frame_of = self._frame_table(frame_of, imgs.shape[0], B)
+        self.box_state, self.cropbox32, self.state = self._first_frame(imgs, self.frame_of, regions)
+        self.regions = _upload(regions, torch.float64, self.device)
+        self.offsets = torch.zeros((B, 2), device=self.device, dtype=torch.float32)
+        self.frame = torch.zeros((B,), device=self.device, dtype=torch.int32)
+        # per-frame buffers, made once (each is consumed on the same stream before the next frame overwrites it)
+        self._crops = torch.empty((B, self.crop, self.crop, 3), device=self.device, dtype=torch.float32)
+        self._X = torch.empty((B, NUM_FEATURES + 1, self.cell.input_ldx), device=self.device, dtype=torch.float32)
+
+    # ---- host -> device plumbing (no synchronising call)
+    def _images(self, images):
+        if torch.is_tensor(images):
+            t = images if images.dtype == torch.uint8 else images.to(torch.float32)
+            t = t if t.device == self.device else (t.pin_memory() if not t.is_cuda else t).to(self.device, non_blocking=True)
+        else:
+            a = np.asarray(images)
+            t = _upload(a, torch.uint8 if a.dtype == np.uint8 else torch.float32, self.device)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        if t.dim() != 4:
+            raise _lib.NtkError("images must be [F,H,W,3]")
+        return t.contiguous()
+
+    def _frame_table(self, frame_of, F, n):
+        if frame_of is None:
+            if F != 1 and F != n:
+                raise _lib.NtkError("%d images for %d trackers: pass frame_of" % (F, n))
+            return (torch.zeros((n,), device=self.device, dtype=torch.int32) if F == 1 else
+                    torch.arange(n, device=self.device, dtype=torch.int32))
+        if torch.is_tensor(frame_of) and frame_of.is_cuda:
+            t = frame_of.to(torch.int32).contiguous()
+        else:
+            t = _upload(np.asarray(frame_of).reshape(-1), torch.int32, self.device)
+        if t.shape[0] != n:
+            raise _lib.NtkError("frame_of has %d entries for %d trackers" % (t.shape[0], n))
+        return t
+
+    def _mask(self, active, shape):
+        if torch.is_tensor(active) and active.is_cuda:
+            t = active.to(torch.uint8).contiguous()
+        else:
+            t = _upload(np.asarray(active).astype(bool), torch.uint8, self.device)
+        if tuple(t.shape) != tuple(shape):
+            raise _lib.NtkError("active has shape %s, expected %s" % (tuple(t.shape), tuple(shape)))
+        return t
+
+    # ---- the pieces of one pass (scripts/dev_online_batch_timing.py puts events between them)
+    def _crop(self, imgs, frame_of, cropbox32, out=None):
+        return crop_and_resize_batch(imgs, frame_of, cropbox32, self.crop, self.mean, out=out)
+
+    def _trunk(self, crops):
+        return self.vgg(crops, **self._vgg_kw)
+
+    def _serialize(self, fmap, gts0, X=None):
+        """Q8 serialisation (delimiter row first): [n, 65, ldx] on the device."""
+        n, ldx = fmap.shape[0], self.cell.input_ldx
+        if X is None:
+            X = torch.empty((n, NUM_FEATURES + 1, ldx), device=self.device, dtype=torch.float32)
+        _lib.check(_lib.lib().ntk_gather_serialize_online(_P(fmap), _np(gts0), _P(X), n, 1, fmap.shape[1], fmap.shape[2],
+                                                          fmap.shape[3], ldx, GRID_START, GRID_STEP, GRID_N, _lib.stream()),
+                   "ntk_gather_serialize_online")
+        return X
+
+    def _sequence(self, X, mask):
+        """65 steps from self.state; with a mask, an inactive tracker's rows of the new state are its old ones."""
+        logits, _o, new, _rec = self.cell.run_sequence(X, self.state, record=False, want_outputs=False)
+        if mask is not None:
+            for k, v in new.items():
+                select_rows(mask, v, self.state[k], out=v)
+        self.state = new
+        return logits
+
+    def _update_boxes(self, logits, mask):
+        _lib.check(_lib.lib().ntk_track_boxes_update(_P(logits), self.B, logits.shape[1], float(self.cropbox_grid),
+                                                     float(self.bbox_grid), _np(mask), _P(self.box_state), _P(self.cropbox32),
+                                                     _P(self.regions), _P(self.offsets), _P(self.frame), _lib.stream()),
+                   "ntk_track_boxes_update")
+
+    def _first_frame(self, imgs, frame_of, regions):
+        """NTMTracker.__init__ over the given trackers: box state from the regions (host geometry: the regions arrive from the
+        host anyway), heat-map rows, zero state, one pass whose output is discarded.  -> (box state [n,10] f64, crop boxes
+        [n,4] fp32, cell state at batch n), all on the device."""
+        n = regions.shape[0]
+        H, W = imgs.shape[1], imgs.shape[2]
+        rows, gts = np.empty((n, STATE_DOUBLES), dtype=np.float64), np.empty((n, NUM_FEATURES), dtype=np.float32)
+        for i, (x1, y1, w, h) in enumerate(regions.tolist()):
+            bbox = (y1, x1, y1 + h, x1 + w)
+            nb = list(bbox) if (x1 < 1 and y1 < 1 and w < 1 and h < 1) else normalize_bbox((W, H), bbox)
+            cb = calculate_cropbox(nb, self.cropbox_grid, self.bbox_grid)
+            rows[i] = [W, H] + list(nb) + list(cb)
+            gts[i] = generate_gt(apply_transformation(nb, calculate_transformation(cb)), self.cropbox_grid, self.bbox_grid).reshape(-1)
+        box_state = _upload(rows, torch.float64, self.device)
+        cropbox32 = box_state[:, 6:10].to(torch.float32).contiguous()
+        X = self._serialize(self._trunk(self._crop(imgs, frame_of, cropbox32)), _upload(gts, torch.float32, self.device))
+        _logits, _o, state, _rec = self.cell.run_sequence(X, self.cell.zero_state(n), record=False, want_outputs=False)
+        return box_state, cropbox32, state                      # this output is discarded (test_tracker.py:146-148)
+
+    # ---- public
+    def reset(self, slots, images, regions, frame_of=None):
+        """Start new objects in the given slots (the first-frame pass on a sub-batch of len(slots) trackers, scattered into
+        the slots); every other slot is untouched.  ``frame_of`` indexes ``images`` for this pass only (default: one image
+        for all, or one per slot in order); the table ``track`` reads is not changed."""
+        slots = [int(s) for s in slots]
+        regions = np.asarray(regions, dtype=np.float64).reshape(-1, 4)
+        if len(slots) != regions.shape[0] or len(set(slots)) != len(slots) or not all(0 <= s < self.B for s in slots):
+            raise _lib.NtkError("reset: slots %s (distinct, in [0,%d)) for %d regions" % (slots, self.B, regions.shape[0]))
+        imgs = self._images(images)
+        box_state, cropbox32, state = self._first_frame(imgs, self._frame_table(frame_of, imgs.shape[0], len(slots)), regions)
+        idx = _upload(np.asarray(slots), torch.int64, self.device)
+        self.box_state.index_copy_(0, idx, box_state)
+        self.cropbox32.index_copy_(0, idx, cropbox32)
+        for k, v in state.items():
+            self.state[k].index_copy_(0, idx, v)
+        self.regions.index_copy_(0, idx, _upload(regions, torch.float64, self.device))
+        self.offsets.index_fill_(0, idx, 0)
+        self.frame.index_fill_(0, idx, 0)
+
+    def track(self, images, frame_of=None, active=None):
+        """One frame for every (active) tracker -> regions [B,4] (x, y, width, height) float64 on the device; an inactive
+        tracker keeps its state, box, frame count and last region.  Everything is enqueued on the current stream."""
+        imgs = self._images(images)
+        if frame_of is not None:
+            self.frame_of = self._frame_table(frame_of, imgs.shape[0], self.B)
+        mask = None if active is None else self._mask(active, (self.B,))
+        self._step(imgs, mask)
+        return self.regions.clone()
+
+    def _step(self, imgs, mask):
+        crops = self._crop(imgs, self.frame_of, self.cropbox32, out=self._crops)
+        X = self._serialize(self._trunk(crops), None, X=self._X)
+        self._update_boxes(self._sequence(X, mask), mask)
+
+    def track_clip(self, frames, active=None):
+        """frames [T,F,H,W,3] -> regions [T,B,4] float64 on the device: T calls of track on one stream, no synchronisation.
+        active: [T,B] (nullable)."""
+        T = len(frames)
+        if not torch.is_tensor(frames) and not isinstance(frames, (list, tuple)):
+            a = np.asarray(frames)
+            frames = _upload(a, torch.uint8 if a.dtype == np.uint8 else torch.float32, self.device)
+        masks = None if active is None else self._mask(active, (T, self.B))
+        out = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
+        for t in range(T):
+            self._step(self._images(frames[t]), None if masks is None else masks[t])
+            out[t].copy_(self.regions)
+        return out
