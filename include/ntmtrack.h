@@ -516,6 +516,8 @@ int ntk_ntm_init_state_bwd(const float* v, const float* dout, float* dv, int n, 
  * write_vectors, erase_vectors, free_gate, allocation_gate, write_gate, read_mode,
  * write_keys, write_strengths, read_keys, read_strengths (row hid = biases),
  * Wy [ldy][OP] (rows [h ; reads], row Ky = bias).  State tensors are updated IN PLACE.
+ * Range (else NTK_ERR_UNSUPPORTED): N a multiple of 4 up to 1024, W a multiple of 4 up to 256,
+ * R 1..4, Wn 1..8, R*W <= 1024, hid 1..1024, O 1..16, and a per-shape LDS layout of at most 160 KiB.
  * --------------------------------------------------------------------- */
 int ntk_dnc_padded_dims(int N, int W, int R, int Wn, int hid, int O,
                         int* I, int* IP, int* K, int* ldz, int* ldh, int* Ky, int* ldy, int* OP);
@@ -666,7 +668,8 @@ int ntk_dnc_access_step_fwd(const float* iface_raw, int ldr, const float* memory
  * gradient w.r.t. the NEW state's field (zeros when the loss does not see it), out = gradient w.r.t. the previous state's
  * (write weights get none: they reach the next usage under stop_gradient only, addressing.py:302).  d_iface_raw [B,IP]
  * (IP from ntk_dnc_padded_dims): gradient w.r.t. the raw interface; the ten linears' gradients are GEMMs over it.
- * N and W multiples of 4, R <= 4, Wn <= 4.  Workspace: ntk_dnc_access_step_bwd_workspace_bytes. */
+ * N and W multiples of 4, R <= 4, Wn <= 4, R*W <= 1020 (the step runs through ntk_dnc_seq_bwd with a controller of 4 units:
+ * its K = R*W + 4 <= 1024).  Workspace: ntk_dnc_access_step_bwd_workspace_bytes. */
 size_t ntk_dnc_access_step_bwd_workspace_bytes(int B, int N, int W, int R, int Wn);
 int ntk_dnc_access_step_bwd(const float* iface_raw, int ldr, const float* memory, const float* read_weights,
                             const float* write_weights, const float* link, const float* precedence, const float* usage,
@@ -682,7 +685,9 @@ int ntk_dnc_access_step_bwd(const float* iface_raw, int ldr, const float* memory
  * gradients follow as ntk_gemm_tn_f32 over the recorded rows.
  * Segmented BPTT (long sequences, config 5): run the segments last to first, re-recording each from its
  * checkpointed state; gM / gL are NOT re-zeroed between segments and gcarry [B, (Wn+1)*N + R*N + ldkT + hid]
- * (optional, may be null) carries the remaining state gradients: read when carry_in != 0, always written. */
+ * (optional, may be null) carries the remaining state gradients: read when carry_in != 0, always written.
+ * Range (else NTK_ERR_UNSUPPORTED): the forward's with Wn 1..4, hid a multiple of 4, K = R*W + hid <= 1024 (one
+ * thread per element of d[reads_prev ; h_prev]) and its own LDS layout of at most 160 KiB. */
 int ntk_dnc_seq_bwd(int B, int S, int N, int W, int R, int Wn, int hid, int O, float clip_value,
                     const float* WrT, int ldkT, const float* WiT, int ldhT, const float* Wy,
                     const float* mem0, const float* link0, const float* usage0, const float* rw0,

@@ -495,6 +495,18 @@ __global__ __launch_bounds__(CT) void dnc_cluster_fwd_kernel(DncClFwdArgs a0) {
         } else if (rec && g == 0 && tid < RWd + (C.ldy - C.Ky)) {
             a.rec_yin[bt * C.ldy + C.Ky + (tid - RWd)] = (tid == RWd) ? 1.f : 0.f;
         }
+        if constexpr (!FIX) {
+            if (RWd >= CT) {                                   // R W reaches 1024: a second pass, and no thread past the read words
+                for (int i = tid + CT; i < RWd; i += CT) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) s += sPart[w * RWd + i];
+                    sZ[i] = s;
+                    if (rec && g == 0) a.rec_yin[bt * C.ldy + hid + i] = s;
+                }
+                if (rec && g == 0) for (int i = C.Ky + tid; i < C.ldy; i += CT) a.rec_yin[bt * C.ldy + i] = (i == C.Ky) ? 1.f : 0.f;
+            }
+        }
         __syncthreads();
         CL_STAMP(14);
     }

@@ -761,6 +761,8 @@ extern "C" int ntk_dnc_seq_bwd(int B, int S, int N, int W, int R, int Wn, int hi
                 NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_bwd: N=%d W=%d R=%d unsupported", N, W, R);
     NTK_REQUIRE(hid >= 4 && (hid % 4) == 0 && hid <= DT && R * W <= DT && O >= 1 && O <= 16, NTK_ERR_UNSUPPORTED,
                 "ntk_dnc_seq_bwd: hidden=%d (multiple of 4) output=%d", hid, O);
+    // B16 sums the gradient into [reads_prev ; h_prev] with one thread per element
+    NTK_REQUIRE(a.d.K <= DT, NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_bwd: reads*word + hidden = %d exceeds one workgroup (%d threads)", a.d.K, DT);
     NTK_REQUIRE(ldkT >= a.d.K && (ldkT % 4) == 0 && ldhT >= hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE,
                 "ntk_dnc_seq_bwd: ldkT=%d ldhT=%d", ldkT, ldhT);
     NTK_REQUIRE(WrT && WiT && Wy && mem0 && link0 && usage0 && rw0 && ww0 && prec0 && hc0 && rec_gates && rec_c && rec_ifc &&

@@ -184,13 +184,13 @@ __global__ __launch_bounds__(DT) void dnc_seq_fwd_kernel(DncFwdArgs a, DncLds L)
                 a.rec_hc[bt * d.ldh + tid] = dnc_clip(h2, clipv);
                 a.rec_yin[bt * d.ldy + tid] = dnc_clip(h2, clipv);
             }
-        } else if (rec && tid - hid < d.ldh - hid) {
-            a.rec_hc[bt * d.ldh + tid] = (tid == hid) ? 1.f : 0.f;
         }
+        // bias and padding columns, strided: at hid = 1024 no thread has an index of its own past the hidden units
+        if (rec) for (int i = hid + tid; i < d.ldh; i += DT) a.rec_hc[bt * d.ldh + i] = (i == hid) ? 1.f : 0.f;
         __syncthreads();
         // ------------------------------------------------------------ P2: interface
-        if (tid < nslI * icg) {
-            const int cg = tid % icg, ks = tid / icg;
+        for (int q = tid; q < nslI * icg; q += DT) {           // more than one pass only above 1024 column groups (IP > 4096: nslI = 1)
+            const int cg = q % icg, ks = q / icg;
             const int k0 = ks * kperI, k1 = min(hid, k0 + kperI);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
             if (k0 < k1) acc = ntk_stream_matvec<4>(Wi4 + cg, icg, sZ + RWd, k0, k1, hid);
@@ -478,9 +478,8 @@ __global__ __launch_bounds__(DT) void dnc_seq_fwd_kernel(DncFwdArgs a, DncLds L)
             for (int sl = 0; sl < nslR4; ++sl) s += sPart[sl * RWd + tid];
             sZ[tid] = s;
             if (rec) a.rec_yin[bt * d.ldy + hid + tid] = s;
-        } else if (rec && tid >= RWd && tid < RWd + (d.ldy - d.Ky)) {
-            a.rec_yin[bt * d.ldy + d.Ky + (tid - RWd)] = (tid == RWd) ? 1.f : 0.f;
         }
+        if (rec) for (int i = d.Ky + tid; i < d.ldy; i += DT) a.rec_yin[bt * d.ldy + i] = (i == d.Ky) ? 1.f : 0.f;      // as rec_hc: R W may be 1024
         __syncthreads();
         for (int o = wave; o < d.O; o += DW) {                // y = clip([h ; reads] Wy + by)   (dnc.py:118-122)
             float s = 0.f;

@@ -267,7 +267,10 @@ class DNC(object):
             n = 1
             for v in s:
                 n *= v
-            return torch.empty((B * cap * n,), device=self.device)[:B * S * n].view((B, S) + s)
+            t = torch.empty((B * cap * n,), device=self.device)
+            if self.poison_records:
+                t.fill_(float("nan"))
+            return t[:B * S * n].view((B, S) + s)
         N, W, R, Wn, hid = self.N, self.W, self.R, self.Wn, self.hid
         return {"z": e(self.ldz), "gates": e(hid, 4), "c": e(hid), "hc": e(self.ldh), "yin": e(self.ldy), "ifc": e(self.IP),
                 "u": e(N), "ww": e(Wn, N), "rw": e(R, N), "cw": e(Wn, N), "cr": e(R, N), "al": e(Wn, N), "p": e(Wn, N),
@@ -279,6 +282,9 @@ class DNC(object):
     record_budget_bytes = 96 << 30      # a third of an MI355X's 288 GB: two record sets may be alive at a time (allocator caching)
     #: steps per BPTT segment; None = derive from record_budget_bytes (whole sequence when it fits)
     bptt_segment = None
+    #: tests: the record tensors start as NaN instead of whatever the caching allocator hands back, so that an element the forward
+    #: kernel never writes is seen (a stale 1.0 of an earlier run in a bias column would pass for the right value)
+    poison_records = False
     last_record = None
     last_segments = None
     #: how many trailing segments the forward pass of a segmented run records itself (2 = as many as may be alive at a time)

@@ -156,6 +156,10 @@ def test_dnc_unsupported_shapes_fail_loudly(cuda):
     core = DNC({"memory_size": 20, "word_size": 6, "num_reads": 5, "num_writes": 1}, {"hidden_size": 16}, 2, 20, input_dim=10, device=cuda)
     with pytest.raises(NtkError):                    # at most 4 read heads
         core.run_sequence(torch.zeros((2, 1, 10), device=cuda))
+    core = DNC({"memory_size": 16, "word_size": 128, "num_reads": 4, "num_writes": 1}, {"hidden_size": 516}, 2, 20, input_dim=10, device=cuda)
+    core.run_sequence(torch.zeros((2, 1, 10), device=cuda), record=True)
+    with pytest.raises(NtkError):                    # the BPTT takes reads*word + hidden <= 1024 (here 1028)
+        core.backward_sequence(core.last_X, torch.zeros((1, 2, 2), device=cuda))
 
 
 def test_dnc_offset_tracker_pipeline(cuda):
@@ -271,7 +275,7 @@ def test_dnc_bptt_gradients_match_autograd_oracle(cuda, name, Din, O, N, W, R, W
         err = float(np.max(np.abs(got - ref)) / scale)
         err32 = float(np.max(np.abs(pt32[k].grad.double().numpy() - ref)) / scale)
         worst[k] = (err, err32)
-        if err > max(1e-4, 3 * err32):
+        if not err <= max(1e-4, 3 * err32):                    # not `err > ...`: a NaN gradient must not pass
             bad[k] = (err, err32)
     print("%s/%s relative gradient error (HIP, float32 oracle) vs float64: %s" % (name, form, {k: ("%.1e" % a, "%.1e" % b) for k, (a, b) in worst.items()}))
     # the training step's form: no re-layout, nothing returned, the same gradients in params.grad (packed layout; its padding is
@@ -415,7 +419,7 @@ def test_dnc_full_length_bptt_gradients_match_autograd_oracle(cuda):
         err = float(np.max(np.abs(gh - g64[k])))
         e_own, e_glob = err / (own + 1e-30), err / gmax
         print("  %-36s %.3e  %.3e  %.3e" % (k, own, e_own, e_glob))
-        if e_glob > 3e-4 or (own >= 1e-2 * gmax and e_own > 2e-3):
+        if not (e_glob <= 3e-4 and (own < 1e-2 * gmax or e_own <= 2e-3)):                  # a NaN gradient must not pass
             bad[k] = (e_own, e_glob)
     assert not bad, bad
 
@@ -430,7 +434,21 @@ CLUSTER_CASES = [
     # confirms it, hand off through plain stores kept in that XCD's L2 (csrc/dnc_cluster.h)
     ("c3_shape_b8_same_xcd", 256, 64, 4, 200, 6, 8, (8,)),
     ("small_64x16_b16_same_xcd", 64, 16, 2, 24, 7, 16, (4, 8)),
+    # the edges of the cluster planners' range (tests/test_dnc_shapes_gpu.py compares the same shapes with the oracles)
+    ("upk1_64x16", 64, 16, 1, 4, 6, 3, (8,)),                 # one hidden unit per workgroup: four of the eight own none
+    ("n192_r3", 192, 20, 3, 36, 5, 2, (4, 8)),                # memory_size is no power of two
+    ("w256_r4_64x256", 64, 256, 4, 32, 4, 2, (4,)),           # 454 interface column groups, R W = 1024 against 512 threads
+    ("hid1024_128x4", 128, 4, 1, 1024, 3, 2, (2, 8)),         # W / 4 = 1; 512 hidden units per workgroup at k 2
+    ("n512_512x16", 512, 16, 2, 40, 3, 1, (4,)),              # memory-partitioned form only
 ]
+# (case, form, direction) the planners refuse at every cluster size listed: the tests below assert that nothing ran in cluster form
+CLUSTER_REFUSED = {
+    ("n512_512x16", "lds", "fwd"),           # 128 KiB of link rows per workgroup at k 8 beside 40 KiB of replicated memory
+    ("n512_512x16", "lds", "bwd"),           # and its BPTT stops at memory_size 256
+}
+# the BPTT comparison's reference is the one-workgroup kernel, which takes reads * word + hidden <= 1024 (the two shapes beyond it
+# are compared with float64 autograd in tests/test_dnc_shapes_gpu.py)
+CLUSTER_BPTT_CASES = [c for c in CLUSTER_CASES if c[3] * c[2] + c[4] <= 1024]
 
 
 @pytest.mark.parametrize("form", ["lds", "mp"])
@@ -491,7 +509,7 @@ def test_dnc_cluster_forward_equals_single_workgroup_kernel(cuda, name, N, W, R,
             np.testing.assert_allclose(a_.cpu().numpy(), b_.cpu().numpy(), err_msg="%s k=%d" % (nm, k), **tol)
         for nm in G.DNC.REC_NAMES:
             np.testing.assert_allclose(rec[nm].cpu().numpy(), ref_rec[nm].cpu().numpy(), err_msg="record %s k=%d" % (nm, k), **tol)
-    assert tried >= 1, "no cluster size of %s was usable" % (ks,)
+    assert tried == 0 if (name, form, "fwd") in CLUSTER_REFUSED else tried >= 1, "cluster sizes %s: %d usable" % (ks, tried)
 
 
 def test_dnc_cluster_forward_full_length_is_deterministic(cuda):
@@ -519,7 +537,7 @@ def test_dnc_cluster_forward_full_length_is_deterministic(cuda):
 
 
 @pytest.mark.parametrize("form", ["lds", "mp"])
-@pytest.mark.parametrize("name,N,W,R,hid,S,B,ks", CLUSTER_CASES, ids=[c[0] for c in CLUSTER_CASES])
+@pytest.mark.parametrize("name,N,W,R,hid,S,B,ks", CLUSTER_BPTT_CASES, ids=[c[0] for c in CLUSTER_BPTT_CASES])
 def test_dnc_cluster_bptt_equals_single_workgroup_kernel(cuda, name, N, W, R, hid, S, B, ks, form):
     """Cluster BPTT (d(link) rows LDS resident and split k ways, d(memory) in registers, two exchanges per step) against
     the one-workgroup-per-sequence BPTT kernel (itself checked against torch autograd above) on the same recorded
@@ -577,7 +595,7 @@ def test_dnc_cluster_bptt_equals_single_workgroup_kernel(cuda, name, N, W, R, hi
             a_, b_ = seg[kk].cpu().numpy(), got[kk].cpu().numpy()
             err = float(np.max(np.abs(a_ - b_)) / (np.max(np.abs(b_)) + 1e-30))
             assert err < 2e-5, "segmented %s k=%d: %.3e" % (kk, k, err)
-    assert tried >= 1
+    assert tried == 0 if (name, form, "bwd") in CLUSTER_REFUSED else tried >= 1, "cluster sizes %s: %d usable" % (ks, tried)
 
 
 @pytest.mark.parametrize("form", ["lds", "mp"])

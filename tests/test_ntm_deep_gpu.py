@@ -160,7 +160,7 @@ def test_fused_bptt_ten_frames_within_the_float32_oracle_error(cuda):
         err = float(np.max(np.abs(got[k].numpy().astype(np.float64) - ref))) / scale
         err32 = float(np.max(np.abs(grads32[k].astype(np.float64) - ref))) / scale
         worst[k] = (err, err32)
-        if err > max(1e-4, 3 * err32):
+        if not err <= max(1e-4, 3 * err32):                    # not `err > ...`: a NaN gradient must not pass
             bad[k] = (err, err32)
     print("T=10 L=2 relative gradient error (HIP, float32 oracle) vs float64: %s" % {k: ("%.1e" % a, "%.1e" % b) for k, (a, b) in worst.items()})
     assert not bad, bad

@@ -249,7 +249,7 @@ def _check_grads(name, got, ref64, ref32):
     for k in sorted(ref64):
         err, err32 = _relerr(got[k], ref64[k]), _relerr(ref32[k], ref64[k])
         worst[k] = (err, err32)
-        if err > max(1e-4, 3 * err32):
+        if not err <= max(1e-4, 3 * err32):                    # not `err > ...`: a NaN gradient must not pass
             bad[k] = (err, err32)
         elif err > 1e-4:
             branch.append(k)

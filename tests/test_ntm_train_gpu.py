@@ -99,7 +99,7 @@ def test_bptt_gradients_match_autograd_oracle(cuda, name, kw, D, T, B, scale):
     for k in sorted(grads_ref):
         err, err32 = _relerr(got[k].numpy(), grads_ref[k]), _relerr(grads32[k].astype(np.float64), grads_ref[k])
         worst[k] = (err, err32)
-        if err > max(1e-4, 3 * err32):
+        if not err <= max(1e-4, 3 * err32):                    # not `err > ...`: a NaN gradient must not pass
             bad[k] = (err, err32)
     print("%s relative gradient error (HIP, float32 oracle) vs float64: %s" % (name, {k: ("%.1e" % a, "%.1e" % b_) for k, (a, b_) in worst.items()}))
     assert not bad, bad
