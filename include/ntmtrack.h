@@ -760,6 +760,21 @@ int ntk_track_boxes_update(const float* logits, int B, int S, double cropbox_gri
  * recurrent state of a tracker that sat a frame out. */
 int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);
 
+/* Masked row copy of up to NTK_STATE_KEEP_MAX_TENSORS fp32 tensors in ONE launch: for every b < B with (mask[b] != 0) ==
+ * (keep_where != 0) and every i < ntensors, row b of src[i] (row_floats[i] floats at src[i] + b * row_floats[i]) is copied to row
+ * b of dst[i]; no other row is read or written (a workgroup of an unselected row exits on the mask alone).  The online DNC
+ * tracker keeps the recurrent state of a tracker that sits a frame out with it: rows with mask 0 are saved before the in-place
+ * forward pass and put back after it, and an active tracker's state is never copied.
+ * mask uint8 [B] and the pointer tables src / dst [ntensors] lie in DEVICE memory (upload the tables once); row_floats
+ * [ntensors] is a HOST array, read before the launch and passed to the kernel by value.  src[i] and dst[i] must not overlap.
+ * Rows whose size is a multiple of 4 floats on 16-byte aligned bases move in 16-byte accesses, any other row one float at a
+ * time; a row size of 0 is allowed (nothing moves).  Plain vector stores only.
+ * Errors, before any launch: NTK_ERR_BAD_PTR for a null mask / table / row_floats; NTK_ERR_BAD_SHAPE for B < 1 or > 65535,
+ * ntensors < 1 or > NTK_STATE_KEEP_MAX_TENSORS, a negative row size, or 2^31 chunks of 1024 floats per row set. */
+#define NTK_STATE_KEEP_MAX_TENSORS 16
+int ntk_dnc_state_keep(const unsigned char* mask, int keep_where, int B, int ntensors, const float* const* src, float* const* dst,
+                       const long long* row_floats, void* stream);
+
 /* tf.image.resize_images(img, [out_h, out_w]) (bilinear, TF-1 defaults) -- direct_offset_output.py:193 */
 int ntk_resize_bilinear(const float* image, int H, int W, int C, float* out, int out_h, int out_w, void* stream);
 

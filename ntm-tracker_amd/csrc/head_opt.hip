@@ -501,6 +501,37 @@ __global__ void select_rows_kernel(const unsigned char* __restrict__ mask, const
     out[idx] = mask[idx / (size_t)n] ? a[idx] : b_[idx];
 }
 
+// Masked row copy of several tensors in one launch: for every b with (mask[b] != 0) == keep_where, row b of src[i] is copied to
+// row b of dst[i], i < ntensors (rows of rows.n[i] floats).  Grid (chunks, B): workgroup x copies chunk x of the list of all
+// tensors' chunks of KEEP_CHUNK floats (rows.first[i] = index of tensor i's first chunk).  A workgroup whose row is not selected
+// exits before it reads a table or touches a row.  16-byte loads and stores where the row size and both bases allow, else
+// one float per lane.
+constexpr int KEEP_CHUNK = 1024;             // floats per workgroup: one 16-byte access per lane; a 512 x 512 link row is 256 workgroups
+struct KeepRows {
+    long long n[NTK_STATE_KEEP_MAX_TENSORS];
+    int first[NTK_STATE_KEEP_MAX_TENSORS + 1];
+};
+
+__global__ __launch_bounds__(256) void dnc_state_keep_kernel(const unsigned char* __restrict__ mask, int keep_where, int ntensors,
+                                                            const float* const* __restrict__ src, float* const* __restrict__ dst,
+                                                            KeepRows rows) {
+    const int b = blockIdx.y;
+    if ((mask[b] != 0) != (keep_where != 0)) return;
+    int i = 0;
+    while (i + 1 < ntensors && (int)blockIdx.x >= rows.first[i + 1]) ++i;
+    const long long n = rows.n[i];
+    const long long off = (long long)((int)blockIdx.x - rows.first[i]) * KEEP_CHUNK;
+    const int len = (int)(n - off < KEEP_CHUNK ? n - off : KEEP_CHUNK);
+    const float* s = src[i] + (size_t)b * (size_t)n + (size_t)off;
+    float* d = dst[i] + (size_t)b * (size_t)n + (size_t)off;
+    if ((n & 3) == 0 && ((((uintptr_t)s) | ((uintptr_t)d)) & 15u) == 0) {
+        for (int j = 4 * (int)threadIdx.x; j < len; j += 4 * 256)
+            *reinterpret_cast<float4*>(d + j) = *reinterpret_cast<const float4*>(s + j);
+    } else {
+        for (int j = (int)threadIdx.x; j < len; j += 256) d[j] = s[j];
+    }
+}
+
 // tf.image.resize_images(..., BILINEAR) with TF-1 defaults (align_corners=False, no half-pixel centres):
 // src = dst * (in / out); neighbours floor(src) and min(floor(src)+1, in-1)
 __global__ void resize_bilinear_kernel(const float* __restrict__ img, int H, int W, int C, float* __restrict__ out,
@@ -581,6 +612,29 @@ extern "C" int ntk_select_rows(const unsigned char* mask, const float* a, const 
     NTK_REQUIRE((total + 255) / 256 < 2147483647UL, NTK_ERR_BAD_SHAPE, "ntk_select_rows: B=%d n=%d: too many elements", B, n);
     select_rows_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(mask, a, b, out, total, n);
     NTK_CHECK_LAUNCH("ntk_select_rows");
+    return NTK_OK;
+}
+
+extern "C" int ntk_dnc_state_keep(const unsigned char* mask, int keep_where, int B, int ntensors, const float* const* src,
+                                  float* const* dst, const long long* row_floats, void* stream) {
+    NTK_REQUIRE(mask && src && dst && row_floats, NTK_ERR_BAD_PTR, "ntk_dnc_state_keep: null pointer");
+    NTK_REQUIRE(B >= 1 && B <= 65535, NTK_ERR_BAD_SHAPE, "ntk_dnc_state_keep: B=%d (1..65535)", B);
+    NTK_REQUIRE(ntensors >= 1 && ntensors <= NTK_STATE_KEEP_MAX_TENSORS, NTK_ERR_BAD_SHAPE, "ntk_dnc_state_keep: ntensors=%d (1..%d)",
+                ntensors, NTK_STATE_KEEP_MAX_TENSORS);
+    KeepRows rows = {};
+    long long chunks = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        NTK_REQUIRE(row_floats[i] >= 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_state_keep: row_floats[%d]=%lld", i, row_floats[i]);
+        rows.n[i] = row_floats[i];
+        rows.first[i] = (int)chunks;
+        chunks += (row_floats[i] + KEEP_CHUNK - 1) / KEEP_CHUNK;
+        NTK_REQUIRE(chunks < 2147483647LL, NTK_ERR_BAD_SHAPE, "ntk_dnc_state_keep: row_floats[%d]=%lld: too many elements per row", i,
+                    row_floats[i]);
+    }
+    rows.first[ntensors] = (int)chunks;
+    if (chunks == 0) return NTK_OK;
+    dnc_state_keep_kernel<<<dim3((unsigned)chunks, (unsigned)B), 256, 0, (hipStream_t)stream>>>(mask, keep_where, ntensors, src, dst, rows);
+    NTK_CHECK_LAUNCH("ntk_dnc_state_keep");
     return NTK_OK;
 }
 

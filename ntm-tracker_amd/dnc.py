@@ -483,6 +483,44 @@ class DNC(object):
         self.last_segments = (xp, ckpt, bounds, recs, seg)
         return out.transpose(0, 1), self._strip_state(st)
 
+    # ---- serving: state resident in the kernels' own layout, updated in place (the online trackers, ntmtrack.online)
+    def serving_state(self, batch_size):
+        """Zero recurrent state for `batch_size` sequences as the forward launchers take it (padded word width, `hc` as
+        [B, 2 hid]), allocated once: serve_projected updates it in place."""
+        return DNCServingState(self, batch_size)
+
+    def serve_projected(self, xproj, B, S, sstate, out=None):
+        """One forward launch over contiguous xproj [B*S, 4*hid] that advances `sstate` (a serving_state(B)) IN PLACE by S
+        steps and records nothing: no clone, pad, strip or concatenation of the state.  The kernel family is the one
+        _launch_fwd takes at this B (last_cluster_form / last_cluster_k say which ran).  -> out [B, S, O] (batch-major).
+        Nothing is synchronised: check_cluster() is the place to ask whether a cluster launch failed."""
+        if sstate.core is not self or sstate.B != B:
+            raise _lib.NtkError("serve_projected: the state was made by %s for batch %d, not by this core for batch %d"
+                                % ("this core" if sstate.core is self else "another core", sstate.B, B))
+        if tuple(xproj.shape) != (B * S, 4 * self.hid):
+            raise _lib.NtkError("serve_projected: xproj is %s, expected %s" % (tuple(xproj.shape), (B * S, 4 * self.hid)))
+        if out is None:
+            out = torch.empty((B, S, self.O), device=self.device)
+        elif tuple(out.shape) != (B, S, self.O):
+            raise _lib.NtkError("serve_projected: out is %s, expected %s" % (tuple(out.shape), (B, S, self.O)))
+        st = sstate
+        recp = [None] * len(self.REC_NAMES)
+        plan = self._cluster_plan(B)
+        self.last_cluster_k = plan[1] if plan else 1
+        self.last_cluster_form = plan[0] if plan else None
+        if plan:
+            fn = _lib.lib().ntk_dnc_cluster_fwd if plan[0] == "lds" else _lib.lib().ntk_dnc_mp_fwd
+            _lib.check(fn(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value, plan[1],
+                          _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(st.mem), _P(st.link), _P(st.usage),
+                          _P(st.rw), _P(st.ww), _P(st.prec), _P(st.reads), _P(st.hc), _P(out), *recp, _P(plan[2]),
+                          _lib.stream()), "ntk_dnc_cluster_fwd" if plan[0] == "lds" else "ntk_dnc_mp_fwd")
+        else:
+            _lib.check(_lib.lib().ntk_dnc_seq_fwd(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value,
+                                                  _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(st.mem), _P(st.link),
+                                                  _P(st.usage), _P(st.rw), _P(st.ww), _P(st.prec), _P(st.reads), _P(st.hc),
+                                                  _P(out), *recp, _lib.stream()), "ntk_dnc_seq_fwd")
+        return out
+
     def _launch_bwd(self, B, S, st0, rec, dout, WrT, ldkT, WiT, ldhT, gM, gL, gcarry, carry_in):
         dev, hid = self.device, self.hid
         acc = st0.access_state
@@ -601,6 +639,72 @@ class DNC(object):
         """One step of the core: (output [B,O], DNCState), dnc.py:84-127."""
         y, new = self.run_sequence(inputs.unsqueeze(0), prev_state)
         return y[0], new
+
+
+class DNCServingState(object):
+    """The eight state buffers of B sequences exactly as the forward launchers take them -- `mem` [B,N,Wp], `link`
+    [B,Wn,N,N], `usage` [B,N], `rw` [B,R,N], `ww` [B,Wn,N], `prec` [B,Wn,N], `reads` [B,R,Wp], `hc` [B, 2 hid] (hidden, then
+    cell), Wp = the word width padded to a multiple of 4 -- zero, contiguous, allocated once.  DNC.serve_projected advances
+    them in place; `to_state()` / `load()` convert from and to the logical DNCState (tests, checkpoints, the first-frame
+    pass), with copies."""
+    NAMES = ("mem", "link", "usage", "rw", "ww", "prec", "reads", "hc")
+
+    def __init__(self, core, batch_size):
+        B = int(batch_size)
+        if B < 1:
+            raise _lib.NtkError("serving_state: batch_size %d" % B)
+        self.core, self.B = core, B
+        z = lambda *s_: torch.zeros(s_, device=core.device, dtype=torch.float32)
+        N, W, R, Wn, hid = core.N, core.W, core.R, core.Wn, core.hid
+        self.mem, self.link, self.usage = z(B, N, W), z(B, Wn, N, N), z(B, N)
+        self.rw, self.ww, self.prec = z(B, R, N), z(B, Wn, N), z(B, Wn, N)
+        self.reads, self.hc = z(B, R, W), z(B, 2 * hid)
+
+    def tensors(self):
+        """The buffers in NAMES order."""
+        return [getattr(self, n) for n in self.NAMES]
+
+    def row_floats(self):
+        """Floats per sequence of each buffer, in NAMES order."""
+        return [t.numel() // self.B for t in self.tensors()]
+
+    def zero_(self):
+        for t in self.tensors():
+            t.zero_()
+        return self
+
+    def to_state(self):
+        """-> a logical DNCState (the caller's word_size), every tensor a copy."""
+        Wl, hid = self.core.word_size, self.core.hid
+        c = lambda t: t.clone()
+        return DNCState(self.reads[..., :Wl].contiguous() if Wl != self.core.W else c(self.reads),
+                        AccessState(self.mem[..., :Wl].contiguous() if Wl != self.core.W else c(self.mem), c(self.rw), c(self.ww),
+                                    TemporalLinkageState(c(self.link), c(self.prec)), c(self.usage)),
+                        LSTMState(self.hc[:, :hid].contiguous(), self.hc[:, hid:].contiguous()))
+
+    def load(self, state, rows=None):
+        """Copy a logical DNCState in: into all B sequences (rows=None; `state` has batch B), or `state`'s sequence j into
+        sequence rows[j] (a list of distinct indices, or an int64 tensor on the state's device); other sequences are untouched.
+        The padded word columns of the loaded sequences become zero."""
+        acc, Wl, hid = state.access_state, self.core.word_size, self.core.hid
+        pairs = ((self.mem[..., :Wl], acc.memory), (self.link, acc.linkage.link), (self.usage, acc.usage), (self.rw, acc.read_weights),
+                 (self.ww, acc.write_weights), (self.prec, acc.linkage.precedence_weights), (self.reads[..., :Wl], state.access_output),
+                 (self.hc[:, :hid], state.controller_state.hidden), (self.hc[:, hid:], state.controller_state.cell))
+        n = self.B if rows is None else len(rows)
+        for dst, src in pairs:
+            if tuple(src.shape) != (n,) + tuple(dst.shape[1:]):
+                raise _lib.NtkError("serving state load: a tensor of shape %s where %s is expected"
+                                    % (tuple(src.shape), (n,) + tuple(dst.shape[1:])))
+        if rows is None:
+            idx = slice(None)
+        else:
+            idx = rows if torch.is_tensor(rows) else torch.as_tensor([int(r) for r in rows], dtype=torch.int64).to(self.mem.device)
+        if Wl != self.core.W:
+            self.mem[idx, :, Wl:] = 0
+            self.reads[idx, :, Wl:] = 0
+        for dst, src in pairs:
+            dst[idx] = src.to(dst.device, torch.float32)
+        return self
 
 
 def run_model(input_sequence, output_size, core=None, **flags):

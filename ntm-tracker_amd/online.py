@@ -9,13 +9,14 @@ Quirk Q8 is kept: inference puts the delimiter row FIRST and reads the output of
 Box geometry (preprocess.py:73-149, :205-240 for behaviour) lives in ntmtrack.geometry.
 """
 import collections
+import ctypes
 import inspect
 
 import numpy as np
 import torch
 
 from . import _lib
-from .ntm import NTMCell, _P, _np
+from .ntm import NTMCell, _P, _np, gemm_nt
 from .tracker import GRID_N, GRID_START, GRID_STEP, NUM_FEATURES
 from .vgg import VGG16Conv43
 
@@ -171,20 +172,27 @@ class BatchNTMTracker(object):
         if cell.dims is None or cell.dims.O != 2:
             raise _lib.NtkError("BatchNTMTracker: the cell must have parameters and output_dim 2 (dy, dx), not %s"
                                 % (None if cell.dims is None else cell.dims.O))
-        self.cell, self.vgg = cell, vgg
+        self.cell = cell
+        self._setup(images, regions, vgg, cell.input_ldx, frame_of, cropbox_grid, bbox_grid, device)
+
+    def _setup(self, images, regions, vgg, ldx, frame_of, cropbox_grid, bbox_grid, device):
+        """Everything of the constructor that does not depend on the kind of core: fields, the first-frame pass (_first_frame),
+        the per-frame buffers.  ldx: padded width of a serialised row."""
+        self.vgg, self._ldx = vgg, ldx
         self.device = torch.device(device)
         self.cropbox_grid, self.bbox_grid = cropbox_grid, bbox_grid
         self.crop = 224
         # asked once, not with a try/except around every frame's trunk pass: a caller's own trunk object may not know the flag
         try:
-            takes_latency = "latency" in inspect.signature(vgg).parameters
+            takes = inspect.signature(vgg).parameters
         except (TypeError, ValueError):
-            takes_latency = False
-        self._vgg_kw = {"latency": True} if takes_latency else {}
+            takes = {}
+        self._vgg_kw = {"latency": True} if "latency" in takes else {}
+        self._vgg_takes_out = "out" in takes
         regions = np.asarray(regions, dtype=np.float64).reshape(-1, 4)
         B = self.B = regions.shape[0]
         if B < 1:
-            raise _lib.NtkError("BatchNTMTracker: no regions")
+            raise _lib.NtkError("%s: no regions" % type(self).__name__)
         self.mean = torch.tensor(VGG_MEAN, device=self.device, dtype=torch.float32)
         imgs = self._images(images)
         self.frame_of = self._frame_table(frame_of, imgs.shape[0], B)
@@ -194,7 +202,7 @@ class BatchNTMTracker(object):
         self.frame = torch.zeros((B,), device=self.device, dtype=torch.int32)
         # per-frame buffers, made once (each is consumed on the same stream before the next frame overwrites it)
         self._crops = torch.empty((B, self.crop, self.crop, 3), device=self.device, dtype=torch.float32)
-        self._X = torch.empty((B, NUM_FEATURES + 1, self.cell.input_ldx), device=self.device, dtype=torch.float32)
+        self._X = torch.empty((B, NUM_FEATURES + 1, ldx), device=self.device, dtype=torch.float32)
 
     # ---- host -> device plumbing (no synchronising call)
     def _images(self, images):
@@ -242,7 +250,7 @@ class BatchNTMTracker(object):
 
     def _serialize(self, fmap, gts0, X=None):
         """Q8 serialisation (delimiter row first): [n, 65, ldx] on the device."""
-        n, ldx = fmap.shape[0], self.cell.input_ldx
+        n, ldx = fmap.shape[0], self._ldx
         if X is None:
             X = torch.empty((n, NUM_FEATURES + 1, ldx), device=self.device, dtype=torch.float32)
         _lib.check(_lib.lib().ntk_gather_serialize_online(_P(fmap), _np(gts0), _P(X), n, 1, fmap.shape[1], fmap.shape[2],
@@ -265,10 +273,8 @@ class BatchNTMTracker(object):
                                                      _P(self.regions), _P(self.offsets), _P(self.frame), _lib.stream()),
                    "ntk_track_boxes_update")
 
-    def _first_frame(self, imgs, frame_of, regions):
-        """NTMTracker.__init__ over the given trackers: box state from the regions (host geometry: the regions arrive from the
-        host anyway), heat-map rows, zero state, one pass whose output is discarded.  -> (box state [n,10] f64, crop boxes
-        [n,4] fp32, cell state at batch n), all on the device."""
+    def _first_frame_inputs(self, imgs, frame_of, regions):
+        """-> (box state [n,10] f64, crop boxes [n,4] fp32, serialised first frame X [n,65,ldx] with its heat-map rows)."""
         n = regions.shape[0]
         H, W = imgs.shape[1], imgs.shape[2]
         rows, gts = np.empty((n, STATE_DOUBLES), dtype=np.float64), np.empty((n, NUM_FEATURES), dtype=np.float32)
@@ -281,8 +287,20 @@ class BatchNTMTracker(object):
         box_state = _upload(rows, torch.float64, self.device)
         cropbox32 = box_state[:, 6:10].to(torch.float32).contiguous()
         X = self._serialize(self._trunk(self._crop(imgs, frame_of, cropbox32)), _upload(gts, torch.float32, self.device))
+        return box_state, cropbox32, X
+
+    def _first_frame(self, imgs, frame_of, regions):
+        """NTMTracker.__init__ over the given trackers: box state from the regions (host geometry: the regions arrive from the
+        host anyway), heat-map rows, zero state, one pass whose output is discarded.  -> (box state [n,10] f64, crop boxes
+        [n,4] fp32, cell state at batch n), all on the device."""
+        box_state, cropbox32, X = self._first_frame_inputs(imgs, frame_of, regions)
+        n = regions.shape[0]
         _logits, _o, state, _rec = self.cell.run_sequence(X, self.cell.zero_state(n), record=False, want_outputs=False)
         return box_state, cropbox32, state                      # this output is discarded (test_tracker.py:146-148)
+
+    def _scatter_state(self, idx, state):
+        for k, v in state.items():
+            self.state[k].index_copy_(0, idx, v)
 
     # ---- public
     def reset(self, slots, images, regions, frame_of=None):
@@ -298,8 +316,7 @@ class BatchNTMTracker(object):
         idx = _upload(np.asarray(slots), torch.int64, self.device)
         self.box_state.index_copy_(0, idx, box_state)
         self.cropbox32.index_copy_(0, idx, cropbox32)
-        for k, v in state.items():
-            self.state[k].index_copy_(0, idx, v)
+        self._scatter_state(idx, state)
         self.regions.index_copy_(0, idx, _upload(regions, torch.float64, self.device))
         self.offsets.index_fill_(0, idx, 0)
         self.frame.index_fill_(0, idx, 0)
@@ -332,3 +349,118 @@ class BatchNTMTracker(object):
             self._step(self._images(frames[t]), None if masks is None else masks[t])
             out[t].copy_(self.regions)
         return out
+
+
+# ---- online DNC trackers: the recurrent state stays in the kernels' own layout and is advanced in place ----------------------
+
+def state_keep(mask, keep_where, B, src_table, dst_table, row_floats):
+    """For every b with (mask[b] != 0) == keep_where: row b of every tensor of the source table -> the same row of the
+    destination table, one launch (ntk_dnc_state_keep).  mask uint8 [B] and the tables (int64 [n] tensors of data
+    pointers) on the device; row_floats a ctypes c_longlong array of n row sizes."""
+    _lib.check(_lib.lib().ntk_dnc_state_keep(_P(mask), int(keep_where), B, len(row_floats), _P(src_table), _P(dst_table), row_floats,
+                                             _lib.stream()), "ntk_dnc_state_keep")
+
+
+class BatchDNCTracker(BatchNTMTracker):
+    """BatchNTMTracker's contract on a DNC core: B online trackers in one pass per frame, nothing read back to the host.  The
+    reference has no online DNC tracker (its DNC script only trains and validates), so this contract is the project's own: the
+    NTM online tracker's, serialisation included (delimiter row first, heat-map rows on the first frame only, the output of the
+    LAST step read: quirk Q8 applies here as it does there).
+
+    ``core``: a built ntmtrack.dnc.DNC (input 514, output 2), or a tracker.DNCOffsetTracker, whose core is taken: that tracker
+    wires the core's two outputs straight to the offsets, so there is no projection outside the core and ``head`` must stay None.
+    ``state`` is the core's serving state (dnc.DNCServingState: the eight buffers as the kernels take them, advanced in place by
+    one launch per frame); ``state.to_state()`` gives the logical DNCState.  A frame with an ``active`` mask saves the inactive
+    trackers' rows, runs the same launch, and puts them back (ntk_dnc_state_keep): an active tracker's state is never copied.
+    The unmasked per-frame path allocates nothing and synchronises nothing; ``check()`` synchronises and raises if a cluster
+    launch failed since the last check."""
+
+    def __init__(self, images, regions, core, vgg, head=None, frame_of=None, cropbox_grid=8, bbox_grid=6, device="cuda"):
+        core = getattr(core, "core", core)
+        if head is not None:
+            raise _lib.NtkError("BatchDNCTracker: the DNC trackers have no projection outside the core; head must be None")
+        if core.D is None or core.O != 2:
+            raise _lib.NtkError("BatchDNCTracker: the core must have parameters and output_size 2 (dy, dx), not %s"
+                                % (None if core.D is None else core.O))
+        self.core = core
+        self._save = None
+        self._setup(images, regions, vgg, core.ldx, frame_of, cropbox_grid, bbox_grid, device)
+        B, S = self.B, NUM_FEATURES + 1
+        # the serialise kernel writes every column of every row on every frame, the padding columns (as zeros) included
+        self._fmap = None
+        self._xproj = torch.empty((B * S, 4 * core.hid), device=self.device, dtype=torch.float32)
+        self._logits = torch.empty((B, S, 2), device=self.device, dtype=torch.float32)
+
+    @classmethod
+    def from_tracker(cls, tracker, images, regions, vgg=None, **kw):
+        """Serve a trained or checkpointed tracker.DNCOffsetTracker: its core, and its trunk unless ``vgg`` is given."""
+        return cls(images, regions, tracker.core, vgg if vgg is not None else tracker.vgg, **kw)
+
+    def _trunk(self, crops, out=None):
+        if out is not None and self._vgg_takes_out:
+            return self.vgg(crops, out=out, **self._vgg_kw)
+        return self.vgg(crops, **self._vgg_kw)
+
+    def _project(self, X, out=None):
+        n = X.shape[0]
+        return gemm_nt(X.view(n * X.shape[1], self._ldx), self.core.WxT, out=out)
+
+    def _first_frame(self, imgs, frame_of, regions):
+        """The first-frame pass over the given trackers from zero serving state; its output is discarded.
+        -> (box state, crop boxes, serving state at batch n)."""
+        box_state, cropbox32, X = self._first_frame_inputs(imgs, frame_of, regions)
+        n = regions.shape[0]
+        sub = self.core.serving_state(n)
+        self.core.serve_projected(self._project(X), n, X.shape[1], sub)
+        return box_state, cropbox32, sub
+
+    def _scatter_state(self, idx, state):
+        self.state.load(state.to_state(), rows=idx)
+
+    def _keep_tables(self):
+        """The second serving state and the device pointer tables of both, made on the first masked frame."""
+        if self._save is None:
+            self._save = self.core.serving_state(self.B)
+            table = lambda st: _upload(np.array([t.data_ptr() for t in st.tensors()], dtype=np.int64), torch.int64, self.device)
+            rows = self.state.row_floats()
+            self._tables = (table(self.state), table(self._save), (ctypes.c_longlong * len(rows))(*rows))
+        return self._tables
+
+    def _sequence(self, X, mask):
+        """65 steps in place on self.state.  With a mask: the inactive trackers' rows are saved first and put back after."""
+        core = self.core
+        xproj = self._project(X, out=self._xproj)
+        if mask is None:
+            return core.serve_projected(xproj, self.B, X.shape[1], self.state, out=self._logits)
+        cur, save, rows = self._keep_tables()
+        state_keep(mask, 0, self.B, cur, save, rows)
+        logits = core.serve_projected(xproj, self.B, X.shape[1], self.state, out=self._logits)
+        state_keep(mask, 0, self.B, save, cur, rows)
+        return logits
+
+    def _step(self, imgs, mask):
+        crops = self._crop(imgs, self.frame_of, self.cropbox32, out=self._crops)
+        if self._fmap is None:
+            self._fmap = torch.empty((self.B, self.crop // 8, self.crop // 8, 512), device=self.device, dtype=torch.float32)
+        X = self._serialize(self._trunk(crops, out=self._fmap), None, X=self._X)
+        self._update_boxes(self._sequence(X, mask), mask)
+
+    def check(self):
+        """Synchronises; raises NtkError if a cluster launch of the core failed since the last check (DNC.check_cluster)."""
+        self.core.check_cluster()
+
+
+class DNCTracker(object):
+    """NTMTracker's contract on a DNC core: ``DNCTracker(image, region, core, vgg)`` then ``track(image) -> Rectangle``.  A
+    BatchDNCTracker of one object (``batch``) whose region is read back to the host after every frame -- the one
+    synchronisation of the online DNC path."""
+
+    def __init__(self, image, region, core, vgg, cropbox_grid=8, bbox_grid=6, device="cuda"):
+        self.batch = BatchDNCTracker(image, [region], core, vgg, cropbox_grid=cropbox_grid, bbox_grid=bbox_grid, device=device)
+        self.frame = 0
+
+    def track(self, image):
+        self.batch._step(self.batch._images(image), None)
+        self.frame += 1
+        self.offsets = self.batch.offsets[0].cpu().numpy()
+        return Rectangle(*self.batch.regions[0].tolist())
