@@ -756,6 +756,50 @@ int ntk_track_boxes_update(const float* logits, int B, int S, double cropbox_gri
                            const unsigned char* active, double* state, float* cropbox32, double* regions,
                            float* offsets, int* frame, void* stream);
 
+/* Per-clip tracking scores accumulated on the device, so that a validation run reads one table back at its end instead of the
+ * regions after every round.  A small bookkeeping kernel, not a compute hot path: one thread per slot b walks its T frames in
+ * order and adds to row clip_of[b] of the table; a clip's sums are therefore added in frame order and are reproducible bit
+ * for bit, and T one-frame calls leave the same bits as one T-frame call.
+ *   regions, gt  double [T,B,4] (x, y, w, h) in pixels: what BatchNTMTracker.track_clip returns, and the ground truth
+ *   active       uint8 [T,B], nullable = every frame active
+ *   clip_of      int32 [B]: the table row of slot b.  A row outside [0, n_clips) skips the slot: nothing of it is read or
+ *                written but clip_of[b] (and its frame_iou entries, NaN).  NO TWO SLOTS MAY NAME THE SAME ROW IN ONE CALL: each
+ *                thread owns its row without atomics, and two slots on one row would lose counts.  (ntmtrack.evaluate.ClipSchedule
+ *                never gives two slots one clip.)
+ *   iou_thr [n_iou], dist_thr [n_dist]: double thresholds in device memory; a count may be 0, then its array may be null
+ *   table        double [n_clips, NTK_SCORE_HEAD + n_iou + n_dist], accumulated IN PLACE; row layout, every field a double and
+ *                every count an exact integer:
+ *     [NTK_SCORE_FRAMES]      frames scored
+ *     [NTK_SCORE_SUM_IOU]     sum of their IoUs
+ *     [NTK_SCORE_SUM_DIST]    sum of the distances between the centres, pixels
+ *     [NTK_SCORE_LOST]        frames with IoU == 0
+ *     [NTK_SCORE_FIRST_LOST]  the value of FRAMES when the first lost frame arrived (= the number of frames scored before
+ *                             it), -1 while the clip has none: THE OWNER INITIALISES THIS FIELD TO -1, every other field to 0
+ *     [NTK_SCORE_HEAD + k]          k < n_iou:  frames with IoU > iou_thr[k]  (strictly, as OTB counts success)
+ *     [NTK_SCORE_HEAD + n_iou + k]  k < n_dist: frames with centre distance <= dist_thr[k]  (precision)
+ *   frame_iou    double [T,B], nullable: the frame's IoU, NaN where the frame was not scored
+ * A frame is scored when it is active and its ground truth is finite with w > 0 and h > 0 (an absent object is written with a
+ * non-finite or empty box); any other frame changes nothing.  A predicted region that is not finite scores IoU 0 and counts as
+ * lost; it adds nothing to SUM_DIST and to no precision count (its distance is taken as infinite).  Negative predicted sizes are
+ * clamped to 0.
+ * Arithmetic: float64 on real-valued rectangles, the VOT / OTB overlap |A n B| / |A u B| without a +1 pixel convention.  Boxes
+ * are taken to corners (x, x + w) and every side is a difference of corners, products are not contracted into FMAs and the
+ * result is clamped to [0, 1]: a box against itself gives exactly 1.0, boxes that only touch exactly 0.0, and integer-valued
+ * boxes the bits of any IEEE evaluation of (ix iy) / ((ap + ag) - ix iy).
+ * Errors, before any launch: NTK_ERR_BAD_PTR for a null regions / gt / clip_of / table; NTK_ERR_BAD_SHAPE, the value named in
+ * ntk_last_error, for T, B or n_clips <= 0, B > 65535, a count < 0 or > NTK_SCORE_MAX_THRESHOLDS, or a count > 0 with a null
+ * threshold array. */
+#define NTK_SCORE_FRAMES      0
+#define NTK_SCORE_SUM_IOU     1
+#define NTK_SCORE_SUM_DIST    2
+#define NTK_SCORE_LOST        3
+#define NTK_SCORE_FIRST_LOST  4
+#define NTK_SCORE_HEAD        5
+#define NTK_SCORE_MAX_THRESHOLDS 256
+int ntk_track_overlap_scores(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
+                             int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr, int n_dist,
+                             double* table, double* frame_iou, void* stream);
+
 /* out[b,:] = mask[b] ? a[b,:] : b[b,:] for fp32 [B,n] rows, mask uint8 [B] on the device (out may alias a or b): keeps the
  * recurrent state of a tracker that sat a frame out. */
 int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);

@@ -493,6 +493,85 @@ __global__ void track_boxes_update_kernel(const float* __restrict__ logits, int 
     if (frame) frame[b] += 1;
 }
 
+// Overlap of two rectangles (x, y, w, h) with w, h >= 0, in float64 on real-valued coordinates (the VOT / OTB overlap).  Both are
+// taken to corners first and every width is a difference of corners, so the intersection of a box with itself has the box's own
+// sides bit for bit: its IoU is a / (a + a - a) = 1.0 exactly, and boxes that only touch meet in a side of exactly 0.
+// Contraction is off in these functions (the header's __dmul_rn is a plain product the compiler may still fuse): a product is
+// rounded before it is added, so integer-valued boxes give the bits of any IEEE float64 evaluation of the same expression.
+__device__ __forceinline__ double rect_iou(double px, double py, double pw, double ph, double gx, double gy, double gw, double gh) {
+#pragma clang fp contract(off)
+    const double px2 = px + pw, py2 = py + ph, gx2 = gx + gw, gy2 = gy + gh;
+    const double ix = fmin(px2, gx2) - fmax(px, gx), iy = fmin(py2, gy2) - fmax(py, gy);
+    if (!(ix > 0 && iy > 0)) return 0.0;
+    const double inter = ix * iy;
+    const double area_p = (px2 - px) * (py2 - py), area_g = (gx2 - gx) * (gy2 - gy);
+    const double uni = (area_p + area_g) - inter;
+    const double iou = inter / uni;
+    if (!(iou > 0)) return 0.0;                 // an intersection that underflowed, or inf / inf of huge boxes
+    return iou > 1.0 ? 1.0 : iou;
+}
+
+__device__ __forceinline__ bool finite4(const double* r) { return isfinite(r[0]) && isfinite(r[1]) && isfinite(r[2]) && isfinite(r[3]); }
+
+// Per-clip tracking scores kept on the device (row layout: include/ntmtrack.h, NTK_SCORE_*).  One thread per slot walks its T
+// frames in order and adds to the row clip_of[b] of the table: the head of the row is carried in registers and written back at the
+// end, the threshold counts are incremented in place.  The row belongs to this thread alone (two slots never share a row: the
+// caller's contract), so a clip's sums are formed in frame order and no atomics are needed.  A slot whose row is outside
+// [0, n_clips) reads nothing but clip_of[b].
+__global__ void track_overlap_scores_kernel(const double* __restrict__ regions, const double* __restrict__ gt,
+                                            const unsigned char* __restrict__ active, const int* __restrict__ clip_of, int T, int B,
+                                            int n_clips, const double* __restrict__ iou_thr, int n_iou,
+                                            const double* __restrict__ dist_thr, int n_dist, double* __restrict__ table,
+                                            double* __restrict__ frame_iou) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const int clip = clip_of[b];
+    if (clip < 0 || clip >= n_clips) {
+        if (frame_iou)
+            for (int t = 0; t < T; ++t) frame_iou[(size_t)t * B + b] = nan;
+        return;
+    }
+    double* row = table + (size_t)clip * (NTK_SCORE_HEAD + n_iou + n_dist);
+    double frames = row[NTK_SCORE_FRAMES], sum_iou = row[NTK_SCORE_SUM_IOU], sum_dist = row[NTK_SCORE_SUM_DIST];
+    double lost = row[NTK_SCORE_LOST], first_lost = row[NTK_SCORE_FIRST_LOST];
+    for (int t = 0; t < T; ++t) {
+        const size_t at = (size_t)t * B + b;
+        const double* g = gt + 4 * at;
+        const bool scored = (!active || active[at]) && finite4(g) && g[2] > 0 && g[3] > 0;
+        if (!scored) {
+            if (frame_iou) frame_iou[at] = nan;
+            continue;
+        }
+        const double* p = regions + 4 * at;
+        double iou = 0.0;
+        if (finite4(p)) {
+            const double pw = fmax(p[2], 0.0), ph = fmax(p[3], 0.0);
+            iou = rect_iou(p[0], p[1], pw, ph, g[0], g[1], g[2], g[3]);
+            const double dx = (p[0] + pw / 2) - (g[0] + g[2] / 2), dy = (p[1] + ph / 2) - (g[1] + g[3] / 2);
+            const double dist = sqrt(dx * dx + dy * dy);
+            sum_dist += dist;
+            for (int k = 0; k < n_dist; ++k)
+                if (dist <= dist_thr[k]) row[NTK_SCORE_HEAD + n_iou + k] += 1.0;
+        }
+        if (iou == 0.0) {
+            if (first_lost < 0) first_lost = frames;
+            lost += 1.0;
+        }
+        for (int k = 0; k < n_iou; ++k)
+            if (iou > iou_thr[k]) row[NTK_SCORE_HEAD + k] += 1.0;
+        sum_iou += iou;
+        frames += 1.0;
+        if (frame_iou) frame_iou[at] = iou;
+    }
+    row[NTK_SCORE_FRAMES] = frames;
+    row[NTK_SCORE_SUM_IOU] = sum_iou;
+    row[NTK_SCORE_SUM_DIST] = sum_dist;
+    row[NTK_SCORE_LOST] = lost;
+    row[NTK_SCORE_FIRST_LOST] = first_lost;
+}
+
 // out[b, :] = mask[b] ? a[b, :] : b_[b, :]   (out may be a or b_: every element is read and written by the same thread)
 __global__ void select_rows_kernel(const unsigned char* __restrict__ mask, const float* a, const float* b_, float* out,
                                    size_t total, int n) {
@@ -602,6 +681,23 @@ extern "C" int ntk_track_boxes_update(const float* logits, int B, int S, double 
     track_boxes_update_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(logits, B, S, cropbox_grid, bbox_grid, active, state,
                                                                             cropbox32, regions, offsets, frame);
     NTK_CHECK_LAUNCH("ntk_track_boxes_update");
+    return NTK_OK;
+}
+
+extern "C" int ntk_track_overlap_scores(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
+                                        int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr,
+                                        int n_dist, double* table, double* frame_iou, void* stream) {
+    NTK_REQUIRE(regions && gt && clip_of && table, NTK_ERR_BAD_PTR, "ntk_track_overlap_scores: null pointer");
+    NTK_REQUIRE(T > 0 && B > 0 && B <= 65535 && n_clips > 0, NTK_ERR_BAD_SHAPE,
+                "ntk_track_overlap_scores: T=%d B=%d (1..65535) n_clips=%d", T, B, n_clips);
+    NTK_REQUIRE(n_iou >= 0 && n_iou <= NTK_SCORE_MAX_THRESHOLDS && n_dist >= 0 && n_dist <= NTK_SCORE_MAX_THRESHOLDS, NTK_ERR_BAD_SHAPE,
+                "ntk_track_overlap_scores: n_iou=%d n_dist=%d (0..%d each)", n_iou, n_dist, NTK_SCORE_MAX_THRESHOLDS);
+    NTK_REQUIRE((n_iou == 0 || iou_thr) && (n_dist == 0 || dist_thr), NTK_ERR_BAD_SHAPE,
+                "ntk_track_overlap_scores: n_iou=%d n_dist=%d but %s is null", n_iou, n_dist,
+                (n_iou > 0 && !iou_thr) ? "iou_thr" : "dist_thr");
+    track_overlap_scores_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, active, clip_of, T, B, n_clips, iou_thr,
+                                                                              n_iou, dist_thr, n_dist, table, frame_iou);
+    NTK_CHECK_LAUNCH("ntk_track_overlap_scores");
     return NTK_OK;
 }
 

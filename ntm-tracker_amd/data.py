@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import discrete_gauss
+from .geometry import apply_transformation, calculate_transformation, discrete_gauss
 
 VGG_MEAN = (123.68, 116.78, 103.94)
 
@@ -90,6 +90,45 @@ def load_frame_record(path_nosuffix, gt_width=8):
         raise ValueError("%s.bin: expected %d float64 values, got %d" % (path_nosuffix, gt_width * gt_width, raw.size))
     return {"cropbox": vals[:4], "bbox": vals[4:8], "image_path": fields[8], "y_offset": float(fields[9]),
             "x_offset": float(fields[10]), "gt": raw.astype(np.float32).reshape(gt_width, gt_width)}
+
+
+def load_frame_region(path_nosuffix):
+    """The object box of one frame record as the tracker's contract takes it (behaviour of validate_tracker.py:12-24): only the
+    ``.txt`` line is read, not the heat-map.  The record holds the box in CROP coordinates; it goes back through the inverse of
+    the crop transformation.  -> (image_path, (x, y, w, h) normalised by (W-1, H-1))."""
+    with open(path_nosuffix + '.txt') as f:
+        fields = f.readline().strip().split(',')
+    if len(fields) < 9:
+        raise ValueError("%s.txt: expected at least 9 comma-separated fields, got %d" % (path_nosuffix, len(fields)))
+    vals = [float(v) for v in fields[:8]]
+    inverse = np.linalg.inv(calculate_transformation(vals[:4]))
+    y1, x1, y2, x2 = apply_transformation(vals[4:8], inverse)
+    return fields[8], (x1, y1, x2 - x1, y2 - y1)
+
+
+def pixel_region(size, normalized_region):
+    """Normalised (x, y, w, h) -> pixels, size = (width, height): the inverse of geometry.normalize_bbox, times (W-1, H-1)."""
+    width, height = size
+    return tuple(np.asarray(normalized_region, dtype=np.float64) * np.array([width - 1, height - 1, width - 1, height - 1], dtype=np.float64))
+
+
+def validation_clips(seqs, image_root=None):
+    """``seqs`` as get_valid_sequences returns them -> one evaluate.Clip per sequence (the reference's validation loop,
+    validate_tracker.py:26-38).  Only the first image's header is opened here (for the frame size); a clip's frames are decoded
+    when the validator schedules it.  The tracker is started with the first region NORMALISED, as the reference passes it (the
+    trackers take a region whose four numbers are below 1 as normalised); the ground truth for scoring is in pixels."""
+    from PIL import Image
+    from .evaluate import Clip
+    clips = []
+    for folder, stems in seqs:
+        records = [load_frame_region(os.path.join(folder, stem)) for stem in stems]
+        paths = [p if image_root is None else os.path.join(image_root, p) for p, _r in records]
+        with Image.open(paths[0]) as im:
+            width, height = im.size
+        regions = np.array([pixel_region((width, height), r) for _p, r in records], dtype=np.float64)
+        decode = lambda paths=paths: np.stack([_decode_image(p) for p in paths])
+        clips.append(Clip(decode, regions, init=records[0][1], size=(height, width)))
+    return clips
 
 
 def _decode_image(path):

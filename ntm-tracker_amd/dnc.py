@@ -698,12 +698,24 @@ class DNCServingState(object):
         if rows is None:
             idx = slice(None)
         else:
-            idx = rows if torch.is_tensor(rows) else torch.as_tensor([int(r) for r in rows], dtype=torch.int64).to(self.mem.device)
+            idx = rows
+            if not torch.is_tensor(rows):
+                idx = torch.as_tensor([int(r) for r in rows], dtype=torch.int64)
+                idx = idx.pin_memory().to(self.mem.device, non_blocking=True) if self.mem.is_cuda else idx
+        # with row indices: index_fill_ / index_copy_, which only enqueue work (indexed assignment of a Python scalar uploads
+        # it through a synchronising copy, and a reset between two rounds of a validation run must not wait for the device); a
+        # list of rows went up through a pinned asynchronous copy above
         if Wl != self.core.W:
-            self.mem[idx, :, Wl:] = 0
-            self.reads[idx, :, Wl:] = 0
+            for t in (self.mem, self.reads):
+                if rows is None:
+                    t[..., Wl:] = 0
+                else:
+                    t[..., Wl:].index_fill_(0, idx, 0)
         for dst, src in pairs:
-            dst[idx] = src.to(dst.device, torch.float32)
+            if rows is None:
+                dst[idx] = src.to(dst.device, torch.float32)
+            else:
+                dst.index_copy_(0, idx, src.to(dst.device, torch.float32))
         return self
 
 

@@ -1,0 +1,307 @@
+"""Validation over clips on the device: the reference's validate_tracker.py:26-38 (one NTMTracker per clip, one frame at a time,
+nothing scored) as continuous batching over B slots of a BatchNTMTracker / BatchDNCTracker, with the overlap scores of every clip
+accumulated in one device table (ntk_track_overlap_scores) that is read back once, at the end.
+
+  ClipSchedule   which clip sits in which slot in which round (host arithmetic only: no torch, no device)
+  OverlapScores  the device table and its one synchronising read-out
+  Validation     the driver: per round the resets, ONE track_clip and ONE scores.add, no host synchronisation after the first
+                 round of a frame size
+  validate       runs a Validation to the end
+
+The overlap is the VOT / OTB one on real-valued rectangles.  The reference's own bb_iou (test_tracker.py:59-83) is never called
+there, uses a +1 pixel convention and does not clamp an empty intersection: it is not the model here.
+"""
+import collections
+
+import numpy as np
+
+# row layout of the score table: include/ntmtrack.h NTK_SCORE_*
+SCORE_FRAMES, SCORE_SUM_IOU, SCORE_SUM_DIST, SCORE_LOST, SCORE_FIRST_LOST, SCORE_HEAD = 0, 1, 2, 3, 4, 5
+SCORE_MAX_THRESHOLDS = 256
+
+Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
+
+#: one clip of a validation set.  frames: [L,H,W,3] uint8 or float host array, or a callable returning one (called when the clip is
+#: scheduled).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker.  init: the region the tracker is
+#: started with when it is not regions[0] (the reference passes it normalised).  size: (H, W) where frames is a callable, so that
+#: clips can be grouped by frame size without decoding them.
+Clip = collections.namedtuple("Clip", ["frames", "regions", "init", "size"])
+Clip.__new__.__defaults__ = (None, None)
+
+
+class ClipSchedule(object):
+    """Continuous batching of clips over B slots in rounds of T frames.  lengths[i]: frames of clip i INCLUDING its first one,
+    which starts the tracker and is not tracked (so >= 2).  Clips are handed out in index order, at the start of a round, to the
+    lowest free slot; a slot whose clip ends inside a round idles until the round ends.  With fewer clips than B the effective B
+    (``self.B``) is the number of clips.
+
+    Iterating yields Round(resets, frame_index, active, clip_of): ``resets`` a list of (slot, clip) started in this round;
+    ``frame_index`` int64 [T,B], the frame of the slot's clip tracked at (t, b) (0 where inactive); ``active`` uint8 [T,B];
+    ``clip_of`` int32 [B], -1 for a slot without a clip.  No two slots hold the same clip in a round."""
+
+    def __init__(self, lengths, B, T):
+        self.lengths = [int(n) for n in lengths]
+        if int(B) < 1 or int(T) < 1:
+            raise ValueError("ClipSchedule: B=%d T=%d" % (B, T))
+        for i, n in enumerate(self.lengths):
+            if n < 2:
+                raise ValueError("ClipSchedule: clip %d has %d frame(s); a clip needs its first frame and one to track" % (i, n))
+        self.B, self.T = max(1, min(int(B), len(self.lengths))), int(T)
+
+    def __iter__(self):
+        B, T, lengths = self.B, self.T, self.lengths
+        clip, pos, upcoming = [-1] * B, [0] * B, 0
+        while True:
+            resets = []
+            for s in range(B):
+                if clip[s] < 0 and upcoming < len(lengths):
+                    clip[s], pos[s] = upcoming, 1
+                    resets.append((s, upcoming))
+                    upcoming += 1
+            if all(c < 0 for c in clip):
+                return
+            frame_index, active = np.zeros((T, B), dtype=np.int64), np.zeros((T, B), dtype=np.uint8)
+            clip_of = np.asarray(clip, dtype=np.int32)
+            for s in range(B):
+                if clip[s] < 0:
+                    continue
+                n = min(T, lengths[clip[s]] - pos[s])
+                frame_index[:n, s] = np.arange(pos[s], pos[s] + n)
+                active[:n, s] = 1
+                pos[s] += n
+                if pos[s] == lengths[clip[s]]:
+                    clip[s] = -1                    # free from the next round on
+            yield Round(resets, frame_index, active, clip_of)
+
+
+def summarize(table, iou_thresholds, dist_thresholds):
+    """The host arithmetic of OverlapScores.result(): table [n_clips, SCORE_HEAD + n_iou + n_dist] float64 -> dict (see result)."""
+    table = np.asarray(table, dtype=np.float64)
+    iou_thr, dist_thr = np.asarray(iou_thresholds, dtype=np.float64), np.asarray(dist_thresholds, dtype=np.float64)
+    n_iou, n_dist = len(iou_thr), len(dist_thr)
+    frames = table[:, SCORE_FRAMES]
+    scored = frames > 0
+    per = np.where(scored, frames, np.nan)[:, None]                     # a clip without scored frames: NaN means
+    succ, prec = table[:, SCORE_HEAD:SCORE_HEAD + n_iou], table[:, SCORE_HEAD + n_iou:SCORE_HEAD + n_iou + n_dist]
+    clips = {"frames": frames.astype(np.int64), "mean_overlap": table[:, SCORE_SUM_IOU] / per[:, 0],
+             "mean_centre_error": table[:, SCORE_SUM_DIST] / per[:, 0], "lost": table[:, SCORE_LOST].astype(np.int64),
+             "first_lost": table[:, SCORE_FIRST_LOST].astype(np.int64), "success": succ / per, "precision": prec / per}
+    total = frames.sum()
+    over = total if total > 0 else np.nan
+    success_curve, precision_curve = succ.sum(axis=0) / over, prec.sum(axis=0) / over
+    at20 = np.nonzero(dist_thr == 20.0)[0]
+    return {"clips": clips, "iou_thresholds": iou_thr, "dist_thresholds": dist_thr,
+            "frames": int(total), "clips_scored": int(scored.sum()), "clips_without_frames": int((~scored).sum()),
+            "mean_overlap_frames": table[:, SCORE_SUM_IOU].sum() / over,
+            "mean_overlap_clips": float(np.mean(clips["mean_overlap"][scored])) if scored.any() else np.nan,
+            "mean_centre_error_frames": table[:, SCORE_SUM_DIST].sum() / over,
+            "success_curve": success_curve, "success_auc": float(np.mean(success_curve)) if n_iou else np.nan,
+            "precision_curve": precision_curve, "precision_20px": float(precision_curve[at20[0]]) if len(at20) else np.nan,
+            "lost": int(table[:, SCORE_LOST].sum()),
+            "clips_never_lost": int((scored & (table[:, SCORE_FIRST_LOST] < 0)).sum())}
+
+
+class OverlapScores(object):
+    """The score table of n_clips clips ([n_clips, SCORE_HEAD + n_iou + n_dist] float64, ``self.table``) and the two threshold
+    arrays, on the device.  ``add`` is one launch of ntk_track_overlap_scores and synchronises nothing; ``result`` is the one
+    synchronising call."""
+
+    def __init__(self, n_clips, iou_thresholds=None, dist_thresholds=None, device="cuda"):
+        import torch
+        self.iou_thresholds = np.asarray(np.linspace(0, 1, 21) if iou_thresholds is None else iou_thresholds, dtype=np.float64).reshape(-1)
+        self.dist_thresholds = np.asarray(np.arange(0, 51.) if dist_thresholds is None else dist_thresholds, dtype=np.float64).reshape(-1)
+        if int(n_clips) < 1 or max(len(self.iou_thresholds), len(self.dist_thresholds)) > SCORE_MAX_THRESHOLDS:
+            raise ValueError("OverlapScores: n_clips=%d, %d and %d thresholds (at most %d each)"
+                             % (n_clips, len(self.iou_thresholds), len(self.dist_thresholds), SCORE_MAX_THRESHOLDS))
+        self.n_clips, self.device = int(n_clips), torch.device(device)
+        self.table = torch.zeros((self.n_clips, SCORE_HEAD + len(self.iou_thresholds) + len(self.dist_thresholds)),
+                                 dtype=torch.float64, device=self.device)
+        self.table[:, SCORE_FIRST_LOST] = -1
+        self._iou = torch.as_tensor(self.iou_thresholds).to(self.device)
+        self._dist = torch.as_tensor(self.dist_thresholds).to(self.device)
+
+    def _dev(self, x, dtype):
+        import torch
+        from .online import _upload
+        if torch.is_tensor(x) and x.device.type == self.device.type:
+            return x.to(dtype).contiguous()
+        return _upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, self.device)
+
+    def add(self, regions, gt, clip_of, active=None, frame_iou=False):
+        """regions, gt: [T,B,4] or [B,4] (x, y, w, h) pixels; clip_of [B]: the table row of slot b, no row twice (a row outside
+        the table skips the slot); active [T,B] or [B], nullable.  Device tensors are taken as they are, host arrays go up through
+        a pinned asynchronous copy.  frame_iou=True returns the per-frame IoUs [T,B] (NaN where a frame was not scored)."""
+        import torch
+        from . import _lib
+        regions, gt = self._dev(regions, torch.float64), self._dev(gt, torch.float64)
+        if regions.dim() == 2:
+            regions, gt = regions.unsqueeze(0), gt.unsqueeze(0)
+        if regions.dim() != 3 or regions.shape[2] != 4 or gt.shape != regions.shape:
+            raise _lib.NtkError("OverlapScores.add: regions %s and gt %s must both be [T,B,4]" % (tuple(regions.shape), tuple(gt.shape)))
+        T, B = regions.shape[:2]
+        clip_of = self._dev(clip_of, torch.int32)
+        mask = None if active is None else self._dev(active, torch.uint8).reshape(-1, B)
+        if tuple(clip_of.shape) != (B,) or (mask is not None and tuple(mask.shape) != (T, B)):
+            raise _lib.NtkError("OverlapScores.add: clip_of %s / active %s for [T,B] = [%d,%d]"
+                                % (tuple(clip_of.shape), None if mask is None else tuple(mask.shape), T, B))
+        out = torch.empty((T, B), dtype=torch.float64, device=self.device) if frame_iou else None
+        P = _lib.ptr
+        _lib.check(_lib.lib().ntk_track_overlap_scores(P(regions), P(gt), P(mask), P(clip_of), T, B, self.n_clips,
+                                                       P(self._iou) if len(self.iou_thresholds) else None, len(self.iou_thresholds),
+                                                       P(self._dist) if len(self.dist_thresholds) else None, len(self.dist_thresholds),
+                                                       P(self.table), P(out), _lib.stream()), "ntk_track_overlap_scores")
+        return out
+
+    def result(self):
+        """Reads the table back (the one synchronisation).  -> dict: ``clips`` holds per clip ``frames``, ``mean_overlap``,
+        ``mean_centre_error`` (px), ``lost``, ``first_lost`` (frames scored before the first lost one, -1 = never), ``success``
+        [n_clips,n_iou] and ``precision`` [n_clips,n_dist] (rates); over the dataset ``frames``, ``mean_overlap_frames``
+        (frame-weighted), ``mean_overlap_clips`` (clip-weighted), ``mean_centre_error_frames``, ``success_curve`` and
+        ``success_auc`` (the mean of the success rates over the thresholds), ``precision_curve`` and ``precision_20px`` (NaN
+        without a 20 px threshold), ``lost``, ``clips_never_lost``, ``clips_scored`` and ``clips_without_frames``.  A clip with
+        no scored frame has NaN means, is left out of the clip-weighted figures and is counted in ``clips_without_frames``."""
+        return summarize(self.table.cpu().numpy(), self.iou_thresholds, self.dist_thresholds)
+
+
+def _as_clip(c):
+    if isinstance(c, Clip):
+        return c
+    if isinstance(c, dict):
+        return Clip(c["frames"], c["regions"], c.get("init"), c.get("size"))
+    if isinstance(c, (tuple, list)):
+        return Clip(*c)
+    return Clip(c.frames, c.regions, getattr(c, "init", None), getattr(c, "size", None))
+
+
+class _SizeClass(object):
+    def __init__(self, size, members):
+        self.size, self.members, self.tracker = size, members, None      # members: the caller's clip indices, in order
+
+
+class Validation(object):
+    """Validates a tracker over clips: ``make_tracker(first_images [B,H,W,3], regions [B,4])`` -> a BatchNTMTracker or
+    BatchDNCTracker (one per frame size; both share the online contract), ``clips`` a sequence of Clip (or objects / dicts with
+    ``frames`` and ``regions``).  ``step()`` runs one round -- reset for the slots that take a new clip, one track_clip over
+    frames [T,B,H,W,3] with the round's mask, one scores.add -- and returns False when no round was left.  After the first round
+    of a frame size (which builds the tracker, its plans and workspaces) a round makes no host synchronisation.  ``scores`` is
+    the OverlapScores, rows in the caller's clip order; ``regions()`` the tracked regions per clip when return_regions was set."""
+
+    def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda"):
+        import torch
+        self.make_tracker, self.device = make_tracker, torch.device(device)
+        self.clips = [_as_clip(c) for c in clips]
+        if not self.clips:
+            raise ValueError("Validation: no clips")
+        self.B, self.T = int(B), int(T)
+        self._gt = [np.asarray(c.regions, dtype=np.float64).reshape(-1, 4) for c in self.clips]
+        self._held = {}                                 # clip index -> decoded frames, from its reset to its last frame
+        classes = collections.OrderedDict()
+        for i, c in enumerate(self.clips):
+            classes.setdefault(self._size(i), []).append(i)
+        self.classes = [_SizeClass(size, members) for size, members in classes.items()]
+        self.scores = OverlapScores(len(self.clips), iou_thresholds, dist_thresholds, device=self.device)
+        self._keep = [] if return_regions else None     # (device regions [T,B,4], frame_index, active, clip ids) per round
+        self._rounds = self._all_rounds()
+
+    # ---- clips
+    def _frames(self, i):
+        if i not in self._held:
+            f = self.clips[i].frames
+            a = np.asarray(f() if callable(f) else f)
+            if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != len(self._gt[i]):
+                raise ValueError("clip %d: frames %s for %d regions; expected [L,H,W,3]" % (i, a.shape, len(self._gt[i])))
+            self._held[i] = a if a.dtype == np.uint8 else a.astype(np.float32, copy=False)
+        return self._held[i]
+
+    def _size(self, i):
+        c = self.clips[i]
+        if c.size is not None:
+            return (int(c.size[0]), int(c.size[1]))
+        if callable(c.frames):
+            return tuple(np.asarray(c.frames()).shape[1:3])    # no size given: decoded for its shape alone and dropped again (pass
+                                                               # size= to avoid the second decoding when the clip is scheduled)
+        return tuple(np.asarray(c.frames).shape[1:3])
+
+    def _init_region(self, i):
+        c = self.clips[i]
+        return self._gt[i][0] if c.init is None else np.asarray(c.init, dtype=np.float64).reshape(4)
+
+    # ---- rounds
+    def _all_rounds(self):
+        for cls in self.classes:
+            for rnd in ClipSchedule([len(self._gt[i]) for i in cls.members], self.B, self.T):
+                yield cls, rnd
+
+    def step(self):
+        nxt = next(self._rounds, None)
+        if nxt is None:
+            return False
+        self._run(*nxt)
+        return True
+
+    def _run(self, cls, rnd):
+        from .online import _upload
+        import torch
+        T, B = rnd.active.shape
+        H, W = cls.size
+        ids = np.where(rnd.clip_of >= 0, np.asarray(cls.members, dtype=np.int64)[np.maximum(rnd.clip_of, 0)], -1).astype(np.int32)
+        # (1) the slots that take a new clip
+        if rnd.resets:
+            slots = [s for s, _c in rnd.resets]
+            new = [cls.members[c] for _s, c in rnd.resets]
+            firsts = [self._frames(i)[0] for i in new]
+            images = np.stack(firsts).astype(np.uint8 if all(f.dtype == np.uint8 for f in firsts) else np.float32, copy=False)
+            regions = np.stack([self._init_region(i) for i in new])
+            if cls.tracker is None:
+                assert slots == list(range(B))          # the first round of a schedule fills every slot, in order
+                cls.tracker = self.make_tracker(images, regions)
+            else:
+                cls.tracker.reset(slots, images, regions)
+        # (2) frames and ground truth of the round: zero frames (the crop kernel still reads them) and NaN boxes where inactive
+        held = [None if i < 0 else self._frames(int(i)) for i in ids]
+        u8 = all(h is None or h.dtype == np.uint8 for h in held)
+        frames = np.zeros((T, B, H, W, 3), dtype=np.uint8 if u8 else np.float32)
+        gt = np.full((T, B, 4), np.nan, dtype=np.float64)
+        for b in range(B):
+            n = int(rnd.active[:, b].sum())
+            if n:
+                at = rnd.frame_index[:n, b]
+                frames[:n, b] = held[b][at[0]:at[-1] + 1]
+                gt[:n, b] = self._gt[int(ids[b])][at[0]:at[-1] + 1]
+                if at[-1] + 1 == len(self._gt[int(ids[b])]):
+                    del self._held[int(ids[b])]         # the clip has ended
+        active = _upload(rnd.active, torch.uint8, self.device)
+        d_gt = _upload(gt, torch.float64, self.device)
+        d_ids = _upload(ids, torch.int32, self.device)
+        # (3) one pass over the round, (4) one scoring launch
+        out = cls.tracker.track_clip(frames, active=active)
+        self.scores.add(out, d_gt, d_ids, active=active)
+        if self._keep is not None:
+            self._keep.append((out, rnd.frame_index, rnd.active, ids))
+
+    def finish(self):
+        """Runs the remaining rounds; then asks every tracker that can tell (BatchDNCTracker.check) whether a launch failed."""
+        while self.step():
+            pass
+        for cls in self.classes:
+            if cls.tracker is not None and hasattr(cls.tracker, "check"):
+                cls.tracker.check()
+        return self
+
+    def regions(self):
+        """The tracked regions per clip, a list of [L-1,4] float64 host arrays in the caller's clip order (synchronises)."""
+        if self._keep is None:
+            raise ValueError("Validation: made without return_regions=True")
+        out = [np.full((len(g) - 1, 4), np.nan) for g in self._gt]
+        for dev, frame_index, active, ids in self._keep:
+            host = dev.cpu().numpy()
+            for t, b in zip(*np.nonzero(active)):
+                out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
+        return out
+
+
+def validate(make_tracker, clips, B, T, return_regions=False, **kw):
+    """Validation(...) run to its end -> scores.result(), or (result, regions per clip) with return_regions=True."""
+    v = Validation(make_tracker, clips, B, T, return_regions=return_regions, **kw).finish()
+    res = v.scores.result()
+    return (res, v.regions()) if return_regions else res
