@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/ntmtrack.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,6 +29,14 @@ int ntk_device_cu_count();      // api.cpp: compute units of the current device 
             return NTK_ERR_HIP;                                                \
         }                                                                      \
     } while (0)
+
+// Compile-time loop: f(ntk_ic<I0>{}), ..., f(ntk_ic<I1 - 1>{}) -- the index is a constant inside f (register arrays indexed by it
+// stay in registers, `if constexpr` on it drops whole bodies)
+template <int N> using ntk_ic = std::integral_constant<int, N>;
+template <int I0, int I1, class F>
+__device__ __forceinline__ void ntk_static_for(F&& f) {
+    if constexpr (I0 < I1) { f(ntk_ic<I0>{}); ntk_static_for<I0 + 1, I1>(f); }
+}
 
 static inline bool ntk_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 

@@ -27,8 +27,7 @@
 //     rows of a sub-block live in consecutive tiles of one wave, so the 2x2 pool is a register max + one DPP exchange.
 // Same operator, operand rounding and accumulation type as conv_bf16.hip (bf16 operands, fp32 accumulate, one bf16 rounding
 // on store; vgg.py:155-161); the summation ORDER over (chunk, tap, channel) differs, so results agree to fp32 rounding.
-#include "common.h"
-#include <type_traits>
+#include "conv_tiles.h"
 
 // Ablation switches (timing only, results wrong; never defined in the product build): bit 0 no DMA after the prologue, bit 1 no
 // workgroup barrier / DMA wait in the K loop, bit 2 fragments not re-read (one set for the whole kernel), bit 3 no MFMAs, bit 4 no epilogue, bit 5 the un-pooled epilogue without its global stores
@@ -37,11 +36,6 @@
 #endif
 
 namespace {
-
-template <int I0, int I1, class F>
-__device__ __forceinline__ void bp_for(F&& f) {
-    if constexpr (I0 < I1) { f(std::integral_constant<int, I0>{}); bp_for<I0 + 1, I1>(f); }
-}
 
 typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 pbf16x4 __attribute__((ext_vector_type(4)));
@@ -226,33 +220,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int id = blockIdx.x, xcd = id & 7, slotid = id >> 3;
     int cb, sp;
-    if (a.nCB >= 8) {
-        const int kN = a.nCB >> 3;
-        cb = (slotid % kN) * 8 + xcd;
-        sp = slotid / kN;
-    } else {
-        const int per = 8 / a.nCB;
-        cb = xcd % a.nCB;
-        sp = slotid * per + xcd / a.nCB;
-    }
+    conv_tile_wg(blockIdx.x, a.nCB, cb, sp);
     if (sp >= a.NS) return;
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     // ROWS: first pixel of the run, its global row g0 = (frame rf0, row ry0)
     const int rP0 = sp * (32 * PNT), rg0 = ROWS ? rP0 / TW : 0, rf0 = ROWS ? rg0 / H : 0, ry0 = ROWS ? rg0 - rf0 * H : 0;
     if (tid < BN) s_bias[tid] = a.bias[cb * BN + tid];
     if (X3 && tid == BN) s_bias[BN] = *reinterpret_cast<const float*>(a.wq + (size_t)9 * a.Cin * a.Cout);
-    if (!ROWS && tid < NSUB) {
-        const int sq = sp * NSUB + tid;
-        if (sq < a.NQ) {
-            const int bx = sq % a.bxN;
-            const int t1 = sq / a.bxN;
-            s_sbf[tid] = t1 / a.byN; s_sby[tid] = TH * (t1 % a.byN); s_sbx[tid] = TW * bx;
-        } else {
-            s_sbf[tid] = -1; s_sby[tid] = 0; s_sbx[tid] = 0;
-        }
-    }
+    if constexpr (!ROWS) conv_tile_subblocks<NSUB>(s_sbf, s_sby, s_sbx, tid, sp, a.NQ, a.bxN, a.byN, TH, TW, 0, 0);
     __syncthreads();
 
     // the patch image's swizzle: slot of piece 0 of patch pixel p.  ROWS: by the pixel's position in the RUN (28 per row), not in the
@@ -448,7 +424,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
             constexpr int k = decltype(kc)::value;
             if constexpr (k < NDW) { if (more_w) dma_weights1(s + 1, bbuf ^ 1, k); }
             else if constexpr (k < NDW + NDP && part * NDP + (k - NDW) < NPAW) {
-                if (more_p) dma_patch1(chunk + 1, abuf ^ 1, std::integral_constant<int, part * NDP + (k - NDW)>{});
+                if (more_p) dma_patch1(chunk + 1, abuf ^ 1, ntk_ic<part * NDP + (k - NDW)>{});
             }
         };
         const int wa = wa0 + bbuf * SBYTES;
@@ -486,8 +462,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                     for (int nt = 0; nt < 2; ++nt)
                         acc[tm][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p_as_f16x8(w[nt]), p_as_f16x8(x[tm]), acc[tm][nt], 0, 0, 0);
             };
-            using I0 = std::integral_constant<int, 0>;
-            using I1 = std::integral_constant<int, 1>;
+            using I0 = ntk_ic<0>;
+            using I1 = ntk_ic<1>;
             constexpr int NSS = STAPS * 3;                                       // sub-steps of eight MFMAs
             static_assert(NDW + NDP <= NSS, "one DMA per sub-step");
             auto tapstep = [&](auto dc) {
@@ -495,20 +471,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if constexpr (!(BF16P_ABL & 4)) ld_w(dc, I1{}, wl);
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wh[dxi & 1], xh);
-                dma_slot(std::integral_constant<int, 3 * dxi>{});
+                dma_slot(ntk_ic<3 * dxi>{});
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(BF16P_ABL & 4)) ld_x(dc, I1{}, xl);
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wl, xh);
-                dma_slot(std::integral_constant<int, 3 * dxi + 1>{});
+                dma_slot(ntk_ic<3 * dxi + 1>{});
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (dxi + 1 < STAPS && !(BF16P_ABL & 4)) {
-                    ld_w(std::integral_constant<int, dxi + 1>{}, I0{}, wh[(dxi + 1) & 1]);
-                    ld_x(std::integral_constant<int, dxi + 1>{}, I0{}, xh);
+                    ld_w(ntk_ic<dxi + 1>{}, I0{}, wh[(dxi + 1) & 1]);
+                    ld_x(ntk_ic<dxi + 1>{}, I0{}, xh);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wh[dxi & 1], xl);
-                dma_slot(std::integral_constant<int, 3 * dxi + 2>{});
+                dma_slot(ntk_ic<3 * dxi + 2>{});
                 __builtin_amdgcn_sched_barrier(0);
             };
             ld_w(I0{}, I0{}, wh[0]);
@@ -519,7 +495,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm) xl[tm] = xh[tm];
             }
-            bp_for<0, STAPS>(tapstep);
+            ntk_static_for<0, STAPS>(tapstep);
             if constexpr (INF32) {
                 if (more_p) {
 #pragma unroll
@@ -546,7 +522,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         };
         auto step = [&](auto stc) {
             constexpr int st = decltype(stc)::value;
-            if constexpr (st + 1 < NSTEP && !(BF16P_ABL & 4)) load_frags(std::integral_constant<int, st + 1>{}, wf[(st + 1) & 1], xf[(st + 1) & 1]);
+            if constexpr (st + 1 < NSTEP && !(BF16P_ABL & 4)) load_frags(ntk_ic<st + 1>{}, wf[(st + 1) & 1], xf[(st + 1) & 1]);
             __builtin_amdgcn_sched_barrier(0);
             if constexpr ((BF16P_ABL & 8) != 0) return;
 #pragma unroll
@@ -557,23 +533,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                                                                           p_as_bf16x8(xf[(BF16P_ABL & 4) ? 0 : (st & 1)][tm]), acc[tm][nt], 0, 0, 0);
             // this step's share of the stage's DMAs (all of them fit the first steps: NDW + NDP <= 2 NSTEP)
             constexpr int PER = (NDW + NDP + NSTEP - 1) / NSTEP;
-            dma_slot(std::integral_constant<int, st * PER>{});
-            if constexpr (PER > 1) dma_slot(std::integral_constant<int, st * PER + 1>{});
+            dma_slot(ntk_ic<st * PER>{});
+            if constexpr (PER > 1) dma_slot(ntk_ic<st * PER + 1>{});
             static_assert(PER <= 2, "DMAs per step");
             __builtin_amdgcn_sched_barrier(0);
         };
-        if (!(BF16P_ABL & 4) || s == 0) load_frags(std::integral_constant<int, 0>{}, wf[0], xf[0]);
-        bp_for<0, NSTEP>(step);
+        if (!(BF16P_ABL & 4) || s == 0) load_frags(ntk_ic<0>{}, wf[0], xf[0]);
+        ntk_static_for<0, NSTEP>(step);
         if (!(BF16P_ABL & 2)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
     };
     for (int chunk = 0; chunk < NC; ++chunk) {
-        stage_body(chunk, std::integral_constant<int, 0>{});
+        stage_body(chunk, ntk_ic<0>{});
         if constexpr (SPC > 1) {
-            stage_body(chunk, std::integral_constant<int, 1>{});
-            stage_body(chunk, std::integral_constant<int, 2>{});
+            stage_body(chunk, ntk_ic<1>{});
+            stage_body(chunk, ntk_ic<2>{});
         }
         const int flip = (chunk & 1) ? -ABYTES : ABYTES;                        // the next chunk's patch is in the other buffer
 #pragma unroll
@@ -704,10 +680,7 @@ int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipSt
             a.bxN = 1; a.byN = 1;
             const long long NQ = (long long)a.frames * H * W, NS = (NQ + 511) / 512;
             a.NQ = 0; a.NS = (int)NS; a.nCB = a.Cout / BN;
-            long long slots;
-            if (a.nCB >= 8) slots = NS * (a.nCB / 8);
-            else { const int per = 8 / a.nCB; slots = (NS + per - 1) / per; }
-            const unsigned grid = (unsigned)(slots * 8);
+            const unsigned grid = (unsigned)conv_tile_grid(NS, a.nCB);
             if constexpr (NW == 8) {
                 if (out_f32) conv3x3_relu_bf16p_kernel<BN, 28, 21, 1, 32, false, true, 8, true><<<grid, 512, 0, st>>>(a);
                 else conv3x3_relu_bf16p_kernel<BN, 28, 21, 1, 32, false, false, 8, true><<<grid, 512, 0, st>>>(a);
@@ -727,10 +700,7 @@ int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipSt
     const long long NQ = (long long)a.frames * a.bxN * a.byN;
     const long long NS = (NQ + NSUBv - 1) / NSUBv;
     a.NQ = (int)NQ; a.NS = (int)NS; a.nCB = a.Cout / BN;
-    long long slots;
-    if (a.nCB >= 8) slots = NS * (a.nCB / 8);
-    else { const int per = 8 / a.nCB; slots = (NS + per - 1) / per; }
-    const unsigned grid = (unsigned)(slots * 8);
+    const unsigned grid = (unsigned)conv_tile_grid(NS, a.nCB);
 #define BF16P_GO(TW_, TH_, NSUB_)                                                                                             \
     do {                                                                                                                      \
         if (pool) {                                                                                                           \
@@ -773,9 +743,7 @@ static int bf16p_form(int H, int W, int cin, int cout, int pool, int* bn, int* k
     *nw = (rect && cin <= 64 && cout == 64) ? 4 : 8;       // (measured: conv2_1, 64 -> 128 columns, LOSES 4 % as two 64-column halves that both stage the patch)
     *bn = (*nw == 8 && cout % 128 == 0) ? 128 : 64;
     *kc = rect ? 32 : 16;
-    const int nCB = cout / *bn;
-    if (!(nCB <= 8 ? (8 % nCB) == 0 : (nCB % 8) == 0)) return 0;
-    return 1;
+    return conv_tile_ncb_ok(cout / *bn);
 }
 
 extern "C" size_t ntk_vgg_bf16p_packed_elems(int cin, int cout) { return (size_t)9 * cin * cout; }
@@ -840,9 +808,7 @@ static int split3_form(int H, int W, int cin, int cout, int pool, int* bn, int* 
     if (!rect && (pool || W != 28 || H < 20)) return 0;                          // 28-wide maps: runs of rows (conv4_x), un-pooled
     *nw = (rect && cin <= 64 && cout == 64) ? 4 : 8;
     *bn = (*nw == 8 && cout % 128 == 0) ? 128 : 64;
-    const int nCB = cout / *bn;
-    if (!(nCB <= 8 ? (8 % nCB) == 0 : (nCB % 8) == 0)) return 0;
-    return 1;
+    return conv_tile_ncb_ok(cout / *bn);
 }
 
 extern "C" size_t ntk_vgg_split3_packed_elems(int cin, int cout) { return (size_t)18 * cin * cout + 8; }    // + 16 bytes: the scales

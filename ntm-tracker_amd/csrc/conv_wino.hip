@@ -18,7 +18,7 @@
 //   Cross-wave part of A^T M A goes through LDS once per workgroup.
 //   XCD-aware 1-D grid: an XCD keeps one column block, so its U slice stays in that XCD's L2.
 // Results differ from the direct kernel by rounding only (different summation order, ~1e-6 relative per layer).
-#include "common.h"
+#include "conv_tiles.h"
 
 #ifndef WINO_UD
 #define WINO_UD 3      // U prefetch distance in planes (1..3)
@@ -108,30 +108,12 @@ __global__ __launch_bounds__(WT, 2) void conv3x3_wino_kernel(WinoArgs a) {
     __shared__ __attribute__((aligned(16))) float s_V[2 * VSZ];             // 2 x 16 KB (32 KB: also the epilogue's Z)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
     int cb, sp;
-    if (a.nCB >= 8) {
-        const int kN = a.nCB >> 3;
-        cb = (slot % kN) * 8 + xcd;
-        sp = slot / kN;
-    } else {
-        const int per = 8 / a.nCB;
-        cb = xcd % a.nCB;
-        sp = slot * per + xcd / a.nCB;
-    }
+    conv_tile_wg(blockIdx.x, a.nCB, cb, sp);
     if (sp >= a.NS) return;
     const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
     __shared__ int s_sbf[NSUB], s_sby[NSUB], s_sbx[NSUB];
-    if (tid < NSUB) {
-        const int sq = sp * NSUB + tid;
-        if (sq < a.NQ) {
-            const int bx = sq % a.bxN;
-            const int t1 = sq / a.bxN;
-            s_sbf[tid] = t1 / a.byN; s_sby[tid] = 2 * TH * (t1 % a.byN); s_sbx[tid] = 2 * TW * bx;
-        } else {
-            s_sbf[tid] = -1; s_sby[tid] = 0; s_sbx[tid] = 0;
-        }
-    }
+    conv_tile_subblocks<NSUB>(s_sbf, s_sby, s_sbx, tid, sp, a.NQ, a.bxN, a.byN, 2 * TH, 2 * TW, 0, 0);
     __syncthreads();
 
     // ---- patch staging: NPX pixels x 2 float4 slots
@@ -359,13 +341,10 @@ static int wino_form(int frames, int H, int W, int cin, int cout, WinoForm* f) {
     f->byN = f->shape == 3 ? H / 4 : H / 8;
     const long long NQ = (long long)frames * f->byN * f->bxN;
     const long long NS = f->shape == 1 ? (NQ + 1) / 2 : (f->shape == 3 ? (NQ + 7) / 8 : NQ);
-    if (NS >= (1ll << 30) || !(f->nCB <= 8 ? (8 % f->nCB) == 0 : (f->nCB % 8) == 0)) return 0;
+    if (NS >= (1ll << 30) || !conv_tile_ncb_ok(f->nCB)) return 0;
     f->NS = (int)NS;
     f->NQ = (int)NQ;
-    long long slots;                                  // workgroup ids = slots * 8
-    if (f->nCB >= 8) slots = NS * (f->nCB / 8);
-    else { const int per = 8 / f->nCB; slots = (NS + per - 1) / per; }
-    f->grid = slots * 8;
+    f->grid = conv_tile_grid(NS, f->nCB);
     return f->grid < (1ll << 31);
 }
 

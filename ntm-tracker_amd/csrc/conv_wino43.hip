@@ -22,8 +22,11 @@
 //   patch and V are double-buffered: one workgroup barrier per K step.
 //   epilogue: accumulators -> LDS (one 32-channel half at a time), 256 threads = (tile, four adjacent channels) run
 //     A^T M A, bias, ReLU (+ 2x2 pool inside the 4x4 tile) and store one float4 per pixel, NHWC.
-#include "common.h"
-#include <type_traits>
+//
+// Layout of this file: the weight packing; the phases the two kernels share (W43Shape .. w43_out_transform), one copy each;
+// conv3x3_wino43_kernel (four waves); conv3x3_wino43d_kernel (eight waves: what the entries launch); the launcher.  The workgroup
+// map, its grid and the sub-block table are conv_tiles.h's, shared with conv_wino.hip and conv_bf16p.hip.
+#include "conv_tiles.h"
 
 // Diagnostic build only (make prof, -DNTK_CL_PROF): lane 0 of every wave of ONE workgroup accumulates s_memtime deltas per
 // section of the K loop into g_w43_prof[wave][section]; ntk_vgg_wino43_prof() copies them out (read SHARES, not totals).
@@ -98,8 +101,6 @@ __global__ void wino43_pack_kernel(const float* __restrict__ w, float* __restric
     }
 }
 
-template <int N> using ic = std::integral_constant<int, N>;
-
 // B^T of F(4x4,3x3) applied to six values (rows or columns): the pieces the tasks are built from
 __device__ __forceinline__ f32x4 w43_r0(f32x4 d0, f32x4 d2, f32x4 d4) { return 4.f * d0 + (d4 - 5.f * d2); }
 __device__ __forceinline__ f32x4 w43_r5(f32x4 d1, f32x4 d3, f32x4 d5) { return 4.f * d1 + (d5 - 5.f * d3); }
@@ -113,69 +114,47 @@ __device__ __forceinline__ void w43_mfma_v(f32x16& c, float av, float bv) {
     asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
 }
 
-template <bool POOL, int TW, int TH, int NSUB, int PWS, int SPXS>
-__global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_wino43_kernel(Wino43Args a) {
-    constexpr int STILE = TW * TH, NTILE = NSUB * STILE, PW = 4 * TW + 2, PH = 4 * TH + 2, SPX = PW * PH, NPX = NSUB * SPX;
-    constexpr int NPXS = NSUB * SPXS;
-    constexpr int NST = (NPX * 2 + W4T - 1) / W4T;                   // float4 staging slots per thread (2 per pixel)
-    constexpr int RAWF = NPXS * 8 + 64;                              // floats per patch buffer (+ scratch for unused slots)
-    constexpr int VF = 36 * 32 * 8;                                  // floats per V buffer
-    constexpr int ZF = 36 * 32 * 32;                                 // epilogue image of one 32-channel half
-    constexpr int LDSF = (2 * RAWF + 2 * VF) > ZF ? (2 * RAWF + 2 * VF) : ZF;
+// ---------------------------------------------------------------------------------------------------------------------------
+// The phases conv3x3_wino43_kernel (four waves) and conv3x3_wino43d_kernel (eight) share, ONE copy each: the shape constants, the
+// staging slot table, the lane geometry of the transform and of the MFMA operands, the two-patch prologue, the accumulator image
+// and the output transform.  "The same LDS images, the same arithmetic in the same order, the same bits" is then what the text is,
+// not what two texts are kept to be.  Per kernel stay: the K loops, the unit ownership, the epilogue's barrier sequence and the
+// row / column arithmetic of the input transform (plain vector expressions on four waves, packed inline-asm forms on eight).
+
+// compile-time shape of a tile block: NSUB sub-blocks of TW x TH tiles; PWS / SPXS: pixel-slot strides of a patch row / a sub-block
+template <int TW_, int TH_, int NSUB_, int PWS_, int SPXS_>
+struct W43Shape {
+    static constexpr int TW = TW_, TH = TH_, NSUB = NSUB_, PWS = PWS_, SPXS = SPXS_;
+    static constexpr int STILE = TW * TH, NTILE = NSUB * STILE, PW = 4 * TW + 2, PH = 4 * TH + 2, SPX = PW * PH, NPX = NSUB * SPX;
+    static constexpr int NPXS = NSUB * SPXS;
+    static constexpr int NST = (NPX * 2 + 255) / 256;                // float4 staging slots per staging thread (2 per pixel; 256 threads stage: all four waves / the four T waves)
+    static constexpr int RAWF = NPXS * 8 + 64;                       // floats per patch buffer (+ scratch for unused slots)
+    static constexpr int VF = 36 * 32 * 8;                           // floats per V buffer
+    static constexpr int ZF = 36 * 32 * 32;                          // epilogue image of one 32-channel half
+    static constexpr int LDSF = (2 * RAWF + 2 * VF) > ZF ? (2 * RAWF + 2 * VF) : ZF;
     static_assert(NTILE == 32, "tile block = 32 MFMA rows");
     static_assert(LDSF * 4 + 512 <= 160 * 1024, "LDS");
-    __shared__ __attribute__((aligned(16))) float s_mem[LDSF];
-    __shared__ int s_sbf[NSUB], s_sby[NSUB], s_sbx[NSUB];
-    float* s_raw = s_mem;                    // [2][RAWF]
-    float* s_V = s_mem + 2 * RAWF;           // [2][VF]
+};
 
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
-    int cb, sp;
-    if (a.nCB >= 8) {
-        const int kN = a.nCB >> 3;
-        cb = (slot % kN) * 8 + xcd;
-        sp = slot / kN;
-    } else {
-        const int per = 8 / a.nCB;
-        cb = xcd % a.nCB;
-        sp = slot * per + xcd / a.nCB;
-    }
-    if (sp >= a.NS) return;
-    const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
-    if (tid < NSUB) {
-        const int sq = sp * NSUB + tid;
-        if (sq < a.NQ) {
-            const int bx = sq % a.bxN;
-            const int t1 = sq / a.bxN;
-            s_sbf[tid] = t1 / a.byN; s_sby[tid] = 4 * TH * (a.by0 + t1 % a.byN); s_sbx[tid] = 4 * TW * (a.bx0 + bx);
-        } else {
-            s_sbf[tid] = -1; s_sby[tid] = 0; s_sbx[tid] = 0;
-        }
-    }
-    __syncthreads();
+constexpr unsigned W43_OOB = 0x7ffffff0u;                            // source offset of a padding pixel: the buffer unit returns zeros
 
-    // ---- patch staging: NPX pixels x 2 float4 slots per K step through raw buffer loads: ONE resource per K step (its base
-    // advanced by the scalar unit) + a 32-bit byte offset per slot: no vector address arithmetic in the loop.  Padding
-    // pixels carry an out-of-range offset: the buffer unit returns zeros for them.  Slots beyond the patch store into a
-    // scratch area behind the image.
-    const int sq0 = sp * NSUB;
-    const int f0 = (sq0 / a.bxN) / a.byN;                              // first frame this workgroup touches (uniform)
-    const float* pin = a.in + (size_t)f0 * H * W * Cin;
-    const size_t in_left = ((size_t)(a.frames - f0) * H * W * Cin) * sizeof(float);
-    const unsigned in_bytes = (unsigned)(in_left < 0x40000000ull ? in_left : 0x40000000ull);
-    constexpr unsigned W43_OOB = 0x7ffffff0u;
-    unsigned soff[NST];
-    int dst[NST];                                                      // float4 units inside a patch buffer
+// Slot table of staging thread stid (0 .. 255): slot s = stid + 256 k = (patch pixel s >> 1, channel quad s & 1) -> byte offset of
+// its 16 bytes in the input (from frame f0, K step 0) and its float4 index in a patch buffer.  Padding pixels carry an
+// out-of-range offset; slots beyond the patch store into a scratch area behind the image.
+// INB: channel-blocked input.  PACK: offset and destination share one register (see conv3x3_wino43d_kernel).  CONTIG: ablation bit 5.
+template <class S, bool INB, bool PACK, bool CONTIG>
+__device__ __forceinline__ void w43_slot_table(const Wino43Args& a, int stid, int f0, const int* s_sbf, const int* s_sby, const int* s_sbx,
+                                               unsigned (&soff)[S::NST], int (&dst)[S::NST]) {
+    constexpr int TW = S::TW, PH = S::PH, PWS = S::PWS;
+    const int H = a.H, W = a.W, Cin = a.Cin;
 #pragma unroll
-    for (int k = 0; k < NST; ++k) {
-        const int s = tid + k * W4T;
+    for (int k = 0; k < S::NST; ++k) {
+        const int s = stid + k * 256;
         const int px = s >> 1, c4 = s & 1;
-        dst[k] = (NPXS * 8) / 4 + (tid & 15);                           // scratch behind the image
+        dst[k] = (S::NPXS * 8) / 4 + (stid & 15);                       // scratch behind the image
         soff[k] = W43_OOB;
-        if (px < NPX) {
-            const int q = px / SPX, lp = px - q * SPX;
+        if (px < S::NPX) {
+            const int q = px / S::SPX, lp = px - q * S::SPX;
             // lp -> (row, column) of the patch: the aligned 4-pixel segments first, then the 2-pixel row tails, two rows per
             // group of four, so that the eight lanes of a ds_write_b128 group (= 4 pixels) store to 32 different banks: a
             // segment is 128 contiguous bytes; two tails pair up when their rows are 4 bank slots apart mod 8 (rows r, r + 2
@@ -198,38 +177,204 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             const int fq = s_sbf[q];
             const int y = s_sby[q] - 1 + pr, x = s_sbx[q] - 1 + pc;
-            dst[k] = (q * SPXS + pr * PWS + 5 * (pc >> 2) + (pc & 3)) * 2 + c4;
+            dst[k] = (q * S::SPXS + pr * PWS + 5 * (pc >> 2) + (pc & 3)) * 2 + c4;
             if (fq >= 0 && y >= 0 && y < H && x >= 0 && x < W)
-                soff[k] = (unsigned)(((((size_t)(fq - f0) * H + y) * W + x) * Cin + c4 * 4) * sizeof(float));
+                soff[k] = INB ? (unsigned)((((((size_t)(fq - f0) * H + y) * (Cin >> 3)) * W + x) * 8 + c4 * 4) * sizeof(float))
+                              : (unsigned)(((((size_t)(fq - f0) * H + y) * W + x) * Cin + c4 * 4) * sizeof(float));
+        }
+        // ablation bit 5 (timing only, results wrong): the slots of a patch read CONTIGUOUS 16-byte pieces -- what a channel-blocked
+        // activation layout [C/8][H][W][8] would give the staging loads (an upper bound: also drops the halo overlap between patches)
+        if constexpr (CONTIG) soff[k] = (unsigned)(stid + k * 256) * 16u;
+        if constexpr (PACK) soff[k] = (soff[k] == W43_OOB ? 0xfffff000u : (soff[k] >> 4) << 12) | (unsigned)dst[k];
+    }
+}
+
+// ---- transform lane role: tile = lane >> 1, channel quad = lane & 1 -> wbase: floats, this lane's window in a patch buffer;
+// vwbase: floats, its 16 bytes of a V plane (+ plane * 256).
+// ds_read_b128 serves a wave in four NON-contiguous groups of sixteen lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, the same
+// + 32: MI355X_MICROARCH.md, LDS): in terms of the tile a lane pair works on, a group holds the tiles whose bits 1..3 have
+// even (odd) parity.  With 8 sub-blocks of 2x2 tiles (sub-block stride = 4 bank slots mod 16) that needs sub-block bit 2,
+// whose stride is 0 mod 16, on tile bit 3: lanes walk the tiles with bits 3 and 4 swapped (the others are conflict-free as
+// numbered).  Measured on conv3_2: conflict cycles of the window reads 169 M -> 0 per launch.
+template <class S>
+__device__ __forceinline__ void w43_transform_lane(int lane, int& wbase, int& vwbase) {
+    const int pt_u = lane >> 1, pt_c4 = lane & 1;
+    const int pt_tile = (S::TW == 2 && S::TH == 2 && S::NSUB == 8) ? ((pt_u & 7) | ((pt_u & 8) << 1) | ((pt_u & 16) >> 1)) : pt_u;
+    const int pt_q = pt_tile / S::STILE, pt_tl = pt_tile - pt_q * S::STILE;
+    const int pt_tr = pt_tl / S::TW, pt_tc = pt_tl - pt_tr * S::TW;
+    wbase = (pt_q * S::SPXS + 4 * pt_tr * S::PWS + 5 * pt_tc) * 8 + pt_c4 * 4;
+    vwbase = pt_tile * 8 + ((pt_c4 ^ ((pt_tile >> 3) & 1)) * 4);
+}
+// ---- MFMA lane role (mrow = lane & 31: tile row, kh = lane >> 5: K half): this lane's 16 bytes of the A operand of V plane
+// `plane` (floats inside a V buffer); the two halves of a row are swapped in every other group of eight rows
+__device__ __forceinline__ int w43_a_lane(int plane, int mrow, int kh) {
+    return plane * 256 + mrow * 8 + ((kh ^ ((mrow >> 3) & 1)) * 4);
+}
+
+// window element (aa, b) of a lane's tile (rw = patch buffer + wbase): patch row 4 tr + aa, column slot 5 tc + (0,1,2,3,5,6)[b];
+// the rows a task reads: ROLE 0, 1 (plane rows (1,2), (3,4)) rows 1..4, ROLE 2 (row 0) rows 0, 2, 4, ROLE 3 (row 5) rows 1, 3, 5
+template <int ROLE, int PWS>
+__device__ __forceinline__ void w43_window_reads(f32x4 (&D)[4], const float* rw, int b) {
+    constexpr int NR = ROLE <= 1 ? 4 : 3;
+#pragma unroll
+    for (int s = 0; s < NR; ++s) {
+        const int aa = ROLE <= 1 ? 1 + s : (ROLE == 2 ? 2 * s : 1 + 2 * s);
+        D[s] = *reinterpret_cast<const f32x4*>(rw + (aa * PWS + 5 * (b >> 2) + (b & 3)) * 8);
+    }
+}
+// which plane rows a task's row-transformed rows R1 (R2) become: tr_cols(vb, plane row, R) is the kernel's column pass
+template <int ROLE, class Cols>
+__device__ __forceinline__ void w43_tr_finish(Cols&& tr_cols, float* vb, const f32x4 (&R1)[6], const f32x4 (&R2)[6]) {
+    if constexpr (ROLE == 0) { tr_cols(vb, 1, R1); tr_cols(vb, 2, R2); }
+    else if constexpr (ROLE == 1) { tr_cols(vb, 3, R1); tr_cols(vb, 4, R2); }
+    else if constexpr (ROLE == 2) tr_cols(vb, 0, R1);
+    else tr_cols(vb, 5, R1);
+}
+
+// prologue of the K loop: patches 0 and 1 -> raw[0], raw[1] through the kernel's own stage_load(registers, K step) /
+// stage_store(registers, buffer).  Both patches are requested before either is stored: one HBM round trip, not two
+template <int NST, class Load, class Store>
+__device__ __forceinline__ void w43_stage_first_two(int n8, f32x4 (&stage)[NST], Load&& stage_load, Store&& stage_store) {
+    f32x4 stage1[NST];
+    stage_load(stage, 0);
+    stage_load(stage1, n8 > 1 ? 1 : 0);
+    stage_store(stage, 0);
+    stage_store(stage1, 1);
+}
+
+// ---- epilogue: Y = A^T M A, A^T = [[1,1,1,1,1,0],[0,1,-1,2,-2,0],[0,1,1,4,4,0],[0,1,-1,8,-8,1]], one 32-channel half at a time
+// through the image sZ[36 planes][32 tiles][32 channels].  One accumulator (plane, half) into the image (col = lane & 31, kh = lane >> 5):
+__device__ __forceinline__ void w43_z_store(float* sZ, const f32x16& v, int plane, int col, int kh) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = 4 * kh + (r & 3) + 8 * (r >> 2);
+        sZ[(plane * 32 + m) * 32 + col] = v[r];
+    }
+}
+// thread (tid & 255) = (tile m, four adjacent output channels) of half nb: 36 conflict-free ds_read_b128, A^T M A, bias, ReLU
+// (+ 2x2 pool inside the 4x4 tile), one float4 store per pixel.  (tid as it is and the mask in here: masked by the eight-wave
+// caller, its 2x2x8 instantiations spill one more register -- profiles/conv_shared_phases.txt)
+template <class S, bool POOL, bool OUTB>
+__device__ __forceinline__ void w43_out_transform(const Wino43Args& a, const float* sZ, const int* s_sbf, const int* s_sby, const int* s_sbx,
+                                                  int tid, int cb, int nb) {
+    const int H = a.H, W = a.W, Cout = a.Cout;
+    const int m = (tid & 255) >> 3, cq = tid & 7;
+    const int n = 64 * cb + 32 * nb + 4 * cq;
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + n);
+    const int mq = m / S::STILE, ml = m - mq * S::STILE;
+    const int f = s_sbf[mq];
+    if (f >= 0) {
+        const f32x4* zp = reinterpret_cast<const f32x4*>(sZ + m * 32 + 4 * cq);      // + plane * 256 float4
+        // column part: z[k][j] = sum_i AT[k][i] M[i][j]
+        f32x4 z[4][6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            f32x4 mm[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) mm[i] = zp[(i * 6 + j) * 256];
+            const f32x4 s12 = mm[1] + mm[2], d12 = mm[1] - mm[2], s34 = mm[3] + mm[4], d34 = mm[3] - mm[4];
+            z[0][j] = mm[0] + s12 + s34;
+            z[1][j] = d12 + 2.f * d34;
+            z[2][j] = s12 + 4.f * s34;
+            z[3][j] = d12 + 8.f * d34 + mm[5];
+        }
+        f32x4 y[4][4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x4 s12 = z[k][1] + z[k][2], d12 = z[k][1] - z[k][2], s34 = z[k][3] + z[k][4], d34 = z[k][3] - z[k][4];
+            y[k][0] = z[k][0] + s12 + s34;
+            y[k][1] = d12 + 2.f * d34;
+            y[k][2] = s12 + 4.f * s34;
+            y[k][3] = d12 + 8.f * d34 + z[k][5];
+        }
+        const int tr = ml / S::TW, tc = ml - tr * S::TW;
+        const int oy = s_sby[mq] + 4 * tr, ox = s_sbx[mq] + 4 * tc;
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        // output addressing: NHWC [f][y][x][Cout], or channel-blocked per image row [f][y][Cout / 8][x][8] (n is a multiple of 4)
+        const int Ho = POOL ? (H >> 1) : H, Wo = POOL ? (W >> 1) : W;
+        const size_t xstep = OUTB ? 8 : (size_t)Cout, ystep = (size_t)Cout * Wo;
+        float* const obase = OUTB ? a.out + (size_t)f * Cout * Ho * Wo + (size_t)(n >> 3) * Wo * 8 + (n & 7)
+                                  : a.out + (size_t)f * Cout * Ho * Wo + n;
+        if constexpr (POOL) {
+            float* op = obase + (size_t)(oy >> 1) * ystep + (size_t)(ox >> 1) * xstep;
+#pragma unroll
+            for (int aa = 0; aa < 2; ++aa)
+#pragma unroll
+                for (int b = 0; b < 2; ++b) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        v[e] = fmaxf(fmaxf(y[2 * aa][2 * b][e], y[2 * aa][2 * b + 1][e]), fmaxf(y[2 * aa + 1][2 * b][e], y[2 * aa + 1][2 * b + 1][e]));
+                    v = v + bv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
+                    // blocked output: a lane pair writes 32 bytes of a 128-byte line that the next three stores complete --
+                    // plain stores (L2 merges the line); non-temporal ones would go out as four partial writes
+                    if constexpr (OUTB) *reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep) = v;
+                    else W43_STORE(reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep), v);
+                }
+        } else {
+            float* op = obase + (size_t)oy * ystep + (size_t)ox * xstep;
+#pragma unroll
+            for (int aa = 0; aa < 4; ++aa)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    f32x4 v = y[aa][b] + bv;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
+                    if constexpr (OUTB) *reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep) = v;
+                    else W43_STORE(reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep), v);
+                }
         }
     }
+}
+
+template <bool POOL, int TW, int TH, int NSUB, int PWS, int SPXS>
+__global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv3x3_wino43_kernel(Wino43Args a) {
+    using S = W43Shape<TW, TH, NSUB, PWS, SPXS>;
+    constexpr int NST = S::NST, RAWF = S::RAWF, VF = S::VF;
+    __shared__ __attribute__((aligned(16))) float s_mem[S::LDSF];
+    __shared__ int s_sbf[NSUB], s_sby[NSUB], s_sbx[NSUB];
+    float* s_raw = s_mem;                    // [2][RAWF]
+    float* s_V = s_mem + 2 * RAWF;           // [2][VF]
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int cb, sp;
+    conv_tile_wg(blockIdx.x, a.nCB, cb, sp);
+    if (sp >= a.NS) return;
+    const int H = a.H, W = a.W, Cin = a.Cin;
+    conv_tile_subblocks<NSUB>(s_sbf, s_sby, s_sbx, tid, sp, a.NQ, a.bxN, a.byN, 4 * TH, 4 * TW, a.by0, a.bx0);
+    __syncthreads();
+
+    // ---- patch staging: NPX pixels x 2 float4 slots per K step through raw buffer loads: ONE resource per K step (its base
+    // advanced by the scalar unit) + a 32-bit byte offset per slot: no vector address arithmetic in the loop.  Padding
+    // pixels carry an out-of-range offset: the buffer unit returns zeros for them.  Slots beyond the patch store into a
+    // scratch area behind the image.
+    const int sq0 = sp * NSUB;
+    const int f0 = (sq0 / a.bxN) / a.byN;                              // first frame this workgroup touches (uniform)
+    const float* pin = a.in + (size_t)f0 * H * W * Cin;
+    const size_t in_left = ((size_t)(a.frames - f0) * H * W * Cin) * sizeof(float);
+    const unsigned in_bytes = (unsigned)(in_left < 0x40000000ull ? in_left : 0x40000000ull);
+    unsigned soff[NST];
+    int dst[NST];                                                      // float4 units inside a patch buffer
+    w43_slot_table<S, false, false, false>(a, tid, f0, s_sbf, s_sby, s_sbx, soff, dst);
     f32x4 stage[NST];
-    auto stage_load = [&](int cs) {                                    // K step cs: channels 8 cs .. 8 cs + 7
+    auto stage_load = [&](f32x4 (&st)[NST], int cs) {                  // K step cs: channels 8 cs .. 8 cs + 7
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pin + cs * 8), 0, (int)(in_bytes - cs * 32), 0x00020000);
 #pragma unroll
-        for (int k = 0; k < NST; ++k) stage[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, soff[k], 0, W43_STAGE_AUX));
+        for (int k = 0; k < NST; ++k) st[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, soff[k], 0, W43_STAGE_AUX));
     };
-    auto stage_store = [&](int buf) {
+    auto stage_store = [&](const f32x4 (&st)[NST], int buf) {
         f32x4* rb = reinterpret_cast<f32x4*>(s_raw + buf * RAWF);
 #pragma unroll
-        for (int k = 0; k < NST; ++k) rb[dst[k]] = stage[k];
+        for (int k = 0; k < NST; ++k) rb[dst[k]] = st[k];
     };
 
-    // ---- transform lane role: tile = lane >> 1, channel quad = lane & 1
-    // ds_read_b128 serves a wave in four NON-contiguous groups of sixteen lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31}, the same
-    // + 32: MI355X_MICROARCH.md, LDS): in terms of the tile a lane pair works on, a group holds the tiles whose bits 1..3 have
-    // even (odd) parity.  With 8 sub-blocks of 2x2 tiles (sub-block stride = 4 bank slots mod 16) that needs sub-block bit 2,
-    // whose stride is 0 mod 16, on tile bit 3: lanes walk the tiles with bits 3 and 4 swapped (the others are conflict-free as
-    // numbered).  Measured on conv3_2: conflict cycles of the window reads 169 M -> 0 per launch.
-    const int pt_u = lane >> 1, pt_c4 = lane & 1;
-    const int pt_tile = (TW == 2 && TH == 2 && NSUB == 8) ? ((pt_u & 7) | ((pt_u & 8) << 1) | ((pt_u & 16) >> 1)) : pt_u;
-    const int pt_q = pt_tile / STILE, pt_tl = pt_tile - pt_q * STILE;
-    const int pt_tr = pt_tl / TW, pt_tc = pt_tl - pt_tr * TW;
-    const int wbase = (pt_q * SPXS + 4 * pt_tr * PWS + 5 * pt_tc) * 8 + pt_c4 * 4;                  // floats
-    const int vwbase = pt_tile * 8 + ((pt_c4 ^ ((pt_tile >> 3) & 1)) * 4);                          // floats, + plane * 256
-    // ---- MFMA lane role
+    int wbase, vwbase;                                                 // transform lane role (floats; vwbase + plane * 256)
+    w43_transform_lane<S>(lane, wbase, vwbase);
     const int mrow = lane & 31, kh = lane >> 5;
-    const int vabase = wave * 9 * 256 + mrow * 8 + ((kh ^ ((mrow >> 3) & 1)) * 4);                   // floats, + j * 256
+    const int vabase = w43_a_lane(9 * wave, mrow, kh);                     // MFMA lane role (floats, + j * 256)
     const int n8 = Cin / 8;
 
     // planes 0..7 (accumulation registers), plane 8 (VGPRs, w43_mfma_v).  Work balance: the two waves with the heavy transform
@@ -258,16 +403,8 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #endif
     auto k_loop = [&](auto role_c) {
         constexpr int ROLE = decltype(role_c)::value;
-        constexpr int NR = ROLE <= 1 ? 4 : 3;                       // window rows the task reads
         f32x4 D[4], R1[6], R2[6];
-        // window element (aa, b) of this lane's tile: patch row 4 tr + aa, column slot 5 tc + (0,1,2,3,5,6)[b]
-        auto tr_reads = [&](const float* rp, int b) {
-#pragma unroll
-            for (int s = 0; s < NR; ++s) {
-                const int aa = ROLE <= 1 ? 1 + s : (ROLE == 2 ? 2 * s : 1 + 2 * s);
-                D[s] = *reinterpret_cast<const f32x4*>(rp + wbase + (aa * PWS + 5 * (b >> 2) + (b & 3)) * 8);
-            }
-        };
+        auto tr_reads = [&](const float* rp, int b) { w43_window_reads<ROLE, PWS>(D, rp + wbase, b); };
         auto tr_rows = [&](int b) {
             if constexpr (ROLE == 0) {                          // rows 1, 2:  (d4 - 4 d2) +- (d3 - 4 d1)
                 const f32x4 t1 = D[3] - 4.f * D[1], t2 = D[2] - 4.f * D[0];
@@ -293,28 +430,11 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             *reinterpret_cast<f32x4*>(o + 4 * 256) = t3 - 2.f * u;
             *reinterpret_cast<f32x4*>(o + 5 * 256) = w43_r5(R[1], R[3], R[5]);
         };
-        auto tr_finish = [&](float* vb) {
-            if constexpr (ROLE == 0) { tr_cols(vb, 1, R1); tr_cols(vb, 2, R2); }
-            else if constexpr (ROLE == 1) { tr_cols(vb, 3, R1); tr_cols(vb, 4, R2); }
-            else if constexpr (ROLE == 2) tr_cols(vb, 0, R1);
-            else tr_cols(vb, 5, R1);
-        };
+        auto tr_finish = [&](float* vb) { w43_tr_finish<ROLE>(tr_cols, vb, R1, R2); };
 
         // prologue: patches 0 and 1 -> raw[0], raw[1]; patch 0 transformed -> V[0]; U of the first plane group requested
         W43_STAMP(16);
-        {
-            // both patches are requested before either is stored: one HBM round trip, not two
-            f32x4 stage1[NST];
-            const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pin + (n8 > 1 ? 8 : 0)), 0,
-                                                                                   (int)(in_bytes - (n8 > 1 ? 32 : 0)), 0x00020000);
-            stage_load(0);
-#pragma unroll
-            for (int k = 0; k < NST; ++k) stage1[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, soff[k], 0, W43_STAGE_AUX));
-            stage_store(0);
-            f32x4* rb1 = reinterpret_cast<f32x4*>(s_raw + RAWF);
-#pragma unroll
-            for (int k = 0; k < NST; ++k) rb1[dst[k]] = stage1[k];
-        }
+        w43_stage_first_two(n8, stage, stage_load, stage_store);
         __syncthreads();
         W43_STAMP(17);
 #pragma unroll
@@ -363,7 +483,7 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             if (!DONOR && g == 2) Bx[set] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, uxlane, c * 73728, 0));
         };
-        const int vxbase = (9 * (ROLE & 1) + 8) * 256 + mrow * 8 + ((kh ^ ((mrow >> 3) & 1)) * 4);      // the donated plane's A operand
+        const int vxbase = w43_a_lane(9 * (ROLE & 1) + 8, mrow, kh);         // the donated plane's A operand
         load_B(0, 0, 0);
         W43_STAMP(18);
 
@@ -383,7 +503,7 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             // the previous K step's last twelve MFMAs (its group 2 sits in A set PAR ^ 1 and B set PAR ^ 1)
             if (PAR == 1 || c8 > 0) {
                 __builtin_amdgcn_sched_barrier(0);
-                mfma_half(ic<2>{}, ic<1>{}, ic<PAR ^ 1>{}, ic<PAR ^ 1>{});
+                mfma_half(ntk_ic<2>{}, ntk_ic<1>{}, ntk_ic<PAR ^ 1>{}, ntk_ic<PAR ^ 1>{});
                 __builtin_amdgcn_sched_barrier(0);
             }
             // A set PAR ^ 1 is free now: group 1's operands are requested a whole group ahead (the groups alternate between
@@ -394,7 +514,7 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int g = 0; g < 3; ++g) {
                 const int bs = (PAR + g) & 1;
                 if constexpr (!(W43_ABL & 1)) { if (g < 2) load_B(c8, g + 1, bs ^ 1); else load_B(cn, 0, bs ^ 1); }
-                if constexpr (!(W43_ABL & 4)) if (g == 0) stage_load(cs);
+                if constexpr (!(W43_ABL & 4)) if (g == 0) stage_load(stage, cs);
                 W43_STAMP(1);
                 // a plane group's 24 MFMAs in two halves (K pairs 0-1, 2-3) with one of the gap's two transform columns
                 // after each: the window reads of a column get 12 MFMAs (768 cycles) of cover -- with one wave per SIMD a
@@ -403,11 +523,11 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 for (int half = 0; half < 2; ++half) {
                     __builtin_amdgcn_sched_barrier(0);
                     if (!(g == 2 && half == 1)) {                   // (2, 1) is issued at the top of the next K step
-                        if (g == 0 && half == 0) mfma_half(ic<0>{}, ic<0>{}, ic<PAR>{}, ic<PAR>{});
-                        if (g == 0 && half == 1) mfma_half(ic<0>{}, ic<1>{}, ic<PAR>{}, ic<PAR>{});
-                        if (g == 1 && half == 0) mfma_half(ic<1>{}, ic<0>{}, ic<PAR ^ 1>{}, ic<PAR ^ 1>{});
-                        if (g == 1 && half == 1) mfma_half(ic<1>{}, ic<1>{}, ic<PAR ^ 1>{}, ic<PAR ^ 1>{});
-                        if (g == 2 && half == 0) mfma_half(ic<2>{}, ic<0>{}, ic<PAR>{}, ic<PAR>{});
+                        if (g == 0 && half == 0) mfma_half(ntk_ic<0>{}, ntk_ic<0>{}, ntk_ic<PAR>{}, ntk_ic<PAR>{});
+                        if (g == 0 && half == 1) mfma_half(ntk_ic<0>{}, ntk_ic<1>{}, ntk_ic<PAR>{}, ntk_ic<PAR>{});
+                        if (g == 1 && half == 0) mfma_half(ntk_ic<1>{}, ntk_ic<0>{}, ntk_ic<PAR ^ 1>{}, ntk_ic<PAR ^ 1>{});
+                        if (g == 1 && half == 1) mfma_half(ntk_ic<1>{}, ntk_ic<1>{}, ntk_ic<PAR ^ 1>{}, ntk_ic<PAR ^ 1>{});
+                        if (g == 2 && half == 0) mfma_half(ntk_ic<2>{}, ntk_ic<0>{}, ntk_ic<PAR>{}, ntk_ic<PAR>{});
                     }
                     __builtin_amdgcn_sched_barrier(0);
                     W43_STAMP(2 + 4 * g + 2 * half);
@@ -423,7 +543,7 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                             for (int pl = 0; pl < 3; ++pl) if constexpr (!(W43_ABL & 16)) As[PAR][pl] = *reinterpret_cast<const f32x4*>(vcur + (6 + pl) * 256);
                             if constexpr (!DONOR && !(W43_ABL & 16)) Axs[PAR] = *reinterpret_cast<const f32x4*>(s_V + PAR * VF + vxbase);
                         } else if (g == 2) {
-                            if constexpr (!(W43_ABL & 4)) stage_store(PAR);
+                            if constexpr (!(W43_ABL & 4)) stage_store(stage, PAR);
                         }
                         if constexpr (!(W43_ABL & 2)) {
                             tr_rows(2 * g + 1);
@@ -436,22 +556,21 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         };
         for (int c8 = 0; c8 < n8; c8 += 2) {
-            k_step(c8, ic<0>{});
-            k_step(c8 + 1, ic<1>{});
+            k_step(c8, ntk_ic<0>{});
+            k_step(c8 + 1, ntk_ic<1>{});
         }
-        mfma_half(ic<2>{}, ic<1>{}, ic<1>{}, ic<1>{});             // the last K step's (odd parity: n8 is even) deferred MFMAs
+        mfma_half(ntk_ic<2>{}, ntk_ic<1>{}, ntk_ic<1>{}, ntk_ic<1>{});             // the last K step's (odd parity: n8 is even) deferred MFMAs
     };
-    if (wave == 0) k_loop(ic<0>{});
-    else if (wave == 1) k_loop(ic<1>{});
-    else if (wave == 2) k_loop(ic<2>{});
-    else k_loop(ic<3>{});
+    if (wave == 0) k_loop(ntk_ic<0>{});
+    else if (wave == 1) k_loop(ntk_ic<1>{});
+    else if (wave == 2) k_loop(ntk_ic<2>{});
+    else k_loop(ntk_ic<3>{});
 
 #ifdef NTK_CL_PROF
     W43_STAMP(15);
 #endif
-    // ---- epilogue: Y = A^T M A, A^T = [[1,1,1,1,1,0],[0,1,-1,2,-2,0],[0,1,1,4,4,0],[0,1,-1,8,-8,1]]
+    // ---- epilogue (w43_z_store, w43_out_transform)
     float* sZ = s_mem;                                   // [36][32 tiles][32 channels]
-    const int col = lane & 31;
     // the asm-form MFMAs (the last instructions of the K loop) have written their results before anything reads them: a
     // 16-pass MFMA needs 18 passes of distance to a dependent VALU / LDS instruction
     asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
@@ -462,84 +581,13 @@ __global__ __launch_bounds__(W4T) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
             if (j == 8 && nb == 1 && wave < 2) continue;            // that unit was accumulated by wave + 2 (accx)
-            const f32x16 v = j < 8 ? (nb == 0 ? acc[j][0] : acc[j][1]) : (nb == 0 ? accv[0] : accv[1]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = 4 * kh + (r & 3) + 8 * (r >> 2);
-                sZ[((9 * wave + j) * 32 + m) * 32 + col] = v[r];
-            }
+            w43_z_store(sZ, j < 8 ? (nb == 0 ? acc[j][0] : acc[j][1]) : (nb == 0 ? accv[0] : accv[1]), 9 * wave + j, mrow, kh);
         }
-        if (nb == 1 && wave >= 2) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = 4 * kh + (r & 3) + 8 * (r >> 2);
-                sZ[((9 * (wave - 2) + 8) * 32 + m) * 32 + col] = accx[r];
-            }
-        }
+        if (nb == 1 && wave >= 2) w43_z_store(sZ, accx, 9 * (wave - 2) + 8, mrow, kh);
         W43_STAMP(20);
         __syncthreads();
         W43_STAMP(21);
-        // thread = (tile m, four adjacent output channels): 36 conflict-free ds_read_b128, one float4 store per pixel
-        const int m = tid >> 3, cq = tid & 7;
-        const int n = 64 * cb + 32 * nb + 4 * cq;
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + n);
-        const int mq = m / STILE, ml = m - mq * STILE;
-        const int f = s_sbf[mq];
-        if (f >= 0) {
-            const f32x4* zp = reinterpret_cast<const f32x4*>(sZ + m * 32 + 4 * cq);      // + plane * 256 float4
-            // column part: z[k][j] = sum_i AT[k][i] M[i][j]
-            f32x4 z[4][6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                f32x4 mm[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) mm[i] = zp[(i * 6 + j) * 256];
-                const f32x4 s12 = mm[1] + mm[2], d12 = mm[1] - mm[2], s34 = mm[3] + mm[4], d34 = mm[3] - mm[4];
-                z[0][j] = mm[0] + s12 + s34;
-                z[1][j] = d12 + 2.f * d34;
-                z[2][j] = s12 + 4.f * s34;
-                z[3][j] = d12 + 8.f * d34 + mm[5];
-            }
-            f32x4 y[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 s12 = z[k][1] + z[k][2], d12 = z[k][1] - z[k][2], s34 = z[k][3] + z[k][4], d34 = z[k][3] - z[k][4];
-                y[k][0] = z[k][0] + s12 + s34;
-                y[k][1] = d12 + 2.f * d34;
-                y[k][2] = s12 + 4.f * s34;
-                y[k][3] = d12 + 8.f * d34 + z[k][5];
-            }
-            const int tr = ml / TW, tc = ml - tr * TW;
-            const int oy = s_sby[mq] + 4 * tr, ox = s_sbx[mq] + 4 * tc;
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            if constexpr (POOL) {
-                float* op = a.out + (((size_t)f * (H >> 1) + (oy >> 1)) * (W >> 1) + (ox >> 1)) * Cout + n;
-#pragma unroll
-                for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            v[e] = fmaxf(fmaxf(y[2 * aa][2 * b][e], y[2 * aa][2 * b + 1][e]), fmaxf(y[2 * aa + 1][2 * b][e], y[2 * aa + 1][2 * b + 1][e]));
-                        v = v + bv;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
-                        W43_STORE(reinterpret_cast<f32x4*>(op + ((size_t)aa * (W >> 1) + b) * Cout), v);
-                    }
-            } else {
-                float* op = a.out + (((size_t)f * H + oy) * W + ox) * Cout + n;
-#pragma unroll
-                for (int aa = 0; aa < 4; ++aa)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        f32x4 v = y[aa][b] + bv;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
-                        W43_STORE(reinterpret_cast<f32x4*>(op + ((size_t)aa * W + b) * Cout), v);
-                    }
-            }
-        }
+        w43_out_transform<S, POOL, false>(a, sZ, s_sbf, s_sby, s_sbx, tid, cb, nb);
         W43_STAMP(22);
     }
 #ifdef NTK_CL_PROF
@@ -607,19 +655,12 @@ __device__ unsigned long long g_w43d_prof[8][12];
 // conv1_1 itself stays NHWC: its store-bound row kernel is 0.45 - 0.7 ms slower writing eight 1 KB runs per wave.)
 template <bool POOL, int TW, int TH, int NSUB, int PWS, int SPXS, bool INB = false, bool OUTB = false>
 __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_wino43d_kernel(Wino43Args a) {
-    constexpr int STILE = TW * TH, NTILE = NSUB * STILE, PW = 4 * TW + 2, PH = 4 * TH + 2, SPX = PW * PH, NPX = NSUB * SPX;
-    constexpr int NPXS = NSUB * SPXS;
-    constexpr int NST = (NPX * 2 + 255) / 256;                       // float4 staging slots per thread of the four S waves
+    using S = W43Shape<TW, TH, NSUB, PWS, SPXS>;
+    constexpr int NST = S::NST, RAWF = S::RAWF, VF = S::VF;
     // many slots per thread (the 1x1x32 shape: 9): a slot's source offset and LDS destination share ONE register -- destination
     // (float4 units, < 4096) in the low 12 bits, source offset / 16 above it (the host checks that a block's input span is below 16 MB)
     constexpr bool PACK = NST > 7;
-    constexpr int RAWF = NPXS * 8 + 64;
-    constexpr int VF = 36 * 32 * 8;
-    constexpr int ZF = 36 * 32 * 32;
-    constexpr int LDSF = (2 * RAWF + 2 * VF) > ZF ? (2 * RAWF + 2 * VF) : ZF;
-    static_assert(NTILE == 32, "tile block = 32 MFMA rows");
-    static_assert(LDSF * 4 + 512 <= 160 * 1024, "LDS");
-    __shared__ __attribute__((aligned(16))) float s_mem[LDSF];
+    __shared__ __attribute__((aligned(16))) float s_mem[S::LDSF];
     __shared__ int s_sbf[NSUB], s_sby[NSUB], s_sbx[NSUB];
     float* s_raw = s_mem;                    // [2][RAWF]
     float* s_V = s_mem + 2 * RAWF;           // [2][VF]
@@ -627,29 +668,11 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pg = wave & 3;                                           // plane group (= SIMD)
-    const int id = blockIdx.x, xcd = id & 7, slot = id >> 3;
     int cb, sp;
-    if (a.nCB >= 8) {
-        const int kN = a.nCB >> 3;
-        cb = (slot % kN) * 8 + xcd;
-        sp = slot / kN;
-    } else {
-        const int per = 8 / a.nCB;
-        cb = xcd % a.nCB;
-        sp = slot * per + xcd / a.nCB;
-    }
+    conv_tile_wg(blockIdx.x, a.nCB, cb, sp);
     if (sp >= a.NS) return;
-    const int H = a.H, W = a.W, Cin = a.Cin, Cout = a.Cout;
-    if (tid < NSUB) {
-        const int sq = sp * NSUB + tid;
-        if (sq < a.NQ) {
-            const int bx = sq % a.bxN;
-            const int t1 = sq / a.bxN;
-            s_sbf[tid] = t1 / a.byN; s_sby[tid] = 4 * TH * (a.by0 + t1 % a.byN); s_sbx[tid] = 4 * TW * (a.bx0 + bx);
-        } else {
-            s_sbf[tid] = -1; s_sby[tid] = 0; s_sbx[tid] = 0;
-        }
-    }
+    const int H = a.H, W = a.W, Cin = a.Cin;
+    conv_tile_subblocks<NSUB>(s_sbf, s_sby, s_sbx, tid, sp, a.NQ, a.bxN, a.byN, 4 * TH, 4 * TW, a.by0, a.bx0);
     __syncthreads();
 
     const int sq0 = sp * NSUB;
@@ -657,53 +680,12 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const float* pin = a.in + (size_t)f0 * H * W * Cin;
     const size_t in_left = ((size_t)(a.frames - f0) * H * W * Cin) * sizeof(float);
     const unsigned in_bytes = (unsigned)(in_left < 0x40000000ull ? in_left : 0x40000000ull);
-    constexpr unsigned W43_OOB = 0x7ffffff0u;
     const int n8 = Cin / 8, n8m1 = n8 - 1;
 #ifdef NTK_CL_PROF
     const bool prof_on = blockIdx.x == 1000 && lane == 0;
     unsigned long long prof_acc[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, prof_last = __builtin_amdgcn_s_memtime();
 #endif
 
-    // slot table of a staging thread (stid = tid & 255): as in conv3x3_wino43_kernel
-    auto slot_table = [&](unsigned (&soff)[NST], int (&dst)[NST]) {
-        const int stid = tid & 255;
-#pragma unroll
-        for (int k = 0; k < NST; ++k) {
-            const int s = stid + k * 256;
-            const int px = s >> 1, c4 = s & 1;
-            dst[k] = (NPXS * 8) / 4 + (stid & 15);
-            soff[k] = W43_OOB;
-            if (px < NPX) {
-                const int q = px / SPX, lp = px - q * SPX;
-                constexpr int NFULL = PH * TW * 4;
-                int pr, pc;
-                if (lp < NFULL) {
-                    const int seg = lp >> 2;
-                    pr = seg / TW;
-                    pc = 4 * (seg - pr * TW) + (lp & 3);
-                } else {
-                    const int h = lp - NFULL, ri = h >> 1;
-                    pr = ri;
-                    if (PWS & 1) {
-                        const int w = ri & 3;
-                        const int r = (ri & ~3) + (w == 1 ? 2 : w == 2 ? 1 : w);
-                        if (r < PH) pr = r;
-                    }
-                    pc = 4 * TW + (h & 1);
-                }
-                const int fq = s_sbf[q];
-                const int y = s_sby[q] - 1 + pr, x = s_sbx[q] - 1 + pc;
-                dst[k] = (q * SPXS + pr * PWS + 5 * (pc >> 2) + (pc & 3)) * 2 + c4;
-                if (fq >= 0 && y >= 0 && y < H && x >= 0 && x < W)
-                    soff[k] = INB ? (unsigned)((((((size_t)(fq - f0) * H + y) * (Cin >> 3)) * W + x) * 8 + c4 * 4) * sizeof(float))
-                                  : (unsigned)(((((size_t)(fq - f0) * H + y) * W + x) * Cin + c4 * 4) * sizeof(float));
-            }
-            // ablation bit 5 (timing only, results wrong): the slots of a patch read CONTIGUOUS 16-byte pieces -- what a channel-blocked
-            // activation layout [C/8][H][W][8] would give the staging loads (an upper bound: also drops the halo overlap between patches)
-            if constexpr ((W43_ABL & 32) != 0) soff[k] = (unsigned)(stid + k * 256) * 16u;
-            if constexpr (PACK) soff[k] = (soff[k] == W43_OOB ? 0xfffff000u : (soff[k] >> 4) << 12) | (unsigned)dst[k];
-        }
-    };
     auto slot_src = [&](unsigned w) { return PACK ? ((w >> 8) & ~15u) : w; };
     const unsigned in_window = PACK ? (in_bytes < 0xfffff0u ? in_bytes : 0xfffff0u) : in_bytes;     // the out-of-range marker must stay out of range
 
@@ -711,7 +693,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     //   T waves own units (0..4, 0), waves 2, 3 also (5, 0) and unit (5, 0) of waves 0, 1: 5 / 7 x 16 accumulators;
     //   S waves own units (0..8, 1) and (6..8, 0): 12 x 16 accumulators, 48 MFMAs per K step.
     const int mrow = lane & 31, kh = lane >> 5;
-    const int vabase = pg * 9 * 256 + mrow * 8 + ((kh ^ ((mrow >> 3) & 1)) * 4);                    // floats, + j * 256
+    const int vabase = w43_a_lane(9 * pg, mrow, kh);                                                    // floats, + j * 256
     f32x16 acc[12];
     const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(a.U + (size_t)cb * n8 * 18432), 0, (int)((size_t)n8 * 18432 * sizeof(float)), 0x00020000);
@@ -730,85 +712,8 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     // half 1 by the S waves.  thread = (tile, four adjacent channels)
     float* sZ = s_mem;
     const int col = lane & 31;
-    auto z_store = [&](const f32x16& v, int plane) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = 4 * kh + (r & 3) + 8 * (r >> 2);
-            sZ[((9 * pg + plane) * 32 + m) * 32 + col] = v[r];
-        }
-    };
-    auto out_transform = [&](auto nb_c) {
-        constexpr int nb = decltype(nb_c)::value;
-        const int et = tid & 255;
-        const int m = et >> 3, cq = et & 7;
-        const int n = 64 * cb + 32 * nb + 4 * cq;
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + n);
-        const int mq = m / STILE, ml = m - mq * STILE;
-        const int f = s_sbf[mq];
-        if (f >= 0) {
-            const f32x4* zp = reinterpret_cast<const f32x4*>(sZ + m * 32 + 4 * cq);
-            f32x4 z[4][6];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                f32x4 mm[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) mm[i] = zp[(i * 6 + j) * 256];
-                const f32x4 s12 = mm[1] + mm[2], d12 = mm[1] - mm[2], s34 = mm[3] + mm[4], d34 = mm[3] - mm[4];
-                z[0][j] = mm[0] + s12 + s34;
-                z[1][j] = d12 + 2.f * d34;
-                z[2][j] = s12 + 4.f * s34;
-                z[3][j] = d12 + 8.f * d34 + mm[5];
-            }
-            f32x4 y[4][4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const f32x4 s12 = z[k][1] + z[k][2], d12 = z[k][1] - z[k][2], s34 = z[k][3] + z[k][4], d34 = z[k][3] - z[k][4];
-                y[k][0] = z[k][0] + s12 + s34;
-                y[k][1] = d12 + 2.f * d34;
-                y[k][2] = s12 + 4.f * s34;
-                y[k][3] = d12 + 8.f * d34 + z[k][5];
-            }
-            const int tr = ml / TW, tc = ml - tr * TW;
-            const int oy = s_sby[mq] + 4 * tr, ox = s_sbx[mq] + 4 * tc;
-            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-            // output addressing: NHWC [f][y][x][Cout], or channel-blocked [f][Cout / 8][y][x][8] (n is a multiple of 4)
-            const int Ho = POOL ? (H >> 1) : H, Wo = POOL ? (W >> 1) : W;
-            const size_t xstep = OUTB ? 8 : (size_t)Cout, ystep = (size_t)Cout * Wo;
-            float* const obase = OUTB ? a.out + (size_t)f * Cout * Ho * Wo + (size_t)(n >> 3) * Wo * 8 + (n & 7)
-                                      : a.out + (size_t)f * Cout * Ho * Wo + n;
-            if constexpr (POOL) {
-                float* op = obase + (size_t)(oy >> 1) * ystep + (size_t)(ox >> 1) * xstep;
-#pragma unroll
-                for (int aa = 0; aa < 2; ++aa)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b) {
-                        f32x4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            v[e] = fmaxf(fmaxf(y[2 * aa][2 * b][e], y[2 * aa][2 * b + 1][e]), fmaxf(y[2 * aa + 1][2 * b][e], y[2 * aa + 1][2 * b + 1][e]));
-                        v = v + bv;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
-                        // blocked output: a lane pair writes 32 bytes of a 128-byte line that the next three stores complete --
-                        // plain stores (L2 merges the line); non-temporal ones would go out as four partial writes
-                        if constexpr (OUTB) *reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep) = v;
-                        else W43_STORE(reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep), v);
-                    }
-            } else {
-                float* op = obase + (size_t)oy * ystep + (size_t)ox * xstep;
-#pragma unroll
-                for (int aa = 0; aa < 4; ++aa)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        f32x4 v = y[aa][b] + bv;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], zero[e]);
-                        if constexpr (OUTB) *reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep) = v;
-                        else W43_STORE(reinterpret_cast<f32x4*>(op + (size_t)aa * ystep + (size_t)b * xstep), v);
-                    }
-            }
-        }
-    };
+    auto z_store = [&](const f32x16& v, int plane) { w43_z_store(sZ, v, 9 * pg + plane, col, kh); };
+    auto out_transform = [&](int nb) { w43_out_transform<S, POOL, OUTB>(a, sZ, s_sbf, s_sby, s_sbx, tid, cb, nb); };
 #define W43D_MFMA(C, A, B) C = __builtin_amdgcn_mfma_f32_32x32x2f32(A, B, C, 0, 0, 0)
 
     if (wave < 4) {
@@ -817,50 +722,28 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int j = 0; j < 7; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-        const int pt_u = lane >> 1, pt_c4 = lane & 1;
-        const int pt_tile = (TW == 2 && TH == 2 && NSUB == 8) ? ((pt_u & 7) | ((pt_u & 8) << 1) | ((pt_u & 16) >> 1)) : pt_u;
-        const int pt_q = pt_tile / STILE, pt_tl = pt_tile - pt_q * STILE;
-        const int pt_tr = pt_tl / TW, pt_tc = pt_tl - pt_tr * TW;
-        const int wbase = (pt_q * SPXS + 4 * pt_tr * PWS + 5 * pt_tc) * 8 + pt_c4 * 4;
-        const int vwbase = pt_tile * 8 + ((pt_c4 ^ ((pt_tile >> 3) & 1)) * 4);
+        int wbase, vwbase;
+        w43_transform_lane<S>(lane, wbase, vwbase);
         unsigned soff[NST]; int dst[NST];
-        slot_table(soff, dst);
+        w43_slot_table<S, INB, PACK, (W43_ABL & 32) != 0>(a, tid & 255, f0, s_sbf, s_sby, s_sbx, soff, dst);
         f32x4 stage[NST];
         const int kstep_floats = INB ? W * 8 : 8;                    // one K step further: the next channel block of the image row / the next 8 channels of a pixel
-        auto stage_load = [&](int cs) {
+        auto stage_load = [&](f32x4 (&st)[NST], int cs) {
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pin + (size_t)cs * kstep_floats), 0,
                                                                                   (int)(in_window - (unsigned)cs * (unsigned)kstep_floats * 4u), 0x00020000);
 #pragma unroll
-            for (int k = 0; k < NST; ++k) stage[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, slot_src(soff[k]), 0, W43_STAGE_AUX));
+            for (int k = 0; k < NST; ++k) st[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, slot_src(soff[k]), 0, W43_STAGE_AUX));
         };
-        auto stage_store = [&](int buf) {
+        auto stage_store = [&](const f32x4 (&st)[NST], int buf) {
             f32x4* rb = reinterpret_cast<f32x4*>(s_raw + buf * RAWF);
 #pragma unroll
-            for (int k = 0; k < NST; ++k) rb[PACK ? (int)(soff[k] & 4095u) : dst[k]] = stage[k];
+            for (int k = 0; k < NST; ++k) rb[PACK ? (int)(soff[k] & 4095u) : dst[k]] = st[k];
         };
-        {   // prologue: both patches are requested before either is stored: one HBM round trip
-            f32x4 stage1[NST];
-            const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pin + (n8 > 1 ? kstep_floats : 0)), 0,
-                                                                                   (int)(in_window - (n8 > 1 ? (unsigned)kstep_floats * 4u : 0u)), 0x00020000);
-            stage_load(0);
-#pragma unroll
-            for (int k = 0; k < NST; ++k) stage1[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, slot_src(soff[k]), 0, W43_STAGE_AUX));
-            stage_store(0);
-            f32x4* rb1 = reinterpret_cast<f32x4*>(s_raw + RAWF);
-#pragma unroll
-            for (int k = 0; k < NST; ++k) rb1[PACK ? (int)(soff[k] & 4095u) : dst[k]] = stage1[k];
-        }
+        w43_stage_first_two(n8, stage, stage_load, stage_store);     // prologue: patches 0 and 1 -> raw[0], raw[1]
         auto t_loop = [&](auto role_c) {
             constexpr int ROLE = decltype(role_c)::value;
-            constexpr int NR = ROLE <= 1 ? 4 : 3;
             f32x4 R1[6], R2[6];
-            auto tr_reads = [&](f32x4 (&D)[4], const float* rp, int b) {
-#pragma unroll
-                for (int s = 0; s < NR; ++s) {
-                    const int aa = ROLE <= 1 ? 1 + s : (ROLE == 2 ? 2 * s : 1 + 2 * s);
-                    D[s] = *reinterpret_cast<const f32x4*>(rp + wbase + (aa * PWS + 5 * (b >> 2) + (b & 3)) * 8);
-                }
-            };
+            auto tr_reads = [&](f32x4 (&D)[4], const float* rp, int b) { w43_window_reads<ROLE, PWS>(D, rp + wbase, b); };
             auto tr_rows = [&](const f32x4 (&D)[4], int b) {
                 if constexpr (ROLE == 0) {                          // rows 1, 2:  (d4 - 4 d2) +- (d3 - 4 d1)
                     const f32x4 t1 = w43_fnma4(D[1], D[3]), t2 = w43_fnma4(D[0], D[2]);
@@ -891,12 +774,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (more) tr_reads(D[0], rp, b0 + 2);
                 tr_rows(D[1], b0 + 1);
             };
-            auto tr_finish = [&](float* vb) {
-                if constexpr (ROLE == 0) { tr_cols(vb, 1, R1); tr_cols(vb, 2, R2); }
-                else if constexpr (ROLE == 1) { tr_cols(vb, 3, R1); tr_cols(vb, 4, R2); }
-                else if constexpr (ROLE == 2) tr_cols(vb, 0, R1);
-                else tr_cols(vb, 5, R1);
-            };
+            auto tr_finish = [&](float* vb) { w43_tr_finish<ROLE>(tr_cols, vb, R1, R2); };
             __syncthreads();                                         // patches 0 and 1 are in raw[0], raw[1]
             tr_reads(D[0], s_raw, 0);
             tr_col_pair(s_raw, 0, true);
@@ -916,7 +794,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             constexpr bool HEAVY = ROLE <= 1;
             constexpr int NG1 = HEAVY ? 2 : 4;                       // units of group 1: planes 3, 4 | planes 3, 4, 5 + the adopted one
             f32x4 Bq0[3], Bq1[NG1], As[NG1 > 3 ? NG1 : 3];
-            const int vxbase = (ROLE & 1) * 9 * 256 + 5 * 256 + mrow * 8 + ((kh ^ ((mrow >> 3) & 1)) * 4);    // plane 5 of wave ROLE - 2
+            const int vxbase = w43_a_lane((ROLE & 1) * 9 + 5, mrow, kh);    // plane 5 of wave ROLE - 2
             const unsigned uxbase = (unsigned)lane * 16u + (unsigned)(ROLE & 1) * 18432u + 10u * 1024u;        // unit (5, 0) of wave ROLE - 2
             auto load_g1 = [&](int c, const float* vplanes) {          // B of group 1 (vplanes == nullptr) or its A planes
 #pragma unroll
@@ -960,7 +838,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 }
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) As[pl] = load_plane(vcur, pl);
-                if constexpr (!(W43_ABL & 4)) stage_load(cs);
+                if constexpr (!(W43_ABL & 4)) stage_load(stage, cs);
                 if constexpr (!(W43_ABL & 2)) {
                     tr_col_pair(rnext, 0, true);
                     tr_col_pair(rnext, 2, true);
@@ -974,7 +852,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int q = 0; q < 4; ++q)
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) W43D_MFMA(acc[pl], As[pl][q], Bq0[pl][q]);
-                if constexpr (!(W43_ABL & 4)) stage_store(PAR);      // raw[PAR] was consumed in the previous K step
+                if constexpr (!(W43_ABL & 4)) stage_store(stage, PAR);   // raw[PAR] was consumed in the previous K step
                 load_g1(0, s_V + PAR * VF);
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) Bq0[pl] = load_unit(cn, pl, 0);
@@ -982,8 +860,8 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             };
             W43_STAMP(6);
             for (int c8 = 0; c8 < n8; c8 += 2) {
-                t_step(c8, ic<0>{});
-                t_step(c8 + 1, ic<1>{});
+                t_step(c8, ntk_ic<0>{});
+                t_step(c8 + 1, ntk_ic<1>{});
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -1000,14 +878,14 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 z_store(acc[6], 5 - 18);                             // plane 5 of wave pg - 2
             }
             __syncthreads();                                         // (E1) half 0 is in LDS
-            out_transform(ic<0>{});
+            out_transform(0);
             __syncthreads();                                         // (E2) half 0 has been read
             __syncthreads();                                         // (E3) half 1 is in LDS (S waves)
         };
-        if (wave == 0) t_loop(ic<0>{});
-        else if (wave == 1) t_loop(ic<1>{});
-        else if (wave == 2) t_loop(ic<2>{});
-        else t_loop(ic<3>{});
+        if (wave == 0) t_loop(ntk_ic<0>{});
+        else if (wave == 1) t_loop(ntk_ic<1>{});
+        else if (wave == 2) t_loop(ntk_ic<2>{});
+        else t_loop(ntk_ic<3>{});
     } else {
         // ================== S waves: 48 MFMAs per K step and nothing else ==================
         // group g = units (3g, 1), (3g + 1, 1), (3g + 2, 1), (6 + g, 0) -> acc[4g .. 4g + 3]
@@ -1055,8 +933,8 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         };
         W43_STAMP(6);
         for (int c8 = 0; c8 < n8; c8 += 2) {
-            s_step(c8, ic<0>{});
-            s_step(c8 + 1, ic<1>{});
+            s_step(c8, ntk_ic<0>{});
+            s_step(c8 + 1, ntk_ic<1>{});
         }
         // ---- epilogue, S side
         __builtin_amdgcn_sched_barrier(0);
@@ -1071,7 +949,7 @@ __global__ __launch_bounds__(W4D) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) z_store(acc[4 * g + pl], 3 * g + pl);
         __syncthreads();                                             // (E3)
-        out_transform(ic<1>{});
+        out_transform(1);
     }
 #undef W43D_MFMA
 
@@ -1132,13 +1010,10 @@ static int wino43_form(int frames, int H, int W, int cin, int cout, int y0, int 
     f->by0 = gy0 / THs[shape];
     const long long NQ = (long long)frames * f->byN * f->bxN;
     const long long NS = (NQ + NSUBs[shape] - 1) / NSUBs[shape];
-    if (NS >= (1ll << 30) || !(f->nCB <= 8 ? (8 % f->nCB) == 0 : (f->nCB % 8) == 0)) return NTK_ERR_UNSUPPORTED;
+    if (NS >= (1ll << 30) || !conv_tile_ncb_ok(f->nCB)) return NTK_ERR_UNSUPPORTED;
     f->NS = (int)NS;
     f->NQ = (int)NQ;
-    long long slots;
-    if (f->nCB >= 8) slots = NS * (f->nCB / 8);
-    else { const int per = 8 / f->nCB; slots = (NS + per - 1) / per; }
-    f->grid = slots * 8;
+    f->grid = conv_tile_grid(NS, f->nCB);
     if (f->grid >= (1ll << 31)) return NTK_ERR_UNSUPPORTED;
     // the eight-wave kernel packs a staging slot into one register on the 1x1x32 shape: a block's input span (the frames its 32
     // tiles touch) must stay below 16 MB there

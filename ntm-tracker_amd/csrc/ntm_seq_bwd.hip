@@ -96,11 +96,6 @@ constexpr int BWS_RING = 20, BWS_LAP = 400, BWS_NG = BWS_LAP / 4;
 constexpr int kBwdWsGroups[11] = {14, 16, 7, 4, 10, 14, 7, 9, 6, 6, 7};
 constexpr int bws_sum(int n) { int s = 0; for (int i = 0; i < n; ++i) s += kBwdWsGroups[i]; return s; }
 static_assert(bws_sum(11) == BWS_NG && BWS_LAP % BWS_RING == 0, "one lap per step; the ring's phase is static");
-template <int N> using bwsic = std::integral_constant<int, N>;
-template <int I0, int I1, class F>
-__device__ __forceinline__ void bws_for(F&& f) {
-    if constexpr (I0 < I1) { f(bwsic<I0>{}); bws_for<I0 + 1, I1>(f); }
-}
 
 // SIM (NTM_SIM_*): the similarity of the content addressing, a compile-time mode as in ntm_seq_fwd.hip.  Smooth cosine
 // recomputes sim = k.M_prev[n] / (|k||M_prev[n]| + 1e-3) from the same records and differentiates it through both norms, with
@@ -158,15 +153,15 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
                               c4 = c3 + kBwdWsGroups[3], c5 = c4 + kBwdWsGroups[4], c6 = c5 + kBwdWsGroups[5],
                               c7 = c6 + kBwdWsGroups[6], c8 = c7 + kBwdWsGroups[7];
                 static_assert(c8 + kBwdWsGroups[8] == BWS_NG, "lap");
-                bws_for<c0, c1>(group); __syncthreads();             // 1
-                bws_for<c1, c2>(group); __syncthreads();             // 2
-                bws_for<c2, c3>(group); __syncthreads();             // 3
-                bws_for<c3, c4>(group); __syncthreads();             // 4
-                bws_for<c4, c5>(group); __syncthreads();             // 5
-                bws_for<c5, c6>(group); __syncthreads();             // 6
-                bws_for<c6, c7>(group); __syncthreads();             // 7
-                bws_for<c7, c8>(group); __syncthreads();             // 8
-                bws_for<c8, BWS_NG>(group);
+                ntk_static_for<c0, c1>(group); __syncthreads();             // 1
+                ntk_static_for<c1, c2>(group); __syncthreads();             // 2
+                ntk_static_for<c2, c3>(group); __syncthreads();             // 3
+                ntk_static_for<c3, c4>(group); __syncthreads();             // 4
+                ntk_static_for<c4, c5>(group); __syncthreads();             // 5
+                ntk_static_for<c5, c6>(group); __syncthreads();             // 6
+                ntk_static_for<c6, c7>(group); __syncthreads();             // 7
+                ntk_static_for<c7, c8>(group); __syncthreads();             // 8
+                ntk_static_for<c8, BWS_NG>(group);
                 // every lane stores (lanes 100 .. 127 shadow lane 99: same address, same value; see ntm_seq_fwd_ws.hip)
                 reinterpret_cast<f32x4*>(sPartH)[sls * 50 + cgs] = acc;
                 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -177,9 +172,9 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
                 finish_lap();
                 __syncthreads();                                     // 9: the partials of d h_t are in LDS
                 __syncthreads();                                     // 10: dgates_t are in LDS
-                bws_for<0, kBwdWsGroups[9]>(group);
+                ntk_static_for<0, kBwdWsGroups[9]>(group);
                 __syncthreads();                                     // 11
-                bws_for<kBwdWsGroups[9], G0>(group);
+                ntk_static_for<kBwdWsGroups[9], G0>(group);
                 __syncthreads();                                     // 12
             }
             finish_lap();                                            // d h_{-1}: the gradient of the initial controller state

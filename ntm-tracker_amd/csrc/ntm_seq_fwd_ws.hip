@@ -53,12 +53,6 @@ constexpr int TC = 512, TA = 768;          // compute threads, all threads
 constexpr int RESQ = 20, RESL = 20;        // read rows per compute thread resident in registers / in LDS (2 slices x 40 rows)
 constexpr int NG = Whid / 4;               // groups of four h rows per lap (50)
 
-template <int N> using wsic = std::integral_constant<int, N>;
-template <int I0, int I1, class F>
-__device__ __forceinline__ void ws_for(F&& f) {
-    if constexpr (I0 < I1) { f(wsic<I0>{}); ws_for<I0 + 1, I1>(f); }
-}
-
 // P3 .. P7: groups (4 rows each) the stream waves consume after barriers B2 .. B6 of a step; the other 50 - sum groups are
 // consumed at the top of the next step, before its barrier B1 (that is where the product is handed over).  RING: rows in flight.
 template <int RING, int P3, int P4, int P5, int P6, int P7>
@@ -140,22 +134,22 @@ __global__ __launch_bounds__(TA) void ntm_seq_fwd_ws_kernel(NtmFwdArgs a, NtmLds
             __builtin_amdgcn_sched_barrier(0);
         };
         for (int t = 0; t < S; ++t) {
-            ws_for<PFIN, NG>(group);
+            ntk_static_for<PFIN, NG>(group);
             // every lane stores (lanes 200..255 shadow unit 199: same address, same value): under a lane condition the compiler
             // sinks the whole product of this segment into the branch and parks the ring's refills in scratch, one drained load each
             sPartH4[j] = acc;
             acc = f32x4{0.f, 0.f, 0.f, 0.f};
             WS_BARRIER(1, 0);                                        // B1: the compute waves' read-row partials and this are complete
             WS_BARRIER(1, 1);                                        // B2: h_t is in LDS
-            ws_for<0, P3>(group);
+            ntk_static_for<0, P3>(group);
             WS_BARRIER(1, 2);                                        // B3
-            ws_for<P3, P3 + P4>(group);
+            ntk_static_for<P3, P3 + P4>(group);
             WS_BARRIER(1, 3);                                        // B4
-            ws_for<P3 + P4, P3 + P4 + P5>(group);
+            ntk_static_for<P3 + P4, P3 + P4 + P5>(group);
             WS_BARRIER(1, 4);                                        // B5
-            ws_for<P3 + P4 + P5, P3 + P4 + P5 + P6>(group);
+            ntk_static_for<P3 + P4 + P5, P3 + P4 + P5 + P6>(group);
             WS_BARRIER(1, 5);                                        // B6
-            ws_for<P3 + P4 + P5 + P6, PFIN>(group);
+            ntk_static_for<P3 + P4 + P5 + P6, PFIN>(group);
             WS_BARRIER(1, 6);                                        // B7
         }
 #ifdef NTK_CL_PROF
