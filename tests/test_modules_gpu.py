@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import dnc_oracle as D
+from small_kernel_util import lstm_pointwise64
 
 pytestmark = pytest.mark.gpu
 
@@ -177,21 +178,16 @@ def test_lstm_step_and_maxpool_and_split_loss(cuda):
     c, h, act = (torch.empty((B, hid), device=cuda), torch.empty((B, hid), device=cuda), torch.empty((B, 4 * hid), device=cuda))
     _lib.check(L.ntk_lstm_step_fwd(P(tp), P(tc0), 0.0, P(c), P(h), P(act), B, hid, st), "ntk_lstm_step_fwd")
     # float64 autograd restatement of BasicLSTMCell's pointwise part (i, j, f, o blocks; forget_bias 0)
-    p64 = torch.tensor(pre, dtype=torch.float64, requires_grad=True)
-    c64 = torch.tensor(c0, dtype=torch.float64, requires_grad=True)
-    i, j, f, o = p64.split(hid, dim=1)
-    cr = c64 * torch.sigmoid(f) + torch.sigmoid(i) * torch.tanh(j)
-    hr = torch.tanh(cr) * torch.sigmoid(o)
-    np.testing.assert_allclose(c.cpu().numpy(), cr.detach().numpy(), atol=1e-6)
-    np.testing.assert_allclose(h.cpu().numpy(), hr.detach().numpy(), atol=1e-6)
     dh = rng.standard_normal((B, hid)).astype(np.float32)
     dc = rng.standard_normal((B, hid)).astype(np.float32)
-    ((hr * torch.tensor(dh, dtype=torch.float64)).sum() + (cr * torch.tensor(dc, dtype=torch.float64)).sum()).backward()
+    cr, hr, _act, dpre_ref, dc0_ref = lstm_pointwise64(pre, c0, 0.0, dh, dc)
+    np.testing.assert_allclose(c.cpu().numpy(), cr, atol=1e-6)
+    np.testing.assert_allclose(h.cpu().numpy(), hr, atol=1e-6)
     dpre, dc0 = torch.empty((B, 4 * hid), device=cuda), torch.empty((B, hid), device=cuda)
     tdh, tdc = torch.from_numpy(dh).to(cuda), torch.from_numpy(dc).to(cuda)
     _lib.check(L.ntk_lstm_step_bwd(P(act), P(tc0), P(c), P(tdh), P(tdc), P(dpre), P(dc0), B, hid, st), "ntk_lstm_step_bwd")
-    np.testing.assert_allclose(dpre.cpu().numpy(), p64.grad.numpy(), atol=2e-6)
-    np.testing.assert_allclose(dc0.cpu().numpy(), c64.grad.numpy(), atol=2e-6)
+    np.testing.assert_allclose(dpre.cpu().numpy(), dpre_ref, atol=2e-6)
+    np.testing.assert_allclose(dc0.cpu().numpy(), dc0_ref, atol=2e-6)
     # max pool: bit-exact vs numpy
     x = rng.standard_normal((2, 6, 10, 8)).astype(np.float32)
     out = torch.empty((2, 3, 5, 8), device=cuda)
