@@ -24,7 +24,6 @@
 // grid at one workgroup per CU.
 #pragma once
 #include "dnc_common.h"
-#include <initializer_list>
 
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
@@ -256,13 +255,41 @@ static inline bool dnc_cluster_is_fix(const DncClusterCfg& c) {
     return c.N == 256 && c.W == 64 && c.R == 4 && c.hid == 200 && c.O == 2 && c.k == 8;
 }
 
-// control block of a launch: flags [B][2][k], the error word, the XCC words of the handshake [B][k]; padded to 256 bytes and
-// zeroed before EVERY launch (dnc_cluster_ctrl_zero_bytes); then one more 256-byte line whose first word is the STICKY
-// error word: a one-thread latch kernel enqueued behind every launch ORs the launch's error word into it, no launch clears
-// it (the owner of the workspace zeroes it once), so an abort in an EARLIER launch of a multi-launch pass (segmented
-// forward, re-recording, BPTT) is still there when the caller looks.  The mailbox follows.
-static inline size_t dnc_cluster_ctrl_zero_bytes(int B, int k) { return (((size_t)B * 3 * k + 1) * sizeof(unsigned) + 255) & ~(size_t)255; }
-static inline size_t dnc_cluster_ctrl_bytes(int B, int k) { return dnc_cluster_ctrl_zero_bytes(B, k) + 256; }
+// Control block of a cluster workspace, both forms: flags [B][X][k] (X hand-offs per step: 2 in the LDS-resident form, MPX in
+// the memory-partitioned one), the launch's error word, the XCC words of the handshake [B][k]; padded to 256 bytes and zeroed
+// before EVERY launch (zero_bytes).  One more 256-byte line holds the STICKY error word in its first word: no launch clears it
+// (the owner of the workspace zeroes it once), so an abort in an EARLIER launch of a multi-launch pass (segmented forward,
+// re-recording, BPTT) is still there when the caller looks.  LDS form: the line follows the zeroed part, the mailbox follows it,
+// and a one-thread latch kernel enqueued behind every launch ORs the launch's error word into it.  mp form: the mailbox follows
+// the zeroed part, the line is the workspace's last, and the kernels set it together with the launch's error word.
+// dnc_cluster_ctl is the only place that knows the two layouts.
+constexpr int MPX = 4;        // hand-offs per step of the memory-partitioned form (dnc_mp.h)
+static inline size_t dnc_cluster_ctrl_zero_bytes(int mp_form, int B, int k) {
+    return (((size_t)B * ((mp_form ? MPX : 2) + 1) * k + 1) * sizeof(unsigned) + 255) & ~(size_t)255;
+}
+static inline size_t dnc_cluster_workspace_bytes(int mp_form, int B, int k, size_t mbox_floats) {      // what the *_plan entries answer
+    const size_t zero = dnc_cluster_ctrl_zero_bytes(mp_form, B, k), mbox = mbox_floats * sizeof(float);
+    return mp_form ? zero + ((mbox + 255) & ~(size_t)255) + 256 : zero + 256 + mbox;
+}
+struct DncClusterCtl {
+    unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
+    float* mbox;
+    size_t zero_bytes;
+};
+static inline DncClusterCtl dnc_cluster_ctl(int mp_form, int B, int k, void* workspace, size_t workspace_bytes) {      // workspace_bytes: mp form only
+    char* const w = reinterpret_cast<char*>(workspace);
+    DncClusterCtl c;
+    c.zero_bytes = dnc_cluster_ctrl_zero_bytes(mp_form, B, k);
+    c.flags = reinterpret_cast<unsigned*>(w);
+    c.err = c.flags + (size_t)B * (mp_form ? MPX : 2) * k;
+    c.xcc = c.err + 1;
+    c.sticky = reinterpret_cast<unsigned*>(mp_form ? w + workspace_bytes - 256 : w + c.zero_bytes);
+    c.mbox = reinterpret_cast<float*>(w + c.zero_bytes + (mp_form ? 0 : 256));
+    return c;
+}
+// dnc_cluster_fwd.hip: the bodies of ntk_dnc_{cluster,mp}_status and ntk_dnc_{cluster,mp}_placement
+int dnc_cluster_status(const char* who, int mp_form, const void* workspace, size_t workspace_bytes, int B, int k, int clear_sticky, void* stream);
+int dnc_cluster_placement(const char* who, int mp_form, const void* workspace, int B, int k, int* same_xcd_clusters, void* stream);
 
 // mailbox layout (floats): per sequence [exchange][parity][g][slot]; flags (unsigned): per sequence [exchange][g]
 static inline size_t dnc_cluster_mbox_floats(int B, int k, int slot0, int slot1) {
@@ -273,17 +300,4 @@ static inline size_t dnc_cluster_mbox_floats(int B, int k, int slot0, int slot1)
 static inline bool dnc_cluster_shape_ok(int B, int N, int W, int R, int Wn, int hid, int O) {
     return Wn == 1 && R >= 1 && R <= 4 && N >= 64 && (N % 64) == 0 && N <= CT && W >= 4 && (W % 4) == 0 && W <= 256 && hid >= 4 &&
            hid <= 1024 && O >= 1 && O <= CW - 1 && B >= 1;
-}
-
-// pointer checks of the launchers: `required` non-null, `records` all given or none, `aligned16` 16-byte aligned (a null
-// pointer passes: absent records).  NTK_OK, or the error with its message set.
-static inline int dnc_cluster_check_ptrs(const char* who, std::initializer_list<const void*> required,
-                                         std::initializer_list<const void*> records, std::initializer_list<const void*> aligned16) {
-    for (const void* p : required) NTK_REQUIRE(p != nullptr, NTK_ERR_BAD_PTR, "%s: null pointer", who);
-    int nn = 0;
-    for (const void* p : records) nn += (p != nullptr);
-    NTK_REQUIRE(nn == 0 || nn == (int)records.size(), NTK_ERR_BAD_PTR, "%s: record pointers are all-or-none (%d of %d given)", who, nn,
-                (int)records.size());
-    for (const void* p : aligned16) NTK_REQUIRE(ntk_aligned16(p), NTK_ERR_BAD_PTR, "%s: 16-byte alignment", who);
-    return NTK_OK;
 }

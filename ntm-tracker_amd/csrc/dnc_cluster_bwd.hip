@@ -100,20 +100,12 @@ constexpr __host__ __device__ DncClBwdLds dnc_cl_bwd_lds(const DncClusterCfg& c,
 constexpr DncClBwdGeo kDncClFixBwdGeo = dnc_cl_bwd_geo(kDncClusterFixCfg);
 constexpr DncClBwdLds kDncClFixBwdLds = dnc_cl_bwd_lds(kDncClusterFixCfg, kDncClFixBwdGeo);
 
-struct DncClBwdArgs {
+struct DncClBwdArgs : DncBwdPtrs {
     int B, S, xcd_local, carry_in;
     float clip;
     DncClusterCfg c;
     DncClBwdGeo q;
     DncClBwdLds lds;
-    const float* WrT; const float* Wi; const float* Wy;
-    const float* mem0; const float* link0; const float* usage0; const float* rw0; const float* ww0; const float* prec0;
-    const float* hc0;
-    const float* rec_gates; const float* rec_c; const float* rec_ifc; const float* rec_u; const float* rec_ww;
-    const float* rec_rw; const float* rec_cw; const float* rec_cr; const float* rec_al; const float* rec_p;
-    const float* rec_fwd; const float* rec_bwd; const float* rec_M; const float* rec_L; const float* rec_ypre;
-    const float* dout;
-    float* gM; float* gL; float* dgates; float* dxi; float* dypre; float* gcarry;
     float* mbox; unsigned* flags; unsigned* err;
     unsigned* xcc;         // [B][k] handshake words of cl_same_xcd (control block)
 };
@@ -839,7 +831,7 @@ extern "C" int ntk_dnc_cluster_bwd_plan(int B, int N, int W, int R, int Wn, int 
                       B, N, W, R, Wn, hid);
         return NTK_ERR_UNSUPPORTED;
     }
-    if (workspace_bytes) *workspace_bytes = dnc_cluster_ctrl_bytes(B, kk) + dnc_cluster_mbox_floats(B, kk, q.slot0, q.slot1) * sizeof(float);
+    if (workspace_bytes) *workspace_bytes = dnc_cluster_workspace_bytes(0, B, kk, dnc_cluster_mbox_floats(B, kk, q.slot0, q.slot1));
     return NTK_OK;
 }
 
@@ -853,7 +845,9 @@ extern "C" int ntk_dnc_cluster_bwd(int B, int S, int N, int W, int R, int Wn, in
                                    const float* rec_M, const float* rec_L, const float* rec_ypre,
                                    const float* dout, float* gM, float* gL, float* dgates, float* dxi, float* dypre,
                                    float* gcarry, int carry_in, void* workspace, void* stream) {
-    DncClBwdArgs a;
+    DncClBwdArgs a = {{WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0,
+                       rec_gates, rec_c, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
+                       dout, gM, gL, dgates, dxi, dypre, gcarry}};
     size_t lds_bytes = 0;
     NTK_REQUIRE(B > 0 && S > 0 && k > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_cluster_bwd: B=%d S=%d k=%d", B, S, k);
     const int kk = dnc_cluster_bwd_pick(B, N, W, R, Wn, hid, O, k, a.c, a.q, &lds_bytes);
@@ -862,30 +856,18 @@ extern "C" int ntk_dnc_cluster_bwd(int B, int S, int N, int W, int R, int Wn, in
     NTK_REQUIRE(ldkT == a.q.ldkT, NTK_ERR_BAD_SHAPE, "ntk_dnc_cluster_bwd: ldkT=%d (expected %d = K rounded up to 4)", ldkT, a.q.ldkT);
     a.lds = dnc_cl_bwd_lds(a.c, a.q);
     a.B = B; a.S = S; a.clip = clip_value; a.carry_in = carry_in;
-    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_cluster_bwd", {WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0, rec_gates, rec_c, rec_ifc,
-                                               rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
-                                               dout, gM, gL, dgates, dxi, dypre, workspace}, {},
-                                              {WrT, Wi, rec_gates, rec_M, rec_L, gM, gL, dgates, mem0, link0, workspace});
+    const int rc_ptr = dnc_bwd_check_ptrs("ntk_dnc_cluster_bwd", a, true, workspace);
     if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
-    a.WrT = WrT; a.Wi = Wi; a.Wy = Wy;
-    a.mem0 = mem0; a.link0 = link0; a.usage0 = usage0; a.rw0 = rw0; a.ww0 = ww0; a.prec0 = prec0; a.hc0 = hc0;
-    a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_ifc = rec_ifc; a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw;
-    a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al; a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd;
-    a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre; a.dout = dout; a.gM = gM; a.gL = gL;
-    a.dgates = dgates; a.dxi = dxi; a.dypre = dypre; a.gcarry = gcarry;
-    const size_t ctrl = dnc_cluster_ctrl_bytes(B, k);
-    a.flags = reinterpret_cast<unsigned*>(workspace);
-    a.err = a.flags + (size_t)B * 2 * k;
-    a.xcc = a.err + 1;
-    a.mbox = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ctrl);
+    const DncClusterCtl ctl = dnc_cluster_ctl(0, B, k, workspace, 0);
+    a.mbox = ctl.mbox; a.flags = ctl.flags; a.err = ctl.err; a.xcc = ctl.xcc;
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)dnc_cluster_bwd_kernel<false>, (const void*)dnc_cluster_bwd_kernel<true>};
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, "ntk_dnc_cluster_bwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    hipError_t e = hipMemsetAsync(workspace, 0, dnc_cluster_ctrl_zero_bytes(B, k), (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(workspace, 0, ctl.zero_bytes, (hipStream_t)stream);
     NTK_REQUIRE(e == hipSuccess, NTK_ERR_HIP, "ntk_dnc_cluster_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
 #ifdef NTK_DNC_BWD_GENERIC                                                  // dev build: the benchmark shape through the generic instantiation
     const bool use_fix = false;
@@ -895,7 +877,7 @@ extern "C" int ntk_dnc_cluster_bwd(int B, int S, int N, int W, int R, int Wn, in
     if (use_fix) dnc_cluster_bwd_kernel<true><<<B * k, CT, lds_bytes, (hipStream_t)stream>>>(a);
     else dnc_cluster_bwd_kernel<false><<<B * k, CT, lds_bytes, (hipStream_t)stream>>>(a);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_bwd");
-    dnc_cluster_latch(a.err, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + ctrl - 256), stream);
+    dnc_cluster_latch(ctl.err, ctl.sticky, stream);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_bwd (latch)");
     return NTK_OK;
 }

@@ -78,16 +78,11 @@ constexpr __host__ __device__ DncClFwdLds dnc_cl_fwd_lds(const DncClusterCfg& c)
 }
 constexpr DncClFwdLds kDncClFixFwdLds = dnc_cl_fwd_lds(kDncClusterFixCfg);
 
-struct DncClFwdArgs {
+struct DncClFwdArgs : DncFwdPtrs {
     int B, S, xcd_local;
     float clip;
     DncClusterCfg c;
     DncClFwdLds lds;
-    const float* xproj; const float* Wr; const float* Wi; const float* Wy;
-    float* mem; float* link; float* usage; float* rw; float* ww; float* prec; float* reads; float* hc; float* out;
-    float* rec_z; float* rec_gates; float* rec_c; float* rec_hc; float* rec_yin; float* rec_ifc; float* rec_u;
-    float* rec_ww; float* rec_rw; float* rec_cw; float* rec_cr; float* rec_al; float* rec_p; float* rec_fwd;
-    float* rec_bwd; float* rec_M; float* rec_L; float* rec_ypre;
     float* mbox; unsigned* flags; unsigned* err;
     unsigned* xcc;         // [B][k] handshake words of cl_same_xcd (control block)
 };
@@ -571,10 +566,9 @@ __global__ void dnc_cluster_inject_kernel(unsigned* sticky) { *sticky = 1u; }
 extern "C" int ntk_dnc_cluster_guard(const void* workspace, size_t workspace_bytes, int mp_form, int B, int k, float* loss, float* grad,
                                      size_t n, void* stream) {
     NTK_REQUIRE(workspace && B > 0 && k > 0, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_guard: bad arguments");
-    const char* w = reinterpret_cast<const char*>(workspace);
-    const unsigned* stk = reinterpret_cast<const unsigned*>(mp_form ? w + workspace_bytes - 256 : w + dnc_cluster_ctrl_bytes(B, k) - 256);
     NTK_REQUIRE(!mp_form || workspace_bytes >= 512, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_guard: workspace_bytes");
-    dnc_cluster_guard_kernel<<<64, 256, 0, (hipStream_t)stream>>>(stk, loss, grad, grad ? n : 0);
+    const DncClusterCtl ctl = dnc_cluster_ctl(mp_form, B, k, const_cast<void*>(workspace), workspace_bytes);
+    dnc_cluster_guard_kernel<<<64, 256, 0, (hipStream_t)stream>>>(ctl.sticky, loss, grad, grad ? n : 0);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_guard");
     return NTK_OK;
 }
@@ -583,9 +577,7 @@ extern "C" int ntk_dnc_cluster_guard(const void* workspace, size_t workspace_byt
 extern "C" int ntk_dnc_cluster_inject_abort(void* workspace, size_t workspace_bytes, int mp_form, int B, int k, void* stream) {
     NTK_REQUIRE(workspace && B > 0 && k > 0, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_inject_abort: bad arguments");
     NTK_REQUIRE(!mp_form || workspace_bytes >= 512, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_inject_abort: workspace_bytes");
-    char* w = reinterpret_cast<char*>(workspace);
-    unsigned* stk = reinterpret_cast<unsigned*>(mp_form ? w + workspace_bytes - 256 : w + dnc_cluster_ctrl_bytes(B, k) - 256);
-    dnc_cluster_inject_kernel<<<1, 1, 0, (hipStream_t)stream>>>(stk);
+    dnc_cluster_inject_kernel<<<1, 1, 0, (hipStream_t)stream>>>(dnc_cluster_ctl(mp_form, B, k, workspace, workspace_bytes).sticky);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_inject_abort");
     return NTK_OK;
 }
@@ -622,32 +614,36 @@ extern "C" int ntk_dnc_cluster_plan(int B, int N, int W, int R, int Wn, int hid,
                       B, N, W, R, Wn, hid);
         return NTK_ERR_UNSUPPORTED;
     }
-    if (workspace_bytes) *workspace_bytes = dnc_cluster_ctrl_bytes(B, kk) + dnc_cluster_mbox_floats(B, kk, c.slot0, c.slot1) * sizeof(float);
+    if (workspace_bytes) *workspace_bytes = dnc_cluster_workspace_bytes(0, B, kk, dnc_cluster_mbox_floats(B, kk, c.slot0, c.slot1));
     return NTK_OK;
 }
 
-extern "C" int ntk_dnc_cluster_status(const void* workspace, int B, int k, void* stream) {
-    NTK_REQUIRE(workspace && B > 0 && k > 0, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_status: bad arguments");
+// clear_sticky: read AND clear the sticky word (the LDS form always does)
+int dnc_cluster_status(const char* who, int mp_form, const void* workspace, size_t workspace_bytes, int B, int k, int clear_sticky, void* stream) {
+    NTK_REQUIRE(workspace && B > 0 && k > 0 && (!mp_form || workspace_bytes >= dnc_cluster_ctrl_zero_bytes(1, B, k) + 256), NTK_ERR_BAD_PTR,
+                "%s: bad arguments", who);
+    const DncClusterCtl ctl = dnc_cluster_ctl(mp_form, B, k, const_cast<void*>(workspace), workspace_bytes);
     unsigned e[2] = {0, 0};
-    const unsigned* errw = reinterpret_cast<const unsigned*>(workspace) + (size_t)B * 2 * k;
-    unsigned* stk = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(const_cast<void*>(workspace)) + dnc_cluster_ctrl_bytes(B, k) - 256);
-    hipError_t rc = hipMemcpyAsync(&e[0], errw, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(&e[1], stk, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (rc == hipSuccess) rc = hipMemsetAsync(stk, 0, sizeof(unsigned), (hipStream_t)stream);      // read and clear
+    hipError_t rc = hipMemcpyAsync(&e[0], ctl.err, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (rc == hipSuccess) rc = hipMemcpyAsync(&e[1], ctl.sticky, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if (rc == hipSuccess && clear_sticky) rc = hipMemsetAsync(ctl.sticky, 0, sizeof(unsigned), (hipStream_t)stream);
     if (rc == hipSuccess) rc = hipStreamSynchronize((hipStream_t)stream);
-    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "ntk_dnc_cluster_status: %s", hipGetErrorString(rc));
-    NTK_REQUIRE(e[0] == 0 && e[1] == 0, NTK_ERR_HIP, "ntk_dnc_cluster_status: a cluster hand-off timed out (%s was aborted; its outputs are invalid)",
+    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "%s: %s", who, hipGetErrorString(rc));
+    NTK_REQUIRE(e[0] == 0 && e[1] == 0, NTK_ERR_HIP, "%s: a cluster hand-off timed out (%s was aborted; its outputs are invalid)", who,
                 e[0] ? "the last launch" : "an earlier launch on this workspace");
     return NTK_OK;
 }
+extern "C" int ntk_dnc_cluster_status(const void* workspace, int B, int k, void* stream) {
+    return dnc_cluster_status("ntk_dnc_cluster_status", 0, workspace, 0, B, k, 1, stream);
+}
 
-extern "C" int ntk_dnc_cluster_placement(const void* workspace, int B, int k, int* same_xcd_clusters, void* stream) {
-    NTK_REQUIRE(workspace && same_xcd_clusters && B > 0 && k > 0 && k <= 64, NTK_ERR_BAD_PTR, "ntk_dnc_cluster_placement: bad arguments");
+int dnc_cluster_placement(const char* who, int mp_form, const void* workspace, int B, int k, int* same_xcd_clusters, void* stream) {
+    NTK_REQUIRE(workspace && same_xcd_clusters && B > 0 && k > 0 && k <= 64, NTK_ERR_BAD_PTR, "%s: bad arguments", who);
     std::vector<unsigned> w((size_t)B * k);
-    const unsigned* xcc = reinterpret_cast<const unsigned*>(workspace) + (size_t)B * 2 * k + 1;
+    const unsigned* xcc = dnc_cluster_ctl(mp_form, B, k, const_cast<void*>(workspace), 0).xcc;
     hipError_t rc = hipMemcpyAsync(w.data(), xcc, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
     if (rc == hipSuccess) rc = hipStreamSynchronize((hipStream_t)stream);
-    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "ntk_dnc_cluster_placement: %s", hipGetErrorString(rc));
+    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "%s: %s", who, hipGetErrorString(rc));
     int n = 0;
     for (int b = 0; b < B; ++b) {
         bool same = w[(size_t)b * k] != 0;          // 0 = no handshake ran (batch not a multiple of 8)
@@ -656,6 +652,9 @@ extern "C" int ntk_dnc_cluster_placement(const void* workspace, int B, int k, in
     }
     *same_xcd_clusters = n;
     return NTK_OK;
+}
+extern "C" int ntk_dnc_cluster_placement(const void* workspace, int B, int k, int* same_xcd_clusters, void* stream) {
+    return dnc_cluster_placement("ntk_dnc_cluster_placement", 0, workspace, B, k, same_xcd_clusters, stream);
 }
 
 extern "C" int ntk_dnc_cluster_fwd(int B, int S, int N, int W, int R, int Wn, int hid, int O, float clip_value, int k,
@@ -666,7 +665,9 @@ extern "C" int ntk_dnc_cluster_fwd(int B, int S, int N, int W, int R, int Wn, in
                                    float* rec_ifc, float* rec_u, float* rec_ww, float* rec_rw, float* rec_cw,
                                    float* rec_cr, float* rec_al, float* rec_p, float* rec_fwd, float* rec_bwd,
                                    float* rec_M, float* rec_L, float* rec_ypre, void* workspace, void* stream) {
-    DncClFwdArgs a;
+    DncClFwdArgs a = {{xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out,
+                       rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p,
+                       rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre}};
     size_t lds_bytes = 0;
     NTK_REQUIRE(B > 0 && S > 0 && k > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_cluster_fwd: B=%d S=%d k=%d", B, S, k);
     const int kk = dnc_cluster_pick(B, N, W, R, Wn, hid, O, k, a.c, &lds_bytes);
@@ -674,34 +675,23 @@ extern "C" int ntk_dnc_cluster_fwd(int B, int S, int N, int W, int R, int Wn, in
                 "(ask ntk_dnc_cluster_plan)", k, B, N, W, R, Wn, hid);
     a.lds = dnc_cl_fwd_lds(a.c);
     a.B = B; a.S = S; a.clip = clip_value;
-    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_cluster_fwd", {xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out, workspace},
-                                              {rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al,
-                                               rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre},
-                                              {xproj, Wr, Wi, mem, link, workspace, rec_gates, rec_M, rec_L});
+    const int rc_ptr = dnc_fwd_check_ptrs("ntk_dnc_cluster_fwd", a, true, workspace);
     if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
-    a.xproj = xproj; a.Wr = Wr; a.Wi = Wi; a.Wy = Wy; a.mem = mem; a.link = link; a.usage = usage; a.rw = rw; a.ww = ww;
-    a.prec = prec; a.reads = reads; a.hc = hc; a.out = out;
-    a.rec_z = rec_z; a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_hc = rec_hc; a.rec_yin = rec_yin; a.rec_ifc = rec_ifc;
-    a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw; a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al;
-    a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd; a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre;
-    const size_t ctrl = dnc_cluster_ctrl_bytes(B, k);
-    a.flags = reinterpret_cast<unsigned*>(workspace);
-    a.err = a.flags + (size_t)B * 2 * k;
-    a.xcc = a.err + 1;
-    a.mbox = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ctrl);
+    const DncClusterCtl ctl = dnc_cluster_ctl(0, B, k, workspace, 0);
+    a.mbox = ctl.mbox; a.flags = ctl.flags; a.err = ctl.err; a.xcc = ctl.xcc;
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)dnc_cluster_fwd_kernel<false>, (const void*)dnc_cluster_fwd_kernel<true>};
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 2, "ntk_dnc_cluster_fwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    hipError_t e = hipMemsetAsync(workspace, 0, dnc_cluster_ctrl_zero_bytes(B, k), (hipStream_t)stream);     // flags + error word: zero before EVERY launch
+    hipError_t e = hipMemsetAsync(workspace, 0, ctl.zero_bytes, (hipStream_t)stream);     // flags + error word: zero before EVERY launch
     NTK_REQUIRE(e == hipSuccess, NTK_ERR_HIP, "ntk_dnc_cluster_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
     if (dnc_cluster_is_fix(a.c)) dnc_cluster_fwd_kernel<true><<<B * k, CT, lds_bytes, (hipStream_t)stream>>>(a);
     else dnc_cluster_fwd_kernel<false><<<B * k, CT, lds_bytes, (hipStream_t)stream>>>(a);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_fwd");
-    dnc_cluster_latch(a.err, reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + ctrl - 256), stream);
+    dnc_cluster_latch(ctl.err, ctl.sticky, stream);
     NTK_CHECK_LAUNCH("ntk_dnc_cluster_fwd (latch)");
     return NTK_OK;
 }

@@ -21,8 +21,6 @@
 #pragma once
 #include "dnc_cluster.h"
 
-constexpr int MPX = 4;        // hand-offs per step
-
 struct DncMpCfg {
     int N, W, R, hid, O;
     int I, IP, K, ldz, ldh, Ky, ldy, OP;
@@ -85,18 +83,13 @@ static inline int dnc_mp_shape_of(const DncMpCfg& c) {
     return 0;
 }
 
-// control block of a launch: flags [B][MPX][k], the error word, the XCC words of the handshake [B][k]; padded to 256 bytes;
-// zeroed before EVERY launch.  The mailbox follows, then one 256-byte line whose first word is the STICKY error word: set
-// together with the launch's error word, never cleared by a launch (the owner of the workspace zeroes it once), so that a
-// hand-off that timed out in an earlier launch of a multi-launch pass is still seen when the caller next looks.
-static inline size_t dnc_mp_ctrl_bytes(int B, int k) { return (((size_t)B * (MPX + 1) * k + 1) * sizeof(unsigned) + 255) & ~(size_t)255; }
 static inline size_t dnc_mp_mbox_floats(int B, int k, const int* slot) {
     size_t per = 0;
     for (int e = 0; e < MPX; ++e) per += (size_t)2 * k * slot[e];
     return (size_t)B * per;
 }
 static inline size_t dnc_mp_workspace_bytes(int B, int k, const int* slot) {
-    return dnc_mp_ctrl_bytes(B, k) + ((dnc_mp_mbox_floats(B, k, slot) * sizeof(float) + 255) & ~(size_t)255) + 256;
+    return dnc_cluster_workspace_bytes(1, B, k, dnc_mp_mbox_floats(B, k, slot));
 }
 
 // 16-byte payload loads of a hand-off: raw buffer loads with sc1 (aux 16: the per-CU L1 is bypassed, as the 4- and 8-byte agent-scope

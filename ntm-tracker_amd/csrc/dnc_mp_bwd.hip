@@ -106,20 +106,12 @@ constexpr __host__ __device__ DncMpBwdLds dnc_mp_bwd_lds(const DncMpCfg& c, cons
     return L;
 }
 
-struct DncMpBwdArgs {
+struct DncMpBwdArgs : DncBwdPtrs {
     int B, S, xcd_local, carry_in;
     float clip;
     DncMpCfg c;
     DncMpBwdGeo q;
     DncMpBwdLds lds;
-    const float* WrT; const float* Wi; const float* Wy;
-    const float* mem0; const float* link0; const float* usage0; const float* rw0; const float* ww0; const float* prec0;
-    const float* hc0;
-    const float* rec_gates; const float* rec_c; const float* rec_ifc; const float* rec_u; const float* rec_ww;
-    const float* rec_rw; const float* rec_cw; const float* rec_cr; const float* rec_al; const float* rec_p;
-    const float* rec_fwd; const float* rec_bwd; const float* rec_M; const float* rec_L; const float* rec_ypre;
-    const float* dout;
-    float* gM; float* gL; float* dgates; float* dxi; float* dypre; float* gcarry;
     float* mbox; unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
 };
 
@@ -909,7 +901,9 @@ extern "C" int ntk_dnc_mp_bwd(int B, int S, int N, int W, int R, int Wn, int hid
                               const float* rec_M, const float* rec_L, const float* rec_ypre,
                               const float* dout, float* gM, float* gL, float* dgates, float* dxi, float* dypre,
                               float* gcarry, int carry_in, void* workspace, void* stream) {
-    DncMpBwdArgs a;
+    DncMpBwdArgs a = {{WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0,
+                       rec_gates, rec_c, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
+                       dout, gM, gL, dgates, dxi, dypre, gcarry}};
     size_t lds_bytes = 0;
     NTK_REQUIRE(B > 0 && S > 0 && k > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_mp_bwd: B=%d S=%d k=%d", B, S, k);
     const int kk = dnc_mp_bwd_pick(B, N, W, R, Wn, hid, O, k, a.c, a.q, &lds_bytes);
@@ -918,25 +912,11 @@ extern "C" int ntk_dnc_mp_bwd(int B, int S, int N, int W, int R, int Wn, int hid
     NTK_REQUIRE(ldkT == a.q.ldkT, NTK_ERR_BAD_SHAPE, "ntk_dnc_mp_bwd: ldkT=%d (expected %d = K rounded up to 4)", ldkT, a.q.ldkT);
     a.lds = dnc_mp_bwd_lds(a.c, a.q);
     a.B = B; a.S = S; a.clip = clip_value; a.carry_in = carry_in;
-    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_mp_bwd", {WrT, Wi, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0, rec_gates, rec_c, rec_ifc,
-                                               rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
-                                               dout, gM, gL, dgates, dxi, dypre, workspace}, {},
-                                              {WrT, Wi, rec_gates, rec_M, rec_L, gM, gL, dgates, mem0, link0, workspace});
+    const int rc_ptr = dnc_bwd_check_ptrs("ntk_dnc_mp_bwd", a, true, workspace);
     if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
-    a.WrT = WrT; a.Wi = Wi; a.Wy = Wy;
-    a.mem0 = mem0; a.link0 = link0; a.usage0 = usage0; a.rw0 = rw0; a.ww0 = ww0; a.prec0 = prec0; a.hc0 = hc0;
-    a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_ifc = rec_ifc; a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw;
-    a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al; a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd;
-    a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre; a.dout = dout; a.gM = gM; a.gL = gL;
-    a.dgates = dgates; a.dxi = dxi; a.dypre = dypre; a.gcarry = gcarry;
-    const size_t ctrl = dnc_mp_ctrl_bytes(B, k);
-    const size_t wsb = dnc_mp_workspace_bytes(B, k, a.q.slot);
-    a.flags = reinterpret_cast<unsigned*>(workspace);
-    a.err = a.flags + (size_t)B * MPX * k;
-    a.xcc = a.err + 1;
-    a.mbox = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ctrl);
-    a.sticky = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + wsb - 256);
+    const DncClusterCtl ctl = dnc_cluster_ctl(1, B, k, workspace, dnc_mp_workspace_bytes(B, k, a.q.slot));
+    a.mbox = ctl.mbox; a.flags = ctl.flags; a.err = ctl.err; a.xcc = ctl.xcc; a.sticky = ctl.sticky;
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)dnc_mp_bwd_kernel<0>, (const void*)dnc_mp_bwd_kernel<1>, (const void*)dnc_mp_bwd_kernel<2>,
@@ -944,7 +924,7 @@ extern "C" int ntk_dnc_mp_bwd(int B, int S, int N, int W, int R, int Wn, int hid
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_dnc_mp_bwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    hipError_t e = hipMemsetAsync(workspace, 0, ctrl, (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(workspace, 0, ctl.zero_bytes, (hipStream_t)stream);
     NTK_REQUIRE(e == hipSuccess, NTK_ERR_HIP, "ntk_dnc_mp_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
 #ifdef NTK_DNC_MP_GENERIC
     const int shape = 0;

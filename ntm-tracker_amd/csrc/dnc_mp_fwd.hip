@@ -15,7 +15,6 @@
 #include "dnc_mp.h"
 #include "dnc_cluster_phases.h"
 #include <type_traits>
-#include <vector>
 
 // Diagnostic build only (-DNTK_CL_PROF): workgroup 0's thread 0 adds s_memtime deltas per phase to g_mpf_prof (global atomics: no
 // registers held across the step); ntk_dnc_mp_fwd_prof copies them out.  The stamps serialise the phases: read SHARES.
@@ -69,16 +68,11 @@ constexpr __host__ __device__ DncMpFwdLds dnc_mp_fwd_lds(const DncMpCfg& c) {
     return L;
 }
 
-struct DncMpFwdArgs {
+struct DncMpFwdArgs : DncFwdPtrs {
     int B, S, xcd_local;
     float clip;
     DncMpCfg c;
     DncMpFwdLds lds;
-    const float* xproj; const float* Wr; const float* Wi; const float* Wy;
-    float* mem; float* link; float* usage; float* rw; float* ww; float* prec; float* reads; float* hc; float* out;
-    float* rec_z; float* rec_gates; float* rec_c; float* rec_hc; float* rec_yin; float* rec_ifc; float* rec_u;
-    float* rec_ww; float* rec_rw; float* rec_cw; float* rec_cr; float* rec_al; float* rec_p; float* rec_fwd;
-    float* rec_bwd; float* rec_M; float* rec_L; float* rec_ypre;
     float* mbox; unsigned* flags; unsigned* err; unsigned* xcc; unsigned* sticky;
 };
 
@@ -575,35 +569,11 @@ extern "C" int ntk_dnc_mp_compiled_shape(int N, int W, int R, int Wn, int hid, i
 }
 
 extern "C" int ntk_dnc_mp_status(const void* workspace, size_t workspace_bytes, int B, int k, int clear_sticky, void* stream) {
-    NTK_REQUIRE(workspace && B > 0 && k > 0 && workspace_bytes >= dnc_mp_ctrl_bytes(B, k) + 256, NTK_ERR_BAD_PTR, "ntk_dnc_mp_status: bad arguments");
-    unsigned e[2] = {0, 0};
-    const unsigned* errw = reinterpret_cast<const unsigned*>(workspace) + (size_t)B * MPX * k;
-    const unsigned* stk = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(workspace) + workspace_bytes - 256);
-    hipError_t rc = hipMemcpyAsync(&e[0], errw, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (rc == hipSuccess) rc = hipMemcpyAsync(&e[1], stk, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (rc == hipSuccess && clear_sticky) rc = hipMemsetAsync(const_cast<unsigned*>(stk), 0, sizeof(unsigned), (hipStream_t)stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize((hipStream_t)stream);
-    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "ntk_dnc_mp_status: %s", hipGetErrorString(rc));
-    NTK_REQUIRE(e[0] == 0 && e[1] == 0, NTK_ERR_HIP, "ntk_dnc_mp_status: a cluster hand-off timed out (%s; outputs of that launch are invalid)",
-                e[0] ? "last launch" : "an earlier launch on this workspace");
-    return NTK_OK;
+    return dnc_cluster_status("ntk_dnc_mp_status", 1, workspace, workspace_bytes, B, k, clear_sticky, stream);
 }
 
 extern "C" int ntk_dnc_mp_placement(const void* workspace, int B, int k, int* same_xcd_clusters, void* stream) {
-    NTK_REQUIRE(workspace && same_xcd_clusters && B > 0 && k > 0 && k <= 64, NTK_ERR_BAD_PTR, "ntk_dnc_mp_placement: bad arguments");
-    std::vector<unsigned> w((size_t)B * k);
-    const unsigned* xcc = reinterpret_cast<const unsigned*>(workspace) + (size_t)B * MPX * k + 1;
-    hipError_t rc = hipMemcpyAsync(w.data(), xcc, w.size() * sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
-    if (rc == hipSuccess) rc = hipStreamSynchronize((hipStream_t)stream);
-    NTK_REQUIRE(rc == hipSuccess, NTK_ERR_HIP, "ntk_dnc_mp_placement: %s", hipGetErrorString(rc));
-    int n = 0;
-    for (int b = 0; b < B; ++b) {
-        bool same = w[(size_t)b * k] != 0;          // 0 = no handshake ran (batch not a multiple of 8)
-        for (int g = 1; g < k; ++g) same = same && w[(size_t)b * k + g] == w[(size_t)b * k];
-        n += same ? 1 : 0;
-    }
-    *same_xcd_clusters = n;
-    return NTK_OK;
+    return dnc_cluster_placement("ntk_dnc_mp_placement", 1, workspace, B, k, same_xcd_clusters, stream);
 }
 
 extern "C" int ntk_dnc_mp_fwd(int B, int S, int N, int W, int R, int Wn, int hid, int O, float clip_value, int k,
@@ -614,7 +584,9 @@ extern "C" int ntk_dnc_mp_fwd(int B, int S, int N, int W, int R, int Wn, int hid
                               float* rec_ifc, float* rec_u, float* rec_ww, float* rec_rw, float* rec_cw,
                               float* rec_cr, float* rec_al, float* rec_p, float* rec_fwd, float* rec_bwd,
                               float* rec_M, float* rec_L, float* rec_ypre, void* workspace, void* stream) {
-    DncMpFwdArgs a;
+    DncMpFwdArgs a = {{xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out,
+                       rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p,
+                       rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre}};
     size_t lds_bytes = 0;
     NTK_REQUIRE(B > 0 && S > 0 && k > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_mp_fwd: B=%d S=%d k=%d", B, S, k);
     const int kk = dnc_mp_pick(B, N, W, R, Wn, hid, O, k, a.c, &lds_bytes);
@@ -622,24 +594,11 @@ extern "C" int ntk_dnc_mp_fwd(int B, int S, int N, int W, int R, int Wn, int hid
                 "(ask ntk_dnc_mp_plan)", k, B, N, W, R, Wn, hid);
     a.lds = dnc_mp_fwd_lds(a.c);
     a.B = B; a.S = S; a.clip = clip_value;
-    const int rc_ptr = dnc_cluster_check_ptrs("ntk_dnc_mp_fwd", {xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out, workspace},
-                                              {rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al,
-                                               rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre},
-                                              {xproj, Wr, Wi, mem, link, workspace, rec_gates, rec_M, rec_L});
+    const int rc_ptr = dnc_fwd_check_ptrs("ntk_dnc_mp_fwd", a, true, workspace);
     if (rc_ptr != NTK_OK) return rc_ptr;
     a.xcd_local = (B % 8) == 0 ? 1 : 0;
-    a.xproj = xproj; a.Wr = Wr; a.Wi = Wi; a.Wy = Wy; a.mem = mem; a.link = link; a.usage = usage; a.rw = rw; a.ww = ww;
-    a.prec = prec; a.reads = reads; a.hc = hc; a.out = out;
-    a.rec_z = rec_z; a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_hc = rec_hc; a.rec_yin = rec_yin; a.rec_ifc = rec_ifc;
-    a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw; a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al;
-    a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd; a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre;
-    const size_t ctrl = dnc_mp_ctrl_bytes(B, k);
-    const size_t wsb = dnc_mp_workspace_bytes(B, k, a.c.slot);
-    a.flags = reinterpret_cast<unsigned*>(workspace);
-    a.err = a.flags + (size_t)B * MPX * k;
-    a.xcc = a.err + 1;
-    a.mbox = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + ctrl);
-    a.sticky = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(workspace) + wsb - 256);
+    const DncClusterCtl ctl = dnc_cluster_ctl(1, B, k, workspace, dnc_mp_workspace_bytes(B, k, a.c.slot));
+    a.mbox = ctl.mbox; a.flags = ctl.flags; a.err = ctl.err; a.xcc = ctl.xcc; a.sticky = ctl.sticky;
     {
         static NtkLdsAttrCache lds_cache;
         const void* const ks[] = {(const void*)dnc_mp_fwd_kernel<0>, (const void*)dnc_mp_fwd_kernel<1>, (const void*)dnc_mp_fwd_kernel<2>,
@@ -647,7 +606,7 @@ extern "C" int ntk_dnc_mp_fwd(int B, int S, int N, int W, int R, int Wn, int hid
         const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, "ntk_dnc_mp_fwd");
         if (rc_lds != NTK_OK) return rc_lds;
     }
-    hipError_t e = hipMemsetAsync(workspace, 0, ctrl, (hipStream_t)stream);     // flags + error word: zero before EVERY launch
+    hipError_t e = hipMemsetAsync(workspace, 0, ctl.zero_bytes, (hipStream_t)stream);     // flags + error word: zero before EVERY launch
     NTK_REQUIRE(e == hipSuccess, NTK_ERR_HIP, "ntk_dnc_mp_fwd: hipMemsetAsync: %s", hipGetErrorString(e));
 #ifdef NTK_DNC_MP_GENERIC
     const int shape = 0;

@@ -39,20 +39,9 @@
 // scripts/dev_dnc_stepgrad.py: free_gate 1e-7 -> 8.7e-15 absolute error once the rounding matches).
 #pragma clang fp contract(off)
 
-struct DncBwdArgs {
-    DncDims d;
-    const float* WrT; int ldkT;      // [4*hid][ldkT]
-    const float* WiT; int ldhT;      // [IP][ldhT]
-    const float* Wy;                 // [ldy][OP]
-    const float* mem0; const float* link0; const float* usage0; const float* rw0; const float* ww0;
-    const float* prec0; const float* hc0;
-    const float* rec_gates; const float* rec_c; const float* rec_ifc; const float* rec_u; const float* rec_ww;
-    const float* rec_rw; const float* rec_cw; const float* rec_cr; const float* rec_al; const float* rec_p;
-    const float* rec_fwd; const float* rec_bwd; const float* rec_M; const float* rec_L; const float* rec_ypre;
-    const float* dout;               // [B,S,O]
-    float* gM; float* gL;            // [B,N,W], [B,Wn,N,N] zero-initialised scratch (carried gradients)
-    float* dgates; float* dxi; float* dypre;
-    float* gcarry; int carry_in;     // [B, (Wn+1)*N + R*N + ldkT + hid] gradients carried into state t=-1 (segmented BPTT)
+struct DncBwdArgs : DncDimsFirst, DncBwdPtrs {      // dnc_common.h (Wi holds the transpose WiT here)
+    int ldkT, ldhT;      // leading dimensions of WrT [4*hid][ldkT] and WiT [IP][ldhT]
+    int carry_in;        // gcarry holds what the following segment left behind
 };
 
 struct DncBwdLds {
@@ -676,7 +665,7 @@ __global__ __launch_bounds__(DT) void dnc_seq_bwd_kernel(DncBwdArgs a, DncBwdLds
             const int cg = tid % hg4, sl = tid / hg4;
             const int c0 = sl * nperH, c1 = min(IP, c0 + nperH);
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-            const f32x4* wp4 = reinterpret_cast<const f32x4*>(a.WiT) + (size_t)c0 * hg4 + cg;
+            const f32x4* wp4 = reinterpret_cast<const f32x4*>(a.Wi) + (size_t)c0 * hg4 + cg;
 #pragma unroll 4
             for (int c = c0; c < c1; ++c, wp4 += hg4) acc += sDX[c] * (*wp4);
             sPart4[sl * hg4 + cg] = acc;
@@ -753,7 +742,9 @@ extern "C" int ntk_dnc_seq_bwd(int B, int S, int N, int W, int R, int Wn, int hi
                                const float* rec_M, const float* rec_L, const float* rec_ypre,
                                const float* dout, float* gM, float* gL, float* dgates, float* dxi, float* dypre,
                                float* gcarry, int carry_in, void* stream) {
-    DncBwdArgs a;
+    DncBwdArgs a = {{}, {WrT, WiT, Wy, mem0, link0, usage0, rw0, ww0, prec0, hc0,
+                     rec_gates, rec_c, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre,
+                     dout, gM, gL, dgates, dxi, dypre, gcarry}, ldkT, ldhT, carry_in};
     dnc_fill_dims(a.d, B, S, N, W, R, Wn, hid, O, clip_value);
     NTK_REQUIRE(B > 0 && S > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_seq_bwd: B=%d S=%d", B, S);
     NTK_REQUIRE(Wn >= 1 && Wn <= 4, NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_bwd: num_writes=%d (the BPTT kernels implement 1..4 write heads)", Wn);
@@ -765,20 +756,8 @@ extern "C" int ntk_dnc_seq_bwd(int B, int S, int N, int W, int R, int Wn, int hi
     NTK_REQUIRE(a.d.K <= DT, NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_bwd: reads*word + hidden = %d exceeds one workgroup (%d threads)", a.d.K, DT);
     NTK_REQUIRE(ldkT >= a.d.K && (ldkT % 4) == 0 && ldhT >= hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE,
                 "ntk_dnc_seq_bwd: ldkT=%d ldhT=%d", ldkT, ldhT);
-    NTK_REQUIRE(WrT && WiT && Wy && mem0 && link0 && usage0 && rw0 && ww0 && prec0 && hc0 && rec_gates && rec_c && rec_ifc &&
-                    rec_u && rec_ww && rec_rw && rec_cw && rec_cr && rec_al && rec_p && rec_fwd && rec_bwd && rec_M && rec_L &&
-                    rec_ypre && dout && gM && gL && dgates && dxi && dypre,
-                NTK_ERR_BAD_PTR, "ntk_dnc_seq_bwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(WrT) && ntk_aligned16(WiT) && ntk_aligned16(rec_gates) && ntk_aligned16(rec_M) &&
-                    ntk_aligned16(rec_L) && ntk_aligned16(gM) && ntk_aligned16(gL) && ntk_aligned16(dgates) &&
-                    ntk_aligned16(mem0) && ntk_aligned16(link0),
-                NTK_ERR_BAD_PTR, "ntk_dnc_seq_bwd: 16-byte alignment");
-    a.WrT = WrT; a.ldkT = ldkT; a.WiT = WiT; a.ldhT = ldhT; a.Wy = Wy;
-    a.mem0 = mem0; a.link0 = link0; a.usage0 = usage0; a.rw0 = rw0; a.ww0 = ww0; a.prec0 = prec0; a.hc0 = hc0;
-    a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_ifc = rec_ifc; a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw;
-    a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al; a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd;
-    a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre; a.dout = dout; a.gM = gM; a.gL = gL;
-    a.dgates = dgates; a.dxi = dxi; a.dypre = dypre; a.gcarry = gcarry; a.carry_in = carry_in;
+    const int rc_ptr = dnc_bwd_check_ptrs("ntk_dnc_seq_bwd", a, false, nullptr);
+    if (rc_ptr != NTK_OK) return rc_ptr;
     DncBwdLds L;
     dnc_bwd_lds(a.d, ldkT, ldhT, L);
     const size_t lds_bytes = (size_t)L.total * sizeof(float);

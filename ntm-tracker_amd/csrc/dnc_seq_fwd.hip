@@ -28,42 +28,7 @@
 // in an op-by-op fp32 evaluation.
 #pragma clang fp contract(off)
 
-struct DncFwdArgs {
-    DncDims d;
-    const float* xproj;   // [B,S,4*hid] (n' = unit*4+gate), no bias
-    const float* Wr;      // [ldz][4*hid], row K = bias
-    const float* Wi;      // [ldh][IP],   row hid = bias
-    const float* Wy;      // [ldy][OP],   row Ky = bias
-    // state, updated in place
-    float* mem;           // [B,N,W]
-    float* link;          // [B,Wn,N,N]
-    float* usage;         // [B,N]
-    float* rw;            // [B,R,N]
-    float* ww;            // [B,Wn,N]
-    float* prec;          // [B,Wn,N]
-    float* reads;         // [B,R,W]    (access_output)
-    float* hc;            // [B,2*hid]  (hidden then cell)
-    float* out;           // [B,S,O]
-    // per-step records for BPTT (all nullable, all-or-none)
-    float* rec_z;         // [B,S,ldz]  [reads_prev ; h_prev ; 1 ; 0..]
-    float* rec_gates;     // [B,S,4*hid] activated gates (i, j, sigmoid(f+1), o per unit)
-    float* rec_c;         // [B,S,hid]  cell before clipping
-    float* rec_hc;        // [B,S,ldh]  [clipped h ; 1 ; 0..]
-    float* rec_yin;       // [B,S,ldy]  [clipped h ; reads_t ; 1 ; 0..]
-    float* rec_ifc;       // [B,S,IP]   activated interface
-    float* rec_u;         // [B,S,N]
-    float* rec_ww;        // [B,S,Wn,N]
-    float* rec_rw;        // [B,S,R,N]
-    float* rec_cw;        // [B,S,Wn,N]
-    float* rec_cr;        // [B,S,R,N]
-    float* rec_al;        // [B,S,Wn,N] allocation weights
-    float* rec_p;         // [B,S,Wn,N] precedence after the step
-    float* rec_fwd;       // [B,S,R,Wn,N]
-    float* rec_bwd;       // [B,S,R,Wn,N]
-    float* rec_M;         // [B,S,N,W]
-    float* rec_L;         // [B,S,Wn,N,N]
-    float* rec_ypre;      // [B,S,O]    output before clipping
-};
+struct DncFwdArgs : DncDimsFirst, DncFwdPtrs {};      // dnc_common.h
 
 constexpr int DNC_PFM = 4;    // rows of M a lane group requests per batch
 constexpr int DNC_PFL = 1;    // rows of the link a wave requests per batch (more spill at 128 VGPRs)
@@ -531,7 +496,9 @@ extern "C" int ntk_dnc_seq_fwd(int B, int S, int N, int W, int R, int Wn, int hi
                                float* rec_ifc, float* rec_u, float* rec_ww, float* rec_rw, float* rec_cw,
                                float* rec_cr, float* rec_al, float* rec_p, float* rec_fwd, float* rec_bwd,
                                float* rec_M, float* rec_L, float* rec_ypre, void* stream) {
-    DncFwdArgs a;
+    DncFwdArgs a = {{}, {xproj, Wr, Wi, Wy, mem, link, usage, rw, ww, prec, reads, hc, out,
+                     rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al, rec_p,
+                     rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre}};
     dnc_fill_dims(a.d, B, S, N, W, R, Wn, hid, O, clip_value);
     NTK_REQUIRE(B > 0 && S > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_seq_fwd: B=%d S=%d", B, S);
     NTK_REQUIRE(N >= 4 && (N % 4) == 0 && N <= DT, NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_fwd: memory_size=%d must be a multiple of 4 <= 1024", N);
@@ -539,24 +506,8 @@ extern "C" int ntk_dnc_seq_fwd(int B, int S, int N, int W, int R, int Wn, int hi
     NTK_REQUIRE(R >= 1 && R <= 4 && Wn >= 1 && Wn <= 8, NTK_ERR_UNSUPPORTED, "ntk_dnc_seq_fwd: num_reads=%d (1..4) num_writes=%d (1..8)", R, Wn);
     NTK_REQUIRE(hid >= 1 && hid <= DT && R * W <= DT && O >= 1 && O <= DW, NTK_ERR_UNSUPPORTED,
                 "ntk_dnc_seq_fwd: hidden=%d reads*word=%d output=%d exceed one workgroup", hid, R * W, O);
-    NTK_REQUIRE(xproj && Wr && Wi && Wy && mem && link && usage && rw && ww && prec && reads && hc && out, NTK_ERR_BAD_PTR,
-                "ntk_dnc_seq_fwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(xproj) && ntk_aligned16(Wr) && ntk_aligned16(Wi) && ntk_aligned16(mem) && ntk_aligned16(link),
-                NTK_ERR_BAD_PTR, "ntk_dnc_seq_fwd: xproj/Wr/Wi/mem/link must be 16-byte aligned");
-    a.xproj = xproj; a.Wr = Wr; a.Wi = Wi; a.Wy = Wy; a.mem = mem; a.link = link; a.usage = usage; a.rw = rw; a.ww = ww;
-    a.prec = prec; a.reads = reads; a.hc = hc; a.out = out;
-    {
-        float* recs[] = {rec_z, rec_gates, rec_c, rec_hc, rec_yin, rec_ifc, rec_u, rec_ww, rec_rw, rec_cw, rec_cr, rec_al,
-                         rec_p, rec_fwd, rec_bwd, rec_M, rec_L, rec_ypre};
-        int nn = 0;
-        for (float* r : recs) nn += (r != nullptr);
-        NTK_REQUIRE(nn == 0 || nn == 18, NTK_ERR_BAD_PTR, "ntk_dnc_seq_fwd: record pointers are all-or-none (%d of 18 given)", nn);
-        NTK_REQUIRE(nn == 0 || (ntk_aligned16(rec_gates) && ntk_aligned16(rec_M) && ntk_aligned16(rec_L)), NTK_ERR_BAD_PTR,
-                    "ntk_dnc_seq_fwd: rec_gates/rec_M/rec_L must be 16-byte aligned");
-    }
-    a.rec_z = rec_z; a.rec_gates = rec_gates; a.rec_c = rec_c; a.rec_hc = rec_hc; a.rec_yin = rec_yin; a.rec_ifc = rec_ifc;
-    a.rec_u = rec_u; a.rec_ww = rec_ww; a.rec_rw = rec_rw; a.rec_cw = rec_cw; a.rec_cr = rec_cr; a.rec_al = rec_al;
-    a.rec_p = rec_p; a.rec_fwd = rec_fwd; a.rec_bwd = rec_bwd; a.rec_M = rec_M; a.rec_L = rec_L; a.rec_ypre = rec_ypre;
+    const int rc_ptr = dnc_fwd_check_ptrs("ntk_dnc_seq_fwd", a, false, nullptr);
+    if (rc_ptr != NTK_OK) return rc_ptr;
     DncLds L;
     dnc_fwd_lds(a.d, L);
     const size_t lds_bytes = (size_t)L.total * sizeof(float);

@@ -256,6 +256,16 @@ class DNC(object):
         return self.run_projected(xproj, B, S, prev_state, record=record)
 
     REC_NAMES = ("z", "gates", "c", "hc", "yin", "ifc", "u", "ww", "rw", "cw", "cr", "al", "p", "fwd", "bwd", "M", "L", "ypre")
+    #: the records a BPTT launch takes, in its order (z, hc and yin feed the weight-gradient GEMMs only)
+    BWD_REC_NAMES = tuple(n for n in REC_NAMES if n not in ("z", "hc", "yin"))
+    #: cluster form (None: one workgroup per sequence) -> the symbols that belong to it
+    FORM_SYMBOLS = {
+        None: dict(fwd="ntk_dnc_seq_fwd", bwd="ntk_dnc_seq_bwd"),
+        "lds": dict(fwd="ntk_dnc_cluster_fwd", bwd="ntk_dnc_cluster_bwd", plan="ntk_dnc_cluster_plan", bwd_plan="ntk_dnc_cluster_bwd_plan",
+                    placement="ntk_dnc_cluster_placement"),
+        "mp": dict(fwd="ntk_dnc_mp_fwd", bwd="ntk_dnc_mp_bwd", plan="ntk_dnc_mp_plan", bwd_plan="ntk_dnc_mp_bwd_plan",
+                   placement="ntk_dnc_mp_placement"),
+    }
 
     def _alloc_records(self, B, S, cap=None):
         """Record tensors [B, S, ...].  cap >= S: allocate room for cap steps and return the leading [B, S, ...] part -- segmented
@@ -334,10 +344,10 @@ class DNC(object):
         if cur is None or cur[0] != key:
             L = _lib.lib()
             found = None
-            for f, fn in (("lds", L.ntk_dnc_cluster_bwd_plan if bwd else L.ntk_dnc_cluster_plan),
-                          ("mp", getattr(L, "ntk_dnc_mp_bwd_plan", None) if bwd else L.ntk_dnc_mp_plan)):
-                if form not in (None, f) or fn is None:
+            for f in ("lds", "mp"):
+                if form not in (None, f):
                     continue
+                fn = getattr(L, self.FORM_SYMBOLS[f]["bwd_plan" if bwd else "plan"])
                 k, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
                 rc = fn(B, self.N, self.W, self.R, self.Wn, self.hid, self.O, int(want or 0), ctypes.byref(k), ctypes.byref(nbytes))
                 if rc == 0 and k.value > 1:
@@ -357,32 +367,34 @@ class DNC(object):
     def _cluster_bwd_plan(self, B):
         return self._plan(B, True)
 
+    def _live_plans(self):
+        """(B, form, k, workspace tensor, workspace bytes) of the forward and the BPTT cluster plan, where one is in use."""
+        for c in (self._cluster, self._cluster_b):
+            if c is not None and c[1] is not None:
+                yield (c[0][0],) + tuple(c[1])
+
     def check_cluster(self, clear=True):
         """Synchronise and raise if a hand-off of the cluster launches timed out (the last launch, or -- sticky word -- any
         launch since the last check).  `DNCOffsetTracker.check_step()` calls it (the place a training script reads the loss on
         the host); bench.py calls that after its timed loop.  `clear` applies to the memory-partitioned form only: the
         LDS-resident form's status call always reads AND clears its sticky word."""
-        for c in (self._cluster, self._cluster_b):
-            if c is not None and c[1] is not None:
-                form, k, ws, nbytes = c[1]
-                if form == "lds":
-                    _lib.check(_lib.lib().ntk_dnc_cluster_status(_P(ws), c[0][0], k, _lib.stream()), "ntk_dnc_cluster_status")
-                else:
-                    _lib.check(_lib.lib().ntk_dnc_mp_status(_P(ws), nbytes, c[0][0], k, 1 if clear else 0, _lib.stream()), "ntk_dnc_mp_status")
+        for B, form, k, ws, nbytes in self._live_plans():
+            if form == "lds":                       # the two status entries differ in what they take, not only in name
+                _lib.check(_lib.lib().ntk_dnc_cluster_status(_P(ws), B, k, _lib.stream()), "ntk_dnc_cluster_status")
+            else:
+                _lib.check(_lib.lib().ntk_dnc_mp_status(_P(ws), nbytes, B, k, 1 if clear else 0, _lib.stream()), "ntk_dnc_mp_status")
 
     def guard(self, loss=None, grad=None):
         """Device-side propagation of an aborted cluster launch (no synchronisation): if a hand-off of any cluster launch
         since the last check_cluster() timed out, `loss` and every element of `grad` become NaN (ntk_dnc_cluster_guard).
         NaN rather than zero so that the data-parallel SUM all-reduce carries the failure to every rank: the optimiser
         (RMSPropClip.step -> ntk_rmsprop_clip_step_checked) then skips the update everywhere."""
-        for c in (self._cluster, self._cluster_b):
-            if c is not None and c[1] is not None:
-                form, k, ws, nbytes = c[1]
-                _lib.check(_lib.lib().ntk_dnc_cluster_guard(_P(ws), nbytes, 1 if form == "mp" else 0, c[0][0], k,
-                                                            _P(loss) if loss is not None else None,
-                                                            _P(grad) if grad is not None else None,
-                                                            grad.numel() if grad is not None else 0, _lib.stream()),
-                           "ntk_dnc_cluster_guard")
+        for B, form, k, ws, nbytes in self._live_plans():
+            _lib.check(_lib.lib().ntk_dnc_cluster_guard(_P(ws), nbytes, 1 if form == "mp" else 0, B, k,
+                                                        _P(loss) if loss is not None else None,
+                                                        _P(grad) if grad is not None else None,
+                                                        grad.numel() if grad is not None else 0, _lib.stream()),
+                       "ntk_dnc_cluster_guard")
 
     def inject_abort(self, B, bwd=False):
         """Fault injection (tests): set the sticky error word of the forward (or BPTT) cluster workspace at batch B exactly
@@ -411,18 +423,27 @@ class DNC(object):
         """(clusters that ran the same-XCD form of the hand-offs, clusters) of the last forward / BPTT cluster launches;
         a speed diagnostic only (csrc/dnc_cluster.h).  Synchronises."""
         out = []
-        for c in (self._cluster, self._cluster_b):
-            if c is not None and c[1] is not None:
-                form, k, ws, _nb = c[1]
-                n = ctypes.c_int(0)
-                fn = _lib.lib().ntk_dnc_cluster_placement if form == "lds" else _lib.lib().ntk_dnc_mp_placement
-                _lib.check(fn(_P(ws), c[0][0], k, ctypes.byref(n), _lib.stream()), "ntk_dnc_cluster_placement")
-                out.append((n.value, c[0][0]))
+        for B, form, k, ws, _nb in self._live_plans():
+            n, name = ctypes.c_int(0), self.FORM_SYMBOLS[form]["placement"]
+            _lib.check(getattr(_lib.lib(), name)(_P(ws), B, k, ctypes.byref(n), _lib.stream()), name)
+            out.append((n.value, B))
         return out
 
+    def _call_fwd(self, xproj, B, S, state, out, rec):
+        """THE forward call: the cluster kernels (k CUs per sequence) when a form takes the shape at this B, else one workgroup
+        per sequence.  state: the eight buffers in DNCServingState.NAMES order, updated in place; rec: record tensors by name, or
+        empty."""
+        plan = self._cluster_plan(B)
+        form, k, ws = plan[:3] if plan else (None, 1, None)
+        self.last_cluster_k, self.last_cluster_form = k, form
+        name = self.FORM_SYMBOLS[form]["fwd"]
+        _lib.check(getattr(_lib.lib(), name)(
+            B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value, *((k,) if plan else ()),
+            _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), *[_P(t) for t in state], _P(out),
+            *[(_P(rec[n]) if rec else None) for n in self.REC_NAMES], *((_P(ws),) if plan else ()), _lib.stream()), name)
+
     def _launch_fwd(self, xproj, B, S, st, rec):
-        """One sequence-kernel launch over contiguous xproj [B*S, 4*hid] starting from state `st` (not modified):
-        the cluster kernel (k CUs per sequence) when the shape allows, else one workgroup per sequence."""
+        """One sequence-kernel launch over contiguous xproj [B*S, 4*hid] starting from state `st` (not modified)."""
         acc = st.access_state
         # the kernel updates the state in place: work on private copies
         mem, link = acc.memory.clone().contiguous(), acc.linkage.link.clone().contiguous()
@@ -430,21 +451,7 @@ class DNC(object):
         prec, reads = acc.linkage.precedence_weights.clone().contiguous(), st.access_output.clone().contiguous()
         hc = torch.cat([st.controller_state.hidden, st.controller_state.cell], dim=1).contiguous()
         out = torch.empty((B, S, self.O), device=self.device)
-        recp = [(_P(rec[k]) if rec else None) for k in self.REC_NAMES]
-        plan = self._cluster_plan(B)
-        self.last_cluster_k = plan[1] if plan else 1
-        self.last_cluster_form = plan[0] if plan else None
-        if plan:
-            fn = _lib.lib().ntk_dnc_cluster_fwd if plan[0] == "lds" else _lib.lib().ntk_dnc_mp_fwd
-            _lib.check(fn(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value, plan[1],
-                          _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(mem), _P(link), _P(usage),
-                          _P(rw), _P(ww), _P(prec), _P(reads), _P(hc), _P(out), *recp, _P(plan[2]),
-                          _lib.stream()), "ntk_dnc_cluster_fwd" if plan[0] == "lds" else "ntk_dnc_mp_fwd")
-        else:
-            _lib.check(_lib.lib().ntk_dnc_seq_fwd(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value,
-                                                  _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(mem), _P(link), _P(usage),
-                                                  _P(rw), _P(ww), _P(prec), _P(reads), _P(hc), _P(out), *recp, _lib.stream()),
-                       "ntk_dnc_seq_fwd")
+        self._call_fwd(xproj, B, S, (mem, link, usage, rw, ww, prec, reads, hc), out, rec)
         new = DNCState(reads, AccessState(mem, rw, ww, TemporalLinkageState(link, prec), usage),
                        LSTMState(hc[:, :self.hid].contiguous(), hc[:, self.hid:].contiguous()))
         return out, new
@@ -503,22 +510,7 @@ class DNC(object):
             out = torch.empty((B, S, self.O), device=self.device)
         elif tuple(out.shape) != (B, S, self.O):
             raise _lib.NtkError("serve_projected: out is %s, expected %s" % (tuple(out.shape), (B, S, self.O)))
-        st = sstate
-        recp = [None] * len(self.REC_NAMES)
-        plan = self._cluster_plan(B)
-        self.last_cluster_k = plan[1] if plan else 1
-        self.last_cluster_form = plan[0] if plan else None
-        if plan:
-            fn = _lib.lib().ntk_dnc_cluster_fwd if plan[0] == "lds" else _lib.lib().ntk_dnc_mp_fwd
-            _lib.check(fn(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value, plan[1],
-                          _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(st.mem), _P(st.link), _P(st.usage),
-                          _P(st.rw), _P(st.ww), _P(st.prec), _P(st.reads), _P(st.hc), _P(out), *recp, _P(plan[2]),
-                          _lib.stream()), "ntk_dnc_cluster_fwd" if plan[0] == "lds" else "ntk_dnc_mp_fwd")
-        else:
-            _lib.check(_lib.lib().ntk_dnc_seq_fwd(B, S, self.N, self.W, self.R, self.Wn, self.hid, self.O, self.clip_value,
-                                                  _P(xproj), _P(self.Wr), _P(self.Wi), _P(self.Wy), _P(st.mem), _P(st.link),
-                                                  _P(st.usage), _P(st.rw), _P(st.ww), _P(st.prec), _P(st.reads), _P(st.hc),
-                                                  _P(out), *recp, _lib.stream()), "ntk_dnc_seq_fwd")
+        self._call_fwd(xproj, B, S, sstate.tensors(), out, {})
         return out
 
     def _launch_bwd(self, B, S, st0, rec, dout, WrT, ldkT, WiT, ldhT, gM, gL, gcarry, carry_in):
@@ -533,24 +525,19 @@ class DNC(object):
         def c(t):
             keep.append(t.contiguous())
             return _P(keep[-1])
-        recs = (_P(rec["gates"]), _P(rec["c"]), _P(rec["ifc"]), _P(rec["u"]), _P(rec["ww"]), _P(rec["rw"]), _P(rec["cw"]),
-                _P(rec["cr"]), _P(rec["al"]), _P(rec["p"]), _P(rec["fwd"]), _P(rec["bwd"]), _P(rec["M"]), _P(rec["L"]),
-                _P(rec["ypre"]), _P(dout), _P(gM), _P(gL), _P(dgates), _P(dxi), _P(dypre),
-                _P(gcarry) if gcarry is not None else None, 1 if carry_in else 0)
+        recs = [_P(rec[n]) for n in self.BWD_REC_NAMES]
         state0 = (c(acc.memory), c(acc.linkage.link), c(acc.usage), c(acc.read_weights), c(acc.write_weights),
                   c(acc.linkage.precedence_weights), _P(hc0))
         plan = self._cluster_bwd_plan(B)
-        self.last_cluster_bwd_k = plan[1] if plan else 1
-        self.last_cluster_bwd_form = plan[0] if plan else None
-        if plan:
-            fn = _lib.lib().ntk_dnc_cluster_bwd if plan[0] == "lds" else _lib.lib().ntk_dnc_mp_bwd
-            _lib.check(fn(B, S, self.N, self.W, self.R, self.Wn, hid, self.O, self.clip_value, plan[1],
-                          _P(WrT), ldkT, _P(self.Wi), _P(self.Wy), *state0, *recs, _P(plan[2]), _lib.stream()),
-                       "ntk_dnc_cluster_bwd" if plan[0] == "lds" else "ntk_dnc_mp_bwd")
-        else:
-            _lib.check(_lib.lib().ntk_dnc_seq_bwd(
-                B, S, self.N, self.W, self.R, self.Wn, hid, self.O, self.clip_value,
-                _P(WrT), ldkT, _P(WiT), ldhT, _P(self.Wy), *state0, *recs, _lib.stream()), "ntk_dnc_seq_bwd")
+        form, k, ws = plan[:3] if plan else (None, 1, None)
+        self.last_cluster_bwd_k, self.last_cluster_bwd_form = k, form
+        name = self.FORM_SYMBOLS[form]["bwd"]
+        # the cluster forms read Wi as the forward does; one workgroup per sequence takes its padded transpose
+        weights = (k, _P(WrT), ldkT, _P(self.Wi)) if plan else (_P(WrT), ldkT, _P(WiT), ldhT)
+        _lib.check(getattr(_lib.lib(), name)(
+            B, S, self.N, self.W, self.R, self.Wn, hid, self.O, self.clip_value, *weights, _P(self.Wy), *state0, *recs,
+            _P(dout), _P(gM), _P(gL), _P(dgates), _P(dxi), _P(dypre), _P(gcarry) if gcarry is not None else None,
+            1 if carry_in else 0, *((_P(ws),) if plan else ()), _lib.stream()), name)
         return dgates, dxi, dypre
 
     def _weight_grads(self, X2, rec, dgates, dxi, dypre, BS, accumulate):

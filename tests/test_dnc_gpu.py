@@ -671,3 +671,17 @@ def test_dnc_cluster_abort_reaches_the_loss_without_a_sync(cuda):
         with pytest.raises(NtkError):
             core.check_cluster()
         core.check_cluster()                                                # the word was cleared
+        # the BPTT workspace has a sticky word of its own (another size, so another place in the mp layout): same path
+        core.run_sequence(x, None, record=True)
+        core.backward_sequence(core.last_X, torch.ones((2, 5, 2), device=cuda))
+        loss.fill_(1.0)
+        core.guard(loss, grad)
+        torch.cuda.synchronize()
+        assert float(loss) == 1.0 and bool(torch.isfinite(grad).all()) and float(grad.abs().max()) > 0
+        assert core.inject_abort(2, bwd=True)
+        core.guard(loss, grad)
+        torch.cuda.synchronize()
+        assert torch.isnan(loss).all() and torch.isnan(grad).all()
+        with pytest.raises(NtkError):
+            core.check_cluster()
+        core.check_cluster()

@@ -184,3 +184,62 @@ def test_named_shapes_pin_the_ranges():
     assert not bad, "\n  ".join(bad)
     assert _fwd_lds_bytes(1024, 16, 4, 1, 64, 2) == 153120 and _bwd_lds_bytes(1024, 16, 4, 1, 64, 2) == 237568
     assert _bwd_lds_bytes(676, 16, 4, 1, 64, 2) == 163792 and _bwd_lds_bytes(680, 16, 4, 1, 64, 2) == 164640
+
+
+# ---- the pointer checks of the two entries (csrc/dnc_common.h: dnc_fwd_check_ptrs / dnc_bwd_check_ptrs).  Every refusal happens on
+# the host: nothing is dereferenced, so fake addresses do.
+NTK_ERR_BAD_PTR = -2
+PTR_SHAPE = (64, 16, 2, 1, 24, 2)
+OFF4 = ctypes.c_void_p((1 << 20) + 4)                       # an address = 4 mod 16
+FWD_PTRS = ("xproj", "Wr", "Wi", "Wy", "mem", "link", "usage", "rw", "ww", "prec", "reads", "hc", "out")
+FWD_RECS = ("rec_z", "rec_gates", "rec_c", "rec_hc", "rec_yin", "rec_ifc", "rec_u", "rec_ww", "rec_rw", "rec_cw", "rec_cr", "rec_al",
+            "rec_p", "rec_fwd", "rec_bwd", "rec_M", "rec_L", "rec_ypre")
+FWD_ALIGNED = ("xproj", "Wr", "Wi", "mem", "link", "rec_gates", "rec_M", "rec_L")
+BWD_PTRS = ("WrT", "WiT", "Wy", "mem0", "link0", "usage0", "rw0", "ww0", "prec0", "hc0", "rec_gates", "rec_c", "rec_ifc", "rec_u",
+            "rec_ww", "rec_rw", "rec_cw", "rec_cr", "rec_al", "rec_p", "rec_fwd", "rec_bwd", "rec_M", "rec_L", "rec_ypre", "dout", "gM",
+            "gL", "dgates", "dxi", "dypre", "gcarry")
+BWD_ALIGNED = ("WrT", "WiT", "rec_gates", "rec_M", "rec_L", "gM", "gL", "dgates", "mem0", "link0")
+
+
+def _fwd_with(L, **ptrs):
+    a = dict.fromkeys(FWD_PTRS + FWD_RECS, P)
+    a.update(ptrs)
+    return L.ntk_dnc_seq_fwd(BATCH, STEPS, *PTR_SHAPE, 20.0, *[a[n] for n in FWD_PTRS + FWD_RECS], None)
+
+
+def _bwd_with(L, **ptrs):
+    a = dict.fromkeys(BWD_PTRS, P)
+    a.update(ptrs)
+    N, W, R, Wn, hid, O = PTR_SHAPE
+    v = [a[n] for n in BWD_PTRS]
+    return L.ntk_dnc_seq_bwd(BATCH, STEPS, *PTR_SHAPE, 20.0, v[0], _a4(R * W + hid), v[1], _a4(hid), *v[2:], 0, None)
+
+
+def _refused(L, rc, entry, what, bad):
+    msg = L.ntk_last_error() or b""
+    if rc != NTK_ERR_BAD_PTR or not msg.startswith(entry.encode()):
+        bad.append("%s, %s: returned %d, reason %r" % (entry, what, rc, msg))
+
+
+def test_pointer_checks_of_the_one_workgroup_entries():
+    L = _lib()
+    assert fwd_ok(*PTR_SHAPE) and bwd_ok(*PTR_SHAPE)
+    bad = []
+    for n in FWD_PTRS:
+        _refused(L, _fwd_with(L, **{n: None}), "ntk_dnc_seq_fwd", n + " null", bad)
+    for n in FWD_ALIGNED:
+        _refused(L, _fwd_with(L, **{n: OFF4}), "ntk_dnc_seq_fwd", n + " at 4 mod 16", bad)
+    none = dict.fromkeys(FWD_RECS, None)
+    for n in FWD_RECS:                                       # 1 of 18, and 17 of 18, each record in turn
+        _refused(L, _fwd_with(L, **dict(none, **{n: P})), "ntk_dnc_seq_fwd", "only " + n, bad)
+        _refused(L, _fwd_with(L, **{n: None}), "ntk_dnc_seq_fwd", "all records but " + n, bad)
+    for n in BWD_PTRS[:-1]:
+        _refused(L, _bwd_with(L, **{n: None}), "ntk_dnc_seq_bwd", n + " null", bad)
+    for n in BWD_ALIGNED:
+        _refused(L, _bwd_with(L, **{n: OFF4}), "ntk_dnc_seq_bwd", n + " at 4 mod 16", bad)
+    # past every host-side check, to the device call
+    for what, rc in (("no records", _fwd_with(L, **none)), ("18 records", _fwd_with(L)), ("BPTT", _bwd_with(L)),
+                     ("BPTT without gcarry", _bwd_with(L, gcarry=None))):
+        if rc != NTK_ERR_HIP:
+            bad.append("%s: returned %d, expected the device call to fail (%d)" % (what, rc, NTK_ERR_HIP))
+    assert not bad, "\n  ".join(bad)

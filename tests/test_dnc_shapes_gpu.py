@@ -254,3 +254,73 @@ def test_dnc_edge_shape_bptt(cuda, name, family, k_fwd, k_bwd):
             bad[k] = (err, err32)
     print("%s/%s relative gradient error (HIP, float32 oracle) vs float64: %s" % (name, family, {k: ("%.1e" % a, "%.1e" % b) for k, (a, b) in worst.items()}))
     assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------- pointer checks of the cluster launchers
+NTK_ERR_BAD_SHAPE, NTK_ERR_BAD_PTR = -1, -2
+PTR_DIMS, PTR_B, PTR_S, PTR_K = (64, 16, 2, 1, 24, 2), 2, 3, 4
+FWD_ALIGNED = ("xproj", "Wr", "Wi", "mem", "link", "rec_gates", "rec_M", "rec_L", "workspace")
+BWD_ALIGNED = ("WrT", "Wi", "rec_gates", "rec_M", "rec_L", "gM", "gL", "dgates", "mem0", "link0", "workspace")
+
+
+@pytest.mark.parametrize("form", ["lds", "mp"])
+def test_cluster_launchers_refuse_bad_pointers_before_anything_is_enqueued(cuda, form):
+    """ntk_dnc_cluster_fwd / _bwd and ntk_dnc_mp_fwd / _bwd at (64, 16, 2, 1, 24, 2), B 2, S 3, k 4, with real tensors: each required
+    pointer null in turn (the workspace among them), each pointer of the 16-byte set at an address = 4 mod 16 (the workspace among
+    them), 1 and 17 of the 18 forward records, and ldkT + 4 on the BPTT entries.  Every call is refused with its code and a reason
+    that names the entry; afterwards the two workspaces still hold the pattern they were filled with: nothing was enqueued."""
+    from ntmtrack import _lib
+    from ntmtrack.dnc import DNC
+    L, P = _lib.lib(), _lib.ptr
+    N, W, R, Wn, hid, O = PTR_DIMS
+    B, S, k = PTR_B, PTR_S, PTR_K
+    core = DNC({"memory_size": N, "word_size": W, "num_reads": R, "num_writes": Wn}, {"hidden_size": hid}, O, 20.0, input_dim=DIN, device=cuda)
+    z = lambda *s: torch.zeros(s, device=cuda)
+    rec = core._alloc_records(B, S)
+    ldkT = (core.K + 3) // 4 * 4
+    sym = core.FORM_SYMBOLS[form]
+    ws = {}
+    for d in ("plan", "bwd_plan"):
+        kk, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+        assert getattr(L, sym[d])(B, *PTR_DIMS, k, ctypes.byref(kk), ctypes.byref(nbytes)) == 0 and kk.value == k
+        ws[d] = torch.full(((nbytes.value + 3) // 4,), 1.25, device=cuda)
+    state = dict(mem=z(B, N, W), link=z(B, Wn, N, N), usage=z(B, N), rw=z(B, R, N), ww=z(B, Wn, N), prec=z(B, Wn, N))
+    fwd = dict(xproj=z(B * S, 4 * hid), Wr=core.Wr, Wi=core.Wi, Wy=core.Wy, **state, reads=z(B, R, W), hc=z(B, 2 * hid), out=z(B, S, O))
+    fwd.update({"rec_" + n: rec[n] for n in core.REC_NAMES}, workspace=ws["plan"])
+    bwd = dict(WrT=z(4 * hid, ldkT), Wi=core.Wi, Wy=core.Wy, **{n + "0": t for n, t in state.items()}, hc0=z(B, 2 * hid))
+    bwd.update({"rec_" + n: rec[n] for n in core.BWD_REC_NAMES}, dout=z(B, S, O), gM=z(B, N, W), gL=z(B, Wn, N, N), dgates=z(B, S, 4 * hid),
+               dxi=z(B, S, core.IP), dypre=z(B, S, core.OP), gcarry=None, workspace=ws["bwd_plan"])
+    assert len(fwd) == 13 + 18 + 1 and len(bwd) == 3 + 7 + 15 + 7 + 1
+    off4 = lambda t: ctypes.c_void_p(t.data_ptr() + 4)
+    bad = []
+
+    def call(entry, args, want, what, ld=ldkT, **swap):
+        a = {n: P(t) for n, t in args.items()}
+        a.update(swap)
+        v = list(a.values())
+        if args is fwd:
+            rc = getattr(L, entry)(B, S, *PTR_DIMS, 20.0, k, *v, _lib.stream())
+        else:
+            rc = getattr(L, entry)(B, S, *PTR_DIMS, 20.0, k, v[0], ld, *v[1:-1], 0, v[-1], _lib.stream())
+        msg = L.ntk_last_error() or b""
+        if rc != want or not msg.startswith(entry.encode()):
+            bad.append("%s, %s: returned %d (expected %d), reason %r" % (entry, what, rc, want, msg))
+
+    recs = ["rec_" + n for n in core.REC_NAMES]
+    for n in fwd:
+        if n not in recs:
+            call(sym["fwd"], fwd, NTK_ERR_BAD_PTR, n + " null", **{n: None})
+    for n in FWD_ALIGNED:
+        call(sym["fwd"], fwd, NTK_ERR_BAD_PTR, n + " at 4 mod 16", **{n: off4(fwd[n])})
+    call(sym["fwd"], fwd, NTK_ERR_BAD_PTR, "1 of 18 records", **{n: None for n in recs[1:]})
+    call(sym["fwd"], fwd, NTK_ERR_BAD_PTR, "17 of 18 records", **{recs[-1]: None})
+    for n in bwd:
+        if n != "gcarry":
+            call(sym["bwd"], bwd, NTK_ERR_BAD_PTR, n + " null", **{n: None})
+    for n in BWD_ALIGNED:
+        call(sym["bwd"], bwd, NTK_ERR_BAD_PTR, n + " at 4 mod 16", **{n: off4(bwd[n])})
+    call(sym["bwd"], bwd, NTK_ERR_BAD_SHAPE, "ldkT + 4", ld=ldkT + 4)
+    assert not bad, "\n  ".join(bad)
+    torch.cuda.synchronize()
+    for d, t in ws.items():
+        assert bool((t == 1.25).all()), "%s: the %s workspace was written" % (form, d)
