@@ -800,6 +800,97 @@ int ntk_track_overlap_scores(const double* regions, const double* gt, const unsi
                              int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr, int n_dist,
                              double* table, double* frame_iou, void* stream);
 
+/* First-frame geometry of the online tracker on the device, for the slots that are (re)started on this frame: what
+ * BatchNTMTracker computes on the host when a tracker is made or reset (test_tracker.py:300-329 and :370-405), masked per slot,
+ * so that a restart costs no second pass and no host arithmetic.  A small bookkeeping kernel: one thread per slot, plain vector
+ * stores, float64 without FMA contraction in the operation order of ntmtrack/geometry.py.
+ *   regions_in  double [B,4] (x, y, w, h) in pixels; a region whose four numbers are all < 1 is taken as already normalised
+ *               (test_tracker.py:306-309), any other is divided by (H-1, W-1) (normalize_bbox)
+ *   restart     uint8 [B]
+ *   active      uint8 [B], nullable = all active: read only to form the two masks below
+ *   state       double [B, NTK_TRACK_STATE_DOUBLES]: W and H are read
+ *   cropbox_grid, bbox_grid, sigma: sigma as generate_gt computes it (integer division of bbox_grid by the focus included);
+ *               cropbox_grid must be a whole number g, the heat-map grid is g x g and gts_width must be g * g
+ * A slot with restart[b] != 0: the crop box is the object box scaled about its centre by cropbox_grid / bbox_grid
+ * (calculate_cropbox); state[2..9], cropbox32 fp32 [B,4], regions double [B,4] (= the region given), offsets fp32 [B,2] = 0 and
+ * frame int32 [B] = 0 are written; gts0 fp32 [B, g*g] gets the heat-map row: the object box through the transformation that maps
+ * the crop box to the unit square (apply_transformation), exp(-r^2 / 2 sigma^2) at the cell centres of the grid about the box
+ * centre, values below eps * max dropped, normalised to sum 1 (discrete_gauss), cast to fp32.
+ * A slot with restart[b] == 0: its gts0 row is written as zeros (what ntk_gather_serialize_online takes a null gts0 for: the row
+ * serialises to the same bits) and NOTHING else of it is written.
+ * run_mask, move_mask uint8 [B], both nullable, written for every slot: run_mask = active | restart (the slots whose recurrent
+ * state the frame's sequence advances), move_mask = active & ~restart (the slots whose output moves their box: the output of a
+ * first-frame pass is discarded).
+ * Errors, before any launch: NTK_ERR_BAD_PTR for any other null pointer; NTK_ERR_BAD_SHAPE, the value named in ntk_last_error,
+ * for B outside 1..65535, a grid or sigma <= 0, a cropbox_grid that is not whole or above 1024, gts_width != g * g. */
+int ntk_track_restart_boxes(const double* regions_in, const unsigned char* restart, const unsigned char* active, int B,
+                            double cropbox_grid, double bbox_grid, double sigma, int gts_width, double* state, float* cropbox32,
+                            double* regions, float* offsets, int* frame, float* gts0, unsigned char* run_mask,
+                            unsigned char* move_mask, void* stream);
+
+/* The supervised protocol on the device: a tracker that has lost its object is started again from the ground truth a few frames
+ * later, accuracy is the mean overlap outside a burn-in after every start, robustness the number of failures.  The model is the
+ * behaviour of the VOT toolkit's supervised experiment.  Nothing in the reference pins these rules (its vot.py only hands regions
+ * to the toolkit, which does the restarts itself): THE RULES BELOW ARE THE CONTRACT.
+ * One call is one phase of ONE frame for B slots, one thread per slot; a frame is plan, the tracker's pass, judge.
+ *   state    int32 [B, NTK_SUP_STATE_INTS]: [NTK_SUP_STATE_MODE] NTK_SUP_MODE_TRACK / NTK_SUP_MODE_WAIT, [NTK_SUP_STATE_COUNTDOWN]
+ *            frames until the restart, [NTK_SUP_STATE_SINCE] frames tracked since the last start.  A clip's frame 0 starts the
+ *            slot and counts as a start: THE OWNER SETS THE ROW TO (TRACK, 0, 0) when a slot takes a new clip.
+ *   table    double [n_clips, NTK_SUP_HEAD], row clip_of[b], accumulated in place; every field a double, every count exact:
+ *     [NTK_SUP_VALID]          frames that count towards accuracy
+ *     [NTK_SUP_SUM_IOU]        sum of their overlaps, added in frame order
+ *     [NTK_SUP_FAILURES]       [NTK_SUP_RESTARTS]
+ *     [NTK_SUP_TRACKED]        frames judged
+ *     [NTK_SUP_SKIPPED]        frames a slot sat out while it waited
+ *     [NTK_SUP_FIRST_FAILURE]  the value of TRACKED when the first failure arrived; THE OWNER INITIALISES IT TO -1, the rest to 0
+ *   clip_of  int32 [B]: as for ntk_track_overlap_scores -- a row outside [0, n_clips) skips the slot (code -1 in plan, nothing
+ *            in judge), and NO TWO SLOTS MAY NAME ONE ROW
+ *   gt       double [B,4] (x, y, w, h): this frame's ground truth; valid = finite with w > 0 and h > 0
+ * phase NTK_SUP_PLAN, before the pass (active uint8 [B], nullable = all active; writes track and restart uint8 [B], every entry):
+ *   an inactive slot: code -1, track = restart = 0, nothing else.
+ *   mode TRACK: track[b] = 1 (code 0 until judge has seen the frame).
+ *   mode WAIT: countdown = max(countdown - 1, 0); then, if countdown == 0 and the ground truth is valid: restart[b] = 1,
+ *     RESTARTS += 1, mode TRACK, since = 0, code 1 -- the caller hands restart and this gt to ntk_track_restart_boxes;
+ *     otherwise the slot sits the frame out: SKIPPED += 1, code 3 (a slot whose object is absent on its restart frame waits for
+ *     the first frame that has one).
+ * phase NTK_SUP_JUDGE, after the pass (regions double [B,4]: the tracked regions; track as plan wrote it), slots with track != 0:
+ *   ground truth not valid: since += 1, code 0, counted nowhere.
+ *   otherwise o = the overlap of ntk_track_overlap_scores (the same device function: corners first, no FMA contraction, clamped
+ *     to [0,1], touching boxes exactly 0; a prediction that is not finite scores 0, negative sizes are clamped to 0);
+ *     TRACKED += 1; if o <= failure_overlap: FAILURES += 1, FIRST_FAILURE set if it was < 0, code 2, mode WAIT, countdown = skip;
+ *     else since += 1 and, when since > burn_in, VALID += 1 and SUM_IOU += o; code 0.
+ * So a slot that fails on frame f is restarted on frame f + skip (or the first later frame with an object) and is judged again
+ * from the frame after that.  codes int8 [B] and frame_iou double [B] are nullable: plan writes every code and fills frame_iou
+ * with NaN, judge overwrites both for the slots it judged.  Frames are separate calls, so any split of a clip into calls leaves
+ * the same bits.
+ * Errors, before any launch: NTK_ERR_BAD_SHAPE, the value named in ntk_last_error, for a phase other than the two, B outside
+ * 1..65535, n_clips <= 0, skip < 1, burn_in < 0, failure_overlap outside [0,1); NTK_ERR_BAD_PTR for a null gt / clip_of / state /
+ * table / track, a null restart in plan, a null regions in judge. */
+#define NTK_SUP_PLAN   0
+#define NTK_SUP_JUDGE  1
+#define NTK_SUP_STATE_INTS       3
+#define NTK_SUP_STATE_MODE       0
+#define NTK_SUP_STATE_COUNTDOWN  1
+#define NTK_SUP_STATE_SINCE      2
+#define NTK_SUP_MODE_TRACK  0
+#define NTK_SUP_MODE_WAIT   1
+#define NTK_SUP_VALID          0
+#define NTK_SUP_SUM_IOU        1
+#define NTK_SUP_FAILURES       2
+#define NTK_SUP_RESTARTS       3
+#define NTK_SUP_TRACKED        4
+#define NTK_SUP_SKIPPED        5
+#define NTK_SUP_FIRST_FAILURE  6
+#define NTK_SUP_HEAD           7
+#define NTK_SUP_CODE_INACTIVE (-1)
+#define NTK_SUP_CODE_TRACKED   0
+#define NTK_SUP_CODE_RESTART   1
+#define NTK_SUP_CODE_FAILURE   2
+#define NTK_SUP_CODE_SKIPPED   3
+int ntk_track_supervise(int phase, const double* regions, const double* gt, const unsigned char* active, const int* clip_of, int B,
+                        int n_clips, int skip, int burn_in, double failure_overlap, int* state, double* table,
+                        unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou, void* stream);
+
 /* out[b,:] = mask[b] ? a[b,:] : b[b,:] for fp32 [B,n] rows, mask uint8 [B] on the device (out may alias a or b): keeps the
  * recurrent state of a tracker that sat a frame out. */
 int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);

@@ -123,6 +123,8 @@ def _sig(lib):
         "ntk_crop_and_resize_batch": (c_int, [P] + [c_int] * 5 + [P, P, P, P] + [c_int] * 3 + [ctypes.c_float, P]),
         "ntk_track_boxes_update": (c_int, [P, c_int, c_int, ctypes.c_double, ctypes.c_double] + [P] * 6 + [P]),
         "ntk_track_overlap_scores": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
+        "ntk_track_restart_boxes": (c_int, [P, P, P, c_int] + [ctypes.c_double] * 3 + [c_int] + [P] * 8 + [P]),
+        "ntk_track_supervise": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
         "ntk_select_rows": (c_int, [P, P, P, P, c_int, c_int, P]),
         "ntk_dnc_state_keep": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
         "ntk_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),

@@ -572,6 +572,164 @@ __global__ void track_overlap_scores_kernel(const double* __restrict__ regions, 
     row[NTK_SCORE_FIRST_LOST] = first_lost;
 }
 
+// First-frame geometry of the online tracker for the slots that restart on this frame (BatchNTMTracker._first_frame_inputs on the
+// device, masked): one thread per slot, float64 in the operation order of ntmtrack/geometry.py, no contraction, so the state
+// row, the crop box and the region have the bits of the NumPy path.  The heat-map row is discrete_gauss on the g x g grid about
+// the centre of the object box taken through the crop transformation; the exponentials are evaluated three times (maximum, sum,
+// values) rather than kept in g * g registers.  A slot that does not restart has its gts0 row zeroed and nothing else written.
+__global__ void track_restart_boxes_kernel(const double* __restrict__ regions_in, const unsigned char* __restrict__ restart,
+                                           const unsigned char* __restrict__ active, int B, double cropbox_grid, double bbox_grid,
+                                           double sigma, int g, double* __restrict__ state, float* __restrict__ cropbox32,
+                                           double* __restrict__ regions, float* __restrict__ offsets, int* __restrict__ frame,
+                                           float* __restrict__ gts0, unsigned char* __restrict__ run_mask,
+                                           unsigned char* __restrict__ move_mask) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const bool rs = restart[b] != 0, act = !active || active[b];
+    if (run_mask) run_mask[b] = (rs || act) ? 1 : 0;
+    if (move_mask) move_mask[b] = (act && !rs) ? 1 : 0;
+    float* hm = gts0 + (size_t)b * g * g;
+    if (!rs) {
+        for (int i = 0; i < g * g; ++i) hm[i] = 0.f;
+        return;
+    }
+    double* st = state + (size_t)b * NTK_TRACK_STATE_DOUBLES;
+    const double* rin = regions_in + 4 * (size_t)b;
+    const double x1 = rin[0], y1 = rin[1], rw = rin[2], rh = rin[3];
+    const double w = st[NTK_TRACK_STATE_W], h = st[NTK_TRACK_STATE_H];
+    const bool normalized = x1 < 1 && y1 < 1 && rw < 1 && rh < 1;
+    double n0 = y1, n1 = x1, n2 = y1 + rh, n3 = x1 + rw;
+    if (!normalized) {
+        const double by = h - 1, bx = w - 1;
+        n0 = n0 / by; n1 = n1 / bx; n2 = n2 / by; n3 = n3 / bx;
+    }
+    const double scale = cropbox_grid / bbox_grid;
+    const double cy = (n0 + n2) / 2, cx = (n1 + n3) / 2, hy = (n2 - n0) * scale / 2, hx = (n3 - n1) * scale / 2;
+    const double c0 = cy - hy, c1 = cx - hx, c2 = cy + hy, c3 = cx + hx;
+    double* nb = st + NTK_TRACK_STATE_BBOX;
+    double* ncb = st + NTK_TRACK_STATE_CROPBOX;
+    nb[0] = n0; nb[1] = n1; nb[2] = n2; nb[3] = n3;
+    ncb[0] = c0; ncb[1] = c1; ncb[2] = c2; ncb[3] = c3;
+    float* c32 = cropbox32 + 4 * (size_t)b;
+    c32[0] = (float)c0; c32[1] = (float)c1; c32[2] = (float)c2; c32[3] = (float)c3;
+    double* rg = regions + 4 * (size_t)b;
+    rg[0] = x1; rg[1] = y1; rg[2] = rw; rg[3] = rh;
+    offsets[2 * (size_t)b] = 0.f;
+    offsets[2 * (size_t)b + 1] = 0.f;
+    frame[b] = 0;
+    // the object box through the map that sends the crop box to the unit square (rows (sx, 0, -x1 sx) and (0, sy, -y1 sy))
+    const double sx = 1.0 / (c3 - c1), sy = 1.0 / (c2 - c0);
+    const double tx = -c1 * sx, ty = -c0 * sy;
+    const double ux1 = sx * n1 + tx, ux2 = sx * n3 + tx, uy1 = sy * n0 + ty, uy2 = sy * n2 + ty;
+    const double mx = (ux1 + ux2) / 2., my = (uy1 + uy2) / 2.;
+    const double x0 = 0.5 - mx * g, y0 = 0.5 - my * g, den = 2.0 * sigma * sigma;
+    double top = 0.0;
+    for (int iy = 0; iy < g; ++iy)
+        for (int ix = 0; ix < g; ++ix) {
+            const double ys = y0 + iy, xs = x0 + ix;
+            top = fmax(top, exp(-(ys * ys + xs * xs) / den));
+        }
+    const double cut = 2.220446049250313e-16 * top;             // np.finfo(float64).eps * max
+    double total = 0.0;
+    for (int iy = 0; iy < g; ++iy)
+        for (int ix = 0; ix < g; ++ix) {
+            const double ys = y0 + iy, xs = x0 + ix;
+            const double v = exp(-(ys * ys + xs * xs) / den);
+            total += v < cut ? 0.0 : v;
+        }
+    for (int iy = 0; iy < g; ++iy)
+        for (int ix = 0; ix < g; ++ix) {
+            const double ys = y0 + iy, xs = x0 + ix;
+            double v = exp(-(ys * ys + xs * xs) / den);
+            v = v < cut ? 0.0 : v;
+            hm[iy * g + ix] = (float)(total != 0 ? v / total : v);
+        }
+}
+
+__device__ __forceinline__ bool present4(const double* g) { return finite4(g) && g[2] > 0 && g[3] > 0; }
+
+// The supervised protocol's state machine (contract: include/ntmtrack.h, NTK_SUP_*), one thread per slot, one frame per call.
+// plan decides before the frame's pass what every slot does on it; judge scores the tracked slots after the pass with the one
+// rect_iou of the overlap table and moves a failed slot to WAIT.  The table row belongs to the slot's thread alone.
+__global__ void track_supervise_plan_kernel(const double* __restrict__ gt, const unsigned char* __restrict__ active,
+                                            const int* __restrict__ clip_of, int B, int n_clips, int* __restrict__ state,
+                                            double* __restrict__ table, unsigned char* __restrict__ track,
+                                            unsigned char* __restrict__ restart, signed char* __restrict__ codes,
+                                            double* __restrict__ frame_iou) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (frame_iou) frame_iou[b] = __longlong_as_double(0x7ff8000000000000LL);
+    const int clip = clip_of[b];
+    unsigned char tr = 0, rs = 0;
+    signed char code = NTK_SUP_CODE_INACTIVE;
+    if (clip >= 0 && clip < n_clips && (!active || active[b])) {
+        int* st = state + (size_t)b * NTK_SUP_STATE_INTS;
+        double* row = table + (size_t)clip * NTK_SUP_HEAD;
+        if (st[NTK_SUP_STATE_MODE] == NTK_SUP_MODE_TRACK) {
+            tr = 1;
+            code = NTK_SUP_CODE_TRACKED;
+        } else {
+            const int left = st[NTK_SUP_STATE_COUNTDOWN] > 1 ? st[NTK_SUP_STATE_COUNTDOWN] - 1 : 0;
+            st[NTK_SUP_STATE_COUNTDOWN] = left;
+            if (left == 0 && present4(gt + 4 * (size_t)b)) {
+                rs = 1;
+                code = NTK_SUP_CODE_RESTART;
+                row[NTK_SUP_RESTARTS] += 1.0;
+                st[NTK_SUP_STATE_MODE] = NTK_SUP_MODE_TRACK;
+                st[NTK_SUP_STATE_SINCE] = 0;
+            } else {
+                code = NTK_SUP_CODE_SKIPPED;
+                row[NTK_SUP_SKIPPED] += 1.0;
+            }
+        }
+    }
+    track[b] = tr;
+    restart[b] = rs;
+    if (codes) codes[b] = code;
+}
+
+__global__ void track_supervise_judge_kernel(const double* __restrict__ regions, const double* __restrict__ gt,
+                                             const unsigned char* __restrict__ track, const int* __restrict__ clip_of, int B,
+                                             int n_clips, int skip, int burn_in, double failure_overlap, int* __restrict__ state,
+                                             double* __restrict__ table, signed char* __restrict__ codes,
+                                             double* __restrict__ frame_iou) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int clip = clip_of[b];
+    if (clip < 0 || clip >= n_clips || !track[b]) return;
+    int* st = state + (size_t)b * NTK_SUP_STATE_INTS;
+    const double* g = gt + 4 * (size_t)b;
+    if (!present4(g)) {                                      // tracked, the object absent: the frame is counted nowhere
+        st[NTK_SUP_STATE_SINCE] += 1;
+        if (codes) codes[b] = NTK_SUP_CODE_TRACKED;
+        return;
+    }
+    const double* p = regions + 4 * (size_t)b;
+    double iou = 0.0;
+    if (finite4(p)) iou = rect_iou(p[0], p[1], fmax(p[2], 0.0), fmax(p[3], 0.0), g[0], g[1], g[2], g[3]);
+    double* row = table + (size_t)clip * NTK_SUP_HEAD;
+    const double tracked = row[NTK_SUP_TRACKED];
+    row[NTK_SUP_TRACKED] = tracked + 1.0;
+    if (frame_iou) frame_iou[b] = iou;
+    if (iou <= failure_overlap) {
+        row[NTK_SUP_FAILURES] += 1.0;
+        if (row[NTK_SUP_FIRST_FAILURE] < 0) row[NTK_SUP_FIRST_FAILURE] = tracked;
+        st[NTK_SUP_STATE_MODE] = NTK_SUP_MODE_WAIT;
+        st[NTK_SUP_STATE_COUNTDOWN] = skip;
+        if (codes) codes[b] = NTK_SUP_CODE_FAILURE;
+        return;
+    }
+    const int since = st[NTK_SUP_STATE_SINCE] + 1;
+    st[NTK_SUP_STATE_SINCE] = since;
+    if (since > burn_in) {
+        row[NTK_SUP_VALID] += 1.0;
+        row[NTK_SUP_SUM_IOU] += iou;
+    }
+    if (codes) codes[b] = NTK_SUP_CODE_TRACKED;
+}
+
 // out[b, :] = mask[b] ? a[b, :] : b_[b, :]   (out may be a or b_: every element is read and written by the same thread)
 __global__ void select_rows_kernel(const unsigned char* __restrict__ mask, const float* a, const float* b_, float* out,
                                    size_t total, int n) {
@@ -698,6 +856,47 @@ extern "C" int ntk_track_overlap_scores(const double* regions, const double* gt,
     track_overlap_scores_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, active, clip_of, T, B, n_clips, iou_thr,
                                                                               n_iou, dist_thr, n_dist, table, frame_iou);
     NTK_CHECK_LAUNCH("ntk_track_overlap_scores");
+    return NTK_OK;
+}
+
+extern "C" int ntk_track_restart_boxes(const double* regions_in, const unsigned char* restart, const unsigned char* active, int B,
+                                       double cropbox_grid, double bbox_grid, double sigma, int gts_width, double* state,
+                                       float* cropbox32, double* regions, float* offsets, int* frame, float* gts0,
+                                       unsigned char* run_mask, unsigned char* move_mask, void* stream) {
+    NTK_REQUIRE(regions_in && restart && state && cropbox32 && regions && offsets && frame && gts0, NTK_ERR_BAD_PTR,
+                "ntk_track_restart_boxes: null pointer");
+    NTK_REQUIRE(B > 0 && B <= 65535, NTK_ERR_BAD_SHAPE, "ntk_track_restart_boxes: B=%d (1..65535)", B);
+    NTK_REQUIRE(cropbox_grid > 0 && bbox_grid > 0 && sigma > 0, NTK_ERR_BAD_SHAPE,
+                "ntk_track_restart_boxes: cropbox_grid=%g bbox_grid=%g sigma=%g", cropbox_grid, bbox_grid, sigma);
+    const int g = cropbox_grid <= 1024 ? (int)cropbox_grid : 0;
+    NTK_REQUIRE(g >= 1 && (double)g == cropbox_grid && g * g == gts_width, NTK_ERR_BAD_SHAPE,
+                "ntk_track_restart_boxes: gts_width=%d for cropbox_grid=%g (a whole number up to 1024, gts_width its square)",
+                gts_width, cropbox_grid);
+    track_restart_boxes_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions_in, restart, active, B, cropbox_grid, bbox_grid,
+                                                                             sigma, g, state, cropbox32, regions, offsets, frame,
+                                                                             gts0, run_mask, move_mask);
+    NTK_CHECK_LAUNCH("ntk_track_restart_boxes");
+    return NTK_OK;
+}
+
+extern "C" int ntk_track_supervise(int phase, const double* regions, const double* gt, const unsigned char* active,
+                                   const int* clip_of, int B, int n_clips, int skip, int burn_in, double failure_overlap,
+                                   int* state, double* table, unsigned char* track, unsigned char* restart, signed char* codes,
+                                   double* frame_iou, void* stream) {
+    NTK_REQUIRE(phase == NTK_SUP_PLAN || phase == NTK_SUP_JUDGE, NTK_ERR_BAD_SHAPE,
+                "ntk_track_supervise: phase=%d (NTK_SUP_PLAN or NTK_SUP_JUDGE)", phase);
+    NTK_REQUIRE(gt && clip_of && state && table && track && (phase == NTK_SUP_PLAN ? restart != nullptr : regions != nullptr),
+                NTK_ERR_BAD_PTR, "ntk_track_supervise: null pointer");
+    NTK_REQUIRE(B > 0 && B <= 65535 && n_clips > 0, NTK_ERR_BAD_SHAPE, "ntk_track_supervise: B=%d (1..65535) n_clips=%d", B, n_clips);
+    NTK_REQUIRE(skip >= 1 && burn_in >= 0 && failure_overlap >= 0 && failure_overlap < 1, NTK_ERR_BAD_SHAPE,
+                "ntk_track_supervise: skip=%d (>= 1) burn_in=%d (>= 0) failure_overlap=%g (in [0,1))", skip, burn_in, failure_overlap);
+    if (phase == NTK_SUP_PLAN)
+        track_supervise_plan_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(gt, active, clip_of, B, n_clips, state, table, track,
+                                                                                  restart, codes, frame_iou);
+    else
+        track_supervise_judge_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, track, clip_of, B, n_clips, skip, burn_in,
+                                                                                   failure_overlap, state, table, codes, frame_iou);
+    NTK_CHECK_LAUNCH("ntk_track_supervise");
     return NTK_OK;
 }
 

@@ -4,9 +4,11 @@ accumulated in one device table (ntk_track_overlap_scores) that is read back onc
 
   ClipSchedule   which clip sits in which slot in which round (host arithmetic only: no torch, no device)
   OverlapScores  the device table and its one synchronising read-out
+  Supervisor     the supervised protocol (a lost tracker is restarted from the ground truth): per-slot state and per-clip table
+                 on the device (ntk_track_supervise), decided frame by frame without a read-back
   Validation     the driver: per round the resets, ONE track_clip and ONE scores.add, no host synchronisation after the first
                  round of a frame size
-  validate       runs a Validation to the end
+  validate       runs a Validation to the end; protocol="one_pass" (the default) or "supervised"
 
 The overlap is the VOT / OTB one on real-valued rectangles.  The reference's own bb_iou (test_tracker.py:59-83) is never called
 there, uses a +1 pixel convention and does not clamp an empty intersection: it is not the model here.
@@ -18,6 +20,14 @@ import numpy as np
 # row layout of the score table: include/ntmtrack.h NTK_SCORE_*
 SCORE_FRAMES, SCORE_SUM_IOU, SCORE_SUM_DIST, SCORE_LOST, SCORE_FIRST_LOST, SCORE_HEAD = 0, 1, 2, 3, 4, 5
 SCORE_MAX_THRESHOLDS = 256
+
+# include/ntmtrack.h NTK_SUP_*: the supervised protocol's table row, slot state, modes, phases and per-frame codes
+SUP_VALID, SUP_SUM_IOU, SUP_FAILURES, SUP_RESTARTS, SUP_TRACKED, SUP_SKIPPED, SUP_FIRST_FAILURE, SUP_HEAD = 0, 1, 2, 3, 4, 5, 6, 7
+SUP_STATE_MODE, SUP_STATE_COUNTDOWN, SUP_STATE_SINCE, SUP_STATE_INTS = 0, 1, 2, 3
+SUP_MODE_TRACK, SUP_MODE_WAIT = 0, 1
+SUP_PLAN, SUP_JUDGE = 0, 1
+SUP_CODE_INACTIVE, SUP_CODE_TRACKED, SUP_CODE_RESTART, SUP_CODE_FAILURE, SUP_CODE_SKIPPED = -1, 0, 1, 2, 3
+PROTOCOLS = ("one_pass", "supervised")
 
 Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
 
@@ -163,6 +173,92 @@ class OverlapScores(object):
         return summarize(self.table.cpu().numpy(), self.iou_thresholds, self.dist_thresholds)
 
 
+def summarize_supervised(table):
+    """The host arithmetic of Supervisor.result(): table [n_clips, SUP_HEAD] float64 -> dict.  ``clips`` holds per clip ``accuracy``
+    (SUM_IOU / VALID: the mean overlap outside the burn-in after every start; NaN without a valid frame), ``valid``, ``failures``,
+    ``restarts``, ``tracked`` (frames judged), ``skipped`` and ``first_failure`` (frames judged before the first failure, -1 =
+    never); over the set ``accuracy_clips`` (the mean over the clips that have one), ``accuracy_frames`` (frame-weighted),
+    ``failures``, ``restarts``, ``tracked``, ``skipped``, ``valid``, ``failures_per_100_frames`` (of the judged frames) and
+    ``clips_never_failed``."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, SUP_HEAD)
+    valid = table[:, SUP_VALID]
+    has = valid > 0
+    accuracy = table[:, SUP_SUM_IOU] / np.where(has, valid, np.nan)
+    as_int = lambda c: table[:, c].astype(np.int64)
+    clips = {"accuracy": accuracy, "valid": as_int(SUP_VALID), "failures": as_int(SUP_FAILURES), "restarts": as_int(SUP_RESTARTS),
+             "tracked": as_int(SUP_TRACKED), "skipped": as_int(SUP_SKIPPED), "first_failure": as_int(SUP_FIRST_FAILURE)}
+    tracked, total_valid = table[:, SUP_TRACKED].sum(), valid.sum()
+    return {"clips": clips,
+            "accuracy_clips": float(np.mean(accuracy[has])) if has.any() else np.nan,
+            "accuracy_frames": table[:, SUP_SUM_IOU].sum() / (total_valid if total_valid > 0 else np.nan),
+            "failures": int(table[:, SUP_FAILURES].sum()), "restarts": int(table[:, SUP_RESTARTS].sum()),
+            "tracked": int(tracked), "skipped": int(table[:, SUP_SKIPPED].sum()), "valid": int(total_valid),
+            "failures_per_100_frames": 100.0 * table[:, SUP_FAILURES].sum() / (tracked if tracked > 0 else np.nan),
+            "clips_never_failed": int(((table[:, SUP_TRACKED] > 0) & (table[:, SUP_FIRST_FAILURE] < 0)).sum())}
+
+
+class Supervisor(object):
+    """The supervised protocol for B slots and n_clips clips on the device (the rules: include/ntmtrack.h, ntk_track_supervise): a
+    slot whose overlap falls to ``failure_overlap`` or below has failed, sits ``skip`` frames out and is started again from the
+    ground truth; a frame counts towards accuracy when more than ``burn_in`` frames were tracked since the last start.
+    ``state`` int32 [B, SUP_STATE_INTS] and ``table`` float64 [n_clips, SUP_HEAD] live on the device; ``plan`` and ``judge`` are
+    one launch each and synchronise nothing, ``result`` is the one synchronising call."""
+
+    def __init__(self, B, n_clips, skip=5, burn_in=10, failure_overlap=0.0, device="cuda"):
+        import torch
+        self.B, self.n_clips = int(B), int(n_clips)
+        self.skip, self.burn_in, self.failure_overlap = int(skip), int(burn_in), float(failure_overlap)
+        if self.B < 1 or self.n_clips < 1 or self.skip < 1 or self.burn_in < 0 or not 0 <= self.failure_overlap < 1:
+            raise ValueError("Supervisor: B=%d n_clips=%d skip=%d (>= 1) burn_in=%d (>= 0) failure_overlap=%g (in [0,1))"
+                             % (self.B, self.n_clips, self.skip, self.burn_in, self.failure_overlap))
+        self.device = torch.device(device)
+        self.state = torch.zeros((self.B, SUP_STATE_INTS), dtype=torch.int32, device=self.device)      # (TRACK, 0, 0)
+        self.table = torch.zeros((self.n_clips, SUP_HEAD), dtype=torch.float64, device=self.device)
+        self.table[:, SUP_FIRST_FAILURE] = -1
+        self.track = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
+        self.restart = torch.zeros((self.B,), dtype=torch.uint8, device=self.device)
+        self.codes = None                               # [T,B] int8 of the last track_clip
+
+    def start(self, slots):
+        """The slots take a new clip: their state rows become (TRACK, 0, 0).  An index fill from a pinned upload: no synchronisation."""
+        from .online import _upload
+        import torch
+        slots = [int(s) for s in slots]
+        if not all(0 <= s < self.B for s in slots):
+            raise ValueError("Supervisor.start: slots %s outside [0,%d)" % (slots, self.B))
+        if slots:
+            self.state.index_fill_(0, _upload(np.asarray(slots), torch.int64, self.device), 0)
+
+    def _call(self, phase, regions, gt, active, clip_of, codes, frame_iou):
+        import torch
+        from . import _lib
+        for name, t, dtype, shape in (("regions", regions, torch.float64, (self.B, 4)), ("gt", gt, torch.float64, (self.B, 4)),
+                                      ("active", active, torch.uint8, (self.B,)), ("clip_of", clip_of, torch.int32, (self.B,)),
+                                      ("codes", codes, torch.int8, (self.B,)), ("frame_iou", frame_iou, torch.float64, (self.B,))):
+            if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape):
+                raise _lib.NtkError("Supervisor: %s must be a %s tensor of shape %s" % (name, dtype, shape))
+        P = _lib.ptr
+        _lib.check(_lib.lib().ntk_track_supervise(phase, P(regions), P(gt), P(active), P(clip_of), self.B, self.n_clips, self.skip,
+                                                  self.burn_in, self.failure_overlap, P(self.state), P(self.table), P(self.track),
+                                                  P(self.restart), P(codes), P(frame_iou), _lib.stream()), "ntk_track_supervise")
+
+    def plan(self, gt_t, active_t, clip_of, codes=None, frame_iou=None):
+        """Before the frame's pass.  gt_t float64 [B,4], active_t uint8 [B] (nullable), clip_of int32 [B], on the device.
+        -> (track, restart) uint8 [B]: the masks of the pass (the supervisor's own buffers, overwritten by the next plan).  codes
+        int8 [B] and frame_iou float64 [B] (nullable) are filled for every slot."""
+        self._call(SUP_PLAN, None, gt_t, active_t, clip_of, codes, frame_iou)
+        return self.track, self.restart
+
+    def judge(self, regions, gt_t, clip_of, codes=None, frame_iou=None):
+        """After the pass: the tracked slots (the last plan's ``track``) are scored against gt_t; codes / frame_iou as given to
+        plan are completed."""
+        self._call(SUP_JUDGE, regions, gt_t, None, clip_of, codes, frame_iou)
+
+    def result(self):
+        """Reads the table back (the one synchronisation) -> summarize_supervised(table)."""
+        return summarize_supervised(self.table.cpu().numpy())
+
+
 def _as_clip(c):
     if isinstance(c, Clip):
         return c
@@ -176,6 +272,7 @@ def _as_clip(c):
 class _SizeClass(object):
     def __init__(self, size, members):
         self.size, self.members, self.tracker = size, members, None      # members: the caller's clip indices, in order
+        self.supervisor = None
 
 
 class Validation(object):
@@ -184,10 +281,19 @@ class Validation(object):
     ``frames`` and ``regions``).  ``step()`` runs one round -- reset for the slots that take a new clip, one track_clip over
     frames [T,B,H,W,3] with the round's mask, one scores.add -- and returns False when no round was left.  After the first round
     of a frame size (which builds the tracker, its plans and workspaces) a round makes no host synchronisation.  ``scores`` is
-    the OverlapScores, rows in the caller's clip order; ``regions()`` the tracked regions per clip when return_regions was set."""
+    the OverlapScores, rows in the caller's clip order; ``regions()`` the tracked regions per clip when return_regions was set.
 
-    def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda"):
+    ``protocol="supervised"`` runs the supervised protocol instead (Supervisor; ``skip``, ``burn_in``, ``failure_overlap``): the
+    same schedule and the same resets, a round is one track_clip with the supervisor, which restarts a lost slot from the ground
+    truth inside the pass.  ``supervisor`` then holds the table (``scores`` stays empty), ``codes()`` the per-frame codes per clip
+    beside ``regions()``, whose skipped frames hold NaN.  Still no host synchronisation after the first round of a frame size."""
+
+    def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda",
+                 protocol="one_pass", skip=5, burn_in=10, failure_overlap=0.0):
         import torch
+        if protocol not in PROTOCOLS:
+            raise ValueError("Validation: protocol %r; one of %s" % (protocol, ", ".join(PROTOCOLS)))
+        self.protocol = protocol
         self.make_tracker, self.device = make_tracker, torch.device(device)
         self.clips = [_as_clip(c) for c in clips]
         if not self.clips:
@@ -200,6 +306,8 @@ class Validation(object):
             classes.setdefault(self._size(i), []).append(i)
         self.classes = [_SizeClass(size, members) for size, members in classes.items()]
         self.scores = OverlapScores(len(self.clips), iou_thresholds, dist_thresholds, device=self.device)
+        self._sup_args = (skip, burn_in, failure_overlap) if protocol == "supervised" else None
+        self.supervisor = None                          # made with the first round: it needs the schedule's effective B
         self._keep = [] if return_regions else None     # (device regions [T,B,4], frame_index, active, clip ids) per round
         self._rounds = self._all_rounds()
 
@@ -255,8 +363,16 @@ class Validation(object):
             if cls.tracker is None:
                 assert slots == list(range(B))          # the first round of a schedule fills every slot, in order
                 cls.tracker = self.make_tracker(images, regions)
+                if self._sup_args is not None:          # one state per frame size (its own B), one table for all
+                    cls.supervisor = Supervisor(B, len(self.clips), *self._sup_args, device=self.device)
+                    if self.supervisor is None:
+                        self.supervisor = cls.supervisor
+                    else:
+                        cls.supervisor.table = self.supervisor.table
             else:
                 cls.tracker.reset(slots, images, regions)
+            if cls.supervisor is not None:
+                cls.supervisor.start(slots)
         # (2) frames and ground truth of the round: zero frames (the crop kernel still reads them) and NaN boxes where inactive
         held = [None if i < 0 else self._frames(int(i)) for i in ids]
         u8 = all(h is None or h.dtype == np.uint8 for h in held)
@@ -274,10 +390,15 @@ class Validation(object):
         d_gt = _upload(gt, torch.float64, self.device)
         d_ids = _upload(ids, torch.int32, self.device)
         # (3) one pass over the round, (4) one scoring launch
+        if cls.supervisor is not None:
+            out = cls.tracker.track_clip(frames, active=active, supervisor=cls.supervisor, gt=d_gt, clip_of=d_ids)
+            if self._keep is not None:
+                self._keep.append((out, rnd.frame_index, rnd.active, ids, cls.supervisor.codes))
+            return
         out = cls.tracker.track_clip(frames, active=active)
         self.scores.add(out, d_gt, d_ids, active=active)
         if self._keep is not None:
-            self._keep.append((out, rnd.frame_index, rnd.active, ids))
+            self._keep.append((out, rnd.frame_index, rnd.active, ids, None))
 
     def finish(self):
         """Runs the remaining rounds; then asks every tracker that can tell (BatchDNCTracker.check) whether a launch failed."""
@@ -293,15 +414,36 @@ class Validation(object):
         if self._keep is None:
             raise ValueError("Validation: made without return_regions=True")
         out = [np.full((len(g) - 1, 4), np.nan) for g in self._gt]
-        for dev, frame_index, active, ids in self._keep:
+        for dev, frame_index, active, ids, codes in self._keep:
             host = dev.cpu().numpy()
+            sat_out = None if codes is None else codes.cpu().numpy() == SUP_CODE_SKIPPED
+            for t, b in zip(*np.nonzero(active)):
+                if sat_out is None or not sat_out[t, b]:
+                    out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
+        return out
+
+    def codes(self):
+        """protocol="supervised": what each clip's slot did on each tracked frame, a list of [L-1] int8 host arrays beside
+        ``regions()`` (SUP_CODE_*: 0 tracked, 1 restarted from the ground truth, 2 failure, 3 sat out; the region of a restart
+        frame is the ground truth it was started with, that of a skipped frame NaN) -- together what a VOT trajectory file holds.
+        Synchronises."""
+        if self._keep is None or self.protocol != "supervised":
+            raise ValueError("Validation: codes() needs protocol=\"supervised\" and return_regions=True")
+        out = [np.full((len(g) - 1,), SUP_CODE_INACTIVE, dtype=np.int8) for g in self._gt]
+        for _dev, frame_index, active, ids, codes in self._keep:
+            host = codes.cpu().numpy()
             for t, b in zip(*np.nonzero(active)):
                 out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
         return out
 
 
 def validate(make_tracker, clips, B, T, return_regions=False, **kw):
-    """Validation(...) run to its end -> scores.result(), or (result, regions per clip) with return_regions=True."""
+    """Validation(...) run to its end -> scores.result(), or (result, regions per clip) with return_regions=True.  With
+    protocol="supervised" (and skip=, burn_in=, failure_overlap=) the result is the supervisor's (summarize_supervised) and
+    return_regions=True gives (result, regions per clip, codes per clip)."""
     v = Validation(make_tracker, clips, B, T, return_regions=return_regions, **kw).finish()
+    if v.protocol == "supervised":
+        res = v.supervisor.result()
+        return (res, v.regions(), v.codes()) if return_regions else res
     res = v.scores.result()
     return (res, v.regions()) if return_regions else res

@@ -203,6 +203,7 @@ class BatchNTMTracker(object):
         # per-frame buffers, made once (each is consumed on the same stream before the next frame overwrites it)
         self._crops = torch.empty((B, self.crop, self.crop, 3), device=self.device, dtype=torch.float32)
         self._X = torch.empty((B, NUM_FEATURES + 1, ldx), device=self.device, dtype=torch.float32)
+        self._gts0 = self._zero = None                  # made by the first frame that carries a restart mask
 
     # ---- host -> device plumbing (no synchronising call)
     def _images(self, images):
@@ -321,14 +322,24 @@ class BatchNTMTracker(object):
         self.offsets.index_fill_(0, idx, 0)
         self.frame.index_fill_(0, idx, 0)
 
-    def track(self, images, frame_of=None, active=None):
+    def track(self, images, frame_of=None, active=None, restart=None, restart_regions=None):
         """One frame for every (active) tracker -> regions [B,4] (x, y, width, height) float64 on the device; an inactive
-        tracker keeps its state, box, frame count and last region.  Everything is enqueued on the current stream."""
+        tracker keeps its state, box, frame count and last region.  Everything is enqueued on the current stream.
+
+        ``restart`` (uint8 [B]) with ``restart_regions`` (float64 [B,4], pixels or normalised), both on the device: a slot with
+        restart[b] != 0 is STARTED on this frame's image from restart_regions[b] -- what ``reset([b], image, region)`` means --
+        inside the same pass (one crop launch, one trunk pass, one sequence launch, whatever the masks hold); its region is the
+        one given.  Every other slot is tracked or, with ``active``, left alone."""
         imgs = self._images(images)
         if frame_of is not None:
             self.frame_of = self._frame_table(frame_of, imgs.shape[0], self.B)
         mask = None if active is None else self._mask(active, (self.B,))
-        self._step(imgs, mask)
+        if (restart is None) != (restart_regions is None):
+            raise _lib.NtkError("track: restart and restart_regions come together")
+        if restart is None:
+            self._step(imgs, mask)
+        else:
+            self._step_restart(imgs, mask, *self._restart_args(restart, restart_regions))
         return self.regions.clone()
 
     def _step(self, imgs, mask):
@@ -336,15 +347,83 @@ class BatchNTMTracker(object):
         X = self._serialize(self._trunk(crops), None, X=self._X)
         self._update_boxes(self._sequence(X, mask), mask)
 
-    def track_clip(self, frames, active=None):
+    # ---- a frame on which some slots are started instead of tracked
+    def _restart_args(self, restart, regions):
+        if not (torch.is_tensor(restart) and restart.is_cuda and restart.dtype == torch.uint8 and tuple(restart.shape) == (self.B,)
+                and torch.is_tensor(regions) and regions.is_cuda and regions.dtype == torch.float64
+                and tuple(regions.shape) == (self.B, 4)):
+            raise _lib.NtkError("track: restart must be a uint8 [%d] and restart_regions a float64 [%d,4] device tensor" % (self.B, self.B))
+        return restart.contiguous(), regions.contiguous()
+
+    def _restart_boxes(self, restart, regions, mask):
+        """ntk_track_restart_boxes: the restarted slots' box state, crop boxes, regions and heat-map rows -> (heat-map rows
+        [B,64], the mask of the slots the sequence advances, the mask of the slots whose output moves their box)."""
+        if self._gts0 is None:
+            self._gts0 = torch.empty((self.B, NUM_FEATURES), device=self.device, dtype=torch.float32)
+            self._run_mask = torch.empty((self.B,), device=self.device, dtype=torch.uint8)
+            self._move_mask = torch.empty((self.B,), device=self.device, dtype=torch.uint8)
+        both_int = isinstance(self.bbox_grid, int)
+        sigma = float(self.bbox_grid // 3 if both_int else self.bbox_grid / 3)          # generate_gt's, focus = 3
+        _lib.check(_lib.lib().ntk_track_restart_boxes(_P(regions), _P(restart), _np(mask), self.B, float(self.cropbox_grid),
+                                                      float(self.bbox_grid), sigma, NUM_FEATURES, _P(self.box_state),
+                                                      _P(self.cropbox32), _P(self.regions), _P(self.offsets), _P(self.frame),
+                                                      _P(self._gts0), _P(self._run_mask), _P(self._move_mask), _lib.stream()),
+                   "ntk_track_restart_boxes")
+        return self._gts0, self._run_mask, self._move_mask
+
+    def _features(self, imgs):
+        return self._trunk(self._crop(imgs, self.frame_of, self.cropbox32, out=self._crops))
+
+    def _zero_rows(self, restart):
+        """The restarted slots' rows of the recurrent state become rows of the zero state (made once), in one launch."""
+        if self._zero is None:
+            self._zero = self.cell.zero_state(self.B)
+            self._zero_keys = sorted(self._zero)
+            rows = [self._zero[k].numel() // self.B for k in self._zero_keys]
+            self._zero_rows_c = (ctypes.c_longlong * len(rows))(*rows)
+            self._zero_table = _upload(np.array([self._zero[k].data_ptr() for k in self._zero_keys], dtype=np.int64), torch.int64,
+                                       self.device)
+            self._state_tables = {}
+        # the cell returns its new state in fresh tensors: one pointer table per set of addresses the allocator hands out
+        ptrs = tuple(self.state[k].data_ptr() for k in self._zero_keys)
+        table = self._state_tables.get(ptrs)
+        if table is None:
+            if len(self._state_tables) >= 64:
+                self._state_tables.clear()
+            table = self._state_tables[ptrs] = _upload(np.array(ptrs, dtype=np.int64), torch.int64, self.device)
+        state_keep(restart, 1, self.B, self._zero_table, table, self._zero_rows_c)
+
+    def _step_restart(self, imgs, mask, restart, regions):
+        gts0, run, move = self._restart_boxes(restart, regions, mask)
+        X = self._serialize(self._features(imgs), gts0, X=self._X)
+        self._zero_rows(restart)
+        self._update_boxes(self._sequence(X, None if mask is None else run), move)
+
+    def track_clip(self, frames, active=None, supervisor=None, gt=None, clip_of=None):
         """frames [T,F,H,W,3] -> regions [T,B,4] float64 on the device: T calls of track on one stream, no synchronisation.
-        active: [T,B] (nullable)."""
+        active: [T,B] (nullable).  With a ``supervisor`` (evaluate.Supervisor), the round's ground truth ``gt`` [T,B,4] float64
+        and ``clip_of`` int32 [B] on the device, every frame is plan -> the pass with the planned masks -> judge: a slot that
+        lost its object is restarted from the ground truth inside the pass.  The supervisor's ``codes`` [T,B] int8 then say what
+        each slot did on each frame; a slot that sat a frame out repeats its last region."""
         T = len(frames)
         if not torch.is_tensor(frames) and not isinstance(frames, (list, tuple)):
             a = np.asarray(frames)
             frames = _upload(a, torch.uint8 if a.dtype == np.uint8 else torch.float32, self.device)
         masks = None if active is None else self._mask(active, (T, self.B))
         out = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
+        if supervisor is not None:
+            if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float64 and tuple(gt.shape) == (T, self.B, 4)
+                    and gt.is_contiguous() and clip_of is not None):
+                raise _lib.NtkError("track_clip: a supervisor needs gt as a contiguous float64 [%d,%d,4] device tensor and clip_of"
+                                    % (T, self.B))
+            codes = torch.empty((T, self.B), device=self.device, dtype=torch.int8)
+            for t in range(T):
+                track, restart = supervisor.plan(gt[t], None if masks is None else masks[t], clip_of, codes=codes[t])
+                self._step_restart(self._images(frames[t]), track, restart, gt[t])
+                supervisor.judge(self.regions, gt[t], clip_of, codes=codes[t])
+                out[t].copy_(self.regions)
+            supervisor.codes = codes
+            return out
         for t in range(T):
             self._step(self._images(frames[t]), None if masks is None else masks[t])
             out[t].copy_(self.regions)
@@ -444,6 +523,20 @@ class BatchDNCTracker(BatchNTMTracker):
             self._fmap = torch.empty((self.B, self.crop // 8, self.crop // 8, 512), device=self.device, dtype=torch.float32)
         X = self._serialize(self._trunk(crops, out=self._fmap), None, X=self._X)
         self._update_boxes(self._sequence(X, mask), mask)
+
+    def _features(self, imgs):
+        crops = self._crop(imgs, self.frame_of, self.cropbox32, out=self._crops)
+        if self._fmap is None:
+            self._fmap = torch.empty((self.B, self.crop // 8, self.crop // 8, 512), device=self.device, dtype=torch.float32)
+        return self._trunk(crops, out=self._fmap)
+
+    def _zero_rows(self, restart):
+        """The restarted slots' rows of the serving state become rows of a fresh one (made on first use), in one launch."""
+        if self._zero is None:
+            self._zero = self.core.serving_state(self.B)
+            self._zero_table = _upload(np.array([t.data_ptr() for t in self._zero.tensors()], dtype=np.int64), torch.int64, self.device)
+        cur, _save, rows = self._keep_tables()
+        state_keep(restart, 1, self.B, self._zero_table, cur, rows)
 
     def check(self):
         """Synchronises; raises NtkError if a cluster launch of the core failed since the last check (DNC.check_cluster)."""

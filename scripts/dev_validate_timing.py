@@ -2,13 +2,17 @@
 against the two ways the public API allowed before it, both written here from that API alone (dev tool).
 
   dev_validate_timing.py [--B 16 64] [--clips-per-slot 2] [--T 8] [--passes 3] [--size 360 640] [--commit ID] [--out FILE]
+  dev_validate_timing.py --protocols one_pass supervised [...]      the two protocols of evaluate.validate on clips without failures
 
   recipe   the continuous-batching loop a caller had to write: B slots, BatchNTMTracker.reset for the slots whose clip ended, one
            track_clip with a mask per round, `out.cpu()` and a NumPy scorer per round
   singles  one online.NTMTracker per clip, frame by frame (validate_tracker.py:26-38), every region scored on the host
 
 Synthetic 640 x 360 uint8 clips held as HOST arrays for all three forms (a validation set comes from disk), clip lengths uniform in
-[8, 24], the shapes of profiles/online_batch.txt's cell and trunk with random weights.  Wall-clock time from the first call to the
+[8, 24], the shapes of profiles/online_batch.txt's cell and trunk with random weights.  --protocols: the ground truth of every
+clip is replaced by what the tracker itself returns on it (one untimed one-pass run), so that every overlap is 1 and the supervised
+protocol restarts nothing: what is timed is its per-frame bookkeeping on top of the same passes (profiles/validate_supervised.txt;
+`--protocols one_pass` alone runs on a commit that has no protocol argument yet).  Wall-clock time from the first call to the
 last result on the host, the device idle before and after; the forms alternate pass by pass, pass 0 warms up, the figure is the
 median of the others.  objects.frames/s counts tracked frames (a clip of L frames has L - 1).  profiles/validate.txt holds the output."""
 import argparse
@@ -32,6 +36,8 @@ ap.add_argument("--T", type=int, default=8, help="frames per round")
 ap.add_argument("--passes", type=int, default=3, help="timed passes per form after one warm-up pass")
 ap.add_argument("--size", nargs=2, type=int, default=[360, 640], metavar=("H", "W"))
 ap.add_argument("--commit", default="unknown")
+ap.add_argument("--protocols", nargs="+", choices=["one_pass", "supervised"], default=None,
+                help="time these protocols of evaluate.validate on clips without failures instead of the three forms")
 ap.add_argument("--out", default=None, help="append the report to this file as well")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -133,6 +139,52 @@ def run_singles(clips, _B):
         host_scores(table, np.full(len(pred), i), pred, c.regions[1:])
     return table[:, 1].sum() / table[:, 0].sum()
 
+
+def run_protocols():
+    make = lambda images, regions: online.BatchNTMTracker(images, regions, cell, vgg, device=dev)
+
+    def run(name, clips, B):
+        if name == "one_pass":                       # no protocol argument: the call a commit without one understands
+            return evaluate.validate(make, clips, B, T, device=dev)["mean_overlap_frames"]
+        res = evaluate.validate(make, clips, B, T, device=dev, protocol="supervised")
+        assert res["failures"] == 0 and res["restarts"] == 0, "the clips were meant to have no failure"
+        return res["accuracy_frames"]
+    say("box: %s | torch %s | commit %s | frames %dx%d uint8 on the host | rounds of %d frames | %d timed passes after 1 warm-up"
+        % (torch.cuda.get_device_name(0), torch.__version__, args.commit, W, H, T, args.passes))
+    say("%3s %5s %7s %6s | %s" % ("B", "clips", "obj.fr", "passes", " | ".join("%-10s %8s %9s %9s %7s" % (n, "s", "obj.fr/s", "ms/pass", "spread")
+                                                                             for n in args.protocols)))
+    for B in args.B:
+        clips = make_clips(args.clips_per_slot * B, 100 + B)
+        _res, tracked_regions = evaluate.validate(make, clips, B, T, return_regions=True, device=dev)
+        clips = [evaluate.Clip(c.frames, np.concatenate([c.regions[:1], r])) for c, r in zip(clips, tracked_regions)]
+        assert all(np.isfinite(c.regions).all() and (c.regions[:, 2:] > 0).all() for c in clips)
+        tracked = sum(len(c.regions) - 1 for c in clips)
+        passes = T * sum(1 for _r in evaluate.ClipSchedule([len(c.regions) for c in clips], B, T))    # frame passes of the tracker
+        times, values = {n: [] for n in args.protocols}, {}
+        for it in range(args.passes + 1):
+            for name in args.protocols:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                values[name] = run(name, clips, B)
+                torch.cuda.synchronize()
+                if it > 0:
+                    times[name].append(time.perf_counter() - t0)
+        say("%3d %5d %7d %6d | %s" % (B, len(clips), tracked, passes, " | ".join(
+            "%-10s %8.3f %9.0f %9.3f %7.3f" % (n, med(times[n]), tracked / med(times[n]), 1e3 * med(times[n]) / passes,
+                                              max(times[n]) - min(times[n])) for n in args.protocols)))
+        say("          mean overlap (one_pass) / accuracy (supervised: the frames after the burn-in): %s"
+            % ", ".join("%s %.6f" % (n, values[n]) for n in args.protocols))
+        del clips
+    say("s: wall-clock seconds of one whole validation, median of the timed passes; ms/pass: s over the tracker's frame passes "
+        "(rounds x T, each one crop, one trunk pass, one sequence for B slots); spread: max - min of the timed passes (s).")
+
+
+if args.protocols:
+    run_protocols()
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 FORMS = (("validate", run_validate), ("recipe", run_recipe), ("singles", run_singles))
 say("box: %s | torch %s | commit %s | frames %dx%d uint8 on the host | rounds of %d frames | %d timed passes after 1 warm-up"
