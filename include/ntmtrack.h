@@ -891,6 +891,44 @@ int ntk_track_supervise(int phase, const double* regions, const double* gt, cons
                         int n_clips, int skip, int burn_in, double failure_overlap, int* state, double* table,
                         unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou, void* stream);
 
+/* Polygon ground truth (VOT regions: vot.py:27-33 reads a region line as a rectangle or as a polygon; the VOT sets from 2015 on
+ * annotate every frame with a rotated rectangle of four points).  One layout everywhere: a region is double[NTK_POLY_DOUBLES], the
+ * vertices (x0, y0, x1, y1, ...) in pixels.  The vertices used are the LEADING pairs whose two numbers are both finite, at most
+ * NTK_POLY_MAX_POINTS; the rest is NaN padding.  Either orientation is accepted.  THE POLYGON MUST BE SIMPLE (no
+ * self-intersection): the area of a self-intersecting one is not what the shoelace sum gives, and its overlap is not defined here.
+ * A region is PRESENT when it has at least 3 vertices, its bounding rectangle has w > 0 and h > 0 and its shoelace area is > 0;
+ * anything else is an absent object, exactly as a non-finite or empty box is for the rectangle entries.
+ *
+ * ntk_track_poly_bounds: poly double [n,NTK_POLY_DOUBLES] -> rects double [n,4] = (min x, min y, max x - min x, max y - min y)
+ * over the used vertices: the rectangle vot.py:49-61 (convert_region) hands a tracker that asked for rectangles, and so what a
+ * tracker is (re)started with.  ONE DIFFERENCE: the reference seeds its maxima with sys.float_info.min, the smallest POSITIVE
+ * double, and is therefore wrong for a polygon whose coordinates are all <= 0; here the true maximum is taken.  An absent region
+ * gives four NaNs.  One thread per region, plain vector stores.  Errors: NTK_ERR_BAD_PTR for a null pointer, NTK_ERR_BAD_SHAPE
+ * (n named) for n <= 0.
+ *
+ * ntk_track_overlap_scores_poly: ntk_track_overlap_scores with gt double [T,B,NTK_POLY_DOUBLES].  Table layout, skip rules ("ground
+ * truth finite with w > 0 and h > 0" reads "present"), thresholds, frame_iou, row ownership, frame-order accumulation and the
+ * error checks are those of ntk_track_overlap_scores.  The overlap is |P n R| / (|P| + |R| - |P n R|), R the predicted rectangle
+ * (negative sizes clamped to 0), P the polygon, in float64 without FMA contraction, clamped to [0,1]: P is clipped against the four
+ * sides of R in turn (Sutherland-Hodgman, strict inside tests, a crossing point given the side's own coordinate exactly) and the
+ * shoelace area of the rest is |P n R|.  So a convex polygon whose interior does not reach R's interior -- touching included --
+ * scores exactly 0.0, and an integer-valued axis-aligned 4-gon against an integer rectangle gives the bits of
+ * ntk_track_overlap_scores on the two boxes (1.0 against itself).  The centre distance is taken to the centre of the polygon's
+ * bounding rectangle (that of ntk_track_poly_bounds).
+ *
+ * ntk_track_supervise_poly: ntk_track_supervise with gt double [B,NTK_POLY_DOUBLES]; "valid ground truth" reads "present", the
+ * judge's overlap is the device function of ntk_track_overlap_scores_poly, every other rule and every error check is unchanged.
+ * The caller hands the restarted slots' ntk_track_poly_bounds rectangles to ntk_track_restart_boxes. */
+#define NTK_POLY_MAX_POINTS 8
+#define NTK_POLY_DOUBLES    16
+int ntk_track_poly_bounds(const double* poly, int n, double* rects, void* stream);
+int ntk_track_overlap_scores_poly(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
+                                  int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr, int n_dist,
+                                  double* table, double* frame_iou, void* stream);
+int ntk_track_supervise_poly(int phase, const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
+                             int B, int n_clips, int skip, int burn_in, double failure_overlap, int* state, double* table,
+                             unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou, void* stream);
+
 /* out[b,:] = mask[b] ? a[b,:] : b[b,:] for fp32 [B,n] rows, mask uint8 [B] on the device (out may alias a or b): keeps the
  * recurrent state of a tracker that sat a frame out. */
 int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);

@@ -125,6 +125,9 @@ def _sig(lib):
         "ntk_track_overlap_scores": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
         "ntk_track_restart_boxes": (c_int, [P, P, P, c_int] + [ctypes.c_double] * 3 + [c_int] + [P] * 8 + [P]),
         "ntk_track_supervise": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
+        "ntk_track_poly_bounds": (c_int, [P, c_int, P, P]),
+        "ntk_track_overlap_scores_poly": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
+        "ntk_track_supervise_poly": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
         "ntk_select_rows": (c_int, [P, P, P, P, c_int, c_int, P]),
         "ntk_dnc_state_keep": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
         "ntk_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),

@@ -131,6 +131,63 @@ def validation_clips(seqs, image_root=None):
     return clips
 
 
+def parse_vot_region(line):
+    """One line of a VOT groundtruth.txt as vot.py:27-33 (parse_region) reads it: 4 numbers are a rectangle (x, y, w, h), an even
+    count above 4 a polygon (x0, y0, x1, y1, ...).  -> a list of 4 or of 2P floats, or None for a line that is neither (an absent
+    object).  A polygon of more than evaluate.POLY_MAX_POINTS points is an error: the device layout cannot hold it."""
+    from .evaluate import POLY_DOUBLES, POLY_MAX_POINTS
+    try:
+        tokens = [float(t) for t in line.strip().split(',')]
+    except ValueError:
+        return None
+    if len(tokens) == 4:
+        return tokens
+    if len(tokens) > 4 and len(tokens) % 2 == 0:
+        if len(tokens) > POLY_DOUBLES:
+            raise ValueError("a region of %d points; at most %d are supported" % (len(tokens) // 2, POLY_MAX_POINTS))
+        return tokens
+    return None
+
+
+def vot_clips(root, names=None):
+    """The VOT directory layout -> one evaluate.Clip per sequence.  ``root/list.txt`` names the sequences when ``names`` is None.
+    A sequence folder holds ``groundtruth.txt``, one region per line (parse_vot_region; a line that is neither form is an absent
+    object, a row of NaN), and its frames as ``color/%08d.jpg`` or ``%08d.jpg``, numbered from 1.  Regions are in pixels: [L,4]
+    where every line is a rectangle or absent, else [L,16] polygons padded with NaN (a rectangle line among them as its 4-gon).
+    Only the first image's header is opened here (for ``size``); a clip's frames are decoded when the validator schedules it."""
+    from PIL import Image
+    from .evaluate import Clip, POLY_DOUBLES, rect_polygons
+    if names is None:
+        with open(os.path.join(root, "list.txt")) as f:
+            names = [line.strip() for line in f if line.strip()]
+    clips = []
+    for name in names:
+        folder = os.path.join(root, name)
+        with open(os.path.join(folder, "groundtruth.txt")) as f:
+            lines = f.read().splitlines()
+        while lines and not lines[-1].strip():
+            lines.pop()
+        try:
+            parsed = [parse_vot_region(line) for line in lines]
+        except ValueError as e:
+            raise ValueError("%s: %s" % (os.path.join(folder, "groundtruth.txt"), e))
+        if any(r is not None and len(r) > 4 for r in parsed):
+            regions = np.full((len(parsed), POLY_DOUBLES), np.nan)
+            for i, r in enumerate(parsed):
+                if r is not None:
+                    corners = rect_polygons(r)[:8] if len(r) == 4 else r
+                    regions[i, :len(corners)] = corners
+        else:
+            regions = np.array([[np.nan] * 4 if r is None else r for r in parsed], dtype=np.float64).reshape(-1, 4)
+        sub = "color" if os.path.isdir(os.path.join(folder, "color")) else ""
+        paths = [os.path.join(folder, sub, "%08d.jpg" % (i + 1)) for i in range(len(parsed))]
+        with Image.open(paths[0]) as im:
+            width, height = im.size
+        decode = lambda paths=paths: np.stack([_decode_image(p) for p in paths])
+        clips.append(Clip(decode, regions, size=(height, width)))
+    return clips
+
+
 def _decode_image(path):
     from PIL import Image
     with Image.open(path) as im:

@@ -9,6 +9,12 @@ accumulated in one device table (ntk_track_overlap_scores) that is read back onc
   Validation     the driver: per round the resets, ONE track_clip and ONE scores.add, no host synchronisation after the first
                  round of a frame size
   validate       runs a Validation to the end; protocol="one_pass" (the default) or "supervised"
+  write_trajectory   the toolkit's trajectory file of one clip, from regions() and codes()
+
+The ground truth of a clip is a rectangle per frame ([L,4]) or a polygon per frame ([L,2P], 3 <= P <= 8: VOT regions), which is
+scored as the toolkit scores it -- the polygon against the tracker's rectangle (ntk_track_overlap_scores_poly,
+ntk_track_supervise_poly) -- while the tracker is started and restarted from the polygon's bounding rectangle, as the reference's
+vot.VOT("rectangle") hands it over.  A run without a polygon clip makes exactly the rectangle calls.
 
 The overlap is the VOT / OTB one on real-valued rectangles.  The reference's own bb_iou (test_tracker.py:59-83) is never called
 there, uses a +1 pixel convention and does not clamp an empty intersection: it is not the model here.
@@ -28,15 +34,66 @@ SUP_MODE_TRACK, SUP_MODE_WAIT = 0, 1
 SUP_PLAN, SUP_JUDGE = 0, 1
 SUP_CODE_INACTIVE, SUP_CODE_TRACKED, SUP_CODE_RESTART, SUP_CODE_FAILURE, SUP_CODE_SKIPPED = -1, 0, 1, 2, 3
 PROTOCOLS = ("one_pass", "supervised")
+# include/ntmtrack.h NTK_POLY_*: a polygon region is POLY_DOUBLES doubles, the leading finite pairs its vertices, NaN after them
+POLY_MAX_POINTS, POLY_DOUBLES = 8, 16
 
 Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
 
 #: one clip of a validation set.  frames: [L,H,W,3] uint8 or float host array, or a callable returning one (called when the clip is
-#: scheduled).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker.  init: the region the tracker is
-#: started with when it is not regions[0] (the reference passes it normalised).  size: (H, W) where frames is a callable, so that
+#: scheduled).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker; or [L,2P] polygons (x0, y0, x1, y1,
+#: ...) of 3 <= P <= 8 vertices, rows with fewer padded with NaN, the tracker then starts from row 0's bounding rectangle.  init:
+#: the region the tracker is started with when it is not that (the reference passes it normalised).  size: (H, W) where frames is a callable, so that
 #: clips can be grouped by frame size without decoding them.
 Clip = collections.namedtuple("Clip", ["frames", "regions", "init", "size"])
 Clip.__new__.__defaults__ = (None, None)
+
+
+def pad_polygons(regions):
+    """[..., 2P] polygons, 3 <= P <= POLY_MAX_POINTS -> [..., POLY_DOUBLES] float64, padded with NaN."""
+    a = np.asarray(regions, dtype=np.float64)
+    k = a.shape[-1] if a.ndim else 0
+    if k % 2 or not 6 <= k <= POLY_DOUBLES:
+        raise ValueError("polygon regions have %d columns; 2P with 3 <= P <= %d" % (k, POLY_MAX_POINTS))
+    out = np.full(a.shape[:-1] + (POLY_DOUBLES,), np.nan)
+    out[..., :k] = a
+    return out
+
+
+def rect_polygons(rects):
+    """[..., 4] rectangles (x, y, w, h) -> [..., POLY_DOUBLES] 4-gons (x, y), (x + w, y), (x + w, y + h), (x, y + h); a rectangle that
+    is not finite with w > 0 and h > 0 (an absent object) becomes a region of NaNs (an absent object)."""
+    r = np.asarray(rects, dtype=np.float64)
+    out = np.full(r.shape[:-1] + (POLY_DOUBLES,), np.nan)
+    with np.errstate(invalid="ignore"):
+        x, y, x2, y2 = r[..., 0], r[..., 1], r[..., 0] + r[..., 2], r[..., 1] + r[..., 3]
+        ok = np.isfinite(r).all(axis=-1) & (r[..., 2] > 0) & (r[..., 3] > 0)
+    for i, v in enumerate((x, y, x2, y, x2, y2, x, y2)):
+        out[..., i] = np.where(ok, v, np.nan)
+    return out
+
+
+def polygon_bounds(polys):
+    """The host's ntk_track_poly_bounds: [..., POLY_DOUBLES] -> [..., 4] (min x, min y, max x - min x, max y - min y) over the
+    leading finite pairs, NaN for a region that is not present (fewer than 3 vertices, an empty bounding rectangle, or a shoelace
+    area of 0)."""
+    polys = np.asarray(polys, dtype=np.float64)
+    flat = polys.reshape(-1, POLY_DOUBLES)
+    out = np.full((len(flat), 4), np.nan)
+    for i, g in enumerate(flat):
+        pts = g.reshape(-1, 2)
+        n = 0
+        while n < POLY_MAX_POINTS and np.isfinite(pts[n]).all():
+            n += 1
+        if n < 3:
+            continue
+        x, y = pts[:n, 0], pts[:n, 1]
+        w, h = x.max() - x.min(), y.max() - y.min()
+        dx, dy = x - x[0], y - y[0]
+        with np.errstate(all="ignore"):
+            twice = sum(dx[j] * dy[(j + 1) % n] - dx[(j + 1) % n] * dy[j] for j in range(n))
+        if w > 0 and h > 0 and abs(twice) / 2 > 0:
+            out[i] = (x.min(), y.min(), w, h)
+    return out.reshape(polys.shape[:-1] + (4,))
 
 
 class ClipSchedule(object):
@@ -138,7 +195,8 @@ class OverlapScores(object):
         return _upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, self.device)
 
     def add(self, regions, gt, clip_of, active=None, frame_iou=False):
-        """regions, gt: [T,B,4] or [B,4] (x, y, w, h) pixels; clip_of [B]: the table row of slot b, no row twice (a row outside
+        """regions, gt: [T,B,4] or [B,4] (x, y, w, h) pixels, or gt [T,B,16] / [B,16] polygons (then one launch of
+        ntk_track_overlap_scores_poly); clip_of [B]: the table row of slot b, no row twice (a row outside
         the table skips the slot); active [T,B] or [B], nullable.  Device tensors are taken as they are, host arrays go up through
         a pinned asynchronous copy.  frame_iou=True returns the per-frame IoUs [T,B] (NaN where a frame was not scored)."""
         import torch
@@ -146,8 +204,11 @@ class OverlapScores(object):
         regions, gt = self._dev(regions, torch.float64), self._dev(gt, torch.float64)
         if regions.dim() == 2:
             regions, gt = regions.unsqueeze(0), gt.unsqueeze(0)
-        if regions.dim() != 3 or regions.shape[2] != 4 or gt.shape != regions.shape:
-            raise _lib.NtkError("OverlapScores.add: regions %s and gt %s must both be [T,B,4]" % (tuple(regions.shape), tuple(gt.shape)))
+        poly = gt.dim() == 3 and gt.shape[2] == POLY_DOUBLES
+        if (regions.dim() != 3 or regions.shape[2] != 4 or gt.dim() != 3 or gt.shape[:2] != regions.shape[:2]
+                or gt.shape[2] not in (4, POLY_DOUBLES)):
+            raise _lib.NtkError("OverlapScores.add: regions %s must be [T,B,4] and gt %s [T,B,4] or [T,B,%d]"
+                                % (tuple(regions.shape), tuple(gt.shape), POLY_DOUBLES))
         T, B = regions.shape[:2]
         clip_of = self._dev(clip_of, torch.int32)
         mask = None if active is None else self._dev(active, torch.uint8).reshape(-1, B)
@@ -156,10 +217,11 @@ class OverlapScores(object):
                                 % (tuple(clip_of.shape), None if mask is None else tuple(mask.shape), T, B))
         out = torch.empty((T, B), dtype=torch.float64, device=self.device) if frame_iou else None
         P = _lib.ptr
-        _lib.check(_lib.lib().ntk_track_overlap_scores(P(regions), P(gt), P(mask), P(clip_of), T, B, self.n_clips,
-                                                       P(self._iou) if len(self.iou_thresholds) else None, len(self.iou_thresholds),
-                                                       P(self._dist) if len(self.dist_thresholds) else None, len(self.dist_thresholds),
-                                                       P(self.table), P(out), _lib.stream()), "ntk_track_overlap_scores")
+        name = "ntk_track_overlap_scores_poly" if poly else "ntk_track_overlap_scores"
+        _lib.check(getattr(_lib.lib(), name)(P(regions), P(gt), P(mask), P(clip_of), T, B, self.n_clips,
+                                             P(self._iou) if len(self.iou_thresholds) else None, len(self.iou_thresholds),
+                                             P(self._dist) if len(self.dist_thresholds) else None, len(self.dist_thresholds),
+                                             P(self.table), P(out), _lib.stream()), name)
         return out
 
     def result(self):
@@ -232,18 +294,21 @@ class Supervisor(object):
     def _call(self, phase, regions, gt, active, clip_of, codes, frame_iou):
         import torch
         from . import _lib
-        for name, t, dtype, shape in (("regions", regions, torch.float64, (self.B, 4)), ("gt", gt, torch.float64, (self.B, 4)),
+        poly = torch.is_tensor(gt) and gt.dim() == 2 and gt.shape[1] == POLY_DOUBLES
+        for name, t, dtype, shape in (("regions", regions, torch.float64, (self.B, 4)),
+                                      ("gt", gt, torch.float64, (self.B, POLY_DOUBLES if poly else 4)),
                                       ("active", active, torch.uint8, (self.B,)), ("clip_of", clip_of, torch.int32, (self.B,)),
                                       ("codes", codes, torch.int8, (self.B,)), ("frame_iou", frame_iou, torch.float64, (self.B,))):
             if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape):
                 raise _lib.NtkError("Supervisor: %s must be a %s tensor of shape %s" % (name, dtype, shape))
         P = _lib.ptr
-        _lib.check(_lib.lib().ntk_track_supervise(phase, P(regions), P(gt), P(active), P(clip_of), self.B, self.n_clips, self.skip,
-                                                  self.burn_in, self.failure_overlap, P(self.state), P(self.table), P(self.track),
-                                                  P(self.restart), P(codes), P(frame_iou), _lib.stream()), "ntk_track_supervise")
+        fn = "ntk_track_supervise_poly" if poly else "ntk_track_supervise"
+        _lib.check(getattr(_lib.lib(), fn)(phase, P(regions), P(gt), P(active), P(clip_of), self.B, self.n_clips, self.skip,
+                                           self.burn_in, self.failure_overlap, P(self.state), P(self.table), P(self.track),
+                                           P(self.restart), P(codes), P(frame_iou), _lib.stream()), fn)
 
     def plan(self, gt_t, active_t, clip_of, codes=None, frame_iou=None):
-        """Before the frame's pass.  gt_t float64 [B,4], active_t uint8 [B] (nullable), clip_of int32 [B], on the device.
+        """Before the frame's pass.  gt_t float64 [B,4] (or [B,16] polygons: ntk_track_supervise_poly), active_t uint8 [B] (nullable), clip_of int32 [B], on the device.
         -> (track, restart) uint8 [B]: the masks of the pass (the supervisor's own buffers, overwritten by the next plan).  codes
         int8 [B] and frame_iou float64 [B] (nullable) are filled for every slot."""
         self._call(SUP_PLAN, None, gt_t, active_t, clip_of, codes, frame_iou)
@@ -286,7 +351,11 @@ class Validation(object):
     ``protocol="supervised"`` runs the supervised protocol instead (Supervisor; ``skip``, ``burn_in``, ``failure_overlap``): the
     same schedule and the same resets, a round is one track_clip with the supervisor, which restarts a lost slot from the ground
     truth inside the pass.  ``supervisor`` then holds the table (``scores`` stays empty), ``codes()`` the per-frame codes per clip
-    beside ``regions()``, whose skipped frames hold NaN.  Still no host synchronisation after the first round of a frame size."""
+    beside ``regions()``, whose skipped frames hold NaN.  Still no host synchronisation after the first round of a frame size.
+
+    Clips with polygon regions ([L,2P]) are scored against the polygons in both protocols; their trackers start, and restart, from
+    the polygons' bounding rectangles.  Rectangle clips in the same run are scored as 4-gons.  The polygons go up through the same
+    pinned asynchronous copy, so a round still makes no host synchronisation."""
 
     def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda",
                  protocol="one_pass", skip=5, burn_in=10, failure_overlap=0.0):
@@ -299,7 +368,12 @@ class Validation(object):
         if not self.clips:
             raise ValueError("Validation: no clips")
         self.B, self.T = int(B), int(T)
-        self._gt = [np.asarray(c.regions, dtype=np.float64).reshape(-1, 4) for c in self.clips]
+        # ground truth per clip: [L,4], or, as soon as one clip has polygons, [L,16] for every clip (a rectangle clip as 4-gons)
+        given = [np.asarray(c.regions, dtype=np.float64) for c in self.clips]
+        given = [g if g.ndim == 2 and g.shape[1] != 4 else g.reshape(-1, 4) for g in given]
+        self.polygons = any(g.shape[1] != 4 for g in given)
+        self._gt = [(rect_polygons(g) if g.shape[1] == 4 else pad_polygons(g)) for g in given] if self.polygons else given
+        self._first = [g[0] if g.shape[1] == 4 else polygon_bounds(pad_polygons(g[0])) for g in given]
         self._held = {}                                 # clip index -> decoded frames, from its reset to its last frame
         classes = collections.OrderedDict()
         for i, c in enumerate(self.clips):
@@ -332,7 +406,7 @@ class Validation(object):
 
     def _init_region(self, i):
         c = self.clips[i]
-        return self._gt[i][0] if c.init is None else np.asarray(c.init, dtype=np.float64).reshape(4)
+        return self._first[i] if c.init is None else np.asarray(c.init, dtype=np.float64).reshape(4)
 
     # ---- rounds
     def _all_rounds(self):
@@ -377,7 +451,7 @@ class Validation(object):
         held = [None if i < 0 else self._frames(int(i)) for i in ids]
         u8 = all(h is None or h.dtype == np.uint8 for h in held)
         frames = np.zeros((T, B, H, W, 3), dtype=np.uint8 if u8 else np.float32)
-        gt = np.full((T, B, 4), np.nan, dtype=np.float64)
+        gt = np.full((T, B, POLY_DOUBLES if self.polygons else 4), np.nan, dtype=np.float64)
         for b in range(B):
             n = int(rnd.active[:, b].sum())
             if n:
@@ -447,3 +521,24 @@ def validate(make_tracker, clips, B, T, return_regions=False, **kw):
         return (res, v.regions(), v.codes()) if return_regions else res
     res = v.scores.result()
     return (res, v.regions()) if return_regions else res
+
+
+def write_trajectory(path, first_region, regions, codes=None):
+    """Writes the VOT toolkit's trajectory file of one clip.  Line 1 is ``1``, the initialisation frame (the toolkit's format has
+    the code there and not the region: ``first_region``, the four numbers the tracker was started with, is checked and not
+    written).  Then one line per tracked frame, from ``regions`` [L-1,4] and ``codes`` [L-1] as Validation.regions() and
+    Validation.codes() return them: ``1`` on a restart frame, ``2`` on a failure frame, ``0`` on a frame that was sat out, any other
+    frame ``x,y,w,h`` with four decimals.  ``codes=None`` is the one-pass run: every line after the first is a region."""
+    first = np.asarray(first_region, dtype=np.float64).reshape(-1)
+    regions = np.asarray(regions, dtype=np.float64).reshape(-1, 4)
+    if first.shape != (4,) or not np.isfinite(first).all():
+        raise ValueError("write_trajectory: first_region %s; four finite numbers" % (first.tolist(),))
+    if codes is not None and len(codes) != len(regions):
+        raise ValueError("write_trajectory: %d codes for %d regions" % (len(codes), len(regions)))
+    special = {SUP_CODE_RESTART: "1", SUP_CODE_FAILURE: "2", SUP_CODE_SKIPPED: "0"}
+    lines = ["1"]
+    for t, r in enumerate(regions):
+        code = None if codes is None else special.get(int(codes[t]))
+        lines.append(code if code is not None else "%.4f,%.4f,%.4f,%.4f" % tuple(r))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")

@@ -122,6 +122,7 @@ class NTMTracker(object):
 # ---- batched online tracker: boxes, crops and state stay on the device ---------------------------------------------------
 
 STATE_DOUBLES = 10           # include/ntmtrack.h NTK_TRACK_STATE_*: [w, h, object box y1 x1 y2 x2, crop box y1 x1 y2 x2]
+POLY_DOUBLES = 16            # include/ntmtrack.h NTK_POLY_DOUBLES: one polygon region of the ground truth
 
 
 def _upload(array, dtype, device):
@@ -403,7 +404,9 @@ class BatchNTMTracker(object):
         """frames [T,F,H,W,3] -> regions [T,B,4] float64 on the device: T calls of track on one stream, no synchronisation.
         active: [T,B] (nullable).  With a ``supervisor`` (evaluate.Supervisor), the round's ground truth ``gt`` [T,B,4] float64
         and ``clip_of`` int32 [B] on the device, every frame is plan -> the pass with the planned masks -> judge: a slot that
-        lost its object is restarted from the ground truth inside the pass.  The supervisor's ``codes`` [T,B] int8 then say what
+        lost its object is restarted from the ground truth inside the pass.  ``gt`` may be [T,B,16] polygons (include/ntmtrack.h,
+        NTK_POLY_*): plan and judge take the polygons, a restart starts from the polygon's bounding rectangle, which one
+        ntk_track_poly_bounds launch computes for the whole round.  The supervisor's ``codes`` [T,B] int8 then say what
         each slot did on each frame; a slot that sat a frame out repeats its last region."""
         T = len(frames)
         if not torch.is_tensor(frames) and not isinstance(frames, (list, tuple)):
@@ -412,14 +415,19 @@ class BatchNTMTracker(object):
         masks = None if active is None else self._mask(active, (T, self.B))
         out = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
         if supervisor is not None:
-            if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float64 and tuple(gt.shape) == (T, self.B, 4)
-                    and gt.is_contiguous() and clip_of is not None):
-                raise _lib.NtkError("track_clip: a supervisor needs gt as a contiguous float64 [%d,%d,4] device tensor and clip_of"
-                                    % (T, self.B))
+            if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float64 and gt.dim() == 3
+                    and tuple(gt.shape[:2]) == (T, self.B) and gt.shape[2] in (4, POLY_DOUBLES) and gt.is_contiguous()
+                    and clip_of is not None):
+                raise _lib.NtkError("track_clip: a supervisor needs gt as a contiguous float64 [%d,%d,4] (or [%d,%d,%d]) device "
+                                    "tensor and clip_of" % (T, self.B, T, self.B, POLY_DOUBLES))
+            rects = gt
+            if gt.shape[2] == POLY_DOUBLES:             # what a restart starts from: the polygons' bounding rectangles
+                rects = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
+                _lib.check(_lib.lib().ntk_track_poly_bounds(_P(gt), T * self.B, _P(rects), _lib.stream()), "ntk_track_poly_bounds")
             codes = torch.empty((T, self.B), device=self.device, dtype=torch.int8)
             for t in range(T):
                 track, restart = supervisor.plan(gt[t], None if masks is None else masks[t], clip_of, codes=codes[t])
-                self._step_restart(self._images(frames[t]), track, restart, gt[t])
+                self._step_restart(self._images(frames[t]), track, restart, rects[t])
                 supervisor.judge(self.regions, gt[t], clip_of, codes=codes[t])
                 out[t].copy_(self.regions)
             supervisor.codes = codes
