@@ -644,7 +644,8 @@ int ntk_dnc_write_allocation_weights(const float* usage, const float* write_gate
  * as a contiguous [B,width] array at act + B*offset(field).  _write_weights (:220-257), _erase_and_write (:32-63),
  * _read_weights (:259-303), read words (:151), and the whole step MemoryAccess._build (:113-158) = SURVEY's
  * ntk_dnc_access_step_fwd (its backward: ntk_dnc_access_step_bwd, below).
- * Workspaces (floats): write_weights 2*B*Wn*N + B*Wn; read_weights B*R*N*(1+2*Wn). */
+ * Workspaces (floats): write_weights 2*B*Wn*N + B*Wn; read_weights B*R*N*(1+2*Wn).
+ * ntk_dnc_interface_activations: B, N, W, R, Wn >= 1 and ldr >= the interface width (else NTK_ERR_BAD_SHAPE). */
 int ntk_dnc_interface_activations(const float* raw, int ldr, float* act, int B, int N, int W, int R, int Wn, void* stream);
 int ntk_dnc_write_weights(const float* memory, const float* usage, const float* write_keys, const float* write_strengths,
                           const float* allocation_gate, const float* write_gate, float* write_weights, float* workspace,
@@ -717,7 +718,8 @@ int ntk_gather_serialize_online(const float* fmap, const float* gts0, float* X, 
                                 int grid_n, void* stream);
 
 /* tf.image.crop_and_resize (bilinear, one normalised box y1,x1,y2,x2, extrapolation value) of (image - mean):
- * image [H,W,C] fp32, mean [C] (nullable) -> out [crop_h,crop_w,C]
+ * image [H,W,C] fp32, mean [C] (nullable) -> out [crop_h,crop_w,C]; crop_h * crop_w * C must stay below 2^31 - 256
+ * (else NTK_ERR_BAD_SHAPE, as in the batched entry)
  * replaces: test_tracker.py:344-352 (online) / direct_offset_output.py:207-211 (training input pipeline) */
 int ntk_crop_and_resize(const float* image, int H, int W, int C, const float* mean, float y1, float x1,
                         float y2, float x2, float* out, int crop_h, int crop_w, float extrapolation,

@@ -265,6 +265,7 @@ extern "C" int ntk_dnc_write_allocation_weights(const float* usage, const float*
 extern "C" int ntk_dnc_interface_activations(const float* raw, int ldr, float* act, int B, int N, int W, int R, int Wn,
                                              void* stream) {
     NTK_REQUIRE(raw && act, NTK_ERR_BAD_PTR, "ntk_dnc_interface_activations: null pointer");
+    NTK_REQUIRE(N > 0 && W > 0 && R > 0 && Wn > 0, NTK_ERR_BAD_SHAPE, "ntk_dnc_interface_activations: N=%d W=%d R=%d Wn=%d", N, W, R, Wn);
     DncDims d;
     dnc_fill_dims(d, B, 1, N, W, R, Wn, 4, 1, 0.f);
     NTK_REQUIRE(B > 0 && ldr >= d.I, NTK_ERR_BAD_SHAPE, "ntk_dnc_interface_activations: B=%d ldr=%d (interface %d)", B, ldr, d.I);

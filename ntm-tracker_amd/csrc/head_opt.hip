@@ -924,8 +924,9 @@ extern "C" int ntk_crop_and_resize(const float* image, int H, int W, int C, cons
     NTK_REQUIRE(image && out, NTK_ERR_BAD_PTR, "ntk_crop_and_resize: null pointer");
     NTK_REQUIRE(H > 0 && W > 0 && C > 0 && crop_h > 0 && crop_w > 0, NTK_ERR_BAD_SHAPE,
                 "ntk_crop_and_resize: H=%d W=%d C=%d crop=%dx%d", H, W, C, crop_h, crop_w);
-    const int total = crop_h * crop_w * C;
-    crop_resize_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(image, H, W, C, mean, y1, x1, y2, x2, out,
+    const long total = (long)crop_h * crop_w * C;
+    NTK_REQUIRE(total < 2147483647L - 256, NTK_ERR_BAD_SHAPE, "ntk_crop_and_resize: crop=%dx%d C=%d: too many elements", crop_h, crop_w, C);
+    crop_resize_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(image, H, W, C, mean, y1, x1, y2, x2, out,
                                                                              crop_h, crop_w, extrapolation);
     NTK_CHECK_LAUNCH("ntk_crop_and_resize");
     return NTK_OK;

@@ -1,5 +1,6 @@
-"""Shared pieces of the small-kernel tests (test_gemm_gpu.py, test_small_kernels_gpu.py, test_modules_gpu.py): NaN-guarded
-device buffers and the float64 restatements that more than one file compares against."""
+"""Shared pieces of the small-kernel tests (test_gemm_gpu.py, test_small_kernels_gpu.py, test_modules_gpu.py,
+test_module_shapes_gpu.py, test_image_kernels_gpu.py): NaN-guarded device buffers and the float64 restatements that more than one
+file compares against."""
 import ctypes
 
 import numpy as np
@@ -52,6 +53,55 @@ class Guarded(object):
         h = self.buf.view(torch.int32).cpu().numpy().copy()
         h[self.before:self.before + self.rows, :self.cols] = self.payload
         return bool((h == self.payload).all())
+
+
+class FlatGuarded(object):
+    """A contiguous fp32 array of `shape` inside a NaN-filled device buffer, `pad` words (a multiple of 4: the array stays 16-byte
+    aligned) in front of and behind it.  An output starts as GUARD_NAN throughout; an operand (init given) carries `payload` only
+    around it -- INPUT_NAN, so that a read past its end turns the result into a NaN that is not the guard's."""
+
+    def __init__(self, shape, device, init=None, payload=None, pad=64):
+        shape = tuple(shape) if isinstance(shape, (tuple, list)) else (shape,)
+        self.payload = payload if payload is not None else (GUARD_NAN if init is None else INPUT_NAN)
+        self.n, self.pad = int(np.prod(shape)), pad
+        self.buf = nan_tensor(self.n + 2 * pad, device, self.payload)
+        self.view = self.buf[pad:pad + self.n].view(shape)
+        if init is not None:
+            self.view.copy_(to_dev(np.array(np.broadcast_to(init, shape), np.float32), device))
+        self.ptr = vptr(self.view)
+
+    def numpy(self):
+        return self.view.cpu().numpy()
+
+    def guards_intact(self):
+        return still_guard(self.buf[:self.pad], self.payload) and still_guard(self.buf[self.pad + self.n:], self.payload)
+
+    def written(self):
+        """The array on the host, after asserting that every element was written with a number and no guard word was touched."""
+        a = self.numpy()
+        assert not np.isnan(a).any(), "%d of %d output elements are NaN" % (int(np.isnan(a).sum()), a.size)
+        assert self.guards_intact(), "guard words around the output were overwritten"
+        return a
+
+
+def raw_bytes_equal(a, b):
+    """Bit-for-bit equality of two arrays of one shape and type (-0.0 differs from 0.0, NaNs compare by payload)."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def resize_ref(img, OH, OW):
+    """float64 restatement of resize_bilinear_kernel's contract (tf.image.resize_images, BILINEAR, TF-1 defaults): src = dst *
+    (in / out), neighbours floor(src) and min(floor(src) + 1, in - 1)."""
+    img = np.asarray(img, np.float64)
+    H, W, C = img.shape
+    ys = np.arange(OH) * (H / OH); xs = np.arange(OW) * (W / OW)
+    y0 = np.floor(ys).astype(int); x0 = np.floor(xs).astype(int)
+    y1 = np.minimum(y0 + 1, H - 1); x1 = np.minimum(x0 + 1, W - 1)
+    fy = (ys - y0)[:, None, None]; fx = (xs - x0)[None, :, None]
+    top = img[y0][:, x0] + (img[y0][:, x1] - img[y0][:, x0]) * fx
+    bot = img[y1][:, x0] + (img[y1][:, x1] - img[y1][:, x0]) * fx
+    return top + (bot - top) * fy
 
 
 def lstm_pointwise64(pre, c_prev, forget_bias=0.0, dh=None, dc=None):

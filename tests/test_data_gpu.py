@@ -6,19 +6,9 @@ import pytest
 import torch
 
 from oracle import online_oracle as OO
+from small_kernel_util import resize_ref as _resize_ref
 
 pytestmark = pytest.mark.gpu
-
-
-def _resize_ref(img, OH, OW):
-    H, W, C = img.shape
-    ys = np.arange(OH) * (H / OH); xs = np.arange(OW) * (W / OW)
-    y0 = np.floor(ys).astype(int); x0 = np.floor(xs).astype(int)
-    y1 = np.minimum(y0 + 1, H - 1); x1 = np.minimum(x0 + 1, W - 1)
-    fy = (ys - y0)[:, None, None]; fx = (xs - x0)[None, :, None]
-    top = img[y0][:, x0] + (img[y0][:, x1] - img[y0][:, x0]) * fx
-    bot = img[y1][:, x0] + (img[y1][:, x1] - img[y1][:, x0]) * fx
-    return top + (bot - top) * fy
 
 
 def test_get_input_matches_numpy_chain(cuda, tmp_path):
