@@ -747,7 +747,7 @@ __global__ __launch_bounds__(CT) void dnc_cluster_bwd_kernel(DncClBwdArgs a0) {
                 dh = sDHC[u0 + tid];
                 for (int sl = 0; sl < Q.nslH; ++sl) dh += sPart[sl * upk + tid];
             }
-            dncc_bwd_lstm(C, a, st, dh, pf_gates, pf_c, pf_cprev);
+            dncc_bwd_lstm(C, a, st, dh, pf_gates, pf_c, pf_cprev, t == 0);
         }
         __syncthreads();
         CLB_STAMP(14);

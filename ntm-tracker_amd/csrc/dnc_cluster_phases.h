@@ -662,15 +662,19 @@ __device__ __forceinline__ void dncc_bwd_carry_vectors(const Cfg& C, const DncCl
     for (int n = s.tid; n < N; n += CT) s.sgP[n] = s.sDPp[n];                   // carried d(precedence_{t-1})
 }
 
-// B15: clip + snt.LSTM backward of the own units (dh: d(clipped h) of unit u0 + tid; gates, c, cprev: its records)
+// B15: clip + snt.LSTM backward of the own units (dh: d(clipped h) of unit u0 + tid; gates, c, cprev: its records; first: step 0 of
+// the launch, cprev_rec is the caller's hc0)
 template <class Cfg, class Args>
-__device__ __forceinline__ void dncc_bwd_lstm(const Cfg& C, const Args& a, const DncClBwdSt& s, float dh, f32x4 gg, float c2, float cprev_rec) {
+__device__ __forceinline__ void dncc_bwd_lstm(const Cfg& C, const Args& a, const DncClBwdSt& s, float dh, f32x4 gg, float c2, float cprev_rec,
+                                              bool first) {
     const int tid = s.tid;
     const float clipv = s.clipv;
     if (tid < s.u1 - s.u0) {
         const int u = s.u0 + tid;
         const float gi = gg[0], gj = gg[1], gf = gg[2], go = gg[3];
-        const float cprev = dnc_clip(cprev_rec, clipv);       // the recorded cell is pre-clip; the carried state was clipped
+        // the recorded cell is pre-clip, the carried state was clipped; hc0 is what the forward started from, as given (an initial cell
+        // beyond the clip entered the forward's c' = f c + i j unclipped: dnc_seq_bwd.hip B15 does the same)
+        const float cprev = first ? cprev_rec : dnc_clip(cprev_rec, clipv);
         const float tc = cl_tanh(c2);
         const float h2 = tc * go;
         const float dh2 = (clipv <= 0.f || fabsf(h2) < clipv) ? dh : 0.f;

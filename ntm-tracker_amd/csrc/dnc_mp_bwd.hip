@@ -809,7 +809,7 @@ __global__ __launch_bounds__(CT) void dnc_mp_bwd_kernel(DncMpBwdArgs a0) {
         }
         __syncthreads();
         // ------------------------------------------------------------ B15: clip + snt.LSTM backward of the own units
-        dncc_bwd_lstm(C, a, st, (tid < nU) ? sDHC[u0 + tid] + sPart[tid] : 0.f, pf_gates, pf_c, pf_cprev);
+        dncc_bwd_lstm(C, a, st, (tid < nU) ? sDHC[u0 + tid] + sPart[tid] : 0.f, pf_gates, pf_c, pf_cprev, t == 0);
         __syncthreads();
         MP_STAMP(18);      // B14, B15
         // ------------------------------------------------------------ B16: partial d[reads_prev ; h_prev] over the own gate columns

@@ -284,26 +284,30 @@ def sonnet_lstm(x, state, W, b, forget_bias=1.0):
     return h2.astype(x.dtype), LSTMState(h2.astype(x.dtype), c2.astype(x.dtype))
 
 
-def dnc_step(cfg, params, x, prev):
-    """DNC._build (dnc.py:84-127)."""
+def dnc_step(cfg, params, x, prev, trace=None):
+    """DNC._build (dnc.py:84-127).  trace: a dict that collects, per step, h, c and y before clipping."""
     B = x.shape[0]
     a = cfg.access
     ci = np.concatenate([x.reshape(B, -1), prev.access_output.reshape(B, -1)], axis=1)
     h, cs = sonnet_lstm(ci, prev.controller_state, params["lstm/w_gates"], params["lstm/b_gates"])
+    pre = (h, cs.cell)
     h = clip(cfg, h)
     cs = LSTMState(clip(cfg, cs.hidden), clip(cfg, cs.cell))
     reads, acc, inp = access_step(a, params, h, prev.access_state)
     y = np.concatenate([h, reads.reshape(B, -1)], axis=1) @ params["output_linear/w"] + params["output_linear/b"]
+    if trace is not None:
+        for nm, v in (("h", pre[0]), ("c", pre[1]), ("y", y.astype(x.dtype))):
+            trace.setdefault(nm, []).append(v)
     y = clip(cfg, y.astype(x.dtype))
     return y, DNCState(reads, acc, cs), inp
 
 
-def run_model(cfg, params, inputs_tm, state=None):
+def run_model(cfg, params, inputs_tm, state=None, trace=None):
     """direct_offset_output_with_dnc.py:66-88: dynamic_rnn over TIME-MAJOR inputs [S,B,D] -> [S,B,O]."""
     S, B, _ = inputs_tm.shape
     st = state or dnc_initial_state(cfg, B, inputs_tm.dtype)
     ys = []
     for t in range(S):
-        y, st, _ = dnc_step(cfg, params, inputs_tm[t], st)
+        y, st, _ = dnc_step(cfg, params, inputs_tm[t], st, trace)
         ys.append(y)
     return np.stack(ys, 0), st

@@ -70,7 +70,7 @@ def write_allocation_weights(usage, write_gates, Wn):
     return torch.stack(out, 1)
 
 
-def access_step(cfg, p, h, prev):
+def access_step(cfg, p, h, prev, trace=None):
     B = h.shape[0]
     N, W, R, Wn = cfg.N, cfg.W, cfg.R, cfg.Wn
     lin = lambda name: h @ p["memory_access/%s/w" % name] + p["memory_access/%s/b" % name]
@@ -84,6 +84,8 @@ def access_step(cfg, p, h, prev):
     bw = lin("write_strengths")
     kr = lin("read_keys").reshape(B, R, W)
     br = lin("read_strengths")
+    if trace is not None:
+        trace.setdefault("strengths", []).append(torch.cat([bw, br], 1).detach())
     # Freeness (addressing.py:279-305), write weights under stop_gradient
     wwp = prev.write_weights.detach()
     usage = prev.usage + (1 - prev.usage) * (1 - torch.prod(1 - wwp, dim=1))
@@ -112,11 +114,19 @@ def initial_state(cfg, B, dtype=torch.float64):
                     LSTMState(z(B, cfg.hid), z(B, cfg.hid)))
 
 
-def clip(cfg, x):
-    return torch.clamp(x, -cfg.clip, cfg.clip) if cfg.clip > 0 else x
+def clip(cfg, x, straight_through=False):
+    """clip_by_value; straight_through: the same value, the gradient passed as if the clip were not there (a MUTANT for tests that
+    want to know whether they would see a dropped gradient mask; the reference has no such thing)."""
+    if not cfg.clip > 0:
+        return x
+    y = torch.clamp(x, -cfg.clip, cfg.clip)
+    return x + (y - x).detach() if straight_through else y
 
 
-def dnc_step(cfg, p, x, prev):
+def dnc_step(cfg, p, x, prev, straight_through=(), trace=None):
+    """straight_through: which of the three clips ("h", "c", "y") pass their gradient unmasked (forward unchanged).  trace: a dict
+    that collects, per step, the LSTM's sigmoid / tanh arguments ("gates": [B, 4 hid] as i, j, f + 1, o), the strength
+    pre-activations and h, c, y before clipping."""
     B = x.shape[0]
     hid = cfg.hid
     ci = torch.cat([x.reshape(B, -1), prev.access_output.reshape(B, -1)], 1)
@@ -124,18 +134,22 @@ def dnc_step(cfg, p, x, prev):
     i, j, f, o = g[:, :hid], g[:, hid:2 * hid], g[:, 2 * hid:3 * hid], g[:, 3 * hid:]
     c2 = torch.sigmoid(f + 1.0) * prev.controller_state.cell + torch.sigmoid(i) * torch.tanh(j)
     h2 = torch.tanh(c2) * torch.sigmoid(o)
-    h = clip(cfg, h2)
-    cs = LSTMState(clip(cfg, h2), clip(cfg, c2))
-    reads, acc = access_step(cfg.access, p, h, prev.access_state)
+    h = clip(cfg, h2, "h" in straight_through)
+    cs = LSTMState(clip(cfg, h2, "h" in straight_through), clip(cfg, c2, "c" in straight_through))
+    reads, acc = access_step(cfg.access, p, h, prev.access_state, trace)
     y = torch.cat([h, reads.reshape(B, -1)], 1) @ p["output_linear/w"] + p["output_linear/b"]
-    return clip(cfg, y), DNCState(reads, acc, cs)
+    if trace is not None:
+        trace.setdefault("gates", []).append(torch.cat([i, j, f + 1.0, o], 1).detach())
+        for nm, v in (("h", h2), ("c", c2), ("y", y)):
+            trace.setdefault(nm, []).append(v.detach())
+    return clip(cfg, y, "y" in straight_through), DNCState(reads, acc, cs)
 
 
-def run_model(cfg, p, inputs_tm, state=None):
+def run_model(cfg, p, inputs_tm, state=None, straight_through=(), trace=None):
     S, B, _ = inputs_tm.shape
     st = state or initial_state(cfg, B, inputs_tm.dtype)
     ys = []
     for t in range(S):
-        y, st = dnc_step(cfg, p, inputs_tm[t], st)
+        y, st = dnc_step(cfg, p, inputs_tm[t], st, straight_through, trace)
         ys.append(y)
     return torch.stack(ys, 0), st

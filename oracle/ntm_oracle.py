@@ -202,13 +202,16 @@ def zero_state(cfg, params, batch):
     }
 
 
-def basic_lstm_cell(x, state, W, b, forget_bias=0.0):
+def basic_lstm_cell(x, state, W, b, forget_bias=0.0, pre=None):
     """TF1 BasicLSTMCell, state_is_tuple=False: state = [c, h];
     [i, j, f, o] = split([x, h] @ W + b); c' = c*sig(f + fb) + sig(i)*tanh(j);
-    h' = tanh(c') * sig(o).  (call site ntm_cell.py:45-50, forget_bias=0.0)"""
+    h' = tanh(c') * sig(o).  (call site ntm_cell.py:45-50, forget_bias=0.0)
+    pre: a list that receives the gate pre-activations [B, 4 hid]."""
     hid = W.shape[1] // 4
     c, h = state[:, :hid], state[:, hid:]
     g = (np.concatenate([x, h], axis=1) @ W + b).astype(x.dtype)
+    if pre is not None:
+        pre.append(g)
     i, j, f, o = g[:, :hid], g[:, hid:2 * hid], g[:, 2 * hid:3 * hid], g[:, 3 * hid:]
     c2 = c * sigmoid(f + x.dtype.type(forget_bias)) + sigmoid(i) * np.tanh(j)
     h2 = np.tanh(c2) * sigmoid(o)
@@ -229,12 +232,12 @@ def ntm_step(cfg, params, x, state):
 
     # :101-105 controller (MultiRNNCell over BasicLSTMCell, forget_bias 0, Q7)
     inp = np.concatenate([x, read_prev.reshape(B, R * Md)], axis=1)
-    new_cs = []
+    new_cs, gates_pre = [], []
     hid = cfg.hidden
     for l in range(cfg.layers):
         st = cs[:, 2 * hid * l:2 * hid * (l + 1)]
         inp, st2 = basic_lstm_cell(inp, st, params["lstm/cell_%d/weights" % l],
-                                   params["lstm/cell_%d/biases" % l], 0.0)
+                                   params["lstm/cell_%d/biases" % l], 0.0, gates_pre)
         new_cs.append(st2)
     h = inp
     new_cs = np.concatenate(new_cs, axis=1)
@@ -271,7 +274,8 @@ def ntm_step(cfg, params, x, state):
     new_state = {"M": M, "w": w, "read": read, "controller_state": new_cs}
     debug = {"k": k, "beta": beta, "g": g, "sw": sw, "gamma": gamma, "erase": erase,
              "add": add, "similarity": sim, "w_content_focused": wc, "w_gated": wg,
-             "w_conv": wv, "w_conv_powed": pw, "w": w, "M_write": M_write.astype(dt), "M_erase": M_erase.astype(dt), "h": h, "u": u}
+             "w_conv": wv, "w_conv_powed": pw, "w": w, "M_write": M_write.astype(dt), "M_erase": M_erase.astype(dt), "h": h, "u": u,
+             "gates_pre": gates_pre}
     return out, logit, new_state, debug
 
 

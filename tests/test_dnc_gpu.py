@@ -191,6 +191,8 @@ BWD_CASES = [
     # name, D, O, N, W, R, Wn, hid, clip, S, B, zero initial state?
     ("small_random_state", 10, 3, 16, 8, 2, 1, 16, 20.0, 5, 2, False),
     ("small_zero_state", 12, 2, 32, 12, 3, 1, 24, 20.0, 6, 2, True),
+    # at clip 0.4 only the CELL clips (|h| = |tanh(c) o| stays below it and y hardly reaches it), and N = 16 runs on the one-workgroup
+    # kernels alone: tests/test_dnc_values_gpu.py has the clip active on h, c and y (clip 0.15) on every kernel family
     ("tight_clip", 10, 2, 16, 8, 2, 1, 16, 0.4, 4, 2, False),
     ("c3_shape", 514, 2, 256, 64, 4, 1, 200, 20.0, 4, 1, False),
     ("c5_shape", 514, 2, 512, 128, 4, 1, 200, 20.0, 3, 1, False),
