@@ -738,6 +738,27 @@ int ntk_crop_and_resize_batch(const void* images, int dtype, int F, int H, int W
                               const float* boxes, const float* mean, float* out, int B, int crop_h, int crop_w,
                               float extrapolation, void* stream);
 
+/* The training input of n frames in ONE launch: out[i] = crop_and_resize(resize_images(frame i, [resize_h, resize_w]) - mean,
+ * boxes[i]) -> out fp32 [n,crop_h,crop_w,C], the composition direct_offset_output.py:193-211 performs per frame
+ * (ntk_resize_bilinear, then ntk_crop_and_resize).  The resized image is never stored: each of the crop stage's four taps is
+ * a pixel of the resized image computed from four source bytes (16 byte loads per output element), by the same two device
+ * functions the single-stage kernels run.  flip_x != 0: output column x holds crop column crop_w-1-x (reverse_image, :203-204).
+ * pixels: uint8, pixels_bytes long, the frames packed one after another, each of its own size; every pixel converted to fp32
+ * exactly.  frame_table int64 [n,7], DEVICE memory, row i = byte_offset, H, W, y0, x0, h, w:
+ *   H x W is the frame's FULL size -- all arithmetic uses it; (y0, x0, h, w) is the sub-rectangle of the frame that is present in
+ *   `pixels`, row-major h*w*C bytes from byte_offset (any byte address: loads are single bytes, no alignment is assumed).
+ *   Packing only the rectangle the crop can touch (data.crop_source_rect) gives the bits of packing the full frame.
+ * No tap can fault: every source index is clamped into the row's rectangle before the load, and a row with h < 1 or w < 1, a
+ * rectangle outside H x W, H or W outside 1..2^30, or bytes outside [0, pixels_bytes) is never dereferenced -- its crop is
+ * `extrapolation` everywhere (the rule of ntk_crop_and_resize_batch for a frame index outside [0, F)).
+ * boxes fp32 [n,4] (y1,x1,y2,x2 normalised, DEVICE memory); mean [C] (nullable).  Plain vector stores only.
+ * Errors, before any launch: NTK_ERR_BAD_PTR for a null pixels / frame_table / boxes / out; NTK_ERR_BAD_SHAPE for n outside
+ * 1..65535, C outside 1..4, resize_h / resize_w / crop_h / crop_w < 1, pixels_bytes < 1, or crop_h * crop_w * C >= 2^31 - 256. */
+#define NTK_FRAME_TABLE_COLS 7
+int ntk_frames_crop_batch(const unsigned char* pixels, long long pixels_bytes, const long long* frame_table, const float* boxes,
+                          const float* mean, float* out, int n, int C, int resize_h, int resize_w, int crop_h, int crop_w,
+                          int flip_x, float extrapolation, void* stream);
+
 /* Per-frame box bookkeeping of the online tracker (test_tracker.py:274-329) for B trackers on the device, one thread per
  * tracker; the offsets are the fp32 tanh the single tracker takes and the shifted box is the fp32 sum it forms, everything after that is double precision.  Box state: double [B, NTK_TRACK_STATE_DOUBLES], per tracker
  *   [0] image width w   [1] image height h   [2..5] normalised object box (y1,x1,y2,x2)   [6..9] crop box (y1,x1,y2,x2)

@@ -11,6 +11,9 @@ Two generations exist in the reference:
      hot path consumes: batch_img [B*T,224,224,3] (mean-subtracted), batch_gt [B*T,8,8], y_offsets, x_offsets.
 Host-side file parsing is plain Python; the image math (resize to 720x1280, mean subtraction, crop_and_resize to
 224x224) runs in HIP kernels.  ``SyntheticSequences`` produces the same four tensors without a dataset.
+``get_input`` does the image math frame by frame; ``get_input_batch`` (second half of this file) gives the same tensors, bit for
+bit, from ONE launch over the packed uint8 frames, with the decoding on a thread pool, and ``InputPrefetcher`` stages the next
+batch while the current one trains (``train.fit`` is the loop that uses them).
 """
 import os
 
@@ -252,3 +255,380 @@ class SyntheticSequences(object):
         offs[:, 0, :] = 0
         d = self.device
         return frames.to(d), gts.to(d), offs[:, :, 0].reshape(-1).to(d), offs[:, :, 1].reshape(-1).to(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The batched input path: uint8 frames packed into one pinned buffer, three uploads and ONE ntk_frames_crop_batch launch per
+# batch (get_input above stays as the per-frame statement of the same contract; the two give the same bits).
+# ---------------------------------------------------------------------------------------------------------------------------
+
+RESIZE_TO = (720, 1280)
+CROP = (224, 224)
+FRAME_TABLE_COLS = 7            # byte_offset, H, W, y0, x0, h, w  (NTK_FRAME_TABLE_COLS)
+MAX_FRAMES_PER_LAUNCH = 65535   # blockIdx.y = frame
+
+
+def default_workers():
+    """Decoder threads: the CPUs this process may run on, at most 16 (never the machine's CPU count)."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def _axis_source_range(size, resized, crop_n, lo, hi, margin):
+    """One axis of crop_source_rect: (first, count) of the source indices the composed sampling can touch, or None."""
+    scale = float(resized - 1)
+    if crop_n > 1:
+        step = (hi - lo) * scale / float(crop_n - 1)
+        ends = (lo * scale, lo * scale + float(crop_n - 1) * step)
+    else:
+        ends = (0.5 * (lo + hi) * scale,) * 2
+    a, b = min(ends), max(ends)
+    if not (np.isfinite(a) and np.isfinite(b)) or b < -1.0 or a > scale + 1.0:
+        return None
+    # taps of the crop stage are rows floor(v) and ceil(v) of the resized image for the samples v inside [0, resized-1]; one
+    # resized row more on either side absorbs the fp32 rounding of v against this float64 restatement
+    r0 = int(max(0.0, np.floor(max(a, 0.0)) - 1.0))
+    r1 = int(min(scale, np.ceil(min(b, scale)) + 1.0))
+    # resized row r reads source rows floor(r * size / resized) and the next one
+    ratio = float(size) / float(resized)
+    s0 = int(np.floor(r0 * ratio)) - margin
+    s1 = int(np.floor(r1 * ratio)) + 1 + margin
+    s0, s1 = max(0, min(s0, size - 1)), max(0, min(s1, size - 1))
+    return s0, s1 - s0 + 1
+
+
+def crop_source_rect(size_hw, cropbox, resize_to=RESIZE_TO, crop=CROP, margin=2):
+    """The rectangle (y0, x0, h, w) of a source image of size_hw = (H, W) that ntk_frames_crop_batch can read for `cropbox`
+    (y1, x1, y2, x2, normalised): the source pixels behind every tap of crop_and_resize(resize_images(image, resize_to), cropbox)
+    to `crop`, widened by one row / column of the resized image (the kernel's fp32 sample positions against this float64
+    restatement) and by `margin` source pixels, clipped to the image.  A box whose samples all fall outside the image touches
+    nothing: the result is then the 1x1 rectangle at the origin.  Pure NumPy, float64."""
+    H, W = int(size_hw[0]), int(size_hw[1])
+    y1, x1, y2, x2 = [float(v) for v in cropbox]
+    rows = _axis_source_range(H, int(resize_to[0]), int(crop[0]), y1, y2, int(margin))
+    cols = _axis_source_range(W, int(resize_to[1]), int(crop[1]), x1, x2, int(margin))
+    if rows is None or cols is None:
+        return 0, 0, 1, 1
+    return rows[0], cols[0], rows[1], cols[1]
+
+
+def check_frame_table(table, pixels_bytes, channels):
+    """Host validation of a frame table (the kernel repeats it per row and turns a bad row into the extrapolation value; here a
+    bad row is an error, since the host built it): every rectangle non-empty, inside its image and inside the buffer."""
+    t = np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != FRAME_TABLE_COLS or t.dtype != np.int64:
+        raise ValueError("frame table must be int64 [n,%d], not %s %s" % (FRAME_TABLE_COLS, t.dtype, t.shape))
+    for i, (off, H, W, y0, x0, h, w) in enumerate(t.tolist()):
+        if H < 1 or W < 1 or h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError("frame table row %d: rectangle y0=%d x0=%d h=%d w=%d leaves the %dx%d image" % (i, y0, x0, h, w, H, W))
+        if off < 0 or off + h * w * channels > pixels_bytes:
+            raise ValueError("frame table row %d: bytes [%d, %d) leave the buffer of %d bytes"
+                             % (i, off, off + h * w * channels, pixels_bytes))
+
+
+class Staging(object):
+    """One set of host staging buffers of the batched path, owned and reused by the caller: pixels (uint8), the frame table
+    (int64 [n,7]), the boxes (fp32 [n,4]) and the labels (fp32 [n,66]: the 8x8 heat-map, y offset, x offset).  Pinned where a
+    device is present (pin=None), so that the uploads can be asynchronous.  Buffers grow when a batch needs more."""
+
+    def __init__(self, pin=None):
+        self.pin = torch.cuda.is_available() if pin is None else bool(pin)
+        self.pixels = self._new((0,), torch.uint8)
+        self.table = self._new((0, FRAME_TABLE_COLS), torch.int64)
+        self.boxes = self._new((0, 4), torch.float32)
+        self.labels = self._new((0, 66), torch.float32)
+
+    def _new(self, shape, dtype):
+        return torch.empty(shape, dtype=dtype, pin_memory=self.pin)
+
+    def fits(self, nbytes, n):
+        return self.pixels.numel() >= nbytes and self.table.shape[0] >= n
+
+    def ensure(self, nbytes, n):
+        """Grow (with a quarter of headroom, so that batches of slightly different size do not grow it again)."""
+        if self.pixels.numel() < nbytes:
+            self.pixels = self._new((nbytes + nbytes // 4,), torch.uint8)
+        if self.table.shape[0] < n:
+            self.table = self._new((n, FRAME_TABLE_COLS), torch.int64)
+            self.boxes = self._new((n, 4), torch.float32)
+            self.labels = self._new((n, 66), torch.float32)
+
+
+class PackedFrames(object):
+    """pack_frames' result: views of the first `nbytes` bytes / n rows of a Staging set."""
+
+    def __init__(self, staging, nbytes, n, channels, resize_to, crop):
+        self.staging, self.nbytes, self.n, self.channels = staging, nbytes, n, channels
+        self.resize_to, self.crop = tuple(resize_to), tuple(crop)
+        self.pixels, self.table, self.boxes = staging.pixels[:nbytes], staging.table[:n], staging.boxes[:n]
+
+
+def pack_frames(images, cropboxes, resize_to=RESIZE_TO, crop=CROP, margin=2, pack="rect", staging=None, pad=0, grow=True):
+    """uint8 images [H_i,W_i,C] and their crop boxes -> PackedFrames: the pixels ntk_frames_crop_batch may read, packed one frame
+    after another behind `pad` leading bytes, with the int64 frame table and the fp32 boxes.  pack="rect" packs only
+    crop_source_rect of each frame, pack="full" all of it (same crops, bit for bit; more bytes).  `staging`: the Staging set to
+    fill (made when None); it grows when the batch needs more -- unless grow=False, when a batch that does not fit is packed
+    into a fresh unpinned set instead (a thread that must make no device-runtime call packs this way).  Every table row is
+    validated (check_frame_table)."""
+    if pack not in ("rect", "full"):
+        raise ValueError("pack must be 'rect' or 'full', not %r" % (pack,))
+    n = len(images)
+    if n < 1 or len(cropboxes) != n:
+        raise ValueError("pack_frames: %d images, %d crop boxes" % (n, len(cropboxes)))
+    C = int(images[0].shape[2])
+    rows, off = [], int(pad)
+    for img, box in zip(images, cropboxes):
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != C:
+            raise ValueError("pack_frames: images must be uint8 [H,W,%d], not %s %s" % (C, img.dtype, img.shape))
+        H, W = img.shape[:2]
+        y0, x0, h, w = crop_source_rect((H, W), box, resize_to, crop, margin) if pack == "rect" else (0, 0, H, W)
+        rows.append((off, H, W, y0, x0, h, w))
+        off += h * w * C
+    nbytes = off
+    if staging is None:
+        staging = Staging()
+    if not staging.fits(nbytes, n):
+        if not grow:
+            staging = Staging(pin=False)
+        staging.ensure(nbytes, n)
+    table = staging.table.numpy()[:n]
+    table[:] = np.asarray(rows, dtype=np.int64)
+    check_frame_table(table, nbytes, C)
+    staging.boxes.numpy()[:n] = np.asarray(cropboxes, dtype=np.float64).reshape(n, 4).astype(np.float32)
+    buf = staging.pixels.numpy()
+    buf[:pad] = 0
+    for img, (o, _H, _W, y0, x0, h, w) in zip(images, rows):
+        buf[o:o + h * w * C].reshape(h, w, C)[...] = img[y0:y0 + h, x0:x0 + w]
+    return PackedFrames(staging, nbytes, n, C, resize_to, crop)
+
+
+_MEANS = {}
+
+
+def _vgg_mean(dev):
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _MEANS:
+        _MEANS[key] = torch.tensor(VGG_MEAN, device=dev)
+    return _MEANS[key]
+
+
+def frames_crop_batch(packed, device="cuda", mean=None, flip_x=False, extrapolation=0.0, out=None):
+    """Upload a PackedFrames (pixels, table, boxes: one asynchronous copy each when the staging is pinned) and crop it on the
+    current stream: -> fp32 [n,crop_h,crop_w,C] on the device; ONE ntk_frames_crop_batch launch per 65 535 frames."""
+    L, P = _lib.lib(), _lib.ptr
+    dev = torch.device(device)
+    n, C, (ch, cw) = packed.n, packed.channels, packed.crop
+    pix = packed.pixels.to(dev, non_blocking=True)
+    table = packed.table.to(dev, non_blocking=True)
+    boxes = packed.boxes.to(dev, non_blocking=True)
+    if out is None:
+        out = torch.empty((n, ch, cw, C), device=dev)
+    elif tuple(out.shape) != (n, ch, cw, C) or out.dtype != torch.float32:
+        raise _lib.NtkError("frames_crop_batch: out must be fp32 %s, not %s %s" % ((n, ch, cw, C), out.dtype, tuple(out.shape)))
+    for s in range(0, n, MAX_FRAMES_PER_LAUNCH):
+        e = min(n, s + MAX_FRAMES_PER_LAUNCH)
+        _lib.check(L.ntk_frames_crop_batch(P(pix), packed.nbytes, P(table[s:e]), P(boxes[s:e]), P(mean), P(out[s:e]), e - s, C,
+                                           packed.resize_to[0], packed.resize_to[1], ch, cw, 1 if flip_x else 0,
+                                           float(extrapolation), _lib.stream()), "ntk_frames_crop_batch")
+    return out
+
+
+def _decode_image_u8(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+def _load_frame(name, image_root):
+    rec = load_frame_record(name)
+    path = rec["image_path"] if image_root is None else os.path.join(image_root, rec["image_path"])
+    return rec, _decode_image_u8(path)
+
+
+class StagedBatch(object):
+    """A batch on the host, ready for upload_staged: the packed frames and, in the same Staging set, the labels."""
+
+    def __init__(self, names, packed):
+        self.names, self.packed = names, packed
+        self.labels = packed.staging.labels[:packed.n]
+        self.uploaded = None            # event after the uploads (set by upload_staged on a device)
+
+
+def stage_batch(frame_names_nosuffix, image_root=None, pool=None, pack="rect", staging=None, grow=True):
+    """Host half of get_input_batch: read and decode the records and images (on `pool`'s threads when given), pack them.
+    No device-runtime call is made when grow=False."""
+    names = list(frame_names_nosuffix)
+    if pool is not None:
+        loaded = list(pool.map(lambda nm: _load_frame(nm, image_root), names))
+    else:
+        loaded = [_load_frame(nm, image_root) for nm in names]
+    packed = pack_frames([img for _r, img in loaded], [r["cropbox"] for r, _i in loaded], pack=pack, staging=staging, grow=grow)
+    lab = packed.staging.labels.numpy()[:len(names)]
+    for i, (rec, _img) in enumerate(loaded):
+        lab[i, :64] = rec["gt"].reshape(-1)
+        lab[i, 64], lab[i, 65] = rec["y_offset"], rec["x_offset"]
+    return StagedBatch(names, packed)
+
+
+def upload_staged(staged, device="cuda", reverse_image=False):
+    """Device half of get_input_batch, on the current stream: -> get_input's four tensors."""
+    dev = torch.device(device)
+    batch_img = frames_crop_batch(staged.packed, dev, mean=_vgg_mean(dev), flip_x=reverse_image)
+    lab = staged.labels.to(dev, non_blocking=True)
+    if dev.type == "cuda":
+        staged.uploaded = torch.cuda.Event()
+        staged.uploaded.record()
+    batch_gt = lab[:, :64].reshape(-1, 8, 8).contiguous()
+    y_off, x_off = lab[:, 64].contiguous(), lab[:, 65].contiguous()
+    if reverse_image:                                   # :187-188; the image itself is flipped by the kernel
+        x_off = -x_off
+    return batch_img, batch_gt, y_off, x_off
+
+
+def get_input_batch(frame_names_nosuffix, device="cuda", reverse_image=False, image_root=None, workers=None, pack="rect",
+                    staging=None):
+    """get_input's contract -- (batch_img [n,224,224,3], batch_gt [n,8,8], y_offsets [n], x_offsets [n]), x_offsets negated and
+    the crops flipped when reverse_image is set -- and its bits, in one launch: the records and images are read and decoded by
+    `workers` threads (default_workers() when None; threads, not processes, and they make no device-runtime call), the uint8
+    pixels each crop can touch are packed into pinned memory (`staging`, reused by the caller across batches), and after three
+    asynchronous uploads ntk_frames_crop_batch resizes, subtracts the mean, crops and flips on the current stream.  A caller
+    that reuses `staging` must not call again before the previous call's uploads have run (synchronise the stream, or use
+    InputPrefetcher, which alternates two sets)."""
+    from concurrent.futures import ThreadPoolExecutor
+    workers = default_workers() if workers is None else int(workers)
+    if workers > 1 and len(frame_names_nosuffix) > 1:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            staged = stage_batch(frame_names_nosuffix, image_root, pool, pack, staging)
+    else:
+        staged = stage_batch(frame_names_nosuffix, image_root, None, pack, staging)
+    return upload_staged(staged, device, reverse_image)
+
+
+class InputPrefetcher(object):
+    """Iterator over `batches` (an iterable of lists of frame names, consumed lazily) that yields each as a StagedBatch, in order, while a background thread
+    already stages the next one: batch i+1 is read, decoded (by `workers` pool threads) and packed into the other of `depth`
+    Staging sets while the caller trains on batch i.  The background threads make no device-runtime call: uploads and the
+    launch (upload_staged) stay on the consumer's thread, and a batch that outgrows its pinned set is packed unpinned and
+    moved into a grown pinned set by the consumer.  A set is handed back to the background thread when the consumer asks for the
+    next batch, after the uploads from it have run.  An exception while staging batch i is re-raised by the __next__ that
+    would have returned batch i.  close() stops and joins the threads; it is also called by __del__ and on leaving a
+    ``with`` block.  `stage`: the staging function, stage(names, staging) -> StagedBatch (default: stage_batch)."""
+
+    def __init__(self, batches, depth=2, image_root=None, workers=None, pack="rect", stage=None):
+        import queue
+        import threading
+        from concurrent.futures import ThreadPoolExecutor
+        if depth < 1:
+            raise ValueError("depth must be at least 1, not %d" % depth)
+        self._batches = batches         # any iterable of name lists, consumed as the run goes (a generator: nothing is built ahead)
+        self._sets = [Staging() for _ in range(depth)]
+        self._free, self._ready = queue.Queue(), queue.Queue()
+        for k in range(depth):
+            self._free.put(k)
+        self._held = None               # (set index, StagedBatch) the consumer is using
+        self._next, self._closed, self._done = 0, False, False
+        self._stop = threading.Event()
+        workers = default_workers() if workers is None else int(workers)
+        self._pool = ThreadPoolExecutor(max_workers=workers) if workers > 1 else None
+        if stage is None:
+            stage = lambda names, staging: stage_batch(names, image_root, self._pool, pack, staging, grow=False)
+        self._stage = stage
+        self._thread = threading.Thread(target=self._produce, name="ntmtrack-input-prefetch", daemon=True)
+        self._thread.start()
+
+    _END = object()                     # after the last batch
+
+    def _produce(self):
+        import queue
+        source, i = iter(self._batches), 0
+        while True:
+            k = None
+            while k is None:
+                if self._stop.is_set():
+                    return
+                try:
+                    k = self._free.get(timeout=0.05)
+                except queue.Empty:
+                    pass
+            try:
+                names = next(source)
+            except StopIteration:
+                self._ready.put((i, k, None, self._END))
+                return
+            except BaseException as e:          # noqa: B902 -- the source of batches itself failed: nothing can follow
+                self._ready.put((i, k, None, e))
+                self._ready.put((i + 1, None, None, self._END))
+                return
+            try:
+                item = (i, k, self._stage(names, self._sets[k]), None)
+            except BaseException as e:          # noqa: B902 -- handed to the consumer, which re-raises it at this batch
+                item = (i, k, None, e)
+            self._ready.put(item)
+            i += 1
+
+    def _release(self):
+        if self._held is not None:
+            k, staged = self._held
+            if staged is not None and getattr(staged, "uploaded", None) is not None:
+                staged.uploaded.synchronize()
+            self._held = None
+            self._free.put(k)
+
+    def __iter__(self):
+        return self
+
+    def __len__(self):
+        return len(self._batches)       # TypeError for a generator, as for any iterator without a length
+
+    def __next__(self):
+        import queue
+        if self._closed or self._done:
+            raise StopIteration
+        self._release()
+        while True:
+            try:
+                i, k, staged, err = self._ready.get(timeout=0.05)
+                break
+            except queue.Empty:
+                if not self._thread.is_alive() and self._ready.empty():
+                    raise RuntimeError("InputPrefetcher: the staging thread ended before batch %d" % self._next)
+        if err is self._END:
+            self._done = True
+            raise StopIteration
+        assert i == self._next
+        self._next += 1
+        self._held = (k, staged)
+        if err is not None:
+            raise err
+        packed = getattr(staged, "packed", None)
+        if packed is not None and packed.staging is not self._sets[k]:
+            # the batch outgrew set k: grow the pinned set here, on the consumer's thread, and move the batch into it
+            old, st = packed.staging, self._sets[k]
+            st.ensure(packed.nbytes, packed.n)
+            st.pixels[:packed.nbytes].copy_(old.pixels[:packed.nbytes])
+            for a in ("table", "boxes", "labels"):
+                getattr(st, a)[:packed.n].copy_(getattr(old, a)[:packed.n])
+            staged.packed = PackedFrames(st, packed.nbytes, packed.n, packed.channels, packed.resize_to, packed.crop)
+            staged.labels = st.labels[:packed.n]
+        return staged
+
+    def close(self):
+        if getattr(self, "_closed", True):
+            return
+        self._closed = True
+        self._stop.set()
+        self._thread.join()
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -317,6 +317,13 @@ class NTMOffsetTracker(_TwoStreamPipeline, _Checkpointing):
         self.cell.init_state_backward(g0, self.B)
         return loss, pred
 
+    def eval_loss(self, frames, gts0, offsets):
+        """Forward only, on the caller's stream (after everything the pipeline streams hold): the same un-normalised loss
+        train_step / train_on_submitted return, as a 1-element device tensor.  No gradient is computed and nothing is updated."""
+        self.join()
+        _X, _st0, logits, _ = self.forward_features(self.features(frames), gts0)
+        return offset_loss(logits, offsets, self.T, want_grad=False)[0]
+
     def _flat_grad(self):
         return self.cell.params.grad
 
@@ -435,6 +442,16 @@ class DNCOffsetTracker(_TwoStreamPipeline, _Checkpointing):
         parallel.allreduce_gradients(self.core.params.grad)
         self.opt.step(loss)
         return loss
+
+    def eval_loss(self, frames, gts0, offsets):
+        """Forward only, on the caller's stream (after everything the pipeline streams hold): the same un-normalised loss
+        train_step / train_on_submitted return, as a 1-element device tensor.  No gradient is computed and nothing is updated;
+        an aborted cluster launch shows at the next check_step()."""
+        if self.vgg is None:
+            raise _lib.NtkError("tracker was built without VGG weights")
+        self.join()
+        logits, _ = self.forward_features(self.vgg(frames), gts0)
+        return offset_loss(logits, offsets, self.T, want_grad=False)[0]
 
     def infer(self, frames, gts0):
         if self.vgg is None:
