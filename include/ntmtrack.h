@@ -100,6 +100,20 @@ int ntk_vgg_pack_weights_split3(const float* w_hwio, void* w_packed, int cin, in
 int ntk_vgg_conv3x3_relu_split3(const void* in_split, const void* w_packed, const float* bias, void* out,
                                 int frames, int H, int W, int cin, int cout, int fuse_pool, int in_f32, int out_f32, void* stream);
 
+/* The fused stem: conv1_1 (3 -> 64) computed inside the staging of conv1_2 (64 -> 64, split form), so that conv1_1's
+ * [frames][H][W][64] fp32 map is neither written nor read.  frames_f32: [frames][H][W][3] fp32; w1_packed / bias1: conv1_1's weights as
+ * ntk_vgg_pack_weights(cin 3, cout 64) packs them ([64][32], k = tap * 3 + c) and its 64 biases; w2_packed / bias2: conv1_2's weights
+ * from ntk_vgg_pack_weights_split3(cin 64, cout 64, H, W) and its biases; out as ntk_vgg_conv3x3_relu_split3 (a split map, or fp32 NHWC
+ * with out_f32 = 1; H/2 x W/2 with fuse_pool).  conv1_1 is evaluated in fp32 (fp32 MFMAs over k in order, + bias, ReLU) on every pixel
+ * of a sub-block and its one-pixel halo, clamped and split exactly as an fp32 input map is (in_f32 = 1 above); halo pixels outside the
+ * frame are zero (conv1_2's padding).  Results: bit for bit those of ntk_vgg_conv3x3_relu_f32 + ntk_vgg_conv3x3_relu_split3(in_f32 = 1)
+ * where W is a multiple of 32 (conv1_1's row kernel sums in the same order); equal to fp32 rounding of conv1_1 elsewhere.  Shapes
+ * (ntk_vgg_split3_stem_supported): H, W multiples of 8; sub-blocks of 32x8 and 16x16 run two workgroups per CU, 8x8 (H or W not a
+ * multiple of 16) one.  w2_packed, bias2 and out 16-byte aligned. */
+int ntk_vgg_split3_stem_supported(int H, int W, int fuse_pool);
+int ntk_vgg_conv3x3_relu_split3_stem(const float* frames_f32, const float* w1_packed, const float* bias1, const void* w2_packed,
+                                     const float* bias2, void* out, int frames, int H, int W, int fuse_pool, int out_f32, void* stream);
+
 /* The same operator by fused Winograd F(2x2,3x3) on the fp32 MFMA pipe (2.25x fewer multiplies; results equal to
  * ntk_vgg_conv3x3_relu_f32 up to rounding, ~1e-6 relative per layer).  Weights: U = G g G^T for the 16 transform
  * planes, packed lane-major for the MFMA B operand (ntk_vgg_wino_packed_floats(cin, cout) = 16*cin*cout floats).

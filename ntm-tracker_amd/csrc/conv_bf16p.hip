@@ -28,6 +28,7 @@
 // Same operator, operand rounding and accumulation type as conv_bf16.hip (bf16 operands, fp32 accumulate, one bf16 rounding
 // on store; vgg.py:155-161); the summation ORDER over (chunk, tap, channel) differs, so results agree to fp32 rounding.
 #include "conv_tiles.h"
+#include "conv_stem.h"
 
 // Ablation switches (timing only, results wrong; never defined in the product build): bit 0 no DMA after the prologue, bit 1 no
 // workgroup barrier / DMA wait in the K loop, bit 2 fragments not re-read (one set for the whole kernel), bit 3 no MFMAs, bit 4 no epilogue, bit 5 the un-pooled epilogue without its global stores
@@ -47,6 +48,8 @@ struct Bf16pArgs {
     int bxN, byN;       // sub-blocks per frame
     int NQ, NS;         // sub-blocks in all, workgroups per column block
     int nCB;            // Cout / BN
+    // STEM only: the fp32 frames [frames][H][W][3] and conv1_1's packed weights [64][32] (k = tap * 3 + c) and bias
+    const float* stem_in = nullptr; const float* stem_w = nullptr; const float* stem_b = nullptr;
 };
 
 // One LDS-DMA piece (1 KB per wave): buffer_load_dwordx4 ... lds through inline assembly.  The builtin
@@ -183,10 +186,18 @@ __global__ void split3_pack_kernel(const float* __restrict__ w, _Float16* __rest
 // row (f - f0)(H + 1) + y + 1 - y0, so a tap is the same uniform shift as everywhere else.  H >= 20: at most one frame boundary per run.
 // INF32 (split form, four-wave workgroups): the input is an fp32 NHWC map and the STAGING splits it -- 16-byte pieces through registers
 // (two or three per lane and stage, requested at the top of a stage, split and written to the patch image at its end) instead of DMA.
-// That is how the trunk enters the split form: conv1_1 keeps its fp32 kernel and conv1_2 reads its map as it is.
-template <int BN, int TW, int TH, int NSUB, int KC, bool POOL, bool OUTF32, int NW = 8, bool X3 = false, bool INF32 = false>
+// That is how the trunk enters the split form with a separate conv1_1: conv1_1 keeps its fp32 kernel and conv1_2 reads its map as it is.
+// STEM (split form, four-wave workgroups, conv1_2 only): the input map does not exist -- the patch image of a chunk is COMPUTED from the
+// 3-channel frames: conv1_1 (fp32 MFMAs, k = tap * 3 + c in order, + bias, ReLU) evaluated on the patch's pixels, clamped and split as
+// f32_put does.  The frame patch (the sub-block + two pixels of halo, zeros outside the frame) and conv1_1's 27 x 64 weights stay in
+// LDS for the whole workgroup.  A wave takes tiles of sixteen patch pixels x the chunk's 16 channels (conv_stem.h), two per stage
+// (three on 8x8x4), seven v_mfma_f32_16x16x4_f32 each, spread over the sub-steps of the main loop behind their fp16 MFMAs (first
+// built on the vector ALU: 216 v_fma per lane and stage, none of it hidden -- the fused kernel took as long as the two it replaces).
+// A patch pixel outside the frame is zero, as conv1_2's padding demands.
+template <int BN, int TW, int TH, int NSUB, int KC, bool POOL, bool OUTF32, int NW = 8, bool X3 = false, bool INF32 = false, bool STEM = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv3x3_relu_bf16p_kernel(Bf16pArgs a) {
     static_assert(!INF32 || (X3 && NW == 4), "fp32 input: split form on four waves (the eight-wave form has no registers for the staging)");
+    static_assert(!STEM || (X3 && NW == 4 && !INF32 && (TW & (TW - 1)) == 0 && TW % 2 == 0), "fused stem: split form on four waves, sub-blocks");
     constexpr int PNT = 2 * NW;                                                 // 32-pixel tiles per workgroup
     constexpr bool ROWS = (TW & (TW - 1)) != 0;
     static_assert(!X3 || KC == 32, "split form: 16 real channels = one 32-channel chunk");
@@ -198,7 +209,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     static_assert(!ROWS || TW + 2 <= 32, "runs of rows: the patch row pitch is 32");
     constexpr int PIXB = KC * 2, PIECES = KC / 8, PPP = 1024 / PIXB;            // bytes per pixel row, 16-B pieces per row, rows per DMA
     constexpr int NPA = (NPX + PPP - 1) / PPP;                                  // DMA pieces of the patch
-    constexpr int ABYTES = NPA * 1024;
+    // (STEM: nothing is DMAed into the patch buffers, so they are not rounded up to whole DMA pieces -- the room the frame patch takes)
+    constexpr int ABYTES = STEM ? NPX * PIXB : NPA * 1024;
     // a stage = the taps whose weights share one LDS buffer and one barrier: a kernel row (3 taps) with 32-channel chunks, the whole
     // chunk (9 taps) with 16-channel chunks (its weights are half the size, and its steps half as many per tap)
     constexpr int STAPS = KC == 16 ? 9 : 3, SPC = 9 / STAPS;                    // taps per stage, stages per chunk
@@ -210,7 +222,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     static_assert(ROWS || NSUB * TW * TH == 32 * PNT, "512 (256) output pixels per workgroup");
     constexpr int TRB = POOL ? 0 : NW * TM * 32 * 144;                           // the un-pooled epilogue's transpose image (below)
     constexpr int LDSB = (2 * ABYTES + 2 * SBYTES) > TRB ? (2 * ABYTES + 2 * SBYTES) : TRB;
-    static_assert(LDSB + 1024 <= (NW == 8 ? 160 : 80) * 1024, "LDS");
+    // STEM: the frame patches, conv1_1's weights as [chunk][k][16 channels] and its bias.  8x8x4 patches are too large for two
+    // workgroups per CU beside them (the trunk never runs that shape: its frames are multiples of 32 wide)
+    constexpr int FPW = TW + 4, FPN = STEM ? NSUB * (TH + 4) * FPW * 3 : 4;
+    constexpr int STEMB = STEM ? (FPN + 4 * 27 * 16 + 64) * 4 : 0;
+    static_assert(LDSB + STEMB + 1024 <= ((NW == 8 || (STEM && NSUB > 1)) ? 160 : 80) * 1024, "LDS");
+    __shared__ __attribute__((aligned(16))) float s_fp[FPN];
+    __shared__ __attribute__((aligned(16))) float s_w1[STEM ? 4 * 27 * 16 : 4];
+    __shared__ __attribute__((aligned(16))) float s_b1[STEM ? 64 : 4];
     __shared__ __attribute__((aligned(1024))) unsigned char s_mem[LDSB];
     // s_mem: two patch buffers of ABYTES, then two weight-stage buffers of SBYTES
     __shared__ int s_sbf[NSUB], s_sby[NSUB], s_sbx[NSUB];
@@ -229,7 +248,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     if (tid < BN) s_bias[tid] = a.bias[cb * BN + tid];
     if (X3 && tid == BN) s_bias[BN] = *reinterpret_cast<const float*>(a.wq + (size_t)9 * a.Cin * a.Cout);
     if constexpr (!ROWS) conv_tile_subblocks<NSUB>(s_sbf, s_sby, s_sbx, tid, sp, a.NQ, a.bxN, a.byN, TH, TW, 0, 0);
+    if constexpr (STEM) {
+        for (int e = tid; e < 4 * 27 * 16; e += 64 * NW) {                      // [chunk][k][16] <- packed [64][32]
+            const int k = (e >> 4) % 27;
+            s_w1[e] = a.stem_w[((e / (27 * 16)) * 16 + (e & 15)) * 32 + k];
+        }
+        if (tid < 64) s_b1[tid] = a.stem_b[tid];
+    }
     __syncthreads();
+    if constexpr (STEM) {                                                       // the frame patches: zeros outside the frame and past the batch
+        for (int e = tid; e < FPN; e += 64 * NW) {
+            int q, fy, fx, c, y, x;
+            stem_fp_elem(e, TW, TH, q, fy, fx, c);
+            const bool in = stem_fp_src(fy, fx, s_sby[q], s_sbx[q], H, W, y, x) && s_sbf[q] >= 0;
+            s_fp[e] = in ? a.stem_in[(((size_t)s_sbf[q] * H + y) * W + x) * 3 + c] : 0.f;
+        }
+        __syncthreads();
+    }
 
     // the patch image's swizzle: slot of piece 0 of patch pixel p.  ROWS: by the pixel's position in the RUN (28 per row), not in the
     // patch (32 per row): consecutive run pixels then have consecutive residues mod 16 across row ends, and since 28 = 0 mod 4 the
@@ -293,6 +328,61 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
         for (int e = 0; e < 4; ++e) c[e] = __builtin_amdgcn_fmed3f(v[e], -S3_MAX, S3_MAX);
         s3_split4(c, h, l);
+        *reinterpret_cast<ph16x4*>(s_mem + dst) = h;
+        *reinterpret_cast<ph16x4*>(s_mem + (dst ^ 32)) = l;
+    };
+    // STEM: the patch's pixels in tiles of sixteen; tile wave + NW i is this wave's i-th.  One v_mfma_f32_16x16x4_f32 chain of seven
+    // steps per tile: rows = the chunk's 16 channels (A = conv1_1's weights), columns = the tile's pixels (B = frame-patch values),
+    // k = 4 s + g for lane (g = lane / 16, pi = lane % 16) -- the lane then holds channels 4 g .. 4 g + 3 of pixel pi: the same
+    // four-channel items f32_put splits.  sfo = float offset in s_fp of the pixel's 3 x 3 window, bit 30: the pixel is outside the
+    // frame (conv1_2 reads zero), negative: no such pixel; skof = the offset of operand k of step s (k = 27: a zero weight).
+    constexpr int STILES = (NPX + 15) / 16;
+    constexpr int SNIT = STEM ? (STILES + NW - 1) / NW : 1, SNITS = (SNIT + SPC - 1) / SPC;
+    const int spi = lane & 15, sg = lane >> 4;
+    int sfo[SNIT], skof[7];
+    if constexpr (STEM) {
+#pragma unroll
+        for (int i = 0; i < SNIT; ++i) {
+            const int lp = 16 * (wave + NW * i) + spi;
+            sfo[i] = -1;
+            if (lp < NPX) {
+                int q, py, px;
+                stem_pixel(lp, TW, TH, q, py, px);
+                const bool in = s_sbf[q] >= 0 && stem_inside(py, px, s_sby[q], s_sbx[q], H, W);
+                sfo[i] = stem_fp_corner(q, py, px, TW, TH) | (in ? 0 : 0x40000000);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 7; ++s) skof[s] = 4 * s + sg < 27 ? stem_fp_k(4 * s + sg, TW) : 0;
+    }
+    float swa[7], sxs[SNITS][7];                                                // a stage's operands: weights, and the pixels' values per tile
+    f32x4 sbv, sacc[SNITS];
+    // tile i of this wave: request its operands (and with j = 0 the chunk's weights and biases)
+    auto stem_load = [&](int chunk, int i, int j) {
+        if (j == 0) {
+#pragma unroll
+            for (int s = 0; s < 7; ++s) swa[s] = 4 * s + sg < 27 ? s_w1[(chunk * 27 + 4 * s + sg) * 16 + spi] : 0.f;
+            sbv = *reinterpret_cast<const f32x4*>(s_b1 + chunk * 16 + 4 * sg);
+        }
+        const float* fp = s_fp + (sfo[i] < 0 ? 0 : (sfo[i] & 0xffffff));
+#pragma unroll
+        for (int s = 0; s < 7; ++s) sxs[j][s] = 4 * s + sg < 27 ? fp[skof[s]] : 0.f;
+    };
+    auto stem_mfma = [&](int j, int s) {
+        if (s == 0) sacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        sacc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(swa[s], sxs[j][s], sacc[j], 0, 0, 0);
+    };
+    // ... + bias, ReLU and the split's range in one v_med3, zero outside the frame, split into patch buffer `buf`
+    auto stem_put = [&](int i, int j, int buf) {
+        if (sfo[i] < 0) return;
+        const int lp = 16 * (wave + NW * i) + spi;
+        const bool in = !(sfo[i] & 0x40000000);
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = in ? __builtin_amdgcn_fmed3f(sacc[j][e] + sbv[e], 0.f, S3_MAX) : 0.f;
+        ph16x4 h, l;
+        s3_split4(v, h, l);
+        const int dst = buf * ABYTES + lp * PIXB + (((sg >> 1) ^ a_sw(lp)) << 4) + (sg & 1) * 8;
         *reinterpret_cast<ph16x4*>(s_mem + dst) = h;
         *reinterpret_cast<ph16x4*>(s_mem + (dst ^ 32)) = l;
     };
@@ -398,10 +488,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
         for (int i = 0; i < NIT; ++i)
             if (fdst[i] >= 0) f32_put(v[i], fdst[i]);
-    } else {
+    } else if constexpr (!STEM) {
         dma_patch(0, 0, 0, NPAW);
     }
     dma_weights(0, 0);
+    if constexpr (STEM) {                                                       // chunk 0's patch image, while the weights land
+#pragma unroll
+        for (int i = 0; i < SNIT; ++i) {
+            stem_load(0, i, 0);
+#pragma unroll
+            for (int s = 0; s < 7; ++s) stem_mfma(0, s);
+            stem_put(i, 0, 0);
+        }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -418,7 +517,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
         // they stop both waves of every SIMD at once (ablation: 24 % of the kernel); behind eight queued MFMAs the other wave
         // of the SIMD has the pipe meanwhile.
         constexpr int NDW = (NPB + NW - 1) / NW;                                 // weight pieces per wave and stage
-        constexpr int NDP = INF32 ? 0 : (NPAW + SPC - 1) / SPC;                  // patch pieces per wave and stage
+        constexpr int NDP = (INF32 || STEM) ? 0 : (NPAW + SPC - 1) / SPC;        // patch pieces per wave and stage
         const bool more_w = !(BF16P_ABL & 1) && s + 1 < NSTG, more_p = !(BF16P_ABL & 1) && chunk + 1 < NC;
         auto dma_slot = [&](auto kc) {                                           // k-th DMA of this stage
             constexpr int k = decltype(kc)::value;
@@ -427,6 +526,29 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 if (more_p) dma_patch1(chunk + 1, abuf ^ 1, ntk_ic<part * NDP + (k - NDW)>{});
             }
         };
+        // STEM: this stage's tiles of the next chunk's patch: operands requested at the top of the stage, their 7 SNITS fp32 MFMAs
+        // spread over the nine sub-steps, each tile split into the other patch buffer behind its last MFMA
+        constexpr int SPER = (7 * SNITS + 8) / 9;                                // fp32 MFMAs per sub-step
+        auto stem_slot = [&](auto kc) {
+            if constexpr (STEM) {
+                constexpr int k = decltype(kc)::value;
+                if (more_p) {
+#pragma unroll
+                    for (int u = k * SPER; u < (k + 1) * SPER && u < 7 * SNITS; ++u) {
+                        if (part * SNITS + u / 7 >= SNIT) continue;
+                        stem_mfma(u / 7, u % 7);
+                        if (u % 7 == 6) stem_put(part * SNITS + u / 7, u / 7, abuf ^ 1);
+                    }
+                }
+            }
+        };
+        if constexpr (STEM) {
+            if (more_p) {
+#pragma unroll
+                for (int j = 0; j < SNITS; ++j)
+                    if (part * SNITS + j < SNIT) stem_load(chunk + 1, part * SNITS + j, j);
+            }
+        }
         const int wa = wa0 + bbuf * SBYTES;
         f32x4 fst[NITS];                                                         // INF32: this stage's share of the next chunk's patch
         if constexpr (INF32) {
@@ -472,11 +594,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wh[dxi & 1], xh);
                 dma_slot(ntk_ic<3 * dxi>{});
+                stem_slot(ntk_ic<3 * dxi>{});
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (!(BF16P_ABL & 4)) ld_x(dc, I1{}, xl);
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wl, xh);
                 dma_slot(ntk_ic<3 * dxi + 1>{});
+                stem_slot(ntk_ic<3 * dxi + 1>{});
                 __builtin_amdgcn_sched_barrier(0);
                 if constexpr (dxi + 1 < STAPS && !(BF16P_ABL & 4)) {
                     ld_w(ntk_ic<dxi + 1>{}, I0{}, wh[(dxi + 1) & 1]);
@@ -485,6 +609,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
                 __builtin_amdgcn_sched_barrier(0);
                 mm(wh[dxi & 1], xl);
                 dma_slot(ntk_ic<3 * dxi + 2>{});
+                stem_slot(ntk_ic<3 * dxi + 2>{});
                 __builtin_amdgcn_sched_barrier(0);
             };
             ld_w(I0{}, I0{}, wh[0]);
@@ -671,7 +796,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(2, 2)))
     }
 }
 
-template <int BN, int KC, int NW, bool X3 = false, bool INF32 = false>
+template <int BN, int KC, int NW, bool X3 = false, bool INF32 = false, bool STEM = false>
 int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipStream_t st) {
     Bf16pArgs a = a0;
     if constexpr (X3 && !INF32) {
@@ -704,11 +829,11 @@ int bf16p_launch(const Bf16pArgs& a0, int H, int W, int pool, int out_f32, hipSt
 #define BF16P_GO(TW_, TH_, NSUB_)                                                                                             \
     do {                                                                                                                      \
         if (pool) {                                                                                                           \
-            if (out_f32) conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, true, true, NW, X3, INF32><<<grid, 64 * NW, 0, st>>>(a);     \
-            else conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, true, false, NW, X3, INF32><<<grid, 64 * NW, 0, st>>>(a);            \
+            if (out_f32) conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, true, true, NW, X3, INF32, STEM><<<grid, 64 * NW, 0, st>>>(a);     \
+            else conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, true, false, NW, X3, INF32, STEM><<<grid, 64 * NW, 0, st>>>(a);            \
         } else {                                                                                                              \
-            if (out_f32) conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, false, true, NW, X3, INF32><<<grid, 64 * NW, 0, st>>>(a);    \
-            else conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, false, false, NW, X3, INF32><<<grid, 64 * NW, 0, st>>>(a);           \
+            if (out_f32) conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, false, true, NW, X3, INF32, STEM><<<grid, 64 * NW, 0, st>>>(a);    \
+            else conv3x3_relu_bf16p_kernel<BN, TW_, TH_, NSUB_, KC, false, false, NW, X3, INF32, STEM><<<grid, 64 * NW, 0, st>>>(a);           \
         }                                                                                                                     \
     } while (0)
     if constexpr (KC == 32 && NW == 8) {
@@ -864,5 +989,32 @@ extern "C" int ntk_vgg_conv3x3_relu_split3(const void* in_split, const void* w_p
     else rc = bf16p_launch<64, 32, 8, true>(a, H, W, fuse_pool, out_f32, st);
     NTK_REQUIRE(rc == NTK_OK, rc, "ntk_vgg_conv3x3_relu_split3: no instantiation for this shape");
     NTK_CHECK_LAUNCH("ntk_vgg_conv3x3_relu_split3");
+    return NTK_OK;
+}
+
+// The FUSED STEM: conv1_1 (3 -> 64, fp32 FMAs) computed inside the staging of conv1_2 (64 -> 64, split form) -- conv1_1's
+// [frames][H][W][64] map is never written or read.  Shapes: those of the four-wave split form (H, W multiples of 8).
+extern "C" int ntk_vgg_split3_stem_supported(int H, int W, int fuse_pool) {
+    int bn = 0, nw = 0;
+    return split3_form(H, W, 64, 64, fuse_pool, &bn, &nw) && nw == 4 && (W % 8) == 0 && (H % 8) == 0;
+}
+
+extern "C" int ntk_vgg_conv3x3_relu_split3_stem(const float* frames_f32, const float* w1_packed, const float* bias1, const void* w2_packed,
+                                                const float* bias2, void* out, int frames, int H, int W, int fuse_pool, int out_f32,
+                                                void* stream) {
+    NTK_REQUIRE(frames_f32 && w1_packed && bias1 && w2_packed && bias2 && out, NTK_ERR_BAD_PTR, "ntk_vgg_conv3x3_relu_split3_stem: null pointer");
+    NTK_REQUIRE(ntk_aligned16(w2_packed) && ntk_aligned16(out) && ntk_aligned16(bias2) && (((uintptr_t)frames_f32 | (uintptr_t)w1_packed | (uintptr_t)bias1) & 3u) == 0,
+                NTK_ERR_BAD_PTR, "ntk_vgg_conv3x3_relu_split3_stem: w2_packed, bias2 and out must be 16-byte aligned, the rest 4-byte");
+    NTK_REQUIRE(frames > 0 && H > 0 && W > 0 && ntk_vgg_split3_stem_supported(H, W, fuse_pool), NTK_ERR_UNSUPPORTED,
+                "ntk_vgg_conv3x3_relu_split3_stem: frames=%d H=%d W=%d pool=%d (H, W multiples of 8)", frames, H, W, fuse_pool);
+    NTK_REQUIRE((long long)frames * H * W < (1ll << 31), NTK_ERR_UNSUPPORTED, "ntk_vgg_conv3x3_relu_split3_stem: too many pixels for 32-bit offsets");
+    Bf16pArgs a;
+    a.in = nullptr; a.wq = reinterpret_cast<const __bf16*>(w2_packed); a.bias = bias2; a.out = out;
+    a.frames = frames; a.H = H; a.W = W; a.Cin = 128; a.Cout = 64;            // to the kernel: conv1_2 reads a split map of 64 channels
+    a.bxN = a.byN = a.NQ = a.NS = a.nCB = 0;
+    a.stem_in = frames_f32; a.stem_w = w1_packed; a.stem_b = bias1;
+    const int rc = bf16p_launch<64, 32, 4, true, false, true>(a, H, W, fuse_pool, out_f32, (hipStream_t)stream);
+    NTK_REQUIRE(rc == NTK_OK, rc, "ntk_vgg_conv3x3_relu_split3_stem: no instantiation for this shape");
+    NTK_CHECK_LAUNCH("ntk_vgg_conv3x3_relu_split3_stem");
     return NTK_OK;
 }

@@ -231,10 +231,29 @@ def pack_weights_split3(w_hwio, H, W):
     return wp
 
 
-def conv3x3_relu_split3(x, w_packed, bias, cin, cout, fuse_pool=False, out_f32=False, out=None):
+def split3_stem_supported(H, W, fuse_pool=False):
+    """Frame shapes on which conv1_1 can be computed inside conv1_2's staging (conv3x3_relu_split3(..., stem=...))."""
+    return bool(_lib.lib().ntk_vgg_split3_stem_supported(H, W, 1 if fuse_pool else 0))
+
+
+def conv3x3_relu_split3(x, w_packed, bias, cin, cout, fuse_pool=False, out_f32=False, out=None, stem=None):
     """split map [F,H,W,Cin/16,2,16] (or an fp32 NHWC map [F,H,W,Cin]: the kernel's staging splits it; cin <= 64 and cout == 64 only)
     -> relu(conv3x3_same(x) + b) as a split map (or fp32 NHWC when out_f32): the fp32 product x w accumulated as
-    xh wh + xh wl + xl wh on the 16-bit matrix pipe (fp16 parts, fp32 accumulators)."""
+    xh wh + xh wl + xl wh on the 16-bit matrix pipe (fp16 parts, fp32 accumulators).
+    stem = (w1_packed, bias1), conv1_1's weights from pack_weights: x is then the fp32 FRAMES [F,H,W,3] and the layer (conv1_2,
+    64 -> 64) computes conv1_1's map on the fly in its staging (csrc/conv_bf16p.hip STEM); that map never reaches memory."""
+    if stem is not None:
+        if x.dim() != 4 or x.dtype != torch.float32 or x.shape[3] != 3 or (cin, cout) != (64, 64):
+            raise _lib.NtkError("conv3x3_relu_split3: the fused stem reads fp32 frames [F,H,W,3] and runs a 64 -> 64 layer")
+        F, H, W = x.shape[:3]
+        dst = "nhwc" if out_f32 else "split"
+        if out is None:
+            oh, ow = (H // 2, W // 2) if fuse_pool else (H, W)
+            out = torch.empty(_map_shape(dst, F, oh, ow, cout), device=x.device, dtype=_MAP_DTYPE[dst])
+        _lib.check(_lib.lib().ntk_vgg_conv3x3_relu_split3_stem(_lib.ptr(x), _lib.ptr(stem[0]), _lib.ptr(stem[1]), _lib.ptr(w_packed),
+                                                               _lib.ptr(bias), _lib.ptr(out), F, H, W, 1 if fuse_pool else 0,
+                                                               1 if out_f32 else 0, _lib.stream()), "ntk_vgg_conv3x3_relu_split3_stem")
+        return out
     in_f32 = x.dtype == torch.float32
     return _conv("ntk_vgg_conv3x3_relu_split3", x, "nhwc" if in_f32 else "split", "nhwc" if out_f32 else "split", w_packed, bias,
                  cin, cout, fuse_pool, out, (1 if in_f32 else 0, 1 if out_f32 else 0),
@@ -257,7 +276,8 @@ _STEP_FN = {"direct": "conv3x3_relu", "direct_to_bf16": "conv3x3_relu_f32_to_bf1
             "bf16": "conv3x3_relu_bf16", "bf16p": "conv3x3_relu_bf16p"}
 
 
-def trunk_plan(frames_shape, dtype, form, upto="conv4_3", *, layout, wino_waves, features_window, split3_upto, bf16_form):
+def trunk_plan(frames_shape, dtype, form, upto="conv4_3", *, layout, wino_waves, features_window, split3_upto, bf16_form,
+               stem="separate"):
     """The layers conv1_1 .. `upto` of a [F,H,W,3] chunk as TrunkSteps.  A pure host function: it asks the library's shape
     predicates and touches no device and no weights.  dtype "bf16": the patch form where it takes the layer (bf16_form "patch"), the
     tile form otherwise.  dtype "f32", by `form`:
@@ -267,7 +287,10 @@ def trunk_plan(frames_shape, dtype, form, upto="conv4_3", *, layout, wino_waves,
       "winograd"  with layout "blocked" where the whole trunk can: F(4x4) with channel-blocked maps between the layers; elsewhere
                   NHWC maps and per layer F(4x4) (carrying wino_waves; features_window on a final conv4_3), F(2x2), direct;
       "winograd2" NHWC, per layer F(2x2), direct;  "direct": NHWC, direct.
-    The last step writes fp32 NHWC and is un-pooled when `upto` comes before conv4_3."""
+    The last step writes fp32 NHWC and is un-pooled when `upto` comes before conv4_3.
+    stem "fused": where conv1_2 runs in the split form on conv1_1's fp32 map and the library can compute conv1_1 inside conv1_2's
+    staging (ntk_vgg_split3_stem_supported), step 0 writes the marker layout "stem" -- a map that is never materialised: nothing is
+    launched for it -- and step 1 reads it: one launch for both layers."""
     F, H, W = frames_shape[:3]
     names = [l[0] for l in VGG_LAYERS]
     layers = VGG_LAYERS[:names.index(upto) + 1]
@@ -320,6 +343,10 @@ def trunk_plan(frames_shape, dtype, form, upto="conv4_3", *, layout, wino_waves,
             kernel = "direct"
         steps.append(TrunkStep(name, kernel, src, dst, pool, window, waves))
         h, w = oh, ow
+    if (stem == "fused" and len(steps) > 1 and steps[0].kernel == "direct" and steps[1].kernel == "split3" and steps[1].src == "nhwc"
+            and split3_stem_supported(H, W, steps[1].pool)):
+        steps[0] = steps[0]._replace(dst="stem")
+        steps[1] = steps[1]._replace(src="stem")
     return tuple(steps)
 
 
@@ -360,10 +387,16 @@ class VGG16Conv43(object):
         # implicit-GEMM kernel runs where neither applies (conv1_1, odd frame sizes) and everywhere with "direct"
         # "split3" = the SPLIT form (csrc/conv_bf16p.hip X3: every fp32 product as three fp16 MFMA products of hi / lo parts, fp32
         # accumulators) on conv1_2 .. split3_upto,
-        # the F(4x4) Winograd kernel on the layers after it (on the 28 x 28 maps of conv4_x the two are within 2 %).  conv1_1 keeps its
-        # fp32 kernel (conv1_2's staging splits its map), the last split layer writes fp32 NHWC for the Winograd layers.
+        # the F(4x4) Winograd kernel on the layers after it (on the 28 x 28 maps of conv4_x the two are within 2 %).  conv1_1 is computed
+        # inside conv1_2's staging (self.stem below; as its own fp32 kernel, whose map conv1_2's staging splits, with "separate"), the
+        # last split layer writes fp32 NHWC for the Winograd layers.
         self.split3 = (algo == "split3" and dtype == "f32")
         self.split3_upto = os.environ.get("NTK_SPLIT3_UPTO", "conv4_3")
+        # "fused": conv1_1 is computed inside conv1_2's staging wherever the split trunk runs (no 12.8 MB / frame stem map, one launch
+        # less); "separate": conv1_1 as its own fp32 kernel (the form before; for A/B runs: NTK_TRUNK_STEM=separate)
+        self.stem = os.environ.get("NTK_TRUNK_STEM", "fused")
+        if self.stem not in ("fused", "separate"):
+            raise _lib.NtkError("VGG16Conv43: NTK_TRUNK_STEM must be 'fused' or 'separate'")
         # __call__(..., latency=True) runs a call of fewer frames than this in the Winograd form: with a handful of frames a layer is
         # a few workgroups per CU at most and the pass is bound by one workgroup's critical path, which is shorter in the F(4x4)
         # kernel (224 x 224, one MI355X: 1 frame 0.78 against 0.96 ms, 8 frames 1.00 against 1.09, 12 frames 1.39 against 1.27,
@@ -416,11 +449,13 @@ class VGG16Conv43(object):
         step's layout.  The largest map, conv1_1's, is 12.8 MB per frame; a split or bf16 map has at most the bytes of its layer's
         fp32 map."""
         F, H, W, _ = frames.shape
-        key = (torch.cuda.current_stream(frames.device).cuda_stream, F, H, W)
+        fused = plan[0].dst == "stem"                             # no stem map: the largest map left is conv2_1's, half its bytes
+        key = (torch.cuda.current_stream(frames.device).cuda_stream, F, H, W, fused)
         if key not in self._blocked_ws:
             if len(self._blocked_ws) >= 8:                        # shapes come and go (tests, online tracking): keep the table small
                 self._blocked_ws.clear()
-            ws = (torch.empty(F * H * W * 64, device=frames.device), torch.empty(F * (H // 2) * (W // 2) * 64, device=frames.device))
+            ws = (torch.empty(F * H * W * (32 if fused else 64), device=frames.device),
+                  torch.empty(F * (H // 2) * (W // 2) * 64, device=frames.device))
             self._blocked_ws[key] = (ws, {})
         ws, views = self._blocked_ws[key]
         if plan not in views:
@@ -429,6 +464,9 @@ class VGG16Conv43(object):
             dsts, h, w = [], H, W
             for i, (step, (_name, _cin, cout, _pool)) in enumerate(zip(plan[:-1], VGG_LAYERS)):
                 h, w = (h // 2, w // 2) if step.pool else (h, w)
+                if step.dst == "stem":
+                    dsts.append(None)
+                    continue
                 shape = _map_shape(step.dst, F, h, w, cout)
                 dsts.append(ws[i & 1].view(_MAP_DTYPE[step.dst])[:math.prod(shape)].view(shape))
             views[plan] = dsts
@@ -449,13 +487,13 @@ class VGG16Conv43(object):
             raise _lib.NtkError("VGG16Conv43: this %s trunk has no weights packed for form=%r" % (own, form))
         win = self.features_window
         key = (tuple(frames_shape[:3]), self.dtype, form, upto, self.layout, self.wino_waves, None if win is None else tuple(win),
-               self.split3_upto, self.bf16_form)
+               self.split3_upto, self.bf16_form, self.stem)
         plan = self._plans.get(key)
         if plan is None:
             if len(self._plans) >= 8:
                 self._plans.clear()
             plan = self._plans[key] = trunk_plan(key[0], *key[1:4], layout=key[4], wino_waves=key[5], features_window=key[6],
-                                                 split3_upto=key[7], bf16_form=key[8])
+                                                 split3_upto=key[7], bf16_form=key[8], stem=key[9])
         return plan
 
     def _step_weights(self, step, h, w, device):
@@ -487,7 +525,11 @@ class VGG16Conv43(object):
                 dst = torch.zeros((F, h, w, cout), device=frames.device, dtype=torch.float32)
             else:
                 dst = out
+            if step.dst == "stem":                                # conv1_1 runs inside the next step's launch
+                continue
             kw = {} if step.kernel == "direct_to_bf16" else {"fuse_pool": step.pool}
+            if step.src == "stem":
+                kw["stem"] = self.packed["conv1_1"]
             if step.kernel == "wino43":
                 kw.update(window=step.window, waves=step.waves)
             elif step.kernel == "wino43_blocked":
