@@ -1,6 +1,6 @@
 """CPU: every conv form's shape predicate agrees with its launcher, over a grid of layer shapes.
 
-The trunk picks a conv kernel per layer by asking a predicate (ntk_vgg_split3_supported, ntk_vgg_bf16p_supported, and through
+The trunk picks a conv kernel per layer by asking a predicate (ntk_vgg_split3_supported, ntk_vgg_split3_stem_supported, ntk_vgg_bf16p_supported, and through
 vgg.wino_supported / vgg.wino43_supported ntk_vgg_wino_supported / ntk_vgg_wino43_supported; ntk_vgg_wino43_blocked_supported for
 channel-blocked maps); the entry then picks an instantiation by its own logic.  Here every entry is called with fake pointers
 (non-null, 16-byte aligned, never dereferenced): a shape its predicate accepts must pass every host-side check and reach the launch,
@@ -15,7 +15,7 @@ import torch
 
 pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason="fake pointers: runs only where no device is visible")
 
-NTK_ERR_BAD_SHAPE, NTK_ERR_UNSUPPORTED, NTK_ERR_HIP = -1, -3, -4
+NTK_ERR_BAD_SHAPE, NTK_ERR_BAD_PTR, NTK_ERR_UNSUPPORTED, NTK_ERR_HIP = -1, -2, -3, -4
 FRAMES = 2
 SIDES = (4, 8, 12, 16, 20, 24, 28, 32, 40, 56)
 # out of range: sides that are not multiples of 4, zero sides, 28-wide maps too short for runs of rows (H < 20 is also in SIDES)
@@ -74,6 +74,36 @@ def test_split3_entries_agree_with_their_predicate():
             pack.check(ok, L.ntk_vgg_pack_weights_split3(P, P, cin, cout, H, W, None), H=H, W=W, cin=cin, cout=cout)
     conv.verdict()
     pack.verdict()
+
+
+def test_split3_stem_entry_agrees_with_its_predicate():
+    """The fused stem (ntk_vgg_conv3x3_relu_split3_stem: conv1_1 inside conv1_2's staging) takes exactly the frame shapes
+    ntk_vgg_split3_stem_supported accepts -- those of the four-wave split form at 64 -> 64 channels: H and W multiples of 8 -- with
+    either output; its pixel offsets are 32-bit, its 16-byte accesses (packed conv1_2 weights, output) need aligned pointers, and the
+    frames, which it reads float by float, do not."""
+    from ntmtrack import vgg
+    L = _lib()
+    conv, accepted = _Sweep("ntk_vgg_conv3x3_relu_split3_stem"), 0
+    for H, W in GEOMETRY:
+        for pool in (0, 1):
+            ok = bool(L.ntk_vgg_split3_stem_supported(H, W, pool))
+            assert ok == (vgg.split3_supported(H, W, 64, 64, pool) and H % 8 == 0 and W % 8 == 0), (H, W, pool)
+            assert ok == vgg.split3_stem_supported(H, W, bool(pool)), (H, W, pool)
+            accepted += ok
+            for out_f32 in (0, 1):
+                rc = L.ntk_vgg_conv3x3_relu_split3_stem(P, P, P, P, P, P, FRAMES, H, W, pool, out_f32, None)
+                conv.check(ok, rc, H=H, W=W, pool=pool, out_f32=out_f32)
+    conv.verdict()
+    assert accepted == 72, accepted                  # the 36 maps whose sides are multiples of 8, pooled or not
+    stem = lambda frames=FRAMES, x=P, w2=P, out=P: L.ntk_vgg_conv3x3_relu_split3_stem(x, P, P, w2, P, out, frames, 8, 8, 0, 1, None)
+    assert stem() == NTK_ERR_HIP
+    assert stem(frames=1 << 25) == NTK_ERR_UNSUPPORTED          # 2^31 pixels: one more than a 32-bit pixel offset reaches
+    assert stem(frames=(1 << 25) - 1) == NTK_ERR_HIP
+    assert stem(frames=0) in (NTK_ERR_BAD_SHAPE, NTK_ERR_UNSUPPORTED) and stem(frames=-1) in (NTK_ERR_BAD_SHAPE, NTK_ERR_UNSUPPORTED)
+    at8 = ctypes.c_void_p(P.value + 8)               # 8-byte aligned, not 16
+    assert stem(w2=at8) == NTK_ERR_BAD_PTR and stem(out=at8) == NTK_ERR_BAD_PTR
+    assert stem(x=ctypes.c_void_p(P.value + 4)) == NTK_ERR_HIP  # the frames: 4-byte alignment is enough
+    assert stem(x=ctypes.c_void_p(P.value + 2)) == NTK_ERR_BAD_PTR and stem(x=None) == NTK_ERR_BAD_PTR
 
 
 def test_bf16p_entries_agree_with_their_predicate():
