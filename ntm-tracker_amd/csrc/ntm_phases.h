@@ -11,7 +11,7 @@
 // (a stamped one in ntm_seq_bwd.hip, a plain one in ntm_seq_deep.hip) and the sequence X1 | X2 | R2 | R3 | R4 | B7 | B8a | B8b | B9
 // reads top to bottom in ntm_bwd_heads_step.
 #pragma once
-#include "ntm_fwd_args.h"
+#include "ntm_seq_args.h"
 
 // ------------------------------------------------------------------------------------------------ control layout
 // offsets of k, beta, g, shift, gamma, erase, add inside the unpacked control vector (ntm_cell.py:128-130), the padded widths

@@ -17,9 +17,10 @@
 // The head / memory / unpack half of a step (phases X1 .. B9, ntm_bwd_heads_step), the record prefetch / commit, the per-head
 // reductions and the set-up of the carried dM / dw / dread are in ntm_phases.h, shared with ntm_seq_deep.hip; the step takes this
 // kernel's stamped barrier as a callable.  This file's own: the LSTM backward B10, the gate-weight product B11 with its
-// wave-specialised form (stream waves, resident rows), the LDS carve-up, the plan and the launcher.
+// wave-specialised form (stream waves, resident rows), the plan and the launcher.  The argument struct, the pointer check, the LDS
+// carve-up and the workgroup-size rule are in ntm_seq_args.h, shared with ntm_seq_deep.hip.
 #include "ntm_common.h"
-#include "ntm_phases.h"           // (NtmFwdPlan: ntk_ntm_seq_plan answers for both directions)
+#include "ntm_phases.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -40,48 +41,6 @@ extern "C" int ntk_ntm_bwd_prof(unsigned long long* out16) {
 #else
 #define NTMB_STAMP(i) do { } while (0)
 #endif
-
-struct NtmBwdArgs {
-    NtmDims d;
-    const float* WrT;      // [4*hid][ldkT]  transposed recurrent weights (rows n' = unit*4+gate)
-    const float* WaT;      // [PP][ldhT]     transposed unpack/output weights
-    int ldkT, ldhT;
-    const float* M0; const float* w0; const float* cs0;
-    const float* st_gates; const float* st_c; const float* st_u;
-    const float* st_wc; const float* st_wv; const float* st_w; const float* st_M;
-    const float* dlogits;  // [B,S,O]
-    const float* dM_fin; const float* dw_fin; const float* dread_fin; const float* dcs_fin;  // nullable
-    float* dgates;         // [B,S,4*hid]
-    float* du;             // [B,S,PP]
-    float* dM0; float* dw0; float* dread0; float* dcs0;
-};
-
-static void ntm_bwd_lds(const NtmDims& d, int T, int ldkT, int ldhT, NtmBwdLds& L) {
-    const int MP = d.Md | 1, NM = d.N * MP, HN = d.H * d.N;
-    const int nout = d.H * d.Md + 2 * d.Wh * d.Md;
-    const int nslP = ntm_imin(ntm_imax(1, T / nout), d.N);
-    const int nslZ = ntm_imax(1, T / (ldkT / 4));
-    const int nslH = ntm_imax(1, T / (ldhT / 4));
-    const int nslC = ntm_imax(1, T / d.Md);
-    int part = ntm_imax(nslP * nout, nslZ * ldkT);
-    part = ntm_imax(part, nslH * ldhT);
-    part = ntm_imax(part, nslC * d.Md);
-    part = ntm_imax(part, 32 * d.R * d.Md);                  // the wave-specialised form's read columns of B11: 32 row slices
-    int o = 0;
-    auto take = [&](int n) { int r = o; o += ntm_align4(n); return r; };
-    L.part = take(part);
-    L.dM = take(NM); L.G = take(NM); L.Mp = take(NM); L.Mt = take(d.write_first ? NM : 4);
-    L.dW = take(HN); L.Wp = take(HN); L.Wt = take(HN); L.Wc = take(HN); L.Wv = take(HN); L.Wg = take(HN);
-    L.Dwv = take(HN); L.Dsim = take(HN);
-    L.U = take(d.PP); L.DU = take(d.PP); L.DG = take(4 * d.hid); L.dZ = take(ldkT); L.dC = take(d.hid);
-    L.Gt = take(4 * d.hid); L.Ct = take(d.hid); L.Cp = take(d.hid);
-    L.Khat = take(d.H * d.Md); L.Ks = take(d.H * d.Md); L.Kinv = take(d.H); L.Kss = take(d.H);
-    L.Cinv = take(ntm_norm_floats(d)); L.Css = take(d.Md); L.C2 = take(ntm_norm_floats(d)); L.Dkhat = take(d.H * d.Md);
-    L.Sw = take(d.H * d.SS);
-    L.Red = take(d.H * (NQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
-    L.Dmh = take(d.N * (d.Md | 1));
-    L.total = o;
-}
 
 // WS (benchmark shape only, 768 threads): the h columns of B11 -- d h_{t-1} = dgates_t . Wr^T[:, 80:280], 71 % of the kernel's
 // largest weight stream (42 % of a BPTT step) -- are NOT needed until the LSTM cell backward of the NEXT iteration, ten phases
@@ -309,8 +268,6 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_kernel(NtmBwdArgs a, NtmBwdL
     }
 }
 
-int ntm_validate_dims(const NtmDims& d, const char* who);          // ntm_seq_fwd.hip
-
 // [rows][cols] -> [cols][ldo] (zero padded), used for WrT / WaT once per optimiser step
 __global__ void transpose_pad_kernel(const float* __restrict__ in, int ldi, float* __restrict__ out, int ldo,
                                      int rows, int cols) {
@@ -337,16 +294,7 @@ extern "C" int ntk_transpose_pad(const float* in, int ldi, float* out, int ldo, 
     return NTK_OK;
 }
 
-// What ntk_ntm_seq_bwd launches for a shape: every limit of the BPTT kernels and the kernel a shape takes, host arithmetic only,
-// for the launcher and for the query ntk_ntm_seq_plan alike.
-struct NtmBwdPlan {
-    int kernel;            // NTK_NTM_BWD_*
-    int T;                 // threads the shape's work is laid out over (NtmBwdLds)
-    int threads;           // threads of the workgroup: T, or 768 in the wave-specialised form (two stream waves beside T = 640)
-    NtmBwdLds L;
-    size_t lds_bytes;
-};
-
+// every limit of the BPTT kernels and the kernel a shape takes, host arithmetic only
 static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, const char* who) {
     int rc = ntm_validate_dims(d, who);
     if (rc != NTK_OK) return rc;
@@ -354,20 +302,15 @@ static int ntm_bwd_plan(const NtmDims& d, int ldkT, int ldhT, NtmBwdPlan& p, con
     NTK_REQUIRE(ldkT >= d.K && (ldkT % 4) == 0 && ldhT >= d.hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE,
                 "%s: ldkT=%d (K=%d) ldhT=%d (hid=%d)", who, ldkT, d.K, ldhT, d.hid);
     NTK_REQUIRE(d.SS + 1 <= NQ, NTK_ERR_UNSUPPORTED, "%s: shift_range=%d too wide", who, (d.SS - 1) / 2);
-    int T = d.H * d.N;
-    T = ntm_imax(T, 3 * d.hid);
-    T = ntm_imax(T, d.PP);
-    T = ntm_imax(T, d.K);
-    T = ((T + 63) / 64) * 64;
-    T = ntm_imax(T, d.H * d.Md + d.Md + 2 * d.Wh * d.Md);
     // a thread prefetches at most MAXM elements of the memory: a wide memory under few heads (64 x 72 under two) takes the threads
-    // it needs for that, where it was refused
-    T = ntm_imax(T, (d.N * d.Md + MAXM - 1) / MAXM);
-    T = ((T + 63) / 64) * 64;
+    // it needs for that, where it was refused (this kernel's own clause; the deep BPTT refuses such a memory)
+    const int T = ntm_bwd_threads(d, (d.N * d.Md + MAXM - 1) / MAXM);
     NTK_REQUIRE(T <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= MAXM * T, NTK_ERR_UNSUPPORTED,
                 "%s: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d (max %d per thread of %d) / hidden=%d (3*hidden <= 1024) exceed "
                 "one workgroup", who, d.H * d.N, d.N * d.Md, MAXM, T, d.hid);
-    ntm_bwd_lds(d, T, ldkT, ldhT, p.L);
+    // this kernel's own users of `part`: the partials of B11 over the ldkT columns of Wr^T and, in the wave-specialised form, its read
+    // columns in 32 row slices; the carried dZ is one step input wide (ldkT), dC one layer's cells
+    ntm_bwd_lds(d, T, ldhT, ntm_imax(ntm_bwd_part_floats(T, ldkT), 32 * d.R * d.Md), ldkT, d.hid, p.L);
     const bool fix = (d.N == 128 && d.Md == 20 && d.R == 4 && d.Wh == 1 && d.hid == 200 && d.SS == 3 && d.O == 2 &&
                       T == 640 && !d.write_first && ldkT == 280 && ldhT == 200);
     p.lds_bytes = (size_t)p.L.total * sizeof(float) + 128;                // + the diagnostic build's stamp words
@@ -387,8 +330,7 @@ extern "C" int ntk_ntm_seq_plan_sim(int B, int N, int Md, int R, int Wh, int hid
                                     int similarity,
                                     int ldkT, int ldhT, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
     NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_plan");
-    NtmDims d;
-    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
+    const NtmDims d = ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
     if (ldkT <= 0) ldkT = ntm_align4(d.K);
     if (ldhT <= 0) ldhT = ntm_align4(hid);
     NtmBwdPlan pb;
@@ -409,6 +351,31 @@ extern "C" int ntk_ntm_seq_plan(int B, int N, int Md, int R, int Wh, int hid, in
                                 bwd_kernel, bwd_threads);
 }
 
+// ntk_ntm_seq_bwd behind its plain, *_sim and step entries: similarity, then shape and plan, then pointers, then the launch
+int ntm_seq_bwd_run(const NtmBwdArgs& a, void* stream) {
+    const char* who = "ntk_ntm_seq_bwd";
+    NTM_REQUIRE_SIMILARITY(a.d.similarity, who);
+    NtmBwdPlan p;
+    int rc = ntm_bwd_plan(a.d, a.ldkT, a.ldhT, p, who);
+    if (rc != NTK_OK) return rc;
+    rc = ntm_bwd_check_ptrs(a, who);
+    if (rc != NTK_OK) return rc;
+    typedef void (*kern_t)(NtmBwdArgs, NtmBwdLds);
+    constexpr int AC = NTM_SIM_AS_CODED, SC = NTM_SIM_SMOOTH_COSINE;
+    static const NtmKernelRow<kern_t> rows[] = {
+        {NTK_NTM_BWD_WS, AC, ntm_seq_bwd_kernel<768, true, true>},           // (as coded only)
+        {NTK_NTM_BWD_FIX, AC, ntm_seq_bwd_kernel<768, true>},                {NTK_NTM_BWD_FIX, SC, ntm_seq_bwd_kernel<768, true, false, SC>},
+        {NTK_NTM_BWD_GENERIC768, AC, ntm_seq_bwd_kernel<768, false>},        {NTK_NTM_BWD_GENERIC768, SC, ntm_seq_bwd_kernel<768, false, false, SC>},
+        {NTK_NTM_BWD_GENERIC1024, AC, ntm_seq_bwd_kernel<1024, false>},      {NTK_NTM_BWD_GENERIC1024, SC, ntm_seq_bwd_kernel<1024, false, false, SC>}};
+    static NtkLdsAttrCache lds_cache;
+    kern_t fn;
+    rc = ntm_find_kernel(lds_cache, rows, p.kernel, a.d.similarity, who, fn);
+    if (rc != NTK_OK) return rc;
+    fn<<<a.d.B, p.threads, p.lds_bytes, (hipStream_t)stream>>>(a, p.L);
+    NTK_CHECK_LAUNCH(who);
+    return NTK_OK;
+}
+
 extern "C" int ntk_ntm_seq_bwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
                                int write_first, int similarity,
                                const float* WrT, int ldkT, const float* WaT, int ldhT,
@@ -419,45 +386,9 @@ extern "C" int ntk_ntm_seq_bwd_sim(int B, int S, int N, int Md, int R, int Wh, i
                                const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
                                float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                void* stream) {
-    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_bwd");
-    NtmBwdArgs a;
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
-    NtmBwdPlan p;
-    int rc = ntm_bwd_plan(a.d, ldkT, ldhT, p, "ntk_ntm_seq_bwd");
-    if (rc != NTK_OK) return rc;
-    NTK_REQUIRE(WrT && WaT && M0 && w0 && cs0 && st_gates && st_c && st_u && st_wc && st_wv && st_w && st_M &&
-                    dlogits && dgates && du && dM0 && dw0 && dread0 && dcs0,
-                NTK_ERR_BAD_PTR, "ntk_ntm_seq_bwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(WrT) && ntk_aligned16(WaT) && ntk_aligned16(st_gates) && ntk_aligned16(dgates),
-                NTK_ERR_BAD_PTR, "ntk_ntm_seq_bwd: WrT/WaT/st_gates/dgates must be 16-byte aligned");
-    a.WrT = WrT; a.WaT = WaT; a.ldkT = ldkT; a.ldhT = ldhT; a.M0 = M0; a.w0 = w0; a.cs0 = cs0;
-    a.st_gates = st_gates; a.st_c = st_c; a.st_u = st_u; a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M;
-    a.dlogits = dlogits; a.dM_fin = dM_fin; a.dw_fin = dw_fin; a.dread_fin = dread_fin; a.dcs_fin = dcs_fin;
-    a.dgates = dgates; a.du = du; a.dM0 = dM0; a.dw0 = dw0; a.dread0 = dread0; a.dcs0 = dcs0;
-    {
-        static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_bwd_kernel<768, false>, (const void*)ntm_seq_bwd_kernel<1024, false>, (const void*)ntm_seq_bwd_kernel<768, true>,
-                                  (const void*)ntm_seq_bwd_kernel<768, true, true>,
-                                  (const void*)ntm_seq_bwd_kernel<768, false, false, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_bwd_kernel<1024, false, false, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_bwd_kernel<768, true, false, NTM_SIM_SMOOTH_COSINE>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 7, "ntk_ntm_seq_bwd");
-        if (rc_lds != NTK_OK) return rc_lds;
-    }
-    const hipStream_t st = (hipStream_t)stream;
-    if (similarity == NTM_SIM_SMOOTH_COSINE) {
-        constexpr int SC = NTM_SIM_SMOOTH_COSINE;
-        if (p.kernel == NTK_NTM_BWD_FIX) ntm_seq_bwd_kernel<768, true, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-        else if (p.kernel == NTK_NTM_BWD_GENERIC768) ntm_seq_bwd_kernel<768, false, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-        else if (p.kernel == NTK_NTM_BWD_GENERIC1024) ntm_seq_bwd_kernel<1024, false, false, SC><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-        else NTK_REQUIRE(false, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_bwd: kernel %d has no smooth-cosine form", p.kernel);
-    } else
-    if (p.kernel == NTK_NTM_BWD_WS) ntm_seq_bwd_kernel<768, true, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-    else if (p.kernel == NTK_NTM_BWD_FIX) ntm_seq_bwd_kernel<768, true><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-    else if (p.kernel == NTK_NTM_BWD_GENERIC768) ntm_seq_bwd_kernel<768, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-    else ntm_seq_bwd_kernel<1024, false><<<B, p.threads, p.lds_bytes, st>>>(a, p.L);
-    NTK_CHECK_LAUNCH("ntk_ntm_seq_bwd");
-    return NTK_OK;
+    return ntm_seq_bwd_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), WrT, WaT, ldkT, ldhT, M0, w0, cs0,
+                            st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM_fin, dw_fin, dread_fin, dcs_fin,
+                            dgates, du, dM0, dw0, dread0, dcs0}, stream);
 }
 
 extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
@@ -470,7 +401,8 @@ extern "C" int ntk_ntm_seq_bwd(int B, int S, int N, int Md, int R, int Wh, int h
                                const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
                                float* dgates, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                void* stream) {
-    return ntk_ntm_seq_bwd_sim(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED, WrT, ldkT, WaT, ldhT, M0, w0, cs0,
-                               st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM_fin, dw_fin, dread_fin, dcs_fin,
-                               dgates, du, dM0, dw0, dread0, dcs0, stream);
+    return ntm_seq_bwd_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED), WrT, WaT, ldkT, ldhT, M0, w0,
+                            cs0, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM_fin, dw_fin, dread_fin, dcs_fin,
+                            dgates, du, dM0, dw0, dread0, dcs0}, stream);
 }
+

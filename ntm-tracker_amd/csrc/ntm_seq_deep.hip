@@ -11,42 +11,14 @@
 // its own old h_{k+1}.  The BPTT keeps the carried gradients in the same layout.
 //
 // Shared with the single-layer kernels (ntm_phases.h): the control layout, P2's memory normaliser and P3 .. P8 of the forward step,
-// X1 .. B9 of the BPTT step with its record prefetch / commit, per-head reductions and carried-gradient set-up, the BPTT's LDS
-// carve-up struct and reduction slots (ntm_common.h) and the forward's workgroup size (ntm_pick_threads).  This file's own: the
-// layer loops (P1 / P2 per layer forward, B10 / B11 per layer in the BPTT), the records of the lower layers, the packed weight
-// layouts and their pack kernel, the argument structs (NtmDeepFwdArgs, NtmDeepBwdArgs), the plan and the launchers.
+// X1 .. B9 of the BPTT step with its record prefetch / commit, per-head reductions and carried-gradient set-up; (ntm_seq_args.h): the
+// argument structs (NtmDeepFwdArgs, NtmDeepBwdArgs), the pointer checks, both LDS carve-ups and the workgroup-size rules.  This
+// file's own: the layer loops (P1 / P2 per layer forward, B10 / B11 per layer in the BPTT), the records of the lower layers, the
+// pack kernel of the weight layouts, the plan and the launchers.
 #include "ntm_phases.h"
-#include <initializer_list>
 
 // ------------------------------------------------------------------------------------------------ packed layouts
-// (hid % 4 == 0, see ntk_ntm_seq_deep_supported)
-//   Wx0 [4*hid][ldx]              layer 0's x part, rows n' = unit*4 + gate, columns x (zero padded to ldx = align4(D))
-//   Wf  forward recurrent blocks, columns n' = unit*4 + gate:
-//       layer 0    [rf0][4*hid]   rows read (R*Md) | h_0 (hid) | bias | 0..       rf0 = align4(R*Md + hid + 1)
-//       layer k>=1 [rf1][4*hid]   rows h_{k-1} (hid) | h_k (hid) | bias | 0..     rf1 = align4(2*hid + 1)
-//   Wb  the same blocks transposed (for d[input ; h_prev] = dpre . W^T), rows n' = unit*4 + gate, no bias:
-//       layer 0    [4*hid][cb0]   columns read | h_0 | 0..                        cb0 = align4(R*Md + hid)
-//       layer k>=1 [4*hid][cb1]   columns h_{k-1} | h_k                          cb1 = 2*hid
-// Source (StackedNTMCell's flat buffer): lowerT = the L-1 lower matrices back to back, layer 0 [4*hid][ld0]
-// (columns x | read | h_0 | bias | 0.., ld0 = align4(D + R*Md + hid + 1)), layers 1..L-2 [4*hid][ld1] (columns
-// h_{k-1} | h_k | bias | 0.., ld1 = align4(2*hid + 1)), rows g*hid + unit (TF gate-major); the top layer as the
-// single-layer cell's WxT [4*hid][align4(hid)] (its input h_{L-2}) and Wr [align4(R*Md+hid+1)][4*hid] (read rows unused).
-struct NtmDeepShape {
-    int D, RM, hid, L, ldx, ld0, ld1, ldxt, rf0, rf1, cb0, cb1;
-};
-
-static inline void ntm_deep_shape(NtmDeepShape& s, int D, int RM, int hid, int L) {
-    s.D = D; s.RM = RM; s.hid = hid; s.L = L;
-    s.ldx = ntm_align4(D);
-    s.ld0 = ntm_align4(D + RM + hid + 1);
-    s.ld1 = ntm_align4(2 * hid + 1);
-    s.ldxt = ntm_align4(hid);
-    s.rf0 = ntm_align4(RM + hid + 1);
-    s.rf1 = ntm_align4(2 * hid + 1);
-    s.cb0 = ntm_align4(RM + hid);
-    s.cb1 = 2 * hid;
-}
-
+// (Wx0 / Wf / Wb and NtmDeepShape: ntm_seq_args.h)
 static inline __host__ __device__ size_t ntm_deep_nwx0(const NtmDeepShape& s) { return (size_t)4 * s.hid * s.ldx; }
 static inline __host__ __device__ size_t ntm_deep_nwf(const NtmDeepShape& s) { return (size_t)4 * s.hid * (s.rf0 + (size_t)(s.L - 1) * s.rf1); }
 static inline __host__ __device__ size_t ntm_deep_nwb(const NtmDeepShape& s) { return (size_t)4 * s.hid * (s.cb0 + (size_t)(s.L - 1) * s.cb1); }
@@ -96,41 +68,6 @@ __global__ void ntm_deep_pack_kernel(NtmDeepShape s, const float* __restrict__ l
 }
 
 // ------------------------------------------------------------------------------------------------ forward
-struct NtmDeepFwdArgs {
-    NtmDeepShape s;
-    const float* X;        // [B,S,ldx] input rows (read for the st_buf0 record only)
-    const float* Wf;       // forward blocks (above)
-    const float* cs0;      // [B,2*hid*L]  c_0, h_0, c_1, h_1, ...
-    float* cs_out;         // [B,2*hid*L]
-    // per-step records of the lower layers and of the top layer's input (all nullable)
-    float* st_xtop;        // [B,S,ldxt]         h_{L-2}(t), zero padded
-    float* st_buf0;        // [B,S,ld0]          [x_t | read_{t-1} | h_0(t-1) | 1 | 0..]
-    float* st_bufk;        // [L-2][B,S,ld1]     layer k = 1..L-2: [h_{k-1}(t) | h_k(t-1) | 1 | 0..]
-    float* st_lgates;      // [L-1][B,S,hid,4]   activated gates i, j, f, o of layers 0..L-2
-    float* st_lc;          // [L-1][B,S,hid]     c_k(t) of layers 0..L-2
-};
-
-static inline void ntm_deep_fwd_lds(const NtmDims& d, int NL, int T, NtmLds& L) {
-    const int MP = d.Md | 1;
-    const int nsl = ntm_imax(1, T / d.hid);
-    const int ncg = d.PP / 4;
-    const int nslB = ntm_imin(ntm_imax(1, T / ncg), d.hid);
-    const int RM = d.R * d.Md;
-    const int nslR = ntm_imin(ntm_imax(1, T / RM), d.N);
-    int o = 0;
-    L.part = o; o += ntm_align4(ntm_imax(ntm_imax(nsl * 4 * d.hid, nslB * d.PP), nslR * RM));
-    L.M = o; o += ntm_align4(d.N * MP);
-    L.W = o; o += ntm_align4(d.H * d.N);
-    L.Wg = o; o += ntm_align4(d.H * d.N);
-    L.Z = o; o += ntm_align4(RM + NL * d.hid);
-    L.C = o; o += ntm_align4(NL * d.hid);
-    L.U = o; o += ntm_align4(d.PP);
-    L.Ks = o; o += ntm_align4(d.H * d.Md);
-    L.Cn = o; o += ntm_align4(ntm_norm_floats(d));
-    L.Pw = o; o += ntm_align4(d.H * d.N);
-    L.total = o;
-}
-
 template <int MAXT, int SIM = NTM_SIM_AS_CODED>             // SIM: the similarity of the content addressing, as ntm_seq_fwd.hip
 __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, NtmDeepFwdArgs dp, NtmLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -267,51 +204,6 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_fwd_deep_kernel(NtmFwdArgs a, Nt
 // per layer, top first: B10 (cell backward; the top layer adds dU . Wa^T to its carried dh) and B11 (d[input ; h_prev] = dpre . W^T,
 // streamed).  Layer k's input gradient is added to the carried dh_{k-1} (which layer k-1 consumes next), its h_prev part replaces
 // the carried dh_k; layer 0's splits into the carried dread and dh_0.  Fixed summation order, no atomics: bitwise reproducible.
-struct NtmDeepBwdArgs {
-    NtmDims d;
-    NtmDeepShape s;
-    const float* Wb;       // transposed recurrent blocks (above)
-    const float* WaT;      // [PP][ldhT]
-    int ldhT;
-    const float* M0; const float* w0;
-    const float* cs0;      // [B,2*hid*L]
-    const float* st_gates; const float* st_c; const float* st_u;       // the top layer and the heads, as ntm_seq_bwd.hip
-    const float* st_wc; const float* st_wv; const float* st_w; const float* st_M;
-    const float* st_lgates; const float* st_lc;                        // [L-1][B,S,hid,4], [L-1][B,S,hid]
-    const float* dlogits;  // [B,S,O]
-    const float* dM_fin; const float* dw_fin; const float* dread_fin; const float* dcs_fin;     // nullable; dcs [B,2*hid*L]
-    float* dgates;         // [B,S,4*hid]       top layer, n' = unit*4 + gate
-    float* dpre;           // [L-1][B,S,4*hid]  layers 0..L-2, TF gate-major (g*hid + unit)
-    float* du;             // [B,S,PP]
-    float* dM0; float* dw0; float* dread0; float* dcs0;                // dcs0 [B,2*hid*L]
-};
-
-static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int ldhT, NtmBwdLds& L) {
-    const int MP = d.Md | 1, NM = d.N * MP, HN = d.H * d.N;
-    const int nout = d.H * d.Md + 2 * d.Wh * d.Md;
-    const int nslP = ntm_imin(ntm_imax(1, T / nout), d.N);
-    const int nslH = ntm_imax(1, T / (ldhT / 4));
-    const int nslC = ntm_imax(1, T / d.Md);
-    int part = ntm_imax(nslP * nout, nslH * ldhT);
-    part = ntm_imax(part, nslC * d.Md);
-    for (int cb : {s.cb0, s.cb1}) part = ntm_imax(part, ntm_imax(1, T / (cb / 4)) * cb);
-    int o = 0;
-    auto take = [&](int n) { int r = o; o += ntm_align4(n); return r; };
-    L.part = take(part);
-    L.dM = take(NM); L.G = take(NM); L.Mp = take(NM); L.Mt = take(d.write_first ? NM : 4);
-    L.dW = take(HN); L.Wp = take(HN); L.Wt = take(HN); L.Wc = take(HN); L.Wv = take(HN); L.Wg = take(HN);
-    L.Dwv = take(HN); L.Dsim = take(HN);
-    L.U = take(d.PP); L.DU = take(d.PP); L.DG = take(4 * d.hid);
-    L.dZ = take(s.RM + s.L * d.hid); L.dC = take(s.L * d.hid);
-    L.Gt = take(4 * d.hid); L.Ct = take(d.hid); L.Cp = take(d.hid);
-    L.Khat = take(d.H * d.Md); L.Ks = take(d.H * d.Md); L.Kinv = take(d.H); L.Kss = take(d.H);
-    L.Cinv = take(ntm_norm_floats(d)); L.Css = take(d.Md); L.C2 = take(ntm_norm_floats(d)); L.Dkhat = take(d.H * d.Md);
-    L.Sw = take(d.H * d.SS);
-    L.Red = take(d.H * (NQT + (d.similarity == NTM_SIM_SMOOTH_COSINE ? 1 : 0)) * (d.N / 64));
-    L.Dmh = take(d.N * (d.Md | 1));
-    L.total = o;
-}
-
 template <int MAXT, int SIM = NTM_SIM_AS_CODED>             // SIM: as ntm_seq_bwd.hip
 __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a, NtmBwdLds L) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -427,29 +319,14 @@ __global__ __launch_bounds__(MAXT) void ntm_seq_bwd_deep_kernel(NtmDeepBwdArgs a
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int ntm_validate_dims(const NtmDims& d, const char* who);          // ntm_seq_fwd.hip
-
-// workgroup sizes: the forward takes the single-layer kernels' (ntm_pick_threads); the BPTT's rule is ntk_ntm_seq_bwd's and also
-// covers the 2*hid columns of a layer's input gradient
-
-static int ntm_deep_bwd_threads(const NtmDims& d) {
-    int T = ntm_imax(d.H * d.N, 3 * d.hid);
-    T = ntm_imax(T, d.PP);
-    T = ntm_imax(T, d.K);
-    T = ntm_imax(T, 2 * d.hid);
-    T = ntm_imax(T, d.H * d.Md + d.Md + 2 * d.Wh * d.Md);
-    return ((T + 63) / 64) * 64;
-}
-
-struct NtmDeepPlan {
-    int Tf, Tb;
-    NtmLds Lf;
-    NtmBwdLds Lb;
-    size_t lds_f, lds_b;
-};
-
 // the instantiation a workgroup size takes (both deep kernels): the launchers and ntk_ntm_seq_deep_plan read it here
 static inline int ntm_deep_kernel_id(int T) { return T <= 768 ? NTK_NTM_DEEP_768 : NTK_NTM_DEEP_1024; }
+
+// the deep BPTT's LDS: its own users of `part` are the partials of B11 over the columns of a layer's block of Wb (cb0, cb1); the
+// carried dZ holds every layer's dh behind dread, dC every layer's dc
+static void ntm_deep_bwd_lds(const NtmDims& d, const NtmDeepShape& s, int T, int ldhT, NtmBwdLds& L) {
+    ntm_bwd_lds(d, T, ldhT, ntm_imax(ntm_bwd_part_floats(T, s.cb0), ntm_bwd_part_floats(T, s.cb1)), s.RM + s.L * d.hid, s.L * d.hid, L);
+}
 
 // every limit of the two deep kernels, host arithmetic only
 static int ntm_deep_plan(const NtmDims& d, const NtmDeepShape& s, NtmDeepPlan& p, const char* who) {
@@ -458,12 +335,14 @@ static int ntm_deep_plan(const NtmDims& d, const NtmDeepShape& s, NtmDeepPlan& p
     if (rc != NTK_OK) return rc;
     NTK_REQUIRE((d.hid % 4) == 0, NTK_ERR_UNSUPPORTED, "%s: hidden=%d must be a multiple of 4", who, d.hid);
     NTK_REQUIRE(d.SS + 1 <= NQ, NTK_ERR_UNSUPPORTED, "%s: shift space %d too wide", who, d.SS);
-    p.Tf = ntm_pick_threads(d);
+    p.Tf = ntm_pick_threads(d);                 // the forward takes the single-layer kernels' workgroup size
     NTK_REQUIRE(p.Tf >= d.N, NTK_ERR_UNSUPPORTED, "%s: mem_size %d exceeds the workgroup", who, d.N);
-    p.Tb = ntm_deep_bwd_threads(d);
+    // the BPTT's own clause: the 2*hid columns of a layer's input gradient (3*hid of the common rule already covers them).  Unlike
+    // ntk_ntm_seq_bwd it does not grow the workgroup for a memory of more than MAXM elements per thread: that is refused below
+    p.Tb = ntm_bwd_threads(d, 2 * d.hid);
     NTK_REQUIRE(p.Tb <= 1024 && d.H * d.N <= 1024 && d.N * d.Md <= MAXM * p.Tb, NTK_ERR_UNSUPPORTED,
                 "%s: heads*mem_size=%d (max 1024) / mem_size*mem_dim=%d exceed one workgroup", who, d.H * d.N, d.N * d.Md);
-    ntm_deep_fwd_lds(d, s.L, p.Tf, p.Lf);
+    ntm_fwd_lds(d, p.Tf, p.Lf, s.L);
     ntm_deep_bwd_lds(d, s, p.Tb, ntm_align4(d.hid), p.Lb);
     p.lds_f = (size_t)p.Lf.total * sizeof(float);
     p.lds_b = (size_t)p.Lb.total * sizeof(float);
@@ -473,23 +352,17 @@ static int ntm_deep_plan(const NtmDims& d, const NtmDeepShape& s, NtmDeepPlan& p
 }
 
 extern "C" int ntk_ntm_seq_deep_supported(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L) {
-    NtmDims d;
-    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, 0);
-    NtmDeepShape s;
-    ntm_deep_shape(s, 1, R * Md, hid, L);
-    NtmDeepPlan p;
-    return ntm_deep_plan(d, s, p, "ntk_ntm_seq_deep_supported") == NTK_OK ? 1 : 0;
+    NtmDeepPlan p;                              // (answers for write_first = 0, as coded)
+    return ntm_deep_plan(ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, 0, NTM_SIM_AS_CODED), ntm_deep_shape(1, R * Md, hid, L), p,
+                         "ntk_ntm_seq_deep_supported") == NTK_OK ? 1 : 0;
 }
 
 extern "C" int ntk_ntm_seq_deep_plan_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L, int write_first,
                                          int similarity, int* fwd_kernel, int* fwd_threads, int* bwd_kernel, int* bwd_threads) {
     NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_deep_plan");
-    NtmDims d;
-    ntm_fill_dims(d, B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
-    NtmDeepShape s;
-    ntm_deep_shape(s, 1, R * Md, hid, L);
     NtmDeepPlan p;
-    const bool ok = ntm_deep_plan(d, s, p, "ntk_ntm_seq_deep_plan") == NTK_OK;
+    const bool ok = ntm_deep_plan(ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), ntm_deep_shape(1, R * Md, hid, L),
+                                  p, "ntk_ntm_seq_deep_plan") == NTK_OK;
     if (fwd_kernel) *fwd_kernel = !ok ? 0 : ntm_deep_kernel_id(p.Tf);
     if (fwd_threads) *fwd_threads = ok ? p.Tf : 0;
     if (bwd_kernel) *bwd_kernel = !ok ? 0 : ntm_deep_kernel_id(p.Tb);
@@ -506,8 +379,7 @@ extern "C" int ntk_ntm_seq_deep_plan(int B, int N, int Md, int R, int Wh, int hi
 extern "C" int ntk_ntm_seq_deep_packed_floats(int D, int R, int Md, int hid, int L, size_t* n_wx0, size_t* n_wf, size_t* n_wb) {
     NTK_REQUIRE(D >= 1 && R >= 1 && Md >= 1 && hid >= 1 && L >= 2, NTK_ERR_BAD_SHAPE,
                 "ntk_ntm_seq_deep_packed_floats: D=%d R=%d Md=%d hid=%d L=%d", D, R, Md, hid, L);
-    NtmDeepShape s;
-    ntm_deep_shape(s, D, R * Md, hid, L);
+    const NtmDeepShape s = ntm_deep_shape(D, R * Md, hid, L);
     if (n_wx0) *n_wx0 = ntm_deep_nwx0(s);
     if (n_wf) *n_wf = ntm_deep_nwf(s);
     if (n_wb) *n_wb = ntm_deep_nwb(s);
@@ -522,12 +394,65 @@ extern "C" int ntk_ntm_seq_deep_pack(int D, int R, int Md, int hid, int L, const
     NTK_REQUIRE(lowerT && top_WxT && top_Wr && Wx0 && Wf && Wb, NTK_ERR_BAD_PTR, "ntk_ntm_seq_deep_pack: null pointer");
     NTK_REQUIRE(ntk_aligned16(Wx0) && ntk_aligned16(Wf) && ntk_aligned16(Wb), NTK_ERR_BAD_PTR,
                 "ntk_ntm_seq_deep_pack: Wx0/Wf/Wb must be 16-byte aligned");
-    NtmDeepShape s;
-    ntm_deep_shape(s, D, R * Md, hid, L);
+    const NtmDeepShape s = ntm_deep_shape(D, R * Md, hid, L);
     const size_t n = ntm_deep_nwx0(s) + ntm_deep_nwf(s) + ntm_deep_nwb(s);
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
     ntm_deep_pack_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(s, lowerT, top_WxT, top_Wr, Wx0, Wf, Wb);
     NTK_CHECK_LAUNCH("ntk_ntm_seq_deep_pack");
+    return NTK_OK;
+}
+
+
+// ntk_ntm_seq_fwd_deep behind its plain and *_sim entries: similarity, then shape and plan, then pointers, then the launch.
+// a.Wr, a.cs0 and a.cs_out come null: Wf and the L-layer state are in dp.
+static int ntm_seq_fwd_deep_run(const NtmFwdArgs& a, NtmDeepFwdArgs dp, void* stream) {
+    const char* who = "ntk_ntm_seq_fwd_deep";
+    if (dp.s.L <= 2) dp.st_bufk = nullptr;                  // the record of layers 1 .. L-2
+    NTM_REQUIRE_SIMILARITY(a.d.similarity, who);
+    NTK_REQUIRE(dp.s.D >= 1, NTK_ERR_BAD_SHAPE, "%s: D=%d", who, dp.s.D);
+    NtmDeepPlan p;
+    int rc = ntm_deep_plan(a.d, dp.s, p, who);
+    if (rc != NTK_OK) return rc;
+    rc = ntm_fwd_check_ptrs(a, &dp, who);
+    if (rc != NTK_OK) return rc;
+    typedef void (*kern_t)(NtmFwdArgs, NtmDeepFwdArgs, NtmLds);
+    constexpr int AC = NTM_SIM_AS_CODED, SC = NTM_SIM_SMOOTH_COSINE;
+    static const NtmKernelRow<kern_t> rows[] = {
+        {NTK_NTM_DEEP_768, AC, ntm_seq_fwd_deep_kernel<768>},   {NTK_NTM_DEEP_768, SC, ntm_seq_fwd_deep_kernel<768, SC>},
+        {NTK_NTM_DEEP_1024, AC, ntm_seq_fwd_deep_kernel<1024>}, {NTK_NTM_DEEP_1024, SC, ntm_seq_fwd_deep_kernel<1024, SC>}};
+    static NtkLdsAttrCache lds_cache;
+    kern_t fn;
+    rc = ntm_find_kernel(lds_cache, rows, ntm_deep_kernel_id(p.Tf), a.d.similarity, who, fn);
+    if (rc != NTK_OK) return rc;
+    fn<<<a.d.B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
+    NTK_CHECK_LAUNCH(who);
+    return NTK_OK;
+}
+
+// ntk_ntm_seq_bwd_deep likewise
+static int ntm_seq_bwd_deep_run(const NtmDeepBwdArgs& a, void* stream) {
+    const char* who = "ntk_ntm_seq_bwd_deep";
+    NTM_REQUIRE_SIMILARITY(a.d.similarity, who);
+    NtmDeepPlan p;
+    int rc = ntm_deep_plan(a.d, a.s, p, who);
+    if (rc != NTK_OK) return rc;
+    NTK_REQUIRE(a.ldhT >= a.d.hid && (a.ldhT % 4) == 0, NTK_ERR_BAD_SHAPE, "%s: ldhT=%d (hid=%d)", who, a.ldhT, a.d.hid);
+    rc = ntm_bwd_check_ptrs(a, who);
+    if (rc != NTK_OK) return rc;
+    if (a.ldhT != ntm_align4(a.d.hid)) ntm_deep_bwd_lds(a.d, a.s, p.Tb, a.ldhT, p.Lb);        // the plan laid it out for the smallest ldhT
+    const size_t lds_bytes = (size_t)p.Lb.total * sizeof(float);
+    NTK_REQUIRE(lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "%s: needs %zu B of LDS (> 160 KiB)", who, lds_bytes);
+    typedef void (*kern_t)(NtmDeepBwdArgs, NtmBwdLds);
+    constexpr int AC = NTM_SIM_AS_CODED, SC = NTM_SIM_SMOOTH_COSINE;
+    static const NtmKernelRow<kern_t> rows[] = {
+        {NTK_NTM_DEEP_768, AC, ntm_seq_bwd_deep_kernel<768>},   {NTK_NTM_DEEP_768, SC, ntm_seq_bwd_deep_kernel<768, SC>},
+        {NTK_NTM_DEEP_1024, AC, ntm_seq_bwd_deep_kernel<1024>}, {NTK_NTM_DEEP_1024, SC, ntm_seq_bwd_deep_kernel<1024, SC>}};
+    static NtkLdsAttrCache lds_cache;
+    kern_t fn;
+    rc = ntm_find_kernel(lds_cache, rows, ntm_deep_kernel_id(p.Tb), a.d.similarity, who, fn);
+    if (rc != NTK_OK) return rc;
+    fn<<<a.d.B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
+    NTK_CHECK_LAUNCH(who);
     return NTK_OK;
 }
 
@@ -541,45 +466,26 @@ extern "C" int ntk_ntm_seq_fwd_deep_sim(int B, int S, int N, int Md, int R, int 
                                     float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
                                     float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
                                     void* stream) {
-    const char* who = "ntk_ntm_seq_fwd_deep";
-    NTM_REQUIRE_SIMILARITY(similarity, who);
-    NtmFwdArgs a = {};
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
-    NTK_REQUIRE(D >= 1, NTK_ERR_BAD_SHAPE, "%s: D=%d", who, D);
-    NtmDeepFwdArgs dp = {};
-    ntm_deep_shape(dp.s, D, R * Md, hid, L);
-    NtmDeepPlan p;
-    int rc = ntm_deep_plan(a.d, dp.s, p, who);
-    if (rc != NTK_OK) return rc;
-    NTK_REQUIRE(xproj && Wf && Wa && M0 && w0 && read0 && cs0 && logits && M_out && w_out && read_out && cs_out,
-                NTK_ERR_BAD_PTR, "%s: null pointer", who);
-    NTK_REQUIRE(ntk_aligned16(xproj) && ntk_aligned16(Wf) && ntk_aligned16(Wa) && (!st_gates || ntk_aligned16(st_gates)) &&
-                    (!st_lgates || ntk_aligned16(st_lgates)),
-                NTK_ERR_BAD_PTR, "%s: xproj/Wf/Wa/st_gates/st_lgates must be 16-byte aligned", who);
-    NTK_REQUIRE(!st_gates == !st_c, NTK_ERR_BAD_PTR, "%s: st_gates and st_c go together", who);
-    NTK_REQUIRE(!st_buf0 || X, NTK_ERR_BAD_PTR, "%s: the st_buf0 record needs X", who);
-    a.xproj = xproj; a.Wr = nullptr; a.Wa = Wa; a.M0 = M0; a.w0 = w0; a.read0 = read0; a.cs0 = nullptr;
-    a.logits = logits; a.outputs = outputs; a.M_out = M_out; a.w_out = w_out; a.read_out = read_out; a.cs_out = nullptr;
-    a.st_z = st_z; a.st_gates = st_gates; a.st_c = st_c; a.st_h = st_h; a.st_u = st_u;
-    a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M; a.st_read = st_read;
-    dp.X = X; dp.Wf = Wf; dp.cs0 = cs0; dp.cs_out = cs_out;
-    dp.st_xtop = st_xtop; dp.st_buf0 = st_buf0; dp.st_bufk = (L > 2) ? st_bufk : nullptr; dp.st_lgates = st_lgates; dp.st_lc = st_lc;
-    {
-        static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_fwd_deep_kernel<768>, (const void*)ntm_seq_fwd_deep_kernel<1024>,
-                                  (const void*)ntm_seq_fwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_fwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, who);
-        if (rc_lds != NTK_OK) return rc_lds;
-    }
-    if (similarity == NTM_SIM_SMOOTH_COSINE) {
-        if (ntm_deep_kernel_id(p.Tf) == NTK_NTM_DEEP_768) ntm_seq_fwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
-        else ntm_seq_fwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
-    } else
-    if (ntm_deep_kernel_id(p.Tf) == NTK_NTM_DEEP_768) ntm_seq_fwd_deep_kernel<768><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
-    else ntm_seq_fwd_deep_kernel<1024><<<B, p.Tf, p.lds_f, (hipStream_t)stream>>>(a, dp, p.Lf);
-    NTK_CHECK_LAUNCH(who);
-    return NTK_OK;
+    return ntm_seq_fwd_deep_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), xproj, nullptr, Wa, M0, w0, read0,
+                                 nullptr, logits, outputs, M_out, w_out, read_out, nullptr, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv,
+                                 st_w, st_M, st_read},
+                                {ntm_deep_shape(D, R * Md, hid, L), X, Wf, cs0, cs_out, st_xtop, st_buf0, st_bufk, st_lgates, st_lc}, stream);
+}
+
+extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
+                                    int write_first, int D,
+                                    const float* X, const float* xproj, const float* Wf, const float* Wa,
+                                    const float* M0, const float* w0, const float* read0, const float* cs0,
+                                    float* logits, float* outputs,
+                                    float* M_out, float* w_out, float* read_out, float* cs_out,
+                                    float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
+                                    float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
+                                    float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
+                                    void* stream) {
+    return ntm_seq_fwd_deep_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED), xproj, nullptr, Wa, M0, w0,
+                                 read0, nullptr, logits, outputs, M_out, w_out, read_out, nullptr, st_z, st_gates, st_c, st_h, st_u, st_wc,
+                                 st_wv, st_w, st_M, st_read},
+                                {ntm_deep_shape(D, R * Md, hid, L), X, Wf, cs0, cs_out, st_xtop, st_buf0, st_bufk, st_lgates, st_lc}, stream);
 }
 
 extern "C" int ntk_ntm_seq_bwd_deep_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
@@ -593,59 +499,9 @@ extern "C" int ntk_ntm_seq_bwd_deep_sim(int B, int S, int N, int Md, int R, int 
                                     const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
                                     float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                     void* stream) {
-    const char* who = "ntk_ntm_seq_bwd_deep";
-    NTM_REQUIRE_SIMILARITY(similarity, who);
-    NtmDeepBwdArgs a = {};
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
-    ntm_deep_shape(a.s, 1, R * Md, hid, L);
-    NtmDeepPlan p;
-    int rc = ntm_deep_plan(a.d, a.s, p, who);
-    if (rc != NTK_OK) return rc;
-    NTK_REQUIRE(ldhT >= hid && (ldhT % 4) == 0, NTK_ERR_BAD_SHAPE, "%s: ldhT=%d (hid=%d)", who, ldhT, hid);
-    NTK_REQUIRE(Wb && WaT && M0 && w0 && cs0 && st_gates && st_c && st_u && st_wc && st_wv && st_w && st_M && st_lgates && st_lc &&
-                    dlogits && dgates && dpre && du && dM0 && dw0 && dread0 && dcs0,
-                NTK_ERR_BAD_PTR, "%s: null pointer", who);
-    NTK_REQUIRE(ntk_aligned16(Wb) && ntk_aligned16(WaT) && ntk_aligned16(st_gates) && ntk_aligned16(st_lgates) && ntk_aligned16(dgates),
-                NTK_ERR_BAD_PTR, "%s: Wb/WaT/st_gates/st_lgates/dgates must be 16-byte aligned", who);
-    if (ldhT != ntm_align4(hid)) ntm_deep_bwd_lds(a.d, a.s, p.Tb, ldhT, p.Lb);
-    const size_t lds_bytes = (size_t)p.Lb.total * sizeof(float);
-    NTK_REQUIRE(lds_bytes <= 160 * 1024, NTK_ERR_UNSUPPORTED, "%s: needs %zu B of LDS (> 160 KiB)", who, lds_bytes);
-    a.Wb = Wb; a.WaT = WaT; a.ldhT = ldhT; a.M0 = M0; a.w0 = w0; a.cs0 = cs0;
-    a.st_gates = st_gates; a.st_c = st_c; a.st_u = st_u; a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M;
-    a.st_lgates = st_lgates; a.st_lc = st_lc; a.dlogits = dlogits;
-    a.dM_fin = dM_fin; a.dw_fin = dw_fin; a.dread_fin = dread_fin; a.dcs_fin = dcs_fin;
-    a.dgates = dgates; a.dpre = dpre; a.du = du; a.dM0 = dM0; a.dw0 = dw0; a.dread0 = dread0; a.dcs0 = dcs0;
-    {
-        static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_bwd_deep_kernel<768>, (const void*)ntm_seq_bwd_deep_kernel<1024>,
-                                  (const void*)ntm_seq_bwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_bwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 4, who);
-        if (rc_lds != NTK_OK) return rc_lds;
-    }
-    if (similarity == NTM_SIM_SMOOTH_COSINE) {
-        if (ntm_deep_kernel_id(p.Tb) == NTK_NTM_DEEP_768) ntm_seq_bwd_deep_kernel<768, NTM_SIM_SMOOTH_COSINE><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
-        else ntm_seq_bwd_deep_kernel<1024, NTM_SIM_SMOOTH_COSINE><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
-    } else
-    if (ntm_deep_kernel_id(p.Tb) == NTK_NTM_DEEP_768) ntm_seq_bwd_deep_kernel<768><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
-    else ntm_seq_bwd_deep_kernel<1024><<<B, p.Tb, lds_bytes, (hipStream_t)stream>>>(a, p.Lb);
-    NTK_CHECK_LAUNCH(who);
-    return NTK_OK;
-}
-
-extern "C" int ntk_ntm_seq_fwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
-                                    int write_first, int D,
-                                    const float* X, const float* xproj, const float* Wf, const float* Wa,
-                                    const float* M0, const float* w0, const float* read0, const float* cs0,
-                                    float* logits, float* outputs,
-                                    float* M_out, float* w_out, float* read_out, float* cs_out,
-                                    float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
-                                    float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
-                                    float* st_xtop, float* st_buf0, float* st_bufk, float* st_lgates, float* st_lc,
-                                    void* stream) {
-    return ntk_ntm_seq_fwd_deep_sim(B, S, N, Md, R, Wh, hid, shift_range, O, L, write_first, NTM_SIM_AS_CODED, D, X, xproj, Wf, Wa,
-                                    M0, w0, read0, cs0, logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h,
-                                    st_u, st_wc, st_wv, st_w, st_M, st_read, st_xtop, st_buf0, st_bufk, st_lgates, st_lc, stream);
+    return ntm_seq_bwd_deep_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), ntm_deep_shape(1, R * Md, hid, L),
+                                 Wb, WaT, ldhT, M0, w0, cs0, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, st_lgates, st_lc, dlogits,
+                                 dM_fin, dw_fin, dread_fin, dcs_fin, dgates, dpre, du, dM0, dw0, dread0, dcs0}, stream);
 }
 
 extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int L,
@@ -659,7 +515,7 @@ extern "C" int ntk_ntm_seq_bwd_deep(int B, int S, int N, int Md, int R, int Wh, 
                                     const float* dM_fin, const float* dw_fin, const float* dread_fin, const float* dcs_fin,
                                     float* dgates, float* dpre, float* du, float* dM0, float* dw0, float* dread0, float* dcs0,
                                     void* stream) {
-    return ntk_ntm_seq_bwd_deep_sim(B, S, N, Md, R, Wh, hid, shift_range, O, L, write_first, NTM_SIM_AS_CODED, Wb, WaT, ldhT, M0, w0, cs0,
-                                    st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, st_lgates, st_lc, dlogits, dM_fin, dw_fin,
-                                    dread_fin, dcs_fin, dgates, dpre, du, dM0, dw0, dread0, dcs0, stream);
+    return ntm_seq_bwd_deep_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED),
+                                 ntm_deep_shape(1, R * Md, hid, L), Wb, WaT, ldhT, M0, w0, cs0, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M,
+                                 st_lgates, st_lc, dlogits, dM_fin, dw_fin, dread_fin, dcs_fin, dgates, dpre, du, dM0, dw0, dread0, dcs0}, stream);
 }

@@ -20,7 +20,8 @@
 //
 // P2's normaliser and P3 .. P8 are the phase functions of ntm_phases.h, shared with ntm_seq_fwd_ws.hip and ntm_seq_deep.hip; the
 // barriers between them stay here.  This file's own: the gate product P1 with its resident rows and rolling prefetch, the LSTM
-// cell of P2, the initial / final state, the plan (ntm_fwd_plan, ntm_pick_threads, ntm_validate_dims) and the launcher.
+// cell of P2, the initial / final state, the plan (ntm_fwd_plan, ntm_pick_threads, ntm_validate_dims) and the launcher.  The argument
+// struct, the pointer check and the LDS carve-up are in ntm_seq_args.h.
 #include "ntm_common.h"
 
 // Diagnostic build only (-DNTK_CL_PROF): s_memtime shares per phase, accumulated in LDS by thread 0 of workgroup 0
@@ -312,6 +313,32 @@ extern "C" int ntk_ntm_padded_dims(int N, int Md, int R, int Wh, int hid, int sh
     return NTK_OK;
 }
 
+// ntk_ntm_seq_fwd behind its plain, *_sim and step entries: similarity, then shape and plan, then pointers, then the launch
+int ntm_seq_fwd_run(const NtmFwdArgs& a, void* stream) {
+    const char* who = "ntk_ntm_seq_fwd";
+    NTM_REQUIRE_SIMILARITY(a.d.similarity, who);
+    NtmFwdPlan p;
+    int rc = ntm_fwd_plan(a.d, p, who);
+    if (rc != NTK_OK) return rc;
+    rc = ntm_fwd_check_ptrs(a, nullptr, who);
+    if (rc != NTK_OK) return rc;
+    if (p.kernel == NTK_NTM_FWD_WS) return ntm_seq_fwd_ws_launch(a, p.L, p.lds_bytes, stream);
+    typedef void (*kern_t)(NtmFwdArgs, NtmLds);
+    constexpr int AC = NTM_SIM_AS_CODED, SC = NTM_SIM_SMOOTH_COSINE;
+    static const NtmKernelRow<kern_t> rows[] = {
+        {NTK_NTM_FWD_FIX512, AC, ntm_seq_fwd_kernel<512, 512, 24, 20>},      {NTK_NTM_FWD_FIX512, SC, ntm_seq_fwd_kernel<512, 512, 24, 20, SC>},
+        {NTK_NTM_FWD_GENERIC768, AC, ntm_seq_fwd_kernel<768, 0>},            {NTK_NTM_FWD_GENERIC768, SC, ntm_seq_fwd_kernel<768, 0, 0, 0, SC>},
+        {NTK_NTM_FWD_GENERIC1024, AC, ntm_seq_fwd_kernel<1024, 0>},          {NTK_NTM_FWD_GENERIC1024, SC, ntm_seq_fwd_kernel<1024, 0, 0, 0, SC>},
+        {NTK_NTM_FWD_FIX640_DEV, AC, ntm_seq_fwd_kernel<768, 640>}};         // (planned by the NTK_NTM_FWD_STREAM_ONLY build only)
+    static NtkLdsAttrCache lds_cache;
+    kern_t fn;
+    rc = ntm_find_kernel(lds_cache, rows, p.kernel, a.d.similarity, who, fn);
+    if (rc != NTK_OK) return rc;
+    fn<<<a.d.B, p.T, p.lds_bytes, (hipStream_t)stream>>>(a, p.L);
+    NTK_CHECK_LAUNCH(who);
+    return NTK_OK;
+}
+
 extern "C" int ntk_ntm_seq_fwd_sim(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
                                int write_first, int similarity,
                                const float* xproj, const float* Wr, const float* Wa,
@@ -321,47 +348,9 @@ extern "C" int ntk_ntm_seq_fwd_sim(int B, int S, int N, int Md, int R, int Wh, i
                                float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
                                void* stream) {
-    NTM_REQUIRE_SIMILARITY(similarity, "ntk_ntm_seq_fwd");
-    NtmFwdArgs a;
-    ntm_fill_dims(a.d, B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity);
-    NtmFwdPlan p;
-    int rc = ntm_fwd_plan(a.d, p, "ntk_ntm_seq_fwd");
-    if (rc != NTK_OK) return rc;
-    NTK_REQUIRE(xproj && Wr && Wa && M0 && w0 && read0 && cs0 && logits && M_out && w_out && read_out && cs_out,
-                NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: null pointer");
-    NTK_REQUIRE(ntk_aligned16(xproj) && ntk_aligned16(Wr) && ntk_aligned16(Wa) &&
-                    (!st_gates || ntk_aligned16(st_gates)),
-                NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: xproj/Wr/Wa/st_gates must be 16-byte aligned");
-    NTK_REQUIRE(!st_gates == !st_c, NTK_ERR_BAD_PTR, "ntk_ntm_seq_fwd: st_gates and st_c go together");
-    a.xproj = xproj; a.Wr = Wr; a.Wa = Wa; a.M0 = M0; a.w0 = w0; a.read0 = read0; a.cs0 = cs0;
-    a.logits = logits; a.outputs = outputs; a.M_out = M_out; a.w_out = w_out; a.read_out = read_out; a.cs_out = cs_out;
-    a.st_z = st_z; a.st_gates = st_gates; a.st_c = st_c; a.st_h = st_h; a.st_u = st_u;
-    a.st_wc = st_wc; a.st_wv = st_wv; a.st_w = st_w; a.st_M = st_M; a.st_read = st_read;
-    if (p.kernel == NTK_NTM_FWD_WS) return ntm_seq_fwd_ws_launch(a, p.L, p.lds_bytes, stream);
-    {
-        static NtkLdsAttrCache lds_cache;
-        const void* const ks[] = {(const void*)ntm_seq_fwd_kernel<768, 0>, (const void*)ntm_seq_fwd_kernel<1024, 0>, (const void*)ntm_seq_fwd_kernel<768, 640>,
-                                  (const void*)ntm_seq_fwd_kernel<512, 512, 24, 20>,
-                                  (const void*)ntm_seq_fwd_kernel<768, 0, 0, 0, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_fwd_kernel<1024, 0, 0, 0, NTM_SIM_SMOOTH_COSINE>,
-                                  (const void*)ntm_seq_fwd_kernel<512, 512, 24, 20, NTM_SIM_SMOOTH_COSINE>};
-        const int rc_lds = ntk_raise_lds_limit(lds_cache, ks, 7, "ntk_ntm_seq_fwd");
-        if (rc_lds != NTK_OK) return rc_lds;
-    }
-    const hipStream_t st = (hipStream_t)stream;
-    if (similarity == NTM_SIM_SMOOTH_COSINE) {
-        constexpr int SC = NTM_SIM_SMOOTH_COSINE;
-        if (p.kernel == NTK_NTM_FWD_FIX512) ntm_seq_fwd_kernel<512, 512, 24, 20, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-        else if (p.kernel == NTK_NTM_FWD_GENERIC768) ntm_seq_fwd_kernel<768, 0, 0, 0, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-        else if (p.kernel == NTK_NTM_FWD_GENERIC1024) ntm_seq_fwd_kernel<1024, 0, 0, 0, SC><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-        else NTK_REQUIRE(false, NTK_ERR_UNSUPPORTED, "ntk_ntm_seq_fwd: kernel %d has no smooth-cosine form", p.kernel);
-    } else
-    if (p.kernel == NTK_NTM_FWD_FIX512) ntm_seq_fwd_kernel<512, 512, 24, 20><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-    else if (p.kernel == NTK_NTM_FWD_FIX640_DEV) ntm_seq_fwd_kernel<768, 640><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-    else if (p.kernel == NTK_NTM_FWD_GENERIC768) ntm_seq_fwd_kernel<768, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-    else ntm_seq_fwd_kernel<1024, 0><<<B, p.T, p.lds_bytes, st>>>(a, p.L);
-    NTK_CHECK_LAUNCH("ntk_ntm_seq_fwd");
-    return NTK_OK;
+    return ntm_seq_fwd_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), xproj, Wr, Wa, M0, w0, read0, cs0,
+                            logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M,
+                            st_read}, stream);
 }
 
 extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int hid, int shift_range, int O,
@@ -373,7 +362,7 @@ extern "C" int ntk_ntm_seq_fwd(int B, int S, int N, int Md, int R, int Wh, int h
                                float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read,
                                void* stream) {
-    return ntk_ntm_seq_fwd_sim(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED, xproj, Wr, Wa, M0, w0, read0, cs0,
-                               logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w,
-                               st_M, st_read, stream);
+    return ntm_seq_fwd_run({ntm_dims(B, S, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED), xproj, Wr, Wa, M0, w0, read0,
+                            cs0, logits, outputs, M_out, w_out, read_out, cs_out, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w,
+                            st_M, st_read}, stream);
 }

@@ -2,10 +2,10 @@
 // kernels, the BasicLSTMCell pointwise step, a stand-alone 2x2 max pool and the split loss entry points.
 // The training/inference hot path uses the persistent sequence kernels and the pool fused into the conv epilogue;
 // these exist so a caller that drives the cell one step() at a time (test_tracker.py:340-341) binds the same library.
-#include "common.h"
+#include "ntm_seq_args.h"
 
 // ---------------------------------------------------------------------------------------------------------
-// one NTM cell step = the persistent kernel with S = 1 (ntm_cell.py:53-253)
+// one NTM cell step = the persistent kernel with S = 1 (ntm_cell.py:53-253): the launchers of ntm_seq_fwd.hip / ntm_seq_bwd.hip
 // ---------------------------------------------------------------------------------------------------------
 extern "C" int ntk_ntm_step_fwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
                                 int similarity,
@@ -14,9 +14,9 @@ extern "C" int ntk_ntm_step_fwd_sim(int B, int N, int Md, int R, int Wh, int hid
                                 float* logits, float* outputs, float* M, float* w, float* read, float* cs,
                                 float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                 float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read, void* stream) {
-    return ntk_ntm_seq_fwd_sim(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity, xproj, Wr, Wa, M_prev, w_prev, read_prev,
-                               cs_prev, logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M,
-                               st_read, stream);
+    return ntm_seq_fwd_run({ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), xproj, Wr, Wa, M_prev, w_prev, read_prev,
+                            cs_prev, logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M, st_read},
+                           stream);
 }
 
 extern "C" int ntk_ntm_step_fwd(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
@@ -25,9 +25,9 @@ extern "C" int ntk_ntm_step_fwd(int B, int N, int Md, int R, int Wh, int hid, in
                                 float* logits, float* outputs, float* M, float* w, float* read, float* cs,
                                 float* st_z, float* st_gates, float* st_c, float* st_h, float* st_u,
                                 float* st_wc, float* st_wv, float* st_w, float* st_M, float* st_read, void* stream) {
-    return ntk_ntm_step_fwd_sim(B, N, Md, R, Wh, hid, shift_range, O, write_first, 0, xproj, Wr, Wa, M_prev, w_prev, read_prev, cs_prev,
-                                logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M, st_read,
-                                stream);
+    return ntm_seq_fwd_run({ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED), xproj, Wr, Wa, M_prev, w_prev,
+                            read_prev, cs_prev, logits, outputs, M, w, read, cs, st_z, st_gates, st_c, st_h, st_u, st_wc, st_wv, st_w, st_M,
+                            st_read}, stream);
 }
 
 extern "C" int ntk_ntm_step_bwd_sim(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
@@ -40,9 +40,9 @@ extern "C" int ntk_ntm_step_bwd_sim(int B, int N, int Md, int R, int Wh, int hid
                                 const float* dM, const float* dw, const float* dread, const float* dcs,
                                 float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
                                 void* stream) {
-    return ntk_ntm_seq_bwd_sim(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity, WrT, ldkT, WaT, ldhT, M_prev, w_prev,
-                               cs_prev, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
-                               dM_prev, dw_prev, dread_prev, dcs_prev, stream);
+    return ntm_seq_bwd_run({ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, similarity), WrT, WaT, ldkT, ldhT, M_prev, w_prev,
+                            cs_prev, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
+                            dM_prev, dw_prev, dread_prev, dcs_prev}, stream);
 }
 
 extern "C" int ntk_ntm_step_bwd(int B, int N, int Md, int R, int Wh, int hid, int shift_range, int O, int write_first,
@@ -54,9 +54,9 @@ extern "C" int ntk_ntm_step_bwd(int B, int N, int Md, int R, int Wh, int hid, in
                                 const float* dM, const float* dw, const float* dread, const float* dcs,
                                 float* dgates, float* du, float* dM_prev, float* dw_prev, float* dread_prev, float* dcs_prev,
                                 void* stream) {
-    return ntk_ntm_step_bwd_sim(B, N, Md, R, Wh, hid, shift_range, O, write_first, 0, WrT, ldkT, WaT, ldhT, M_prev, w_prev, cs_prev,
-                                st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
-                                dM_prev, dw_prev, dread_prev, dcs_prev, stream);
+    return ntm_seq_bwd_run({ntm_dims(B, 1, N, Md, R, Wh, hid, shift_range, O, write_first, NTM_SIM_AS_CODED), WrT, WaT, ldkT, ldhT, M_prev,
+                            w_prev, cs_prev, st_gates, st_c, st_u, st_wc, st_wv, st_w, st_M, dlogits, dM, dw, dread, dcs, dgates, du,
+                            dM_prev, dw_prev, dread_prev, dcs_prev}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -27,6 +27,14 @@ def _np(t):
     return None if t is None else _lib.ptr(t)
 
 
+class _Keep(list):
+    """Pointers to contiguous copies of tensors; the copies stay referenced (here) until the launch that reads them is queued."""
+
+    def __call__(self, t):
+        self.append(t.contiguous())
+        return _P(self[-1])
+
+
 class NTMDims(object):
     def __init__(self, input_dim, output_dim, mem_size, mem_dim, shift_range, hidden, read_heads, write_heads):
         self.D = int(input_dim)
@@ -288,23 +296,67 @@ class NTMCell(object):
     FWD_KERNELS = {0: None, 1: "ws", 2: "fixdims-512", 3: "generic-768", 4: "generic-1024", 5: "fixdims-640-dev"}
     BWD_KERNELS = {0: None, 1: "ws", 2: "fix", 3: "generic-768", 4: "generic-1024"}
 
+    def _lead(self, *head, layers=None):
+        """The integers in front of the pointers of every *_sim entry of the C ABI: ``head`` (B, or B and S), the cell's dimensions,
+        the layer count (deep entries), write_first and the similarity mode."""
+        d = self.dims
+        return head + (d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O) + (() if layers is None else (layers,)) + \
+            (1 if self.write_first else 0, self._sim)
+
+    def _plan(self, symbol, names, batch, *extra, layers=None):
+        """A plan query (``symbol``: ntk_ntm_seq_plan_sim or ntk_ntm_seq_deep_plan_sim; ``extra``: its integers behind the lead) as
+        the dict ``plan`` returns; ``names``: the forward's and the BPTT's kernel names by id."""
+        if self.dims is None:
+            raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
+        v = [ctypes.c_int() for _ in range(4)]
+        mask = getattr(_lib.lib(), symbol)(*self._lead(int(batch), layers=layers), *extra, *[ctypes.byref(x) for x in v])
+        msg = _lib.lib().ntk_last_error() if mask != 3 else b""
+        return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": names[0][v[0].value],
+                "fwd_threads": v[1].value, "bwd_kernel": names[1][v[2].value], "bwd_threads": v[3].value,
+                "reason": msg.decode() if msg else ""}
+
     def plan(self, batch):
         """ntk_ntm_seq_plan for this cell (host arithmetic, nothing is launched): a dict with ``forward`` / ``bptt`` (does the
         direction run), ``fwd_kernel`` / ``bwd_kernel`` (names of the header's kernel ids, None where refused), ``fwd_threads`` /
         ``bwd_threads`` and ``reason`` (why a direction is refused, else "").  A cell whose plan has forward but not bptt
         runs run_sequence and raises in backward_sequence."""
-        d = self.dims
-        if d is None:
-            raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
-        v = [ctypes.c_int() for _ in range(4)]
-        mask = _lib.lib().ntk_ntm_seq_plan_sim(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0,
-                                               self._sim, (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4, *[ctypes.byref(x) for x in v])
-        msg = _lib.lib().ntk_last_error() if mask != 3 else b""
-        return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.FWD_KERNELS[v[0].value],
-                "fwd_threads": v[1].value, "bwd_kernel": self.BWD_KERNELS[v[2].value], "bwd_threads": v[3].value,
-                "reason": msg.decode() if msg else ""}
+        return self._plan("ntk_ntm_seq_plan_sim", (self.FWD_KERNELS, self.BWD_KERNELS), batch, 0, 0)      # 0: the smallest ldkT / ldhT
 
     # ---- sequence kernel
+    #: the per-step records of a forward launch, in the order of the C ABI's st_* pointers
+    RECORDS = ("z", "gates", "c", "h", "u", "wc", "wv", "w", "M", "read")
+
+    def _records(self, B, S):
+        """Empty tensors for the ten records of a forward launch (the deep form adds its five, StackedNTMCell._run_fused)."""
+        d = self.dims
+        shapes = {"z": (d.ldz,), "gates": (d.hid, 4), "c": (d.hid,), "h": (d.ldh,), "u": (d.PP,), "wc": (d.H, d.N), "wv": (d.H, d.N),
+                  "w": (d.H, d.N), "M": (d.N, d.Md), "read": (d.R, d.Md)}
+        return {k: torch.empty((B, S) + shapes[k], device=self.device) for k in self.RECORDS}
+
+    def _bptt_weights(self, recurrent=True):
+        """(WrT [4*hid][ldkT], ldkT, WaT [PP][ldhT], ldhT): the transposed, zero-padded weights the BPTT kernels stream, from the
+        parameters as they are now (WrT None where the caller has its own recurrent blocks)."""
+        d, dev, L, st = self.dims, self.device, _lib.lib(), _lib.stream()
+        ldkT, ldhT = (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4
+        WrT = torch.empty((4 * d.hid, ldkT), device=dev) if recurrent else None
+        WaT = torch.empty((d.PP, ldhT), device=dev)
+        if recurrent:
+            _lib.check(L.ntk_transpose_pad(_P(self.params.view("Wr")), 4 * d.hid, _P(WrT), ldkT, d.K, 4 * d.hid, st), "ntk_transpose_pad")
+        _lib.check(L.ntk_transpose_pad(_P(self.params.view("Wa")), d.PP, _P(WaT), ldhT, d.hid, d.PP, st), "ntk_transpose_pad")
+        return WrT, ldkT, WaT, ldhT
+
+    def _weight_grads(self, xin, z, h, dgates, du, workspace, zero_read_rows=False):
+        """The gradients of WxT, Wr and Wa: three k-major contractions over all B*S recorded rows (xin: the rows the gates' input
+        projection read).  zero_read_rows: the cell is the top layer of a deep controller, whose read_prev rows of Wr are structural
+        zeros (read_prev enters at layer 0)."""
+        d, P = self.dims, self.params
+        BS = dgates.shape[0] * dgates.shape[1]
+        gemm_tn(dgates.view(BS, 4 * d.hid), xin.view(BS, -1), P.view("WxT", grad=True), workspace=workspace)
+        gemm_tn(z.view(BS, d.ldz), dgates.view(BS, 4 * d.hid), P.view("Wr", grad=True), workspace=workspace)
+        gemm_tn(h.view(BS, d.ldh), du.view(BS, d.PP), P.view("Wa", grad=True), workspace=workspace)
+        if zero_read_rows:
+            P.view("Wr", grad=True)[:d.RM].zero_()
+
     def _pad_inputs(self, inputs):
         d = self.dims
         B, S, D = inputs.shape
@@ -329,31 +381,16 @@ class NTMCell(object):
         logits = torch.empty((B, S, d.O), device=dev)
         outputs = torch.empty((B, S, d.O), device=dev) if want_outputs else None
         new = self.state_placeholder(B)
-        rec = {}
-        if record:
-            rec = {
-                "z": torch.empty((B, S, d.ldz), device=dev), "gates": torch.empty((B, S, d.hid, 4), device=dev),
-                "c": torch.empty((B, S, d.hid), device=dev), "h": torch.empty((B, S, d.ldh), device=dev),
-                "u": torch.empty((B, S, d.PP), device=dev), "wc": torch.empty((B, S, d.H, d.N), device=dev),
-                "wv": torch.empty((B, S, d.H, d.N), device=dev), "w": torch.empty((B, S, d.H, d.N), device=dev),
-                "M": torch.empty((B, S, d.N, d.Md), device=dev), "read": torch.empty((B, S, d.R, d.Md), device=dev),
-            }
-        g = lambda k: _np(rec.get(k))
-        keep = []                                    # contiguous copies stay referenced until the launch is queued
-
-        def cp(t):
-            keep.append(t.contiguous())
-            return _P(keep[-1])
+        rec = self._records(B, S) if record else {}
+        cp = _Keep()
         # a single step binds the step entry point of the C ABI (same kernel, S = 1)
-        fn, name, lead = ((_lib.lib().ntk_ntm_step_fwd_sim, "ntk_ntm_step_fwd", (B,)) if S == 1 else
+        fn, name, head = ((_lib.lib().ntk_ntm_step_fwd_sim, "ntk_ntm_step_fwd", (B,)) if S == 1 else
                           (_lib.lib().ntk_ntm_seq_fwd_sim, "ntk_ntm_seq_fwd", (B, S)))
         _lib.check(fn(
-            *lead, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
-            _P(xproj), _P(self.params.view("Wr")), _P(self.params.view("Wa")),
+            *self._lead(*head), _P(xproj), _P(self.params.view("Wr")), _P(self.params.view("Wa")),
             cp(state["M"]), cp(state["w"]), cp(state["read"]), cp(state["controller_state"]),
             _P(logits), _np(outputs), _P(new["M"]), _P(new["w"]), _P(new["read"]), _P(new["controller_state"]),
-            g("z"), g("gates"), g("c"), g("h"), g("u"), g("wc"), g("wv"), g("w"), g("M"), g("read"),
-            _lib.stream()), name)
+            *[_np(rec.get(k)) for k in self.RECORDS], _lib.stream()), name)
         rec["xproj"] = xproj
         return logits, outputs, new, rec
 
@@ -366,29 +403,18 @@ class NTMCell(object):
         state).  Returns the gradient w.r.t. the initial state tensors."""
         d, dev, L = self.dims, self.device, _lib.lib()
         B, S, _ = X.shape
-        P = self.params
-        ldkT, ldhT = (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4
+        P, st = self.params, _lib.stream()
         # a shape that runs forward only (see include/ntmtrack.h) is refused here, before anything is launched
-        if not L.ntk_ntm_seq_plan_sim(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
-                                      ldkT, ldhT, None, None, None, None) & 2:
+        if not L.ntk_ntm_seq_plan_sim(*self._lead(B), 0, 0, None, None, None, None) & 2:
             _lib.check(-3, "ntk_ntm_seq_bwd")
-        WrT = torch.empty((4 * d.hid, ldkT), device=dev)
-        WaT = torch.empty((d.PP, ldhT), device=dev)
-        st = _lib.stream()
-        _lib.check(L.ntk_transpose_pad(_P(P.view("Wr")), 4 * d.hid, _P(WrT), ldkT, d.K, 4 * d.hid, st), "ntk_transpose_pad")
-        _lib.check(L.ntk_transpose_pad(_P(P.view("Wa")), d.PP, _P(WaT), ldhT, d.hid, d.PP, st), "ntk_transpose_pad")
+        WrT, ldkT, WaT, ldhT = self._bptt_weights()
         dgates = torch.empty((B, S, 4 * d.hid), device=dev)
         du = torch.empty((B, S, d.PP), device=dev)
         g0 = self.state_placeholder(B)
         df = dfinal or {}
-        keep = []
-
-        def cp(t):
-            keep.append(t.contiguous())
-            return _P(keep[-1])
+        cp = _Keep()
         _lib.check(L.ntk_ntm_seq_bwd_sim(
-            B, S, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
-            _P(WrT), ldkT, _P(WaT), ldhT,
+            *self._lead(B, S), _P(WrT), ldkT, _P(WaT), ldhT,
             cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
             _P(rec["gates"]), _P(rec["c"]), _P(rec["u"]), _P(rec["wc"]), _P(rec["wv"]), _P(rec["w"]), _P(rec["M"]),
             cp(dlogits),
@@ -396,10 +422,7 @@ class NTMCell(object):
             _P(dgates), _P(du), _P(g0["M"]), _P(g0["w"]), _P(g0["read"]), _P(g0["controller_state"]), st),
             "ntk_ntm_seq_bwd")
         BS = B * S
-        # weight gradients: three k-major contractions over all B*S recorded rows
-        gemm_tn(dgates.view(BS, 4 * d.hid), X.view(BS, d.ldx), P.view("WxT", grad=True), workspace=workspace)
-        gemm_tn(rec["z"].view(BS, d.ldz), dgates.view(BS, 4 * d.hid), P.view("Wr", grad=True), workspace=workspace)
-        gemm_tn(rec["h"].view(BS, d.ldh), du.view(BS, d.PP), P.view("Wa", grad=True), workspace=workspace)
+        self._weight_grads(X, rec["z"], rec["h"], dgates, du, workspace)
         #: gradient w.r.t. the (padded) input rows, for callers with a trainable layer in front of the cell (the input
         #: compressor of main.py's trackers): dX = dgates . Wx, one more GEMM -- only when asked for
         self.last_dX = None
@@ -667,25 +690,16 @@ class StackedNTMCell(NTMCell):
     def _fused_ok(self, B):
         if self.fused is False or os.environ.get("NTK_NTM_DEEP_FORM", "") == "stepwise":
             return False
-        d = self.dims
         # the plan, not ntk_ntm_seq_deep_supported: that one answers for write_first = 0, and a write_first cell needs more LDS
-        return _lib.lib().ntk_ntm_seq_deep_plan_sim(B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
-                                                    1 if self.write_first else 0, self._sim, None, None, None, None) == 3
+        return _lib.lib().ntk_ntm_seq_deep_plan_sim(*self._lead(B, layers=self.L), None, None, None, None) == 3
 
     DEEP_KERNELS = {0: None, 1: "deep-768", 2: "deep-1024"}
+    #: the deep forward's records behind NTMCell.RECORDS, in the order of the C ABI
+    DEEP_RECORDS = ("xtop", "buf0", "bufk", "lgates", "lc")
 
     def plan(self, batch):
         """ntk_ntm_seq_deep_plan for this cell: as NTMCell.plan; a refused shape runs step-wise from Python instead."""
-        d = self.dims
-        if d is None:
-            raise _lib.NtkError("plan before the cell has parameters: pass input_dim= or load_state_dict()")
-        v = [ctypes.c_int() for _ in range(4)]
-        mask = _lib.lib().ntk_ntm_seq_deep_plan_sim(int(batch), d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, self.L,
-                                                    1 if self.write_first else 0, self._sim, *[ctypes.byref(x) for x in v])
-        msg = _lib.lib().ntk_last_error() if mask != 3 else b""
-        return {"forward": bool(mask & 1), "bptt": bool(mask & 2), "fwd_kernel": self.DEEP_KERNELS[v[0].value],
-                "fwd_threads": v[1].value, "bwd_kernel": self.DEEP_KERNELS[v[2].value], "bwd_threads": v[3].value,
-                "reason": msg.decode() if msg else ""}
+        return self._plan("ntk_ntm_seq_deep_plan_sim", (self.DEEP_KERNELS, self.DEEP_KERNELS), batch, layers=self.L)
 
     def _pack(self):
         """The controller weights in the deep kernels' layouts (ntk_ntm_seq_deep_pack), from the flat buffer as it is now."""
@@ -723,27 +737,16 @@ class StackedNTMCell(NTMCell):
         if record:
             ldxt, ld0, ld1 = (hid + 3) // 4 * 4, self.params.lower_off[0][1][1], (2 * hid + 1 + 3) // 4 * 4
             e = lambda *shape: torch.empty(shape, device=dev)
-            rec = {
-                "z": e(B, S, d.ldz), "gates": e(B, S, hid, 4), "c": e(B, S, hid), "h": e(B, S, d.ldh), "u": e(B, S, d.PP),
-                "wc": e(B, S, d.H, d.N), "wv": e(B, S, d.H, d.N), "w": e(B, S, d.H, d.N), "M": e(B, S, d.N, d.Md),
-                "read": e(B, S, d.R, d.Md),
-                # the lower layers (k = 0 .. L-2) and the top layer's input
-                "xtop": e(B, S, ldxt), "buf0": e(B, S, ld0), "bufk": e(L - 2, B, S, ld1) if L > 2 else None,
-                "lgates": e(L - 1, B, S, hid, 4), "lc": e(L - 1, B, S, hid),
-            }
-        g = lambda k: _np(rec.get(k))
-        keep = []
-
-        def cp(t):
-            keep.append(t.contiguous())
-            return _P(keep[-1])
+            rec = self.top._records(B, S)
+            # the lower layers (k = 0 .. L-2) and the top layer's input
+            rec.update({"xtop": e(B, S, ldxt), "buf0": e(B, S, ld0), "bufk": e(L - 2, B, S, ld1) if L > 2 else None,
+                        "lgates": e(L - 1, B, S, hid, 4), "lc": e(L - 1, B, S, hid)})
+        cp = _Keep()
         _lib.check(_lib.lib().ntk_ntm_seq_fwd_deep_sim(
-            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self._sim, self.D,
-            _P(X), _P(xproj), _P(Wf), _P(self.top.params.view("Wa")),
+            *self._lead(B, S, layers=L), self.D, _P(X), _P(xproj), _P(Wf), _P(self.top.params.view("Wa")),
             cp(state["M"]), cp(state["w"]), cp(state["read"]), cp(state["controller_state"]),
             _P(logits), _np(outputs), _P(new["M"]), _P(new["w"]), _P(new["read"]), _P(new["controller_state"]),
-            g("z"), g("gates"), g("c"), g("h"), g("u"), g("wc"), g("wv"), g("w"), g("M"), g("read"),
-            g("xtop"), g("buf0"), g("bufk"), g("lgates"), g("lc"), _lib.stream()), "ntk_ntm_seq_fwd_deep")
+            *[_np(rec.get(k)) for k in self.RECORDS + self.DEEP_RECORDS], _lib.stream()), "ntk_ntm_seq_fwd_deep")
         if record:
             rec["Wb"] = Wb                              # the packed weights the BPTT of this pass streams
         self.last_form = "fused"
@@ -784,11 +787,7 @@ class StackedNTMCell(NTMCell):
         hid, L, dev = self.controller_hidden_size, self.L, self.device
         d, lib, stream = self.dims, _lib.lib(), _lib.stream()
         TP = self.top.params
-        ldkT, ldhT = (d.K + 3) // 4 * 4, (d.hid + 3) // 4 * 4
-        WrT = torch.empty((4 * hid, ldkT), device=dev)
-        WaT = torch.empty((d.PP, ldhT), device=dev)
-        _lib.check(lib.ntk_transpose_pad(_P(TP.view("Wr")), 4 * hid, _P(WrT), ldkT, d.K, 4 * hid, stream), "ntk_transpose_pad")
-        _lib.check(lib.ntk_transpose_pad(_P(TP.view("Wa")), d.PP, _P(WaT), ldhT, hid, d.PP, stream), "ntk_transpose_pad")
+        WrT, ldkT, WaT, ldhT = self.top._bptt_weights()
         Wx_top = TP.view("WxT").t().contiguous()                       # [ldx_top][4*hid]: d(top input) = dgates @ WxT
         W_low = [WT.t().contiguous() for WT, _i, _l in self.lower]      # [ld_k][4*hid]
         z = lambda *s_: torch.zeros(s_, device=dev)
@@ -810,8 +809,7 @@ class StackedNTMCell(NTMCell):
             g0 = self.top.state_placeholder(B)
             dlt = dl[:, t].contiguous()
             _lib.check(lib.ntk_ntm_step_bwd_sim(
-                B, d.N, d.Md, d.R, d.Wh, d.hid, d.shift_range, d.O, 1 if self.write_first else 0, self._sim,
-                _P(WrT), ldkT, _P(WaT), ldhT, _P(ts["M"].contiguous()), _P(ts["w"].contiguous()), _P(ts["controller_state"]),
+                *self._lead(B), _P(WrT), ldkT, _P(WaT), ldhT, _P(ts["M"].contiguous()), _P(ts["w"].contiguous()), _P(ts["controller_state"]),
                 _P(r["gates"]), _P(r["c"]), _P(r["u"]), _P(r["wc"]), _P(r["wv"]), _P(r["w"]), _P(r["M"]), _P(dlt),
                 _P(dM), _P(dw), _P(dread), _P(dcs_top),
                 _P(dgates), _P(du), _P(g0["M"]), _P(g0["w"]), _P(g0["read"]), _P(g0["controller_state"]), stream),
@@ -837,11 +835,7 @@ class StackedNTMCell(NTMCell):
         # weight gradients: k-major contractions over all recorded rows (bias = the ones column of the recorded inputs)
         Xtop = torch.stack([st["Xtop"][:, 0] for st in steps], 1).contiguous()
         cat = lambda key: torch.stack([st["top"][key][:, 0] for st in steps], 1).contiguous()
-        gemm_tn(dgates_all.view(BS, 4 * hid), Xtop.view(BS, d.ldx), TP.view("WxT", grad=True), workspace=workspace)
-        gemm_tn(cat("z").view(BS, d.ldz), dgates_all.view(BS, 4 * hid), TP.view("Wr", grad=True), workspace=workspace)
-        gemm_tn(cat("h").view(BS, d.ldh), du_all.view(BS, d.PP), TP.view("Wa", grad=True), workspace=workspace)
-        # the read_prev rows of the fused cell's recurrent matrix are structural zeros here (read_prev enters at layer 0)
-        TP.view("Wr", grad=True)[:d.RM].zero_()
+        self.top._weight_grads(Xtop, cat("z"), cat("h"), dgates_all, du_all, workspace, zero_read_rows=True)
         for k, (WT, in_dim, ld) in enumerate(self.lower):
             bufs = torch.stack([st["lower"][k]["buf"] for st in steps], 1).contiguous()
             gemm_tn(dpre_all[k].view(BS, 4 * hid), bufs.view(BS, ld), self.params.lower(k, grad=True), workspace=workspace)
@@ -852,23 +846,15 @@ class StackedNTMCell(NTMCell):
     def _backward_fused(self, state0, rec, dlogits, dfinal, workspace):
         d, dev, hid, L, lib, st = self.dims, self.device, self.controller_hidden_size, self.L, _lib.lib(), _lib.stream()
         B, S = rec["c"].shape[:2]
-        TP = self.top.params
-        ldhT = (hid + 3) // 4 * 4
-        WaT = torch.empty((d.PP, ldhT), device=dev)
-        _lib.check(lib.ntk_transpose_pad(_P(TP.view("Wa")), d.PP, _P(WaT), ldhT, hid, d.PP, st), "ntk_transpose_pad")
+        _WrT, _ldkT, WaT, ldhT = self.top._bptt_weights(recurrent=False)      # (the recurrent blocks: rec["Wb"])
         dgates = torch.empty((B, S, 4 * hid), device=dev)
         dpre = torch.empty((L - 1, B, S, 4 * hid), device=dev)
         du = torch.empty((B, S, d.PP), device=dev)
         g0 = self.state_placeholder(B)
         df = dfinal or {}
-        keep = []
-
-        def cp(t):
-            keep.append(t.contiguous())
-            return _P(keep[-1])
+        cp = _Keep()
         _lib.check(lib.ntk_ntm_seq_bwd_deep_sim(
-            B, S, d.N, d.Md, d.R, d.Wh, hid, d.shift_range, d.O, L, 1 if self.write_first else 0, self._sim,
-            _P(rec["Wb"]), _P(WaT), ldhT, cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
+            *self._lead(B, S, layers=L), _P(rec["Wb"]), _P(WaT), ldhT, cp(state0["M"]), cp(state0["w"]), cp(state0["controller_state"]),
             _P(rec["gates"]), _P(rec["c"]), _P(rec["u"]), _P(rec["wc"]), _P(rec["wv"]), _P(rec["w"]), _P(rec["M"]),
             _P(rec["lgates"]), _P(rec["lc"]), cp(dlogits),
             _np(df.get("M")), _np(df.get("w")), _np(df.get("read")), _np(df.get("controller_state")),
@@ -876,10 +862,7 @@ class StackedNTMCell(NTMCell):
             "ntk_ntm_seq_bwd_deep")
         BS = B * S
         # weight gradients: the step-wise form's k-major contractions over all recorded rows, into the same layout
-        gemm_tn(dgates.view(BS, 4 * hid), rec["xtop"].view(BS, -1), TP.view("WxT", grad=True), workspace=workspace)
-        gemm_tn(rec["z"].view(BS, d.ldz), dgates.view(BS, 4 * hid), TP.view("Wr", grad=True), workspace=workspace)
-        gemm_tn(rec["h"].view(BS, d.ldh), du.view(BS, d.PP), TP.view("Wa", grad=True), workspace=workspace)
-        TP.view("Wr", grad=True)[:d.RM].zero_()                        # structural zeros (read_prev enters at layer 0)
+        self.top._weight_grads(rec["xtop"], rec["z"], rec["h"], dgates, du, workspace, zero_read_rows=True)
         for k in range(L - 1):
             buf = rec["buf0"] if k == 0 else rec["bufk"][k - 1]
             gemm_tn(dpre[k].view(BS, 4 * hid), buf.view(BS, buf.shape[-1]), self.params.lower(k, grad=True), workspace=workspace)

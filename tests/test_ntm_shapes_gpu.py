@@ -62,6 +62,10 @@ DEEP = [
     Case("deep3_heads15", (64, 4, 8, 7, 64, 1, 2), "deep-1024", "deep-1024", layers=3, B=3, S=5, mode="iid", seed=33),
     Case("deep2_hid280", (64, 12, 2, 2, 280, 1, 2), "deep-1024", "deep-1024", layers=2, wf=1, beta=20, seed=34),  # Tf = Tb = 896
     Case("deep3_hid280", (64, 12, 2, 2, 280, 1, 2), "deep-1024", "deep-1024", layers=3, B=1, S=5, beta=20, seed=35),
+    # the smooth-cosine instantiations above 768 threads, which tests/test_ntm_similarity_gpu.py (deep-768 only) does not launch:
+    # 3 hid = 960 threads in both directions at the smallest memory
+    Case("deep2_hid320_smooth", (64, 8, 1, 1, 320, 1, 2), "deep-1024", "deep-1024", layers=2, S=3, beta=10, gamma=2, seed=62,
+         similarity="smooth_cosine"),
 ]
 CASES = SINGLE + DEEP
 CHAINED = [c for c in CASES if c.name in ("tracker", "hid320", "deep2_tracker")]
