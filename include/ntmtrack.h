@@ -773,6 +773,80 @@ int ntk_frames_crop_batch(const unsigned char* pixels, long long pixels_bytes, c
                           const float* mean, float* out, int n, int C, int resize_h, int resize_w, int crop_h, int crop_w,
                           int flip_x, float extrapolation, void* stream);
 
+/* Baseline JPEG on the device (csrc/jpeg_parse.h, csrc/jpeg_entropy.h, csrc/jpeg_decode.hip): the host walks a file's markers and
+ * removes the byte stuffing, the device decodes the Huffman stream, runs the inverse DCT, upsamples the chroma and converts the
+ * colour with libjpeg's default integer pipeline -- the bits of Pillow's decode -- straight into the `pixels` buffer
+ * ntk_frames_crop_batch reads.
+ *
+ * ntk_jpeg_parse (pure host code, thread-safe, no device-runtime call): file[file_bytes] -> one descriptor of NTK_JPEG_DESC_BYTES
+ * bytes (nullable) and, when stream_dst is given, the scan's entropy-coded bytes with the stuffing removed (FF 00 -> FF), split at
+ * the RSTn markers: segments[k] is the byte offset of segment k in stream_dst and segments[*n_segments] the end, so segment_cap
+ * must be at least *n_segments + 1 and stream_cap at least *stream_bytes (both are reported with stream_dst = NULL, which writes
+ * nothing but the descriptor; file_bytes always suffices for stream_cap).  The descriptor starts with NTK_JPEG_DESC_HDR_WORDS
+ * int32 words (indices below; STREAM_OFF and WS_OFF are int64 at even words), then 4 dequantisation tables uint16 [64] in natural
+ * order, then 4 DC + 4 AC Huffman tables (8-bit lookahead, maxcode / value offset per length, the values).  The caller sets
+ * STREAM_OFF (byte offset of this frame's stream in the batch's stream buffer) and SEG_FIRST (index of its first segment entry).
+ * Returns NTK_OK, NTK_JPEG_HOST_PATH (positive, not an error: the file is not for the device -- not a JPEG, not SOF0, not 8 bit,
+ * 16-bit quantisation tables, several scans or a scan without all components, DNL, 4 components, sampling other than 1x1 / 2x1 /
+ * 2x2 luma over 1x1 chroma, a colour space libjpeg would not read as YCbCr or gray, a side below NTK_JPEG_MIN_SIDE, restart
+ * markers out of sequence or more of them than the MCU grid takes; the descriptor's NCOMP is then 0 and the device skips the
+ * frame) or NTK_ERR_BAD_DATA for a malformed file (reason in ntk_last_error); no byte outside file[0, file_bytes) is read. */
+#define NTK_ERR_BAD_DATA    -5
+#define NTK_JPEG_HOST_PATH   1
+#define NTK_JPEG_MIN_SIDE   16
+#define NTK_JPEG_DESC_BYTES      7936
+#define NTK_JPEG_DESC_HDR_WORDS  32
+#define NTK_JPEG_DESC_H            0
+#define NTK_JPEG_DESC_W            1
+#define NTK_JPEG_DESC_NCOMP        2   /* 1 or 3; 0: not for the device */
+#define NTK_JPEG_DESC_HS           3   /* luma sampling, horizontal (1 or 2) */
+#define NTK_JPEG_DESC_VS           4   /* luma sampling, vertical (1 or 2) */
+#define NTK_JPEG_DESC_RESTART      5   /* restart interval in MCUs, 0 = none */
+#define NTK_JPEG_DESC_MCUS_X       6
+#define NTK_JPEG_DESC_MCUS_Y       7
+#define NTK_JPEG_DESC_NSEG         8
+#define NTK_JPEG_DESC_SEG_FIRST    9
+#define NTK_JPEG_DESC_STREAM_OFF  10   /* int64 */
+#define NTK_JPEG_DESC_WS_OFF      12   /* int64, set by ntk_jpeg_decode_workspace_bytes */
+#define NTK_JPEG_DESC_STREAM_BYTES 14
+#define NTK_JPEG_DESC_TQ          16   /* [3] dequantisation table of each component */
+#define NTK_JPEG_DESC_TD          19   /* [3] DC table */
+#define NTK_JPEG_DESC_TA          22   /* [3] AC table */
+int ntk_jpeg_parse(const unsigned char* file, long long file_bytes, void* desc, unsigned char* stream_dst, long long stream_cap,
+                   int* segments, int segment_cap, long long* stream_bytes, int* n_segments);
+
+/* Workspace of a batch, computed on the HOST from host copies of the descriptors [n] and the frame table [n,7]: per device frame
+ * the int16 coefficients and the uint8 planes of the MCU window its rectangle needs (the rectangle widened by the one chroma
+ * sample per side the triangle upsampling reads, rounded out to MCUs: NTK_JPEG_WS_BYTES_PER_BLOCK per 8x8 block).  Writes each
+ * frame's offset into its descriptor (WS_OFF) -- upload the descriptors after this call -- and returns the total in *bytes.
+ * NTK_ERR_BAD_SHAPE for n outside 1..65535 or a rectangle outside its frame, NTK_ERR_BAD_PTR for a null pointer. */
+#define NTK_JPEG_WS_BYTES_PER_BLOCK 192
+int ntk_jpeg_decode_workspace_bytes(void* descs_host, const long long* frame_table_host, int n, long long* bytes);
+
+/* Decode n frames on `stream`: row i's rectangle (frame_table as in ntk_frames_crop_batch, C = 3) is written as h*w*3 RGB bytes
+ * at byte_offset of `pixels`; a gray file gives Y in all three channels.  All pointers are DEVICE memory: streams (the unstuffed
+ * scans), descs [n] (NTK_JPEG_DESC_BYTES each), segments int32 [n_segments], frame_table int64 [n,7], workspace, status int32 [n].
+ * Three launches: one wave per frame decodes the Huffman stream (lane l takes restart segments l, l+64, ...; only the window's
+ * blocks are stored, and decoding stops after the window's last MCU row), then dequantisation + inverse DCT into planes, then
+ * upsampling + colour into the rectangle.  Plain vector stores only.  The entry allocates nothing: it clears workspace_bytes of
+ * `workspace` and `status` on the stream and launches.  status[i]: NTK_JPEG_STATUS_*; a frame with a non-zero status has
+ * unspecified bytes in its own rectangle and nothing else is touched.  No access rests on trust in the file's bytes:
+ * every stream read is clamped to its segment, every coefficient index is checked, MCU counts come from the descriptor, and a
+ * frame whose descriptor, segment entries, rectangle, pixel bytes or workspace range leave the sizes given here is skipped with
+ * NTK_JPEG_STATUS_BAD_DESC / _WORKSPACE.  A descriptor with NCOMP = 0 is skipped with status 0 (a frame the host decoded).
+ * Errors, before any launch: NTK_ERR_BAD_PTR for a null pointer; NTK_ERR_BAD_SHAPE, the value named in ntk_last_error, for n
+ * outside 1..65535, streams_bytes / n_segments / pixels_bytes < 1, or workspace_bytes < n * NTK_JPEG_WS_BYTES_PER_BLOCK (no frame
+ * needs less than one block). */
+#define NTK_JPEG_STATUS_OK         0
+#define NTK_JPEG_STATUS_BAD_CODE   1   /* a bit pattern no Huffman code matches, or a coefficient index past 63 */
+#define NTK_JPEG_STATUS_TRUNCATED  2   /* a segment ended before its MCUs were decoded */
+#define NTK_JPEG_STATUS_WORKSPACE  3
+#define NTK_JPEG_STATUS_BAD_DESC   4
+#define NTK_JPEG_STATUS_SEGMENTS   5   /* fewer restart segments than the window's MCUs need */
+int ntk_jpeg_decode_batch(const unsigned char* streams, long long streams_bytes, const void* descs, const int* segments,
+                          long long n_segments, const long long* frame_table, unsigned char* pixels, long long pixels_bytes,
+                          void* workspace, long long workspace_bytes, int* status, int n, void* stream);
+
 /* Per-frame box bookkeeping of the online tracker (test_tracker.py:274-329) for B trackers on the device, one thread per
  * tracker; the offsets are the fp32 tanh the single tracker takes and the shifted box is the fp32 sum it forms, everything after that is double precision.  Box state: double [B, NTK_TRACK_STATE_DOUBLES], per tracker
  *   [0] image width w   [1] image height h   [2..5] normalised object box (y1,x1,y2,x2)   [6..9] crop box (y1,x1,y2,x2)

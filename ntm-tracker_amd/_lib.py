@@ -124,6 +124,11 @@ def _sig(lib):
         "ntk_crop_and_resize": (c_int, [P, c_int, c_int, c_int, P] + [ctypes.c_float] * 4 + [P, c_int, c_int, ctypes.c_float, P]),
         "ntk_crop_and_resize_batch": (c_int, [P] + [c_int] * 5 + [P, P, P, P] + [c_int] * 3 + [ctypes.c_float, P]),
         "ntk_frames_crop_batch": (c_int, [P, ctypes.c_longlong, P, P, P, P] + [c_int] * 7 + [ctypes.c_float, P]),
+        "ntk_jpeg_parse": (c_int, [P, ctypes.c_longlong, P, P, ctypes.c_longlong, P, c_int, ctypes.POINTER(ctypes.c_longlong),
+                                   ctypes.POINTER(c_int)]),
+        "ntk_jpeg_decode_workspace_bytes": (c_int, [P, P, c_int, ctypes.POINTER(ctypes.c_longlong)]),
+        "ntk_jpeg_decode_batch": (c_int, [P, ctypes.c_longlong, P, P, ctypes.c_longlong, P, P, ctypes.c_longlong, P, ctypes.c_longlong,
+                                          P, c_int, P]),
         "ntk_track_boxes_update": (c_int, [P, c_int, c_int, ctypes.c_double, ctypes.c_double] + [P] * 6 + [P]),
         "ntk_track_overlap_scores": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
         "ntk_track_restart_boxes": (c_int, [P, P, P, c_int] + [ctypes.c_double] * 3 + [c_int] + [P] * 8 + [P]),

@@ -336,6 +336,11 @@ class Staging(object):
         self.table = self._new((0, FRAME_TABLE_COLS), torch.int64)
         self.boxes = self._new((0, 4), torch.float32)
         self.labels = self._new((0, 66), torch.float32)
+        # decode="device": the unstuffed scans, one descriptor per frame and the restart-segment table (ntk_jpeg_parse writes them)
+        self.streams = self._new((0,), torch.uint8)
+        self.descs = self._new((0, JPEG_DESC_BYTES), torch.uint8)
+        self.segments = self._new((0,), torch.int32)
+        self._device = {}               # device buffers of this set, grown and reused: no allocator call in the steady state
 
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, pin_memory=self.pin)
@@ -352,6 +357,25 @@ class Staging(object):
             self.boxes = self._new((n, 4), torch.float32)
             self.labels = self._new((n, 66), torch.float32)
 
+    def fits_jpeg(self, stream_bytes, n, n_segments):
+        return self.streams.numel() >= stream_bytes and self.descs.shape[0] >= n and self.segments.numel() >= n_segments
+
+    def ensure_jpeg(self, stream_bytes, n, n_segments):
+        if self.streams.numel() < stream_bytes:
+            self.streams = self._new((stream_bytes + stream_bytes // 4,), torch.uint8)
+        if self.descs.shape[0] < n:
+            self.descs = self._new((n, JPEG_DESC_BYTES), torch.uint8)
+        if self.segments.numel() < n_segments:
+            self.segments = self._new((n_segments + n_segments // 4,), torch.int32)
+
+    def device_buffer(self, dev, name, numel, dtype):
+        """The first `numel` elements of this set's device buffer `name` (grown with a quarter of headroom when too small)."""
+        key = (str(dev), name)
+        buf = self._device.get(key)
+        if buf is None or buf.numel() < numel or buf.dtype != dtype:
+            buf = self._device[key] = torch.empty((numel + numel // 4,), dtype=dtype, device=dev)
+        return buf[:numel]
+
 
 class PackedFrames(object):
     """pack_frames' result: views of the first `nbytes` bytes / n rows of a Staging set."""
@@ -360,6 +384,8 @@ class PackedFrames(object):
         self.staging, self.nbytes, self.n, self.channels = staging, nbytes, n, channels
         self.resize_to, self.crop = tuple(resize_to), tuple(crop)
         self.pixels, self.table, self.boxes = staging.pixels[:nbytes], staging.table[:n], staging.boxes[:n]
+        self.jpeg = None                # JpegPart when frames of this batch are decoded on the device (pack_jpeg_frames)
+        self.status = None              # int32 [n] on the device after frames_crop_batch of such a batch
 
 
 def pack_frames(images, cropboxes, resize_to=RESIZE_TO, crop=CROP, margin=2, pack="rect", staging=None, pad=0, grow=True):
@@ -417,8 +443,11 @@ def frames_crop_batch(packed, device="cuda", mean=None, flip_x=False, extrapolat
     L, P = _lib.lib(), _lib.ptr
     dev = torch.device(device)
     n, C, (ch, cw) = packed.n, packed.channels, packed.crop
-    pix = packed.pixels.to(dev, non_blocking=True)
-    table = packed.table.to(dev, non_blocking=True)
+    if packed.jpeg is not None:
+        pix, table, packed.status = decode_packed(packed, dev)
+    else:
+        pix = packed.pixels.to(dev, non_blocking=True)
+        table = packed.table.to(dev, non_blocking=True)
     boxes = packed.boxes.to(dev, non_blocking=True)
     if out is None:
         out = torch.empty((n, ch, cw, C), device=dev)
@@ -451,12 +480,31 @@ class StagedBatch(object):
         self.names, self.packed = names, packed
         self.labels = packed.staging.labels[:packed.n]
         self.uploaded = None            # event after the uploads (set by upload_staged on a device)
+        self.status = None              # decode="device": int32 [n] on the device after upload_staged, one NTK_JPEG_STATUS_* per frame
+
+    def check_status(self):
+        """decode="device": read the decoder's status from the device (this SYNCHRONISES with the stream that decoded) and raise
+        NtkError naming the first frame's file whose status is not zero.  Nothing to do for a host-decoded batch."""
+        if self.status is None:
+            return
+        status = self.status.cpu().numpy()
+        bad = np.nonzero(status)[0]
+        if bad.size:
+            i = int(bad[0])
+            raise _lib.NtkError("device JPEG decode of %s (frame %d of the batch) failed: %s (status %d)"
+                                % (self.packed.jpeg.paths[i], i, JPEG_STATUS.get(int(status[i]), "unknown"), int(status[i])))
 
 
-def stage_batch(frame_names_nosuffix, image_root=None, pool=None, pack="rect", staging=None, grow=True):
+def stage_batch(frame_names_nosuffix, image_root=None, pool=None, pack="rect", staging=None, grow=True, decode="host"):
     """Host half of get_input_batch: read and decode the records and images (on `pool`'s threads when given), pack them.
-    No device-runtime call is made when grow=False."""
+    No device-runtime call is made when grow=False.  decode="device": a baseline JPEG is not decoded here -- its headers are parsed
+    and its scan is copied, unstuffed, into the staging set (ntk_jpeg_parse; ctypes releases the GIL), for ntk_jpeg_decode_batch to
+    decode in upload_staged; any other file (PNG, progressive JPEG, ...) is decoded by Pillow as with decode="host" and its
+    rectangle packed into the same set."""
+    _check_decode(decode)
     names = list(frame_names_nosuffix)
+    if decode == "device":
+        return _stage_batch_device(names, image_root, pool, pack, staging, grow)
     if pool is not None:
         loaded = list(pool.map(lambda nm: _load_frame(nm, image_root), names))
     else:
@@ -473,6 +521,7 @@ def upload_staged(staged, device="cuda", reverse_image=False):
     """Device half of get_input_batch, on the current stream: -> get_input's four tensors."""
     dev = torch.device(device)
     batch_img = frames_crop_batch(staged.packed, dev, mean=_vgg_mean(dev), flip_x=reverse_image)
+    staged.status = staged.packed.status
     lab = staged.labels.to(dev, non_blocking=True)
     if dev.type == "cuda":
         staged.uploaded = torch.cuda.Event()
@@ -485,22 +534,26 @@ def upload_staged(staged, device="cuda", reverse_image=False):
 
 
 def get_input_batch(frame_names_nosuffix, device="cuda", reverse_image=False, image_root=None, workers=None, pack="rect",
-                    staging=None):
+                    staging=None, decode="host"):
     """get_input's contract -- (batch_img [n,224,224,3], batch_gt [n,8,8], y_offsets [n], x_offsets [n]), x_offsets negated and
     the crops flipped when reverse_image is set -- and its bits, in one launch: the records and images are read and decoded by
     `workers` threads (default_workers() when None; threads, not processes, and they make no device-runtime call), the uint8
     pixels each crop can touch are packed into pinned memory (`staging`, reused by the caller across batches), and after three
     asynchronous uploads ntk_frames_crop_batch resizes, subtracts the mean, crops and flips on the current stream.  A caller
     that reuses `staging` must not call again before the previous call's uploads have run (synchronise the stream, or use
-    InputPrefetcher, which alternates two sets)."""
+    InputPrefetcher, which alternates two sets).  decode="device": baseline JPEG files are decoded by ntk_jpeg_decode_batch on the
+    current stream instead of by the threads (same bits; stage_batch); the decoder's status is read before returning -- one
+    synchronisation -- and a frame it could not decode raises NtkError naming the file."""
     from concurrent.futures import ThreadPoolExecutor
     workers = default_workers() if workers is None else int(workers)
     if workers > 1 and len(frame_names_nosuffix) > 1:
         with ThreadPoolExecutor(max_workers=workers) as pool:
-            staged = stage_batch(frame_names_nosuffix, image_root, pool, pack, staging)
+            staged = stage_batch(frame_names_nosuffix, image_root, pool, pack, staging, decode=decode)
     else:
-        staged = stage_batch(frame_names_nosuffix, image_root, None, pack, staging)
-    return upload_staged(staged, device, reverse_image)
+        staged = stage_batch(frame_names_nosuffix, image_root, None, pack, staging, decode=decode)
+    result = upload_staged(staged, device, reverse_image)
+    staged.check_status()
+    return result
 
 
 class InputPrefetcher(object):
@@ -513,12 +566,13 @@ class InputPrefetcher(object):
     would have returned batch i.  close() stops and joins the threads; it is also called by __del__ and on leaving a
     ``with`` block.  `stage`: the staging function, stage(names, staging) -> StagedBatch (default: stage_batch)."""
 
-    def __init__(self, batches, depth=2, image_root=None, workers=None, pack="rect", stage=None):
+    def __init__(self, batches, depth=2, image_root=None, workers=None, pack="rect", stage=None, decode="host"):
         import queue
         import threading
         from concurrent.futures import ThreadPoolExecutor
         if depth < 1:
             raise ValueError("depth must be at least 1, not %d" % depth)
+        _check_decode(decode)
         self._batches = batches         # any iterable of name lists, consumed as the run goes (a generator: nothing is built ahead)
         self._sets = [Staging() for _ in range(depth)]
         self._free, self._ready = queue.Queue(), queue.Queue()
@@ -530,7 +584,7 @@ class InputPrefetcher(object):
         workers = default_workers() if workers is None else int(workers)
         self._pool = ThreadPoolExecutor(max_workers=workers) if workers > 1 else None
         if stage is None:
-            stage = lambda names, staging: stage_batch(names, image_root, self._pool, pack, staging, grow=False)
+            stage = lambda names, staging: stage_batch(names, image_root, self._pool, pack, staging, grow=False, decode=decode)
         self._stage = stage
         self._thread = threading.Thread(target=self._produce, name="ntmtrack-input-prefetch", daemon=True)
         self._thread.start()
@@ -608,6 +662,12 @@ class InputPrefetcher(object):
             for a in ("table", "boxes", "labels"):
                 getattr(st, a)[:packed.n].copy_(getattr(old, a)[:packed.n])
             staged.packed = PackedFrames(st, packed.nbytes, packed.n, packed.channels, packed.resize_to, packed.crop)
+            if packed.jpeg is not None:
+                j = staged.packed.jpeg = packed.jpeg
+                st.ensure_jpeg(j.stream_bytes, packed.n, j.n_segments)
+                st.streams[:j.stream_bytes].copy_(old.streams[:j.stream_bytes])
+                st.descs[:packed.n].copy_(old.descs[:packed.n])
+                st.segments[:j.n_segments].copy_(old.segments[:j.n_segments])
             staged.labels = st.labels[:packed.n]
         return staged
 
@@ -632,3 +692,251 @@ class InputPrefetcher(object):
             self.close()
         except Exception:
             pass
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# decode="device": baseline JPEG decoded by HIP kernels into the pixel buffer ntk_frames_crop_batch reads (csrc/jpeg_decode.hip).
+# The host parses the headers and removes the byte stuffing (ntk_jpeg_parse); everything else runs on the device, in libjpeg's
+# default integer arithmetic: the bytes are Pillow's.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+DECODE_MODES = ("host", "device")
+JPEG_HOST_PATH = 1              # NTK_JPEG_HOST_PATH: the file is not for the device decoder (not an error)
+JPEG_MIN_SIDE = 16
+JPEG_DESC_BYTES = 7936
+JPEG_DESC_HDR_WORDS = 32
+JPEG_DESC = {"H": 0, "W": 1, "NCOMP": 2, "HS": 3, "VS": 4, "RESTART": 5, "MCUS_X": 6, "MCUS_Y": 7, "NSEG": 8, "SEG_FIRST": 9,
+             "STREAM_OFF": 10, "WS_OFF": 12, "STREAM_BYTES": 14, "TQ": 16, "TD": 19, "TA": 22}     # NTK_JPEG_DESC_*
+JPEG_WS_BYTES_PER_BLOCK = 192
+JPEG_STATUS = {0: "ok", 1: "a bit pattern that no Huffman code matches", 2: "the scan ends before the image does",
+               3: "the workspace is too small", 4: "a descriptor or frame table row outside the buffers",
+               5: "fewer restart segments than the image needs"}                                # NTK_JPEG_STATUS_*
+
+
+def _check_decode(decode):
+    if decode not in DECODE_MODES:
+        raise ValueError("decode must be 'host' or 'device', not %r" % (decode,))
+
+
+def _np_ptr(a, byte_offset=0):
+    import ctypes
+    return ctypes.c_void_p(a.ctypes.data + byte_offset)
+
+
+def _jpeg_parse_raw(data, desc, dst, dst_offset, dst_cap, seg, seg_offset, seg_cap, what):
+    """ntk_jpeg_parse on the bytes `data`: desc uint8 [JPEG_DESC_BYTES] (NumPy), dst uint8 / seg int32 NumPy arrays or None.
+    -> (rc, stream_bytes, n_segments); a malformed file raises NtkError naming `what`."""
+    import ctypes
+    sbytes, nseg = ctypes.c_longlong(0), ctypes.c_int(0)
+    rc = _lib.lib().ntk_jpeg_parse(data, len(data), _np_ptr(desc), None if dst is None else _np_ptr(dst, dst_offset), dst_cap,
+                                   None if seg is None else _np_ptr(seg, 4 * seg_offset), seg_cap, ctypes.byref(sbytes),
+                                   ctypes.byref(nseg))
+    if rc < 0:
+        msg = _lib.lib().ntk_last_error()
+        raise _lib.NtkError("%s: %s (%d)" % (what, msg.decode() if msg else "", rc))
+    return rc, sbytes.value, nseg.value
+
+
+class ParsedJpeg(object):
+    """parse_jpeg's result: the descriptor (uint8 [JPEG_DESC_BYTES]; `hdr` its int32 header words, JPEG_DESC names them), the
+    unstuffed scan (`stream`, uint8) and the restart-segment offsets into it (`segments`, int32 [n_segments + 1])."""
+
+    def __init__(self, desc, stream, segments):
+        self.desc, self.stream, self.segments = desc, stream, segments
+        self.hdr = desc[:4 * JPEG_DESC_HDR_WORDS].view(np.int32)
+        h = self.hdr
+        self.height, self.width, self.components = int(h[JPEG_DESC["H"]]), int(h[JPEG_DESC["W"]]), int(h[JPEG_DESC["NCOMP"]])
+        self.sampling = (int(h[JPEG_DESC["HS"]]), int(h[JPEG_DESC["VS"]]))
+        self.restart_interval = int(h[JPEG_DESC["RESTART"]])
+        self.mcus = (int(h[JPEG_DESC["MCUS_Y"]]), int(h[JPEG_DESC["MCUS_X"]]))
+        self.n_segments, self.stream_bytes = int(h[JPEG_DESC["NSEG"]]), int(h[JPEG_DESC["STREAM_BYTES"]])
+
+
+def _read_bytes(bytes_or_path):
+    if isinstance(bytes_or_path, (bytes, bytearray, memoryview)):
+        return bytes(bytes_or_path), "<%d bytes>" % len(bytes_or_path)
+    with open(bytes_or_path, "rb") as f:
+        return f.read(), str(bytes_or_path)
+
+
+def parse_jpeg(bytes_or_path, dst=None):
+    """Parse one file for the device decoder (ntk_jpeg_parse; pure host code) -> ParsedJpeg, or None for a file that is not for
+    the device (not a JPEG, progressive, 12 bit, CMYK, ...: the host path).  A malformed JPEG raises NtkError.  `dst`: a uint8
+    NumPy array to receive the unstuffed scan (at least the file's length always suffices); made when None."""
+    data, what = _read_bytes(bytes_or_path)
+    desc = np.zeros(JPEG_DESC_BYTES, np.uint8)
+    rc, sbytes, nseg = _jpeg_parse_raw(data, desc, None, 0, 0, None, 0, 0, what)
+    if rc == JPEG_HOST_PATH:
+        return None
+    if dst is None:
+        dst = np.empty(max(sbytes, 1), np.uint8)
+    elif dst.dtype != np.uint8 or dst.ndim != 1 or not dst.flags.c_contiguous or dst.size < sbytes:
+        raise ValueError("parse_jpeg: dst must be a contiguous uint8 vector of at least %d bytes" % sbytes)
+    seg = np.zeros(nseg + 1, np.int32)
+    _jpeg_parse_raw(data, desc, dst, 0, dst.size, seg, 0, nseg + 1, what)
+    return ParsedJpeg(desc, dst[:sbytes], seg)
+
+
+class JpegPart(object):
+    """What a PackedFrames holds for the device decoder: sizes of the filled parts of the staging set's streams / segments, the
+    workspace the batch needs, which frames the device decodes, the byte ranges of `pixels` the host filled, and the files."""
+
+    def __init__(self, stream_bytes, n_segments, workspace_bytes, on_device, host_ranges, paths):
+        self.stream_bytes, self.n_segments, self.workspace_bytes = stream_bytes, n_segments, workspace_bytes
+        self.on_device, self.host_ranges, self.paths = on_device, host_ranges, paths
+
+
+def _probe_frame(data, what):
+    """File bytes -> dict: for a device frame `data`, the frame's size and the sizes of its stream and segment table; for any
+    other file `image`, decoded by Pillow (uint8 [H,W,3])."""
+    desc = np.zeros(JPEG_DESC_BYTES, np.uint8)
+    rc, sbytes, nseg = _jpeg_parse_raw(data, desc, None, 0, 0, None, 0, 0, what)
+    if rc == JPEG_HOST_PATH:
+        import io
+        from PIL import Image
+        with Image.open(io.BytesIO(data)) as im:
+            img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        return {"data": None, "image": img, "size": img.shape[:2], "what": what}
+    hdr = desc[:4 * JPEG_DESC_HDR_WORDS].view(np.int32)
+    return {"data": data, "image": None, "size": (int(hdr[JPEG_DESC["H"]]), int(hdr[JPEG_DESC["W"]])), "stream_bytes": sbytes,
+            "n_segments": nseg, "what": what}
+
+
+def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, staging=None, grow=True, pool=None):
+    """_probe_frame results and one rectangle (y0, x0, h, w) per frame -> PackedFrames whose `jpeg` part is filled: the frame
+    table and boxes as pack_frames writes them; per device frame its descriptor, unstuffed scan and segment offsets in the staging
+    set (written by ntk_jpeg_parse on `pool`'s threads: the one copy the file's bytes get); per other frame its rectangle's
+    pixels.  The workspace is sized and each frame's share of it written into its descriptor (ntk_jpeg_decode_workspace_bytes).
+    Staging rules as in pack_frames (`grow`)."""
+    import ctypes
+    n = len(probed)
+    if n < 1 or n > MAX_FRAMES_PER_LAUNCH or len(rects) != n:
+        raise ValueError("pack_jpeg_frames: %d frames (1..%d), %d rectangles" % (n, MAX_FRAMES_PER_LAUNCH, len(rects)))
+    rows, off, soff, goff, place = [], 0, 0, 0, []
+    for pr, (y0, x0, h, w) in zip(probed, rects):
+        H, W = pr["size"]
+        rows.append((off, H, W, y0, x0, h, w))
+        off += h * w * 3
+        place.append((soff, goff))
+        if pr["data"] is not None:
+            soff += (len(pr["data"]) + 15) // 16 * 16           # the unstuffed scan is shorter than the file
+            goff += pr["n_segments"] + 1
+    nbytes, sbytes, nsegs = off, max(soff, 16), max(goff, 2)
+    if staging is None:
+        staging = Staging()
+    if not (staging.fits(nbytes, n) and staging.fits_jpeg(sbytes, n, nsegs)):
+        if not grow:
+            staging = Staging(pin=False)
+        staging.ensure(nbytes, n)
+        staging.ensure_jpeg(sbytes, n, nsegs)
+    table = staging.table.numpy()[:n]
+    table[:] = np.asarray(rows, dtype=np.int64)
+    check_frame_table(table, nbytes, 3)
+    if boxes is not None:
+        staging.boxes.numpy()[:n] = np.asarray(boxes, dtype=np.float64).reshape(n, 4).astype(np.float32)
+    buf, streams, descs, segs = staging.pixels.numpy(), staging.streams.numpy(), staging.descs.numpy(), staging.segments.numpy()
+
+    def fill(i):
+        pr, (o, _H, _W, y0, x0, h, w), (so, go) = probed[i], rows[i], place[i]
+        if pr["data"] is None:
+            descs[i, :4 * JPEG_DESC_HDR_WORDS] = 0              # NCOMP = 0: the device skips the frame
+            buf[o:o + h * w * 3].reshape(h, w, 3)[...] = pr["image"][y0:y0 + h, x0:x0 + w]
+            return
+        _jpeg_parse_raw(pr["data"], descs[i], streams, so, len(pr["data"]), segs, go, pr["n_segments"] + 1, pr["what"])
+        hdr = descs[i, :4 * JPEG_DESC_HDR_WORDS].view(np.int32)
+        hdr[JPEG_DESC["SEG_FIRST"]] = go
+        hdr[JPEG_DESC["STREAM_OFF"]:JPEG_DESC["STREAM_OFF"] + 2].view(np.int64)[0] = so
+
+    list(pool.map(fill, range(n)) if pool is not None else map(fill, range(n)))
+    ws = ctypes.c_longlong(0)
+    _lib.check(_lib.lib().ntk_jpeg_decode_workspace_bytes(_np_ptr(descs), _np_ptr(table), n, ctypes.byref(ws)),
+               "ntk_jpeg_decode_workspace_bytes")
+    packed = PackedFrames(staging, nbytes, n, 3, resize_to, crop)
+    on_device = [pr["data"] is not None for pr in probed]
+    packed.jpeg = JpegPart(sbytes, nsegs, ws.value, on_device,
+                           [(r[0], r[0] + r[5] * r[6] * 3) for r, d in zip(rows, on_device) if not d], [pr["what"] for pr in probed])
+    return packed
+
+
+def decode_packed(packed, device):
+    """Device half of the JPEG path, on the current stream: upload the streams, descriptors, segment offsets and frame table of a
+    PackedFrames with a `jpeg` part, and the pixel ranges the host decoded, into the staging set's device buffers (grown and
+    reused: no allocator call in the steady state but the status vector's), then ONE ntk_jpeg_decode_batch call.
+    -> (pixels uint8 [nbytes], frame table int64 [n,7], status int32 [n]), all on the device."""
+    L, P = _lib.lib(), _lib.ptr
+    dev = torch.device(device)
+    st, j, n = packed.staging, packed.jpeg, packed.n
+    pix = st.device_buffer(dev, "pixels", packed.nbytes, torch.uint8)
+    for o, e in j.host_ranges:
+        pix[o:e].copy_(st.pixels[o:e], non_blocking=True)
+    table = st.device_buffer(dev, "table", n * FRAME_TABLE_COLS, torch.int64).view(n, FRAME_TABLE_COLS)
+    table.copy_(packed.table, non_blocking=True)
+    status = torch.zeros((n,), dtype=torch.int32, device=dev)   # outlives the staging set's reuse: read at a logged step
+    if not any(j.on_device):
+        return pix, table, status
+    streams = st.device_buffer(dev, "streams", j.stream_bytes, torch.uint8)
+    streams.copy_(st.streams[:j.stream_bytes], non_blocking=True)
+    descs = st.device_buffer(dev, "descs", n * JPEG_DESC_BYTES, torch.uint8)
+    descs.copy_(st.descs[:n].view(-1), non_blocking=True)
+    segs = st.device_buffer(dev, "segments", j.n_segments, torch.int32)
+    segs.copy_(st.segments[:j.n_segments], non_blocking=True)
+    ws = st.device_buffer(dev, "workspace", j.workspace_bytes, torch.uint8)
+    _lib.check(L.ntk_jpeg_decode_batch(P(streams), j.stream_bytes, P(descs), P(segs), j.n_segments, P(table), P(pix), packed.nbytes,
+                                       P(ws), j.workspace_bytes, P(status), n, _lib.stream()), "ntk_jpeg_decode_batch")
+    return pix, table, status
+
+
+class DecodedJpegs(object):
+    """decode_jpeg_batch's result: `pixels` uint8 on the device, the frames' rectangles packed one after another as h*w*3 RGB
+    bytes; `table` the int64 [n,7] frame table (NumPy; `table_device` the same on the device: what ntk_frames_crop_batch takes);
+    `status` int32 [n] on the device (0: decoded; JPEG_STATUS names the others); `on_device[i]`: the device decoded frame i
+    (False: Pillow did -- not a baseline JPEG the device takes).  image(i) -> frame i's rectangle as uint8 [h,w,3] (NumPy)."""
+
+    def __init__(self, packed, pixels, table_device, status):
+        self.packed, self.pixels, self.table_device, self.status = packed, pixels, table_device, status
+        self.table = packed.table.numpy().copy()
+        self.on_device = list(packed.jpeg.on_device)
+
+    def image(self, i):
+        off, _H, _W, _y0, _x0, h, w = [int(v) for v in self.table[i]]
+        return self.pixels[off:off + h * w * 3].cpu().numpy().reshape(h, w, 3)
+
+
+def decode_jpeg_batch(streams, rects=None, device="cuda", staging=None):
+    """Decode a batch of image files on the device, on the current stream: `streams` a list of file contents (bytes) or paths;
+    `rects` one (y0, x0, h, w) per file, the part of the image wanted (None: all of it, for that file or for all).  Baseline JPEG
+    files (8 bit, gray or YCbCr with 4:4:4 / 4:2:2 / 4:2:0 sampling, one interleaved scan, sides of 16 pixels or more) are decoded
+    by ntk_jpeg_decode_batch to the bytes Pillow gives; any other file is decoded by Pillow here and uploaded.  Nothing is
+    synchronised: read `status` (or call image()) after the stream has run.  -> DecodedJpegs."""
+    probed = [_probe_frame(*_read_bytes(s)) for s in streams]
+    if rects is None:
+        rects = [None] * len(probed)
+    rects = [(0, 0) + tuple(pr["size"]) if r is None else tuple(int(v) for v in r) for pr, r in zip(probed, rects)]
+    packed = pack_jpeg_frames(probed, rects, staging=staging)
+    pix, table, status = decode_packed(packed, device)
+    return DecodedJpegs(packed, pix, table, status)
+
+
+def _load_frame_device(name, image_root):
+    rec = load_frame_record(name)
+    path = rec["image_path"] if image_root is None else os.path.join(image_root, rec["image_path"])
+    with open(path, "rb") as f:
+        data = f.read()
+    return rec, _probe_frame(data, path)
+
+
+def _stage_batch_device(names, image_root, pool, pack, staging, grow):
+    """stage_batch for decode="device"."""
+    if pack not in ("rect", "full"):
+        raise ValueError("pack must be 'rect' or 'full', not %r" % (pack,))
+    load = lambda nm: _load_frame_device(nm, image_root)
+    loaded = list(pool.map(load, names)) if pool is not None else [load(nm) for nm in names]
+    probed = [pr for _r, pr in loaded]
+    boxes = [r["cropbox"] for r, _p in loaded]
+    rects = [crop_source_rect(pr["size"], box) if pack == "rect" else (0, 0) + tuple(pr["size"]) for pr, box in zip(probed, boxes)]
+    packed = pack_jpeg_frames(probed, rects, boxes, staging=staging, grow=grow, pool=pool)
+    lab = packed.staging.labels.numpy()[:len(names)]
+    for i, (rec, _pr) in enumerate(loaded):
+        lab[i, :64] = rec["gt"].reshape(-1)
+        lab[i, 64], lab[i, 65] = rec["y_offset"], rec["x_offset"]
+    return StagedBatch(names, packed)

@@ -100,7 +100,7 @@ def tracker_inputs(tracker, batch_img, batch_gt, y_off, x_off):
 
 
 def fit(tracker, train_seqs, val_seqs, *, num_epochs=1, validation_interval=100, validation_batch=1, log_interval=10, ckpt_dir,
-        reverse_image=False, image_root=None, seed=0, on_event=None, prefetch=True, workers=None):
+        reverse_image=False, image_root=None, seed=0, on_event=None, prefetch=True, workers=None, decode="host"):
     """Train `tracker` (NTMOffsetTracker or DNCOffsetTracker, built with the VGG weights) on format-(B) sequences as
     data.get_valid_sequences returns them, in Schedule's order; each process of a data-parallel run calls it alike.
     Per step: the next training batch's input is taken from the prefetcher, uploaded and cropped in one launch, and its trunk
@@ -110,7 +110,10 @@ def fit(tracker, train_seqs, val_seqs, *, num_epochs=1, validation_interval=100,
     step % log_interval == 0 and nowhere else: no other synchronisation.  `on_event`, when given, is called with
     ("validate", step, loss), ("checkpoint", step, path) and ("train", step, loss) -- loss None at a step that is not logged.
     prefetch=False decodes on the calling thread instead (measurements).  To resume, load_checkpoint() first: the checkpoint
-    names go on from the tracker's global_step.  -> FitResult."""
+    names go on from the tracker's global_step.  decode="device": baseline JPEG frames are decoded by ntk_jpeg_decode_batch on
+    the device instead of by the prefetcher's threads (data.stage_batch; same bits, so the same losses and parameters).  The
+    decoder's status of every batch since the last look is read where the loop synchronises anyway -- after check_step() at a
+    logged step and at a validation -- and a frame it could not decode raises NtkError naming the file.  -> FitResult."""
     rank, world = parallel.world()
     sched = Schedule(len(train_seqs), len(val_seqs), tracker.B * world, seed, validation_interval, validation_batch, num_epochs,
                      rank, world)
@@ -130,14 +133,21 @@ def fit(tracker, train_seqs, val_seqs, *, num_epochs=1, validation_interval=100,
     dev = tracker.device
     s_vgg, s_ntm = tracker._streams()
     if prefetch:
-        source = data.InputPrefetcher(batches(), depth=2, image_root=image_root, workers=workers)
+        source = data.InputPrefetcher(batches(), depth=2, image_root=image_root, workers=workers, decode=decode)
     else:
         one = data.Staging()
-        source = (data.stage_batch(names, image_root, None, "rect", one) for names in batches())
+        source = (data.stage_batch(names, image_root, None, "rect", one, decode=decode) for names in batches())
+    unchecked = []                      # decode="device": batches whose decoder status has not been read yet
+
+    def check_decoded():
+        while unchecked:
+            unchecked.pop(0).check_status()
 
     def next_inputs():
         staged = next(source)
         frames, gts0, offsets = tracker_inputs(tracker, *data.upload_staged(staged, dev, reverse_image))
+        if staged.status is not None:
+            unchecked.append(staged)
         if not prefetch:
             staged.uploaded.synchronize()           # the one staging set is packed again by the next call
         return frames, gts0, offsets
@@ -156,6 +166,7 @@ def fit(tracker, train_seqs, val_seqs, *, num_epochs=1, validation_interval=100,
             if kind == "validate":
                 losses = [tracker.eval_loss(*next_inputs()) for _b in payload]
                 tracker.check_step()
+                check_decoded()
                 val = float(torch.cat(losses).double().mean().item()) if losses else None
                 res.validation.append((step, val))
                 emit(("validate", step, val))
@@ -171,6 +182,7 @@ def fit(tracker, train_seqs, val_seqs, *, num_epochs=1, validation_interval=100,
             logged = None
             if step % log_interval == 0:
                 tracker.check_step()
+                check_decoded()
                 logged = float(loss.item())
                 res.training.append((step, logged))
             emit(("train", step, logged))

@@ -36,9 +36,14 @@ base = rng.integers(0, 256, size=(90, 160, 3), dtype=np.uint8)
 nseq = N // T
 seqs = []
 hm = discrete_gauss((.5, .5), (8, 8), 1.0)
+ARMS = os.environ.get("ARMS", "all")      # "device": only the device-decode arms (profiles/train_input_device_decode.txt)
+SAVE_KW = {}                              # extra Image.save keywords of the frame set being written
+SET_TAG = [""]
+
+
 def write_seq(s):
     rng = np.random.default_rng(100 + s)
-    d = os.path.join(tmp, "train_seq%03d_0" % s)
+    d = os.path.join(tmp, "train_seq%03d%s_0" % (s, SET_TAG[0]))
     os.makedirs(d)
     stems = []
     for t in range(T):
@@ -46,7 +51,7 @@ def write_seq(s):
         img = np.asarray(Image.fromarray(np.roll(base, (s * 7 + t, s * 3 + 2 * t), axis=(0, 1))).resize((1280, 720), Image.BILINEAR)).astype(np.int16)
         img = np.clip(img + rng.integers(-12, 13, size=img.shape), 0, 255).astype(np.uint8)
         jpg = os.path.join(d, "%06d.JPEG" % t)
-        Image.fromarray(img).save(jpg, quality=90)
+        Image.fromarray(img).save(jpg, quality=90, **SAVE_KW)
         cy, cx, h, w = 0.4 + 0.01 * t, 0.45 + 0.005 * t, 0.3, 0.2
         k = 8.0 / 6.0          # cropbox_grid / bbox_grid of preprocess.py: the crop is the object scaled about its centre
         y1, x1, y2, x2 = cy - h * k / 2, cx - w * k / 2, cy + h * k / 2, cx + w * k / 2
@@ -66,6 +71,96 @@ say("wrote %d JPEG frames 1280x720 in %.1f s (mean %.0f kB)" % (nseq * T, time.p
 names = [os.path.join(d, st) for d, stems in seqs for st in stems]
 n = len(names)
 say("workers = %d (affinity %d)" % (data.default_workers(), len(os.sched_getaffinity(0))))
+
+# ---- a second frame set: the same images written with a restart marker after every MCU row
+SAVE_KW["restart_marker_rows"] = 1
+SET_TAG[0] = "r"
+with ThreadPoolExecutor(max_workers=data.default_workers()) as wp:
+    seqs_rst = list(wp.map(write_seq, range(nseq)))
+names_rst = [os.path.join(d, st) for d, stems in seqs_rst for st in stems]
+
+
+def device_decode_arm(tag, names):
+    """decode="device" per batch: host parse + unstuff on the decoder threads, bytes uploaded, the decode call (entropy + inverse
+    DCT + colour kernels) and the crop kernel by event pairs, the whole call, against the host-decode call on the same frames."""
+    pool = ThreadPoolExecutor(max_workers=data.default_workers())
+    st = data.Staging()
+    stage_times = []
+    for rep in range(3):
+        t0 = time.perf_counter()
+        staged = data.stage_batch(names, None, pool, "rect", st, decode="device")
+        stage_times.append(time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    raw = list(pool.map(lambda nm: open(data.load_frame_record(nm)["image_path"], "rb").read(), names))
+    t_read = time.perf_counter() - t0
+    packed, j = staged.packed, staged.packed.jpeg
+    up_bytes = j.stream_bytes + packed.n * data.JPEG_DESC_BYTES + 4 * j.n_segments + packed.table.numel() * 8
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    decs, crops = [], []
+    mean = data._vgg_mean(dev)
+    out = torch.empty((packed.n, 224, 224, 3), device=dev)
+    L = data._lib.lib()
+    for rep in range(13):
+        e0, e1, e2 = ev(), ev(), ev()
+        e0.record()
+        pix, tab, status = data.decode_packed(packed, dev)                  # uploads + the three decode launches
+        e1.record()
+        box = packed.boxes.to(dev, non_blocking=True)
+        data._lib.check(L.ntk_frames_crop_batch(data._lib.ptr(pix), packed.nbytes, data._lib.ptr(tab), data._lib.ptr(box), data._lib.ptr(mean),
+                                                data._lib.ptr(out), packed.n, 3, 720, 1280, 224, 224, 0, 0.0, data._lib.stream()), "crop")
+        e2.record()
+        torch.cuda.synchronize()
+        if rep >= 3:
+            decs.append(e0.elapsed_time(e1))
+            crops.append(e1.elapsed_time(e2))
+    assert not status.cpu().numpy().any()
+    walls = {}
+    for decode in ("host", "device", "host", "device"):
+        t0 = time.perf_counter()
+        got = data.get_input_batch(names, device=dev, staging=st, decode=decode)
+        torch.cuda.synchronize()
+        walls.setdefault(decode, []).append(time.perf_counter() - t0)
+        if decode == "host":
+            ref = got[0]
+    same = bool(torch.equal(got[0], ref)) and bool(torch.equal(out, ref))
+    say("device decode [%s]: %d frames, %d on the device; restart segments per frame %.1f; file read %.3f s; stage (read + parse + unstuff, "
+        "%d threads) %.3f s (median of 3; first %.3f); uploaded %.1f MB (streams %.1f MB) against %.1f MB of host-decoded rectangles; "
+        "workspace %.1f MB; upload + decode kernels %.3f ms (event pairs, median of 10 after 3 warm-ups; min %.3f max %.3f); crop kernel "
+        "%.3f ms; whole get_input_batch call: device %.3f s, host %.3f s (second of two calls each, alternating); bits equal: %s"
+        % (tag, packed.n, sum(j.on_device), (j.n_segments - packed.n) / packed.n, t_read, data.default_workers(), median(stage_times),
+           stage_times[0], up_bytes / 1e6, j.stream_bytes / 1e6, packed.nbytes / 1e6, j.workspace_bytes / 1e6, median(decs), min(decs),
+           max(decs), median(crops), walls["device"][-1], walls["host"][-1], same))
+    pool.shutdown()
+
+
+device_decode_arm("no restart markers", names)
+device_decode_arm("restart_marker_rows=1", names_rst)
+
+
+def fit_arms(arms):
+    ws = O.init_vgg_weights(np.random.default_rng(0))
+    for tag, frame_seqs, kw in arms:
+        trk = tracker.NTMOffsetTracker(B, T, vgg_weights=ws, device=dev, seed=1)
+        stamps = []
+        # num_epochs epochs of the same sequences: each epoch is nseq // B steps; validation far apart, one loss read at the end
+        t0 = time.perf_counter()
+        res = train.fit(trk, frame_seqs, frame_seqs[:B], num_epochs=6, validation_interval=10 ** 6, validation_batch=1,
+                        log_interval=10 ** 6, ckpt_dir=os.path.join(tmp, "ckpt"), seed=0,
+                        on_event=lambda e: stamps.append((e[0], time.perf_counter())), **kw)
+        torch.cuda.synchronize()
+        per = np.diff([t for k, t in stamps if k == "train"])
+        say("fit %s: %d steps of B=%d T=%d; seconds per step: median %.3f, min %.3f, max %.3f (host time between steps; first "
+            "step excluded); whole run %.1f s" % (tag, res.steps, B, T, median(per), per.min(), per.max(), time.perf_counter() - t0))
+        del trk
+
+
+if ARMS == "device":
+    fit_arms([("decode=host", seqs, dict(decode="host")), ("decode=device", seqs, dict(decode="device")),
+              ("decode=host", seqs, dict(decode="host")), ("decode=device", seqs, dict(decode="device")),
+              ("decode=host, restart rows", seqs_rst, dict(decode="host")), ("decode=device, restart rows", seqs_rst, dict(decode="device"))])
+    import shutil
+    shutil.rmtree(tmp, ignore_errors=True)
+    sys.exit(0)
 
 # ---- the per-frame path
 torch.cuda.synchronize()
