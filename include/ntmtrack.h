@@ -778,6 +778,16 @@ int ntk_frames_crop_batch(const unsigned char* pixels, long long pixels_bytes, c
  * colour with libjpeg's default integer pipeline -- the bits of Pillow's decode -- straight into the `pixels` buffer
  * ntk_frames_crop_batch reads.
  *
+ * The domain of "the bits of Pillow's decode": streams whose dequantised coefficients are what a forward DCT of 8-bit samples
+ * gives -- about +-1024 per coefficient, which every file from a real encoder keeps.  Outside it the two differ: Pillow's
+ * libjpeg-turbo runs a SIMD inverse DCT that saturates 16-bit intermediates, the device keeps int32 throughout (libjpeg's C
+ * code).  Measured (scripts/jpeg_domain_boundary.py): a quality-100 noise file with every quantisation value overwritten by q
+ * decodes alike up to q = 12 (largest dequantised coefficient 2100) and differs from q = 13 on (2275).  Any table index 0..3,
+ * Huffman code lengths up to 16, DC differences up to category 11, restart intervals, fill bytes and repeated DRI / DHT / DQT
+ * segments (the last definition counts) are inside the domain.  One difference in what is accepted: a file whose scan is not
+ * followed by EOI is an error to Pillow (decode="host" raises), while ntk_jpeg_parse accepts it and the device decodes what the
+ * scan holds -- the whole image when only the marker is missing, NTK_JPEG_STATUS_TRUNCATED when the scan ends early.
+ *
  * ntk_jpeg_parse (pure host code, thread-safe, no device-runtime call): file[file_bytes] -> one descriptor of NTK_JPEG_DESC_BYTES
  * bytes (nullable) and, when stream_dst is given, the scan's entropy-coded bytes with the stuffing removed (FF 00 -> FF), split at
  * the RSTn markers: segments[k] is the byte offset of segment k in stream_dst and segments[*n_segments] the end, so segment_cap

@@ -41,6 +41,8 @@ def parse(data):
     p, info = 2, {"quant": {}, "huff": {}, "restart": 0}
     while True:
         assert data[p] == 0xFF
+        while data[p + 1] == 0xFF:             # fill bytes before a marker
+            p += 1
         m = data[p + 1]
         L = (data[p + 2] << 8) | data[p + 3]
         b = data[p + 4:p + 2 + L]
@@ -169,15 +171,15 @@ def _idct8(v, shift):
     return np.stack([(o + r) >> shift for o in out], axis=-1)
 
 
-def idct_blocks(coef, quant):
-    """coef [..., 64] natural order, quant [64] -> uint8-range samples [..., 8, 8]"""
+def idct_blocks(coef, quant, clip=True):
+    """coef [..., 64] natural order, quant [64] -> uint8-range samples [..., 8, 8] (clip=False: before the range limit)"""
     v = (coef * quant).reshape(coef.shape[:-1] + (8, 8))
     v = np.swapaxes(_idct8(np.swapaxes(v, -1, -2), 11), -1, -2)        # columns
     v = _idct8(v, 18)                                                   # rows
-    return np.clip(v + 128, 0, 255)
+    return np.clip(v + 128, 0, 255) if clip else v + 128
 
 
-def planes(info):
+def planes(info, clip=True):
     """-> list of MCU-padded planes (int64), one per component"""
     coef, hs, vs = coefficients(info)
     my, mx, bpm, _ = coef.shape
@@ -186,10 +188,10 @@ def planes(info):
     for c, comp in enumerate(info["comps"]):
         q = info["quant"][comp[3]]
         if c == 0:
-            px = idct_blocks(coef[:, :, :nluma], q).reshape(my, mx, vs, hs, 8, 8)
+            px = idct_blocks(coef[:, :, :nluma], q, clip).reshape(my, mx, vs, hs, 8, 8)
             out.append(px.transpose(0, 2, 4, 1, 3, 5).reshape(my * vs * 8, mx * hs * 8))
         else:
-            px = idct_blocks(coef[:, :, nluma + c - 1], q)
+            px = idct_blocks(coef[:, :, nluma + c - 1], q, clip)
             out.append(px.transpose(0, 2, 1, 3).reshape(my * 8, mx * 8))
     return out, hs, vs
 
@@ -218,14 +220,13 @@ def upsample_h2v2(c, H, W):
     return np.stack([even, odd], axis=-1).reshape(H, 2 * cn_x)[:, :W]
 
 
-def decode(data):
-    """File bytes -> uint8 [H, W, 3], what np.asarray(Image.open(f).convert("RGB")) gives."""
-    info = parse(data)
+def _rgb(info):
+    """-> int64 [H, W, 3] before the last range limit (a gray file: Y three times, already within 0..255)"""
     H, W = info["H"], info["W"]
     pl, hs, vs = planes(info)
     Y = pl[0][:H, :W]
     if len(pl) == 1:
-        return np.stack([Y, Y, Y], axis=-1).astype(np.uint8)
+        return np.stack([Y, Y, Y], axis=-1)
     if hs == 1:
         cb, cr = pl[1][:H, :W], pl[2][:H, :W]
     elif vs == 1:
@@ -237,7 +238,26 @@ def decode(data):
     R = Y + ((F(1.402) * cr + 32768) >> 16)
     G = Y + ((-F(0.34414) * cb - F(0.71414) * cr + 32768) >> 16)
     B = Y + ((F(1.772) * cb + 32768) >> 16)
-    return np.clip(np.stack([R, G, B], axis=-1), 0, 255).astype(np.uint8)
+    return np.stack([R, G, B], axis=-1)
+
+
+def decode(data):
+    """File bytes -> uint8 [H, W, 3], what np.asarray(Image.open(f).convert("RGB")) gives."""
+    return np.clip(_rgb(parse(data)), 0, 255).astype(np.uint8)
+
+
+def clamp_counts(data):
+    """How often the two range limits of the pipeline act inside the image: -> ((samples the inverse DCT gives below 0, above
+    255), (colour values below 0, above 255 after YCbCr -> RGB; (0, 0) for a gray file))."""
+    info = parse(data)
+    H, W = info["H"], info["W"]
+    pl, hs, vs = planes(info, clip=False)
+    lo = hi = 0
+    for c, p in enumerate(pl):
+        p = p[:H, :W] if c == 0 or hs == 1 else p[:-(-H // vs), :-(-W // hs)]
+        lo, hi = lo + int(np.count_nonzero(p < 0)), hi + int(np.count_nonzero(p > 255))
+    rgb = _rgb(info)
+    return (lo, hi), (int(np.count_nonzero(rgb < 0)), int(np.count_nonzero(rgb > 255)))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -291,3 +311,41 @@ def truncated_file():
     data = encode(image(40, 72, "noise", 3), quality=90, subsampling=2)
     start = parse(data)["scan_start"]
     return data[:start + int(0.4 * (len(data) - start))]
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the device entry with guard bytes around every rectangle (GPU tests)
+# ------------------------------------------------------------------------------------------------------------------------------
+
+GUARD = 0xA5
+
+
+def decode_guarded(cuda, files, rects, gap=96):
+    """ntk_jpeg_decode_batch into a buffer filled with GUARD, `gap` bytes before, between and after the rectangles.
+    -> (list of decoded rectangles, status, True when every byte outside the rectangles is still GUARD)"""
+    import torch
+    from ntmtrack import _lib, data
+    probed = [data._probe_frame(f, "file %d" % i) for i, f in enumerate(files)]
+    rects = [(0, 0) + pr["size"] if r is None else r for pr, r in zip(probed, rects)]
+    packed = data.pack_jpeg_frames(probed, rects, staging=data.Staging())
+    assert all(packed.jpeg.on_device)
+    table = packed.table.numpy().copy()
+    table[:, 0] += gap * (1 + np.arange(len(files)))
+    total = packed.nbytes + gap * (len(files) + 1)
+    pix = torch.full((total,), GUARD, dtype=torch.uint8, device=cuda)
+    j, st, n = packed.jpeg, packed.staging, packed.n
+    dev = lambda t: t.to(cuda)
+    streams, descs, segs = dev(st.streams[:j.stream_bytes]), dev(st.descs[:n]), dev(st.segments[:j.n_segments])
+    tab, ws = dev(torch.from_numpy(table)), torch.empty((j.workspace_bytes,), dtype=torch.uint8, device=cuda)
+    status = torch.full((n,), 77, dtype=torch.int32, device=cuda)
+    P = _lib.ptr
+    _lib.check(_lib.lib().ntk_jpeg_decode_batch(P(streams), j.stream_bytes, P(descs), P(segs), j.n_segments, P(tab), P(pix), total,
+                                                P(ws), j.workspace_bytes, P(status), n, _lib.stream()), "ntk_jpeg_decode_batch")
+    torch.cuda.synchronize()
+    out = pix.cpu().numpy()
+    keep = np.ones(total, bool)
+    images = []
+    for off, _H, _W, _y0, _x0, h, w in table.tolist():
+        images.append(out[off:off + h * w * 3].reshape(h, w, 3).copy())
+        keep[off:off + h * w * 3] = False
+    return images, status.cpu().numpy(), bool(np.all(out[keep] == GUARD))

@@ -14,9 +14,6 @@ import jpeg_util as J  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0xA5
-
-
 @pytest.fixture(scope="module")
 def grid():
     return J.grid()
@@ -45,34 +42,7 @@ def test_the_grid_is_pillows_bytes_and_all_of_it_is_decoded_on_the_device(cuda, 
     assert on_device == len(grid), "only %d of %d files were decoded on the device" % (on_device, len(grid))
 
 
-def _decode_guarded(cuda, files, rects, gap=96):
-    """ntk_jpeg_decode_batch into a buffer filled with GUARD, `gap` bytes before, between and after the rectangles.
-    -> (list of decoded rectangles, status, True when every byte outside the rectangles is still GUARD)"""
-    from ntmtrack import _lib, data
-    probed = [data._probe_frame(f, "file %d" % i) for i, f in enumerate(files)]
-    rects = [(0, 0) + pr["size"] if r is None else r for pr, r in zip(probed, rects)]
-    packed = data.pack_jpeg_frames(probed, rects, staging=data.Staging())
-    assert all(packed.jpeg.on_device)
-    table = packed.table.numpy().copy()
-    table[:, 0] += gap * (1 + np.arange(len(files)))
-    total = packed.nbytes + gap * (len(files) + 1)
-    pix = torch.full((total,), GUARD, dtype=torch.uint8, device=cuda)
-    j, st, n = packed.jpeg, packed.staging, packed.n
-    dev = lambda t: t.to(cuda)
-    streams, descs, segs = dev(st.streams[:j.stream_bytes]), dev(st.descs[:n]), dev(st.segments[:j.n_segments])
-    tab, ws = dev(torch.from_numpy(table)), torch.empty((j.workspace_bytes,), dtype=torch.uint8, device=cuda)
-    status = torch.full((n,), 77, dtype=torch.int32, device=cuda)
-    P = _lib.ptr
-    _lib.check(_lib.lib().ntk_jpeg_decode_batch(P(streams), j.stream_bytes, P(descs), P(segs), j.n_segments, P(tab), P(pix), total,
-                                                P(ws), j.workspace_bytes, P(status), n, _lib.stream()), "ntk_jpeg_decode_batch")
-    torch.cuda.synchronize()
-    out = pix.cpu().numpy()
-    keep = np.ones(total, bool)
-    images = []
-    for off, _H, _W, _y0, _x0, h, w in table.tolist():
-        images.append(out[off:off + h * w * 3].reshape(h, w, 3).copy())
-        keep[off:off + h * w * 3] = False
-    return images, status.cpu().numpy(), bool(np.all(out[keep] == GUARD))
+_decode_guarded = J.decode_guarded
 
 
 RECT_FILES = {

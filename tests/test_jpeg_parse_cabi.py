@@ -1,6 +1,8 @@
 """CPU: the host half of the device JPEG decoder through the C ABI -- ntk_jpeg_parse (marker walk, descriptor, unstuffing),
 ntk_jpeg_decode_workspace_bytes, and the refusals of ntk_jpeg_decode_batch, which fire on the host before anything is launched (no
-GPU is needed), naming the offending value in ntk_last_error."""
+GPU is needed), naming the offending value in ntk_last_error.  Every file of the synthetic corpus (tests/jpeg_write.py: table
+indices 2 and 3, fill bytes, repeated DRI / DHT / DQT, ...) is accepted, and its descriptor, unstuffed stream and segment offsets
+are those of the Python restatement.  A scan without EOI is accepted as well: the documented difference to Pillow."""
 import ctypes
 import io
 import os
@@ -12,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import jpeg_util as J  # noqa: E402
+import jpeg_write as JW  # noqa: E402
 
 ONE = ctypes.c_void_p(64)                       # non-null, aligned, never dereferenced: the checks fire first
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ntmtrack.h")
@@ -243,3 +246,64 @@ def test_decode_refuses_null_pointers(L, arg):
 def test_decode_refuses_bad_sizes_and_a_short_workspace_and_names_the_value(L, kw, named):
     assert call(L, **kw) == -1
     assert named in L.ntk_last_error()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the synthetic corpus (tests/jpeg_write.py)
+# ------------------------------------------------------------------------------------------------------------------------------
+
+HUFF_BYTES = 512 + 72 + 72 + 256                # NtkJpegHuff: look uint16 [256], maxcode int32 [18], valoff int32 [18], val uint8 [256]
+
+
+def _assert_descriptor_is_the_restatements(p, info):
+    from ntmtrack import data
+    nc = len(info["comps"])
+    hs, vs = (info["comps"][0][1], info["comps"][0][2]) if nc == 3 else (1, 1)
+    assert (p.height, p.width, p.components, p.sampling) == (info["H"], info["W"], nc, (hs, vs))
+    assert p.mcus == (-(-info["H"] // (8 * vs)), -(-info["W"] // (8 * hs)))
+    assert (p.restart_interval, p.n_segments) == (info["restart"], len(info["segments"]) - 1)
+    D = data.JPEG_DESC
+    for c in range(nc):
+        assert (int(p.hdr[D["TQ"] + c]), int(p.hdr[D["TD"] + c]), int(p.hdr[D["TA"] + c])) == (info["comps"][c][3],) + info["scan"][c]
+    quant = p.desc[128:128 + 512].view(np.uint16).reshape(4, 64)
+    for t, q in info["quant"].items():
+        assert np.array_equal(quant[t], q), "quantisation table %d" % t
+    for (cls, t), (counts, vals) in info["huff"].items():
+        h = p.desc[640 + (cls * 4 + t) * HUFF_BYTES:640 + (cls * 4 + t + 1) * HUFF_BYTES]
+        maxcode, val = h[512:584].view(np.int32), h[656:]
+        assert list(val[:len(vals)]) == list(vals), "Huffman table %d/%d: values" % (cls, t)
+        code, want = 0, [-1] * 18
+        for l in range(1, 17):
+            if counts[l - 1]:
+                want[l] = code + counts[l - 1] - 1
+            code = (code + counts[l - 1]) << 1
+        assert list(maxcode) == want, "Huffman table %d/%d: largest code per length" % (cls, t)
+    assert p.stream.tobytes() == info["stream"] and list(p.segments) == info["segments"]
+    assert p.stream_bytes == len(info["stream"])
+
+
+@pytest.mark.parametrize("name", [n for n, _kw in JW.recipes()])
+def test_every_corpus_file_is_accepted_and_its_descriptor_is_the_restatements(L, name):
+    from ntmtrack import data
+    raw = dict(JW.corpus())[name]
+    desc = np.zeros(data.JPEG_DESC_BYTES, np.uint8)
+    rc, _s, _n = data._jpeg_parse_raw(raw, desc, None, 0, 0, None, 0, 0, name)
+    assert rc == 0, "%s: ntk_jpeg_parse returned %d" % (name, rc)
+    dst = np.full(len(raw), 0xAB, np.uint8)
+    p = data.parse_jpeg(raw, dst=dst)
+    _assert_descriptor_is_the_restatements(p, J.parse(raw))
+    assert np.all(dst[p.stream_bytes:] == 0xAB), "bytes behind the stream were written"
+
+
+def test_a_scan_without_eoi_is_accepted_where_pillow_raises():
+    """include/ntmtrack.h documents the difference: decode="host" raises on such a file, decode="device" decodes what the scan
+    holds (all of the image here; a scan that ends early is NTK_JPEG_STATUS_TRUNCATED)."""
+    from ntmtrack import data
+    whole = dict(JW.corpus())["s444_noise3_33x47"]
+    assert whole.endswith(b"\xff\xd9")
+    cut = whole[:-2]
+    with pytest.raises(OSError):
+        J.pillow_decode(cut)
+    p, q = data.parse_jpeg(cut), data.parse_jpeg(whole)
+    assert p is not None and p.stream.tobytes() == q.stream.tobytes() and list(p.segments) == list(q.segments)
+    assert np.array_equal(p.desc, q.desc)
