@@ -6,7 +6,7 @@
 // What follows describes the kernel on the bf16 operator; the split form differs in what a "step" is, in the epilogue's split and
 // in the 28-wide maps (see the comment in front of the kernel).
 //
-// conv_bf16.hip's kernel re-stages a 128-pixel x 64-channel A tile from L2 for every one of the nine taps and a 128-column
+// conv_direct.hip's bf16 tile kernel re-stages a 128-pixel x 64-channel A tile from L2 for every one of the nine taps and a 128-column
 // B tile beside it: 512 B of global -> LDS traffic per v_mfma_f32_32x32x16_bf16, at four workgroups per CU exactly the
 // 64 B/clk the fill path has -- the kernel sat at 31 % of the matrix peak with the pipe half idle (three
 // experiments on the tile shape, all bound the same way).  This kernel removes the bytes instead:
@@ -25,7 +25,7 @@
 //   * the product is computed TRANSPOSED, D[channel][pixel] (weights as the A operand): a lane then holds four adjacent
 //     channels of one pixel per register quad and stores 8 bytes (bf16) / 16 bytes (fp32) at a time; vertically adjacent
 //     rows of a sub-block live in consecutive tiles of one wave, so the 2x2 pool is a register max + one DPP exchange.
-// Same operator, operand rounding and accumulation type as conv_bf16.hip (bf16 operands, fp32 accumulate, one bf16 rounding
+// Same operator, operand rounding and accumulation type as conv_direct.hip's bf16 tile kernel (bf16 operands, fp32 accumulate, one bf16 rounding
 // on store; vgg.py:155-161); the summation ORDER over (chunk, tap, channel) differs, so results agree to fp32 rounding.
 #include "conv_tiles.h"
 #include "conv_stem.h"

@@ -1,6 +1,6 @@
 // What the tiled conv kernels share (conv_wino.hip, conv_wino43.hip, conv_bf16p.hip): how a 1-D grid is cut into (column block,
 // group of sub-blocks), the launcher's inverse of that map, and the table of a workgroup's sub-blocks.
-// (mfma_f32.hip and conv_bf16.hip cut a frame into row tiles, rt = (li / ctiles) * 8 + xcd: another scheme, not this one.)
+// (conv_direct.hip cuts a frame into row tiles, rt = (li / ctiles) * 8 + xcd, in its conv_row_tile: another scheme, not this one.)
 #pragma once
 #include "common.h"
 

@@ -1,6 +1,6 @@
 // VGG 3x3 convolution as fused Winograd F(4x4,3x3) on the fp32 MFMA pipe (gfx950).
 //
-// out = relu(conv3x3_same(in, w) + b) [+ 2x2/2 max pool] -- the same operator as mfma_f32.hip / conv_wino.hip
+// out = relu(conv3x3_same(in, w) + b) [+ 2x2/2 max pool] -- the same operator as conv_direct.hip / conv_wino.hip
 // (vgg.py:155-161 via slim.conv2d).  Every 4x4 output tile is
 //     Y = A^T [ (G g G^T) (.) (B^T d B) ] A          (Lavin & Gray, interpolation points 0, +-1, +-2, inf),
 // summed over input channels: 36 independent GEMMs  M_p[tile, cout] = sum_c V_p[tile, c] U_p[c, cout], p = 6 i + j --

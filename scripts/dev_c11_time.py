@@ -1,4 +1,4 @@
-"""Dev: time conv1_1 (3 -> 64 channels, 224 x 224, 640 frames) -- the row kernel of csrc/mfma_f32.hip."""
+"""Dev: time conv1_1 (3 -> 64 channels, 224 x 224, 640 frames) -- the row kernel of csrc/conv_direct.hip."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

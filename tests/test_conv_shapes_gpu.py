@@ -187,3 +187,28 @@ def test_every_accepted_channel_pair_matches_float64(cuda, cin, cout):
             if _accepts(form, H, W, cin, cout, pool):
                 _run_checked(form, c, m, pool)
     c.verdict("channel grid, cin=%d cout=%d" % (cin, cout))
+
+
+# Two instantiations of the direct conv (csrc/conv_direct.hip) that the grids above do not reach.
+
+@pytest.mark.parametrize("H,W", ((4, 4), (8, 12), (12, 40), (4, 32), (8, 64)))
+def test_conv1_1_to_bf16_called_on_its_own_matches_float64(cuda, H, W):
+    """ntk_vgg_conv3x3_relu_f32_to_bf16 (fp32 frames in, bf16 map out; elsewhere reached only through the bf16 trunk): the tiny-Cin
+    tile kernel with a bf16 output on the first three maps (rows no multiple of the tile's 128, crossing frame boundaries), the
+    row kernel where W % 32 == 0.  Against the float64 convolution of the fp32 operands, within one bf16 rounding."""
+    from ntmtrack import vgg
+    wts, c = _Weights(cuda, 3, 64), _Checks()
+    m = _Maps(wts, H, W)
+    y = vgg.conv3x3_relu_f32_to_bf16(m.xt, wts.packed("direct"), wts.bt, 3, 64)
+    c.close("direct to bf16", "F=%d H=%d W=%d cin=3 cout=64" % (F, H, W), y, m.ref(False), 2.0 ** -8, bf16_out=True)
+    c.verdict("conv1_1 to bf16, H=%d W=%d" % (H, W))
+
+
+@pytest.mark.parametrize("H,W", ((4, 4), (8, 12), (32, 32)))
+def test_tiny_cin_with_128_column_tiles_matches_float64(cuda, H, W):
+    """cin = 3, cout = 128: the tiny-Cin tile kernel on 128-column tiles, with and without the pool."""
+    wts, c = _Weights(cuda, 3, 128), _Checks()
+    m = _Maps(wts, H, W)
+    for pool in (False, True):
+        _run_checked("direct", c, m, pool)
+    c.verdict("tiny Cin, 128 columns, H=%d W=%d" % (H, W))

@@ -1,4 +1,4 @@
-"""CPU: host-side validation of the plain GEMM entries (csrc/mfma_f32.hip) and of the small kernels that had no refusal
+"""CPU: host-side validation of the plain GEMM entries (csrc/gemm_f32.hip) and of the small kernels that had no refusal
 test yet.  Every pointer is non-null, 16-byte aligned and never dereferenced: the shape check fires before any launch.
 The refusal tests run only where no device is visible (as the other fake-pointer files do): should a check ever go missing,
 the call fails at the launch there instead of handing a made-up address to a kernel."""

@@ -1,4 +1,4 @@
-"""GPU: the plain fp32 MFMA GEMMs of csrc/mfma_f32.hip (ntk_gemm_nt_f32, ntk_gemm_tn_f32) against numpy float64 matmul.
+"""GPU: the plain fp32 MFMA GEMMs of csrc/gemm_f32.hip (ntk_gemm_nt_f32, ntk_gemm_tn_f32) against numpy float64 matmul.
 
 Exact cases: A, B, bias and the initial C hold integers of [-4, 4] stored as fp32, so every partial sum is an integer
 below 16 K + 4 < 2^24 and fp32 arithmetic in ANY summation order is exact: the result must EQUAL the float64 reference.

@@ -118,7 +118,7 @@ def _accepts(L, vgg, step, F, h, w, cin, cout):
         return L.ntk_vgg_split3_supported(h, w, cin, cout, pool) and (step.src == "split" or (cin <= 64 and cout == 64 and h % 8 == 0 and w % 8 == 0))
     if k == "bf16p":
         return L.ntk_vgg_bf16p_supported(h, w, cin, cout, pool)
-    if k == "bf16":                 # the tile kernel (csrc/conv_bf16.hip): 64-channel multiples, sides multiples of 4
+    if k == "bf16":                 # the tile kernel (csrc/conv_direct.hip): 64-channel multiples, sides multiples of 4
         return cin % 64 == 0 and cout % 64 == 0 and h % 4 == 0 and w % 4 == 0
     assert k in ("direct", "direct_to_bf16")
     return (cin == 3 or cin % 32 == 0) and cout % 64 == 0 and h % 4 == 0 and w % 4 == 0

@@ -3,7 +3,7 @@ against (a) the separate pair conv3x3_relu -> conv3x3_relu_split3(fp32 in) on th
 layers; then the default (fused) trunk against the float64 oracle and the separate-stem trunk.
 
 The fused kernel evaluates conv1_1 as a chain of v_mfma_f32_16x16x4_f32 over k = tap * 3 + c in order, from a zero accumulator, bias
-added last.  On frames whose width is a multiple of 32 the separate conv1_1 is the row kernel (csrc/mfma_f32.hip conv_c3_rows_kernel):
+added last.  On frames whose width is a multiple of 32 the separate conv1_1 is the row kernel (csrc/conv_direct.hip conv_c3_rows_kernel):
 the same k order on v_mfma_f32_32x32x2_f32, whose steps round like the same sequence of fused multiply-adds -- there (a) is asserted
 BIT FOR BIT.  On narrower frames the separate conv1_1 is the tile kernel, which sums in another order; what may differ then is
 bounded here from the inputs, in float64, not from what the kernels give:
