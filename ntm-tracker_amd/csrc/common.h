@@ -84,6 +84,19 @@ __device__ __forceinline__ float wave_max(float v) {
     return fmaxf(fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 0)), __int_as_float(__builtin_amdgcn_readlane(b, 16))),
                  fmaxf(__int_as_float(__builtin_amdgcn_readlane(b, 32)), __int_as_float(__builtin_amdgcn_readlane(b, 48))));
 }
+// Workgroup total of per-wave values: v is a wave total (wave_sum) or lane 0's value, red a __shared__ array of one float per wave.
+// One barrier; thread 0 gets the sum over the waves in ascending wave order, starting from 0.f (the order fixes the rounding, and
+// tests reason about it); what the other threads get is not a total.  NW: the number of waves where the kernel fixes it.
+// Every thread of the workgroup must call it (it holds a barrier), and red may not be written again without a further barrier.
+template <int NW = 0>
+__device__ __forceinline__ float block_sum(float v, float* red) {
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    float s = 0.f;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < (NW ? NW : (int)(blockDim.x >> 6)); ++w) s += red[w];
+    return s;
+}
 
 // ntk_stream_matvec (below) with the prefetch cut at the slice's end: rows at or past r1 are not loaded (the loads sit under lane
 // predicates; same products in the same order).  The plain form fetches 2 PF rows past a slice -- 15 rows for nothing per 25-row

@@ -1,5 +1,5 @@
 // Step-granular entry points of the C ABI (SURVEY 8b minimum export set): the single-step forms of the sequence
-// kernels, the BasicLSTMCell pointwise step, a stand-alone 2x2 max pool and the split loss entry points.
+// kernels, the BasicLSTMCell pointwise step and a stand-alone 2x2 max pool (the split loss entries: head_loss.hip).
 // The training/inference hot path uses the persistent sequence kernels and the pool fused into the conv epilogue;
 // these exist so a caller that drives the cell one step() at a time (test_tracker.py:340-341) binds the same library.
 #include "ntm_seq_args.h"
@@ -149,16 +149,4 @@ extern "C" int ntk_maxpool2x2(const float* in, float* out, int n, int H, int W, 
     maxpool2x2_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(in, out, n, H, W, C);
     NTK_CHECK_LAUNCH("ntk_maxpool2x2");
     return NTK_OK;
-}
-
-// loss split in two calls (direct_offset_output.py:581-606): forward = pred + loss, backward = d loss / d logits
-extern "C" int ntk_offset_loss_fwd(const float* logits, const float* offsets, float* pred, float* loss, int B, int T, int NF,
-                                   int O, void* stream) {
-    NTK_REQUIRE(loss, NTK_ERR_BAD_PTR, "ntk_offset_loss_fwd: null pointer");
-    return ntk_offset_loss(logits, offsets, pred, loss, nullptr, B, T, NF, O, stream);
-}
-extern "C" int ntk_offset_loss_bwd(const float* logits, const float* offsets, float* dlogits, int B, int T, int NF, int O,
-                                   void* stream) {
-    NTK_REQUIRE(dlogits, NTK_ERR_BAD_PTR, "ntk_offset_loss_bwd: null pointer");
-    return ntk_offset_loss(logits, offsets, nullptr, nullptr, dlogits, B, T, NF, O, stream);
 }

@@ -1,4 +1,4 @@
-"""GPU: the image kernels of csrc/head_opt.hip -- crop_resize_kernel (ntk_crop_and_resize), crop_resize_batch_kernel<float> and
+"""GPU: the image kernels of csrc/image_crop.hip -- crop_resize_kernel (ntk_crop_and_resize), crop_resize_batch_kernel<float> and
 <unsigned char> (ntk_crop_and_resize_batch), resize_bilinear_kernel (ntk_resize_bilinear) -- against
 oracle/online_oracle.crop_and_resize and small_kernel_util.resize_ref in float64, through the C entries with device pointers.
 

@@ -1,5 +1,5 @@
 """CPU: host-side validation of the stand-alone DNC module entries (csrc/dnc_modules.hip), the stand-alone NTM ops
-(csrc/ntm_ops.hip) and the image entries (csrc/head_opt.hip).  Conventions of tests/test_gemm_cabi.py: every pointer is
+(csrc/ntm_ops.hip) and the image entries (csrc/image_crop.hip).  Conventions of tests/test_gemm_cabi.py: every pointer is
 non-null, 16-byte aligned and never dereferenced (the check fires before any launch), and the tests run only where no device is
 visible -- should a check ever go missing, the call fails at the launch there instead of handing a made-up address to a kernel.
 Each refusal returns the code the header documents and leaves the entry's name in ntk_last_error()."""

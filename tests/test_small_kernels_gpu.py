@@ -1,5 +1,5 @@
 """GPU: the small kernels around the recurrent cores -- the single-workgroup loss heads, the serialisers, the optimiser and
-the elementwise kernels (csrc/head_opt.hip, csrc/step_api.hip, transpose_pad of csrc/ntm_seq_bwd.hip) -- each on its own,
+the elementwise kernels (csrc/head_loss.hip, csrc/optimizer.hip, csrc/step_api.hip, transpose_pad of csrc/ntm_seq_bwd.hip) -- each on its own,
 against the float64 oracle (oracle/ntm_oracle.py; gradients from float64 torch autograd), at the sizes where their loops
 change shape: a lane stride that runs or not, a wave stride with and without a remainder, one workgroup and several, the
 grid-stride loops.  Every output buffer is NaN before the call.
@@ -336,7 +336,7 @@ GN_SIZES = [1, 255, 256, 257, 4095, 4096, 4097, 3 * 4096 + 5, 1024 * 4096 + 3]
 @pytest.mark.parametrize("n", GN_SIZES)
 def test_global_norm(cuda, n):
     """Bound: all terms are non-negative, so the relative error of the fp32 sum is at most depth * 2^-24 with depth the longest
-    chain of roundings on the way to the sum.  From the code (csrc/head_opt.hip): sumsq_partial_kernel squares (1 rounding, none
+    chain of roundings on the way to the sum.  From the code (csrc/optimizer.hip): sumsq_partial_kernel squares (1 rounding, none
     when fused), each thread adds its 4096 / 256 = 16 terms (16), wave_sum adds 4 + 3 times (7), thread 0 adds the 4 wave sums
     (4); sumsq_final_kernel: each of the 1024 threads adds ceil(nblocks / 1024) partials, wave_sum (7), thread 0 adds 16 wave
     sums (16): depth = 1 + 16 + 7 + 4 + ceil(nblocks / 1024) + 7 + 16 = 51 + ceil(nblocks / 1024).  The square root halves the
