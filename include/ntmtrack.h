@@ -1050,6 +1050,35 @@ int ntk_track_supervise_poly(int phase, const double* regions, const double* gt,
                              int B, int n_clips, int skip, int burn_in, double failure_overlap, int* state, double* table,
                              unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou, void* stream);
 
+/* Validation from image files decoded on the device (ntk_jpeg_decode_batch): which frames of a round may be tracked and scored.
+ * A file can turn out undecodable only on the device; this entry turns such a frame off in the round's mask before the tracker
+ * and the scoring launch read it, so that nothing is read back per round.  One launch per round, one thread per slot, which
+ * walks its T frames in order; a table row belongs to its slot's thread alone (NO TWO SLOTS MAY NAME ONE ROW), so there are no
+ * atomics: plain vector loads and stores.
+ *   status       int32 [n_status]: the decoder's NTK_JPEG_STATUS_* per file of the round
+ *   cell_index   int32 [T,B]: the file of cell (t, b) as an index into status; -1 = the cell has no device-decoded file, its
+ *                status is 0.  An index >= n_status counts as NTK_JPEG_STATUS_BAD_DESC: nothing outside status is read.
+ *   start_index  int32 [B]: the index of the slot's starting frame if the slot was reset this round, else -1
+ *   clip_of      int32 [B]: the table row of slot b; a row outside [0, n_clips) leaves everything of the slot as it is
+ *   dead         uint8 [B], in/out: the slot's clip started from an undecodable frame.  Written when start_index[b] >= 0
+ *                (dead = the starting frame's status != 0, which also goes to START_STATUS), carried over rounds otherwise.
+ *   active       uint8 [T,B], in/out.  For each t in order with active[t,b] != 0: a dead slot -> active = 0, MASKED += 1;
+ *                else a status != 0 -> active = 0, FAILED += 1 and, while FIRST_FAILED < 0, FIRST_FAILED = DECODED + FAILED +
+ *                MASKED as they stood before this frame and FIRST_STATUS = the status; else DECODED += 1.
+ *   table        int64 [n_clips, NTK_CLIPDEC_HEAD], accumulated in place: THE OWNER INITIALISES FIRST_FAILED TO -1, the rest to 0.
+ * Rounds are separate calls and the row carries the counts, so any split of a clip's frames into calls leaves the same bits.
+ * Errors, before any launch: NTK_ERR_BAD_PTR for any null pointer; NTK_ERR_BAD_SHAPE, the value named in ntk_last_error, for T,
+ * B, n_clips or n_status <= 0 or B > 65535. */
+#define NTK_CLIPDEC_DECODED       0  /* active frames of the clip whose pixels are good (status 0, or no device file) */
+#define NTK_CLIPDEC_FAILED        1  /* active frames whose decode status was not 0: made inactive */
+#define NTK_CLIPDEC_MASKED        2  /* active frames made inactive because the clip's STARTING frame failed */
+#define NTK_CLIPDEC_FIRST_FAILED  3  /* index among the clip's active frames (0 = first tracked frame) of the first failure; -1 = none */
+#define NTK_CLIPDEC_FIRST_STATUS  4  /* that frame's NTK_JPEG_STATUS_*; 0 = none */
+#define NTK_CLIPDEC_START_STATUS  5  /* status of the clip's starting frame */
+#define NTK_CLIPDEC_HEAD          6
+int ntk_track_decode_mask(const int* status, int n_status, const int* cell_index, const int* start_index, const int* clip_of,
+                          int T, int B, int n_clips, unsigned char* dead, unsigned char* active, long long* table, void* stream);
+
 /* out[b,:] = mask[b] ? a[b,:] : b[b,:] for fp32 [B,n] rows, mask uint8 [B] on the device (out may alias a or b): keeps the
  * recurrent state of a tracker that sat a frame out. */
 int ntk_select_rows(const unsigned char* mask, const float* a, const float* b, float* out, int B, int n, void* stream);

@@ -292,6 +292,54 @@ __global__ void track_supervise_judge_kernel(const double* __restrict__ regions,
     if (codes) codes[b] = NTK_SUP_CODE_TRACKED;
 }
 
+// Which frames of a round a file-fed validation may use (contract: include/ntmtrack.h, NTK_CLIPDEC_*): one thread per slot walks
+// its T frames in order, turns off every active frame whose pixels the decoder did not deliver and counts in the row clip_of[b]
+// of the table, which belongs to this thread alone.  status is read only at indices inside [0, n_status).
+__global__ void track_decode_mask_kernel(const int* __restrict__ status, int n_status, const int* __restrict__ cell_index,
+                                         const int* __restrict__ start_index, const int* __restrict__ clip_of, int T, int B,
+                                         int n_clips, unsigned char* __restrict__ dead, unsigned char* __restrict__ active,
+                                         long long* __restrict__ table) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int clip = clip_of[b];
+    if (clip < 0 || clip >= n_clips) return;
+    long long* row = table + (size_t)clip * NTK_CLIPDEC_HEAD;
+    const int start = start_index[b];
+    unsigned char is_dead = dead[b];
+    if (start >= 0) {
+        const int s = start < n_status ? status[start] : NTK_JPEG_STATUS_BAD_DESC;
+        is_dead = s != 0;
+        dead[b] = is_dead;
+        row[NTK_CLIPDEC_START_STATUS] = s;
+    }
+    long long decoded = row[NTK_CLIPDEC_DECODED], failed = row[NTK_CLIPDEC_FAILED], masked = row[NTK_CLIPDEC_MASKED];
+    long long first_failed = row[NTK_CLIPDEC_FIRST_FAILED], first_status = row[NTK_CLIPDEC_FIRST_STATUS];
+    for (int t = 0; t < T; ++t) {
+        const size_t at = (size_t)t * B + b;
+        if (!active[at]) continue;
+        const int i = cell_index[at];
+        const int s = i < 0 ? 0 : (i < n_status ? status[i] : NTK_JPEG_STATUS_BAD_DESC);
+        if (is_dead) {
+            active[at] = 0;
+            masked += 1;
+        } else if (s != 0) {
+            active[at] = 0;
+            if (first_failed < 0) {
+                first_failed = decoded + failed + masked;
+                first_status = s;
+            }
+            failed += 1;
+        } else {
+            decoded += 1;
+        }
+    }
+    row[NTK_CLIPDEC_DECODED] = decoded;
+    row[NTK_CLIPDEC_FAILED] = failed;
+    row[NTK_CLIPDEC_MASKED] = masked;
+    row[NTK_CLIPDEC_FIRST_FAILED] = first_failed;
+    row[NTK_CLIPDEC_FIRST_STATUS] = first_status;
+}
+
 extern "C" int ntk_track_poly_bounds(const double* poly, int n, double* rects, void* stream) {
     NTK_REQUIRE(poly && rects, NTK_ERR_BAD_PTR, "ntk_track_poly_bounds: null pointer");
     NTK_REQUIRE(n > 0, NTK_ERR_BAD_SHAPE, "ntk_track_poly_bounds: n=%d", n);
@@ -367,4 +415,17 @@ extern "C" int ntk_track_supervise_poly(int phase, const double* regions, const 
                                         double* frame_iou, void* stream) {
     return track_supervise<true>("ntk_track_supervise_poly", phase, regions, gt, active, clip_of, B, n_clips, skip, burn_in,
                                  failure_overlap, state, table, track, restart, codes, frame_iou, stream);
+}
+
+extern "C" int ntk_track_decode_mask(const int* status, int n_status, const int* cell_index, const int* start_index,
+                                     const int* clip_of, int T, int B, int n_clips, unsigned char* dead, unsigned char* active,
+                                     long long* table, void* stream) {
+    NTK_REQUIRE(status && cell_index && start_index && clip_of && dead && active && table, NTK_ERR_BAD_PTR,
+                "ntk_track_decode_mask: null pointer");
+    NTK_REQUIRE(T > 0 && B > 0 && B <= 65535 && n_clips > 0 && n_status > 0, NTK_ERR_BAD_SHAPE,
+                "ntk_track_decode_mask: T=%d B=%d (1..65535) n_clips=%d n_status=%d", T, B, n_clips, n_status);
+    track_decode_mask_kernel<<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(status, n_status, cell_index, start_index, clip_of, T, B,
+                                                                           n_clips, dead, active, table);
+    NTK_CHECK_LAUNCH("ntk_track_decode_mask");
+    return NTK_OK;
 }

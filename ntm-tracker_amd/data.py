@@ -15,6 +15,7 @@ Host-side file parsing is plain Python; the image math (resize to 720x1280, mean
 bit, from ONE launch over the packed uint8 frames, with the decoding on a thread pool, and ``InputPrefetcher`` stages the next
 batch while the current one trains (``train.fit`` is the loop that uses them).
 """
+import collections
 import os
 
 import numpy as np
@@ -115,13 +116,32 @@ def pixel_region(size, normalized_region):
     return tuple(np.asarray(normalized_region, dtype=np.float64) * np.array([width - 1, height - 1, width - 1, height - 1], dtype=np.float64))
 
 
-def validation_clips(seqs, image_root=None):
+CLIP_FRAMES = ("arrays", "files")
+
+
+def _clip_frames(paths, frames):
+    """What a clip reader puts into Clip.frames: frames="arrays" a callable that decodes the whole clip with Pillow (float32
+    [L,H,W,3]) when the validator schedules it; frames="files" the list of paths itself -- a file clip, which the validator reads
+    a round at a time (evaluate.Validation, decode=)."""
+    if frames == "files":
+        return list(paths)
+    return lambda paths=paths: np.stack([_decode_image(p) for p in paths])
+
+
+def _check_clip_frames(frames):
+    if frames not in CLIP_FRAMES:
+        raise ValueError("frames must be 'arrays' or 'files', not %r" % (frames,))
+
+
+def validation_clips(seqs, image_root=None, frames="arrays"):
     """``seqs`` as get_valid_sequences returns them -> one evaluate.Clip per sequence (the reference's validation loop,
     validate_tracker.py:26-38).  Only the first image's header is opened here (for the frame size); a clip's frames are decoded
-    when the validator schedules it.  The tracker is started with the first region NORMALISED, as the reference passes it (the
-    trackers take a region whose four numbers are below 1 as normalised); the ground truth for scoring is in pixels."""
+    when the validator schedules it (frames="files": a round at a time, from the paths; _clip_frames).  The tracker is started
+    with the first region NORMALISED, as the reference passes it (the trackers take a region whose four numbers are below 1 as
+    normalised); the ground truth for scoring is in pixels."""
     from PIL import Image
     from .evaluate import Clip
+    _check_clip_frames(frames)
     clips = []
     for folder, stems in seqs:
         records = [load_frame_region(os.path.join(folder, stem)) for stem in stems]
@@ -129,8 +149,7 @@ def validation_clips(seqs, image_root=None):
         with Image.open(paths[0]) as im:
             width, height = im.size
         regions = np.array([pixel_region((width, height), r) for _p, r in records], dtype=np.float64)
-        decode = lambda paths=paths: np.stack([_decode_image(p) for p in paths])
-        clips.append(Clip(decode, regions, init=records[0][1], size=(height, width)))
+        clips.append(Clip(_clip_frames(paths, frames), regions, init=records[0][1], size=(height, width)))
     return clips
 
 
@@ -152,14 +171,16 @@ def parse_vot_region(line):
     return None
 
 
-def vot_clips(root, names=None):
+def vot_clips(root, names=None, frames="arrays"):
     """The VOT directory layout -> one evaluate.Clip per sequence.  ``root/list.txt`` names the sequences when ``names`` is None.
     A sequence folder holds ``groundtruth.txt``, one region per line (parse_vot_region; a line that is neither form is an absent
     object, a row of NaN), and its frames as ``color/%08d.jpg`` or ``%08d.jpg``, numbered from 1.  Regions are in pixels: [L,4]
     where every line is a rectangle or absent, else [L,16] polygons padded with NaN (a rectangle line among them as its 4-gon).
-    Only the first image's header is opened here (for ``size``); a clip's frames are decoded when the validator schedules it."""
+    Only the first image's header is opened here (for ``size``); a clip's frames are decoded when the validator schedules it
+    (frames="files": a round at a time, from the paths; _clip_frames)."""
     from PIL import Image
     from .evaluate import Clip, POLY_DOUBLES, rect_polygons
+    _check_clip_frames(frames)
     if names is None:
         with open(os.path.join(root, "list.txt")) as f:
             names = [line.strip() for line in f if line.strip()]
@@ -186,8 +207,7 @@ def vot_clips(root, names=None):
         paths = [os.path.join(folder, sub, "%08d.jpg" % (i + 1)) for i in range(len(parsed))]
         with Image.open(paths[0]) as im:
             width, height = im.size
-        decode = lambda paths=paths: np.stack([_decode_image(p) for p in paths])
-        clips.append(Clip(decode, regions, size=(height, width)))
+        clips.append(Clip(_clip_frames(paths, frames), regions, size=(height, width)))
     return clips
 
 
@@ -517,6 +537,92 @@ def stage_batch(frame_names_nosuffix, image_root=None, pool=None, pack="rect", s
     return StagedBatch(names, packed)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# Validation from files: the files of ONE round of evaluate.Validation, staged as one set whose pixel buffer IS the round's
+# [T,B,H,W,3] block with the starting frames of the slots reset in the round behind it.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+RoundFiles = collections.namedtuple("RoundFiles", ["size", "T", "B", "cells", "starts"])
+RoundFiles.__doc__ = """The files of one round: size (H, W) of the clips' frames; cells a list of (t, b, file) for the active cells
+that have a file; starts a list of (slot, file), the starting frames of the slots reset in the round, in reset order.  A file is a
+path or the file's bytes."""
+
+
+class StagedRound(object):
+    """stage_round's result.  `packed`: the PackedFrames (full-frame rectangles; with decode="host" every frame is in its host
+    ranges).  `cell_index` int32 [T,B]: the row of cell (t, b) in the set, -1 where the round has no file for it; `start_index`
+    int32 [B]: the row of the slot's starting frame, -1 for a slot that is not reset; `names` the files' names, by row.  Rows
+    are the cells in (t, b) order, then the starting frames."""
+
+    def __init__(self, packed, spec, cell_index, start_index, names):
+        self.packed, self.spec, self.cell_index, self.start_index, self.names = packed, spec, cell_index, start_index, names
+        self.uploaded = None            # event after the uploads (set by the consumer on a device)
+
+    def host_frames(self):
+        """-> (frames uint8 [T,B,H,W,3], starting frames uint8 [n_resets,H,W,3]): views of the pinned pixel buffer.  Whole only
+        with decode="host"; cells without a file are zero."""
+        (H, W), T, B, n = self.spec.size, self.spec.T, self.spec.B, len(self.spec.starts)
+        block = T * B * H * W * 3
+        buf = self.packed.staging.pixels.numpy()
+        return buf[:block].reshape(T, B, H, W, 3), buf[block:block + n * H * W * 3].reshape(n, H, W, 3)
+
+
+def _file_name(f, row):
+    return "<%d bytes, file %d of the round>" % (len(f), row) if isinstance(f, (bytes, bytearray, memoryview)) else str(f)
+
+
+def stage_round(spec, staging=None, pool=None, grow=True, decode="device"):
+    """Host half of one validation round from files (``spec``: a RoundFiles) -> StagedRound.  Only the round's files are read, on
+    `pool`'s threads when given.  decode="device": a baseline JPEG is parsed and its scan copied, unstuffed, into the set
+    (ntk_jpeg_parse) for ntk_jpeg_decode_batch; any other file (PNG, progressive JPEG, ...) is decoded by Pillow into the same
+    set, as in stage_batch.  decode="host": Pillow decodes every file.  The frame table's offsets put cell (t, b) at byte
+    (t * B + b) * H * W * 3 and the k-th starting frame at (T * B + k) * H * W * 3, so the pixel buffer holds the round's
+    [T,B,H,W,3] block and [n_resets,H,W,3] behind it without a further copy.  A file whose size is not the clip's is a ValueError
+    naming it, as are more than MAX_FRAMES_PER_LAUNCH files.  No device-runtime call is made when grow=False.  Usable as
+    InputPrefetcher's ``stage`` (with `batches` an iterable of RoundFiles)."""
+    _check_decode(decode)
+    (H, W), T, B = spec.size, int(spec.T), int(spec.B)
+    files = [f for _t, _b, f in spec.cells] + [f for _s, f in spec.starts]
+    n = len(files)
+    if n < 1 or n > MAX_FRAMES_PER_LAUNCH:
+        raise ValueError("stage_round: %d files in one round; 1..%d (MAX_FRAMES_PER_LAUNCH) can be staged" % (n, MAX_FRAMES_PER_LAUNCH))
+    names = [_file_name(f, i) for i, f in enumerate(files)]
+
+    def load(i):
+        data, _what = _read_bytes(files[i])
+        try:
+            return _probe_frame(data, names[i]) if decode == "device" else _pillow_frame(data, names[i])
+        except _lib.NtkError:
+            raise
+        except Exception as e:          # Pillow's errors do not name the file
+            raise ValueError("%s: %s" % (names[i], e))
+
+    probed = list(pool.map(load, range(n))) if pool is not None else [load(i) for i in range(n)]
+    for pr in probed:
+        if tuple(pr["size"]) != (H, W):
+            raise ValueError("%s: the file is %dx%d (height x width) but its clip's frames are %dx%d"
+                             % (pr["what"], pr["size"][0], pr["size"][1], H, W))
+    frame = H * W * 3
+    cell_index, start_index = np.full((T, B), -1, dtype=np.int32), np.full((B,), -1, dtype=np.int32)
+    offsets = []
+    for i, (t, b, _f) in enumerate(spec.cells):
+        if not (0 <= t < T and 0 <= b < B) or cell_index[t, b] >= 0:
+            raise ValueError("stage_round: cell (%d, %d) outside [%d,%d] or named twice" % (t, b, T, B))
+        cell_index[t, b] = i
+        offsets.append((t * B + b) * frame)
+    for k, (slot, _f) in enumerate(spec.starts):
+        if not 0 <= slot < B or start_index[slot] >= 0:
+            raise ValueError("stage_round: slot %d outside [0,%d) or reset twice" % (slot, B))
+        start_index[slot] = len(spec.cells) + k
+        offsets.append((T * B + k) * frame)
+    total = (T * B + len(spec.starts)) * frame
+    packed = pack_jpeg_frames(probed, [(0, 0, H, W)] * n, staging=staging, grow=grow, pool=pool, offsets=(offsets, total))
+    if decode == "host":                # the block goes to the tracker as it is: cells without a file are zero frames
+        block = packed.staging.pixels.numpy()[:T * B * frame].reshape(T * B, frame)
+        block[(cell_index < 0).reshape(-1)] = 0
+    return StagedRound(packed, spec, cell_index, start_index, names)
+
+
 def upload_staged(staged, device="cuda", reverse_image=False):
     """Device half of get_input_batch, on the current stream: -> get_input's four tensors."""
     dev = torch.device(device)
@@ -786,42 +892,52 @@ class JpegPart(object):
         self.on_device, self.host_ranges, self.paths = on_device, host_ranges, paths
 
 
+def _pillow_frame(data, what):
+    """File bytes -> _probe_frame's dict of a frame the host decodes: `image`, by Pillow (uint8 [H,W,3])."""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        img = np.asarray(im.convert("RGB"), dtype=np.uint8)
+    return {"data": None, "image": img, "size": img.shape[:2], "what": what}
+
+
 def _probe_frame(data, what):
     """File bytes -> dict: for a device frame `data`, the frame's size and the sizes of its stream and segment table; for any
     other file `image`, decoded by Pillow (uint8 [H,W,3])."""
     desc = np.zeros(JPEG_DESC_BYTES, np.uint8)
     rc, sbytes, nseg = _jpeg_parse_raw(data, desc, None, 0, 0, None, 0, 0, what)
     if rc == JPEG_HOST_PATH:
-        import io
-        from PIL import Image
-        with Image.open(io.BytesIO(data)) as im:
-            img = np.asarray(im.convert("RGB"), dtype=np.uint8)
-        return {"data": None, "image": img, "size": img.shape[:2], "what": what}
+        return _pillow_frame(data, what)
     hdr = desc[:4 * JPEG_DESC_HDR_WORDS].view(np.int32)
     return {"data": data, "image": None, "size": (int(hdr[JPEG_DESC["H"]]), int(hdr[JPEG_DESC["W"]])), "stream_bytes": sbytes,
             "n_segments": nseg, "what": what}
 
 
-def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, staging=None, grow=True, pool=None):
+def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, staging=None, grow=True, pool=None, offsets=None):
     """_probe_frame results and one rectangle (y0, x0, h, w) per frame -> PackedFrames whose `jpeg` part is filled: the frame
     table and boxes as pack_frames writes them; per device frame its descriptor, unstuffed scan and segment offsets in the staging
     set (written by ntk_jpeg_parse on `pool`'s threads: the one copy the file's bytes get); per other frame its rectangle's
     pixels.  The workspace is sized and each frame's share of it written into its descriptor (ntk_jpeg_decode_workspace_bytes).
-    Staging rules as in pack_frames (`grow`)."""
+    Staging rules as in pack_frames (`grow`).  `offsets`: (byte offset of each frame's rectangle in the pixel buffer, the buffer's
+    size in bytes) -- the caller's own layout, checked like every table row; None packs the rectangles back to back."""
     import ctypes
     n = len(probed)
     if n < 1 or n > MAX_FRAMES_PER_LAUNCH or len(rects) != n:
         raise ValueError("pack_jpeg_frames: %d frames (1..%d), %d rectangles" % (n, MAX_FRAMES_PER_LAUNCH, len(rects)))
+    if offsets is not None and len(offsets[0]) != n:
+        raise ValueError("pack_jpeg_frames: %d offsets for %d frames" % (len(offsets[0]), n))
     rows, off, soff, goff, place = [], 0, 0, 0, []
-    for pr, (y0, x0, h, w) in zip(probed, rects):
+    for i, (pr, (y0, x0, h, w)) in enumerate(zip(probed, rects)):
         H, W = pr["size"]
+        if offsets is not None:
+            off = int(offsets[0][i])
         rows.append((off, H, W, y0, x0, h, w))
         off += h * w * 3
         place.append((soff, goff))
         if pr["data"] is not None:
             soff += (len(pr["data"]) + 15) // 16 * 16           # the unstuffed scan is shorter than the file
             goff += pr["n_segments"] + 1
-    nbytes, sbytes, nsegs = off, max(soff, 16), max(goff, 2)
+    nbytes, sbytes, nsegs = off if offsets is None else int(offsets[1]), max(soff, 16), max(goff, 2)
     if staging is None:
         staging = Staging()
     if not (staging.fits(nbytes, n) and staging.fits_jpeg(sbytes, n, nsegs)):
@@ -858,10 +974,11 @@ def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, 
     return packed
 
 
-def decode_packed(packed, device):
+def decode_packed(packed, device, uploaded=None):
     """Device half of the JPEG path, on the current stream: upload the streams, descriptors, segment offsets and frame table of a
     PackedFrames with a `jpeg` part, and the pixel ranges the host decoded, into the staging set's device buffers (grown and
-    reused: no allocator call in the steady state but the status vector's), then ONE ntk_jpeg_decode_batch call.
+    reused: no allocator call in the steady state but the status vector's), then ONE ntk_jpeg_decode_batch call.  `uploaded`: an
+    event recorded behind the uploads and before the launch (what the owner of the pinned set waits for before refilling it).
     -> (pixels uint8 [nbytes], frame table int64 [n,7], status int32 [n]), all on the device."""
     L, P = _lib.lib(), _lib.ptr
     dev = torch.device(device)
@@ -873,6 +990,8 @@ def decode_packed(packed, device):
     table.copy_(packed.table, non_blocking=True)
     status = torch.zeros((n,), dtype=torch.int32, device=dev)   # outlives the staging set's reuse: read at a logged step
     if not any(j.on_device):
+        if uploaded is not None:
+            uploaded.record()
         return pix, table, status
     streams = st.device_buffer(dev, "streams", j.stream_bytes, torch.uint8)
     streams.copy_(st.streams[:j.stream_bytes], non_blocking=True)
@@ -881,6 +1000,8 @@ def decode_packed(packed, device):
     segs = st.device_buffer(dev, "segments", j.n_segments, torch.int32)
     segs.copy_(st.segments[:j.n_segments], non_blocking=True)
     ws = st.device_buffer(dev, "workspace", j.workspace_bytes, torch.uint8)
+    if uploaded is not None:
+        uploaded.record()
     _lib.check(L.ntk_jpeg_decode_batch(P(streams), j.stream_bytes, P(descs), P(segs), j.n_segments, P(table), P(pix), packed.nbytes,
                                        P(ws), j.workspace_bytes, P(status), n, _lib.stream()), "ntk_jpeg_decode_batch")
     return pix, table, status

@@ -7,7 +7,9 @@ accumulated in one device table (ntk_track_overlap_scores) that is read back onc
   Supervisor     the supervised protocol (a lost tracker is restarted from the ground truth): per-slot state and per-clip table
                  on the device (ntk_track_supervise), decided frame by frame without a read-back
   Validation     the driver: per round the resets, ONE track_clip and ONE scores.add, no host synchronisation after the first
-                 round of a frame size
+                 round of a frame size.  Clips given as image files are read a round at a time, a round ahead (data.stage_round,
+                 data.InputPrefetcher), and with decode="device" decoded on the device on a second stream
+                 (ntk_jpeg_decode_batch), ntk_track_decode_mask turning off the frames that could not be decoded
   validate       runs a Validation to the end; protocol="one_pass" (the default) or "supervised"
   write_trajectory   the toolkit's trajectory file of one clip, from regions() and codes()
 
@@ -36,11 +38,16 @@ SUP_CODE_INACTIVE, SUP_CODE_TRACKED, SUP_CODE_RESTART, SUP_CODE_FAILURE, SUP_COD
 PROTOCOLS = ("one_pass", "supervised")
 # include/ntmtrack.h NTK_POLY_*: a polygon region is POLY_DOUBLES doubles, the leading finite pairs its vertices, NaN after them
 POLY_MAX_POINTS, POLY_DOUBLES = 8, 16
+# include/ntmtrack.h NTK_CLIPDEC_*: the per-clip row of ntk_track_decode_mask (validation from files decoded on the device)
+CLIPDEC_DECODED, CLIPDEC_FAILED, CLIPDEC_MASKED, CLIPDEC_FIRST_FAILED, CLIPDEC_FIRST_STATUS, CLIPDEC_START_STATUS, CLIPDEC_HEAD = \
+    0, 1, 2, 3, 4, 5, 6
+ON_UNDECODED = ("raise", "skip")
 
 Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
 
 #: one clip of a validation set.  frames: [L,H,W,3] uint8 or float host array, or a callable returning one (called when the clip is
-#: scheduled).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker; or [L,2P] polygons (x0, y0, x1, y1,
+#: scheduled), or a list / tuple of L image files (paths, or the files' bytes): a FILE CLIP, read a round at a time and never held
+#: whole (size may then be None: it is read from the first file's header).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker; or [L,2P] polygons (x0, y0, x1, y1,
 #: ...) of 3 <= P <= 8 vertices, rows with fewer padded with NaN, the tracker then starts from row 0's bounding rectangle.  init:
 #: the region the tracker is started with when it is not that (the reference passes it normalised).  size: (H, W) where frames is a callable, so that
 #: clips can be grouped by frame size without decoding them.
@@ -338,6 +345,8 @@ class _SizeClass(object):
     def __init__(self, size, members):
         self.size, self.members, self.tracker = size, members, None      # members: the caller's clip indices, in order
         self.supervisor = None
+        self.files, self.prefetcher, self.dead = False, None, None       # file clips: their rounds' prefetcher; decode="device": the
+                                                                         # slots whose clip started from an undecodable frame
 
 
 class Validation(object):
@@ -355,13 +364,34 @@ class Validation(object):
 
     Clips with polygon regions ([L,2P]) are scored against the polygons in both protocols; their trackers start, and restart, from
     the polygons' bounding rectangles.  Rectangle clips in the same run are scored as 4-gons.  The polygons go up through the same
-    pinned asynchronous copy, so a round still makes no host synchronisation."""
+    pinned asynchronous copy, so a round still makes no host synchronisation.
+
+    File clips (Clip.frames a list of paths or bytes) are read a round at a time: a background data.InputPrefetcher reads round
+    r + 1 with ``workers`` pool threads (data.default_workers() when None) into one of ``prefetch`` pinned sets while round r
+    runs.  ``decode="host"``: Pillow decodes on those threads and the round runs as it does from arrays.  ``decode="device"``:
+    the round's files are decoded by ONE ntk_jpeg_decode_batch on a decode stream of this Validation's own, a round ahead of the
+    tracker; ntk_track_decode_mask turns off every frame the decoder could not deliver (and every frame of a clip whose starting
+    frame it could not), the tracker and the scores take the device tensors and the masked ``active``.  The two streams are
+    ordered by events alone ("set k decoded", "set k consumed"); the only host wait is the prefetcher's, for the uploads from
+    the pinned set it is about to refill.  ``finish()`` reads the per-clip decode table once: ``on_undecoded="raise"`` raises
+    NtkError naming the first undecodable file, ``"skip"`` leaves it at the report (``decode_report``, and ``"decode"`` in
+    validate's result).  A frame size holds either only file clips or none; array and callable clips run the code they always
+    ran, whatever ``decode`` says."""
 
     def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda",
-                 protocol="one_pass", skip=5, burn_in=10, failure_overlap=0.0):
+                 protocol="one_pass", skip=5, burn_in=10, failure_overlap=0.0, decode="host", prefetch=2, workers=None,
+                 on_undecoded="raise"):
         import torch
+        from . import data
         if protocol not in PROTOCOLS:
             raise ValueError("Validation: protocol %r; one of %s" % (protocol, ", ".join(PROTOCOLS)))
+        data._check_decode(decode)
+        if on_undecoded not in ON_UNDECODED:
+            raise ValueError("Validation: on_undecoded %r; one of %s" % (on_undecoded, ", ".join(ON_UNDECODED)))
+        if int(prefetch) < 1:
+            raise ValueError("Validation: prefetch=%d; at least 1" % prefetch)
+        self.decode, self.prefetch, self.on_undecoded = decode, int(prefetch), on_undecoded
+        self.workers = data.default_workers() if workers is None else max(1, int(workers))
         self.protocol = protocol
         self.make_tracker, self.device = make_tracker, torch.device(device)
         self.clips = [_as_clip(c) for c in clips]
@@ -375,10 +405,24 @@ class Validation(object):
         self._gt = [(rect_polygons(g) if g.shape[1] == 4 else pad_polygons(g)) for g in given] if self.polygons else given
         self._first = [g[0] if g.shape[1] == 4 else polygon_bounds(pad_polygons(g[0])) for g in given]
         self._held = {}                                 # clip index -> decoded frames, from its reset to its last frame
+        self._is_file = [isinstance(c.frames, (list, tuple)) for c in self.clips]
+        for i, c in enumerate(self.clips):
+            if self._is_file[i] and len(c.frames) != len(self._gt[i]):
+                raise ValueError("clip %d: %d files for %d regions" % (i, len(c.frames), len(self._gt[i])))
         classes = collections.OrderedDict()
         for i, c in enumerate(self.clips):
             classes.setdefault(self._size(i), []).append(i)
         self.classes = [_SizeClass(size, members) for size, members in classes.items()]
+        for cls in self.classes:
+            cls.files = any(self._is_file[i] for i in cls.members)
+            if cls.files and not all(self._is_file[i] for i in cls.members):
+                raise ValueError("Validation: the %dx%d clips are file clips and others (clips %s): a frame size holds either only "
+                                 "file clips or none" % (cls.size + (cls.members,)))
+        self.has_files = any(self._is_file)
+        self.decode_report = None                       # set by finish() of a run that had file clips
+        self._pool = self._decode_stream = self._dec_table = None
+        self._on_device = self._on_host = 0
+        self._consumed = {}                             # id(staging set) -> event: the tracking stream has read the set's buffers
         self.scores = OverlapScores(len(self.clips), iou_thresholds, dist_thresholds, device=self.device)
         self._sup_args = (skip, burn_in, failure_overlap) if protocol == "supervised" else None
         self.supervisor = None                          # made with the first round: it needs the schedule's effective B
@@ -399,6 +443,12 @@ class Validation(object):
         c = self.clips[i]
         if c.size is not None:
             return (int(c.size[0]), int(c.size[1]))
+        if self._is_file[i]:                            # the header of the first file
+            import io
+            from PIL import Image
+            f = c.frames[0]
+            with Image.open(io.BytesIO(bytes(f)) if isinstance(f, (bytes, bytearray, memoryview)) else f) as im:
+                return (int(im.size[1]), int(im.size[0]))
         if callable(c.frames):
             return tuple(np.asarray(c.frames()).shape[1:3])    # no size given: decoded for its shape alone and dropped again (pass
                                                                # size= to avoid the second decoding when the clip is scheduled)
@@ -421,18 +471,98 @@ class Validation(object):
         self._run(*nxt)
         return True
 
+    # ---- file clips: the round's files, staged a round ahead
+    def _round_files(self, cls, rnd):
+        """-> data.RoundFiles of a round of file clips: the file of every active cell and the starting frames of the resets."""
+        from .data import RoundFiles
+        T, B = rnd.active.shape
+        cells = [(int(t), int(b), self.clips[cls.members[int(rnd.clip_of[b])]].frames[int(rnd.frame_index[t, b])])
+                 for t, b in zip(*np.nonzero(rnd.active))]
+        starts = [(int(s), self.clips[cls.members[c]].frames[0]) for s, c in rnd.resets]
+        return RoundFiles(cls.size, T, B, cells, starts)
+
+    def _staged_round(self, cls):
+        """The next staged round of the class, from its prefetcher (made with the class's first round of files)."""
+        from . import data
+        if cls.prefetcher is None:
+            if self._pool is None and self.workers > 1:
+                from concurrent.futures import ThreadPoolExecutor
+                self._pool = ThreadPoolExecutor(max_workers=self.workers)
+            lengths = [len(self._gt[i]) for i in cls.members]
+            specs = (self._round_files(cls, rnd) for rnd in ClipSchedule(lengths, self.B, self.T))
+            stage = lambda spec, staging: data.stage_round(spec, staging, self._pool, grow=False, decode=self.decode)
+            cls.prefetcher = data.InputPrefetcher(specs, depth=self.prefetch, workers=1, stage=stage, decode=self.decode)
+        try:
+            return next(cls.prefetcher)
+        except StopIteration:
+            raise RuntimeError("Validation: the prefetcher ended before the schedule did")
+
+    def _decode_on_device(self, cls, rnd, staged, d_ids):
+        """Steps 1-3 of a decode="device" round: the uploads and ONE ntk_jpeg_decode_batch on the decode stream, then, on the
+        tracking stream and behind the "decoded" event, ntk_track_decode_mask.  -> (frames [T,B,H,W,3] and starting frames
+        [n_resets,H,W,3], uint8 views of the set's device pixel buffer, the masked active [T,B]); the caller records the set's
+        "consumed" event when the round's launches are enqueued."""
+        from . import _lib, data
+        from .online import _upload
+        import torch
+        T, B = rnd.active.shape
+        H, W = cls.size
+        tracking = torch.cuda.current_stream(self.device)
+        if self._decode_stream is None:
+            self._decode_stream = torch.cuda.Stream(self.device)
+            self._dec_table = torch.zeros((len(self.clips), CLIPDEC_HEAD), dtype=torch.int64, device=self.device)
+            self._dec_table[:, CLIPDEC_FIRST_FAILED] = -1
+            self._decode_stream.wait_stream(tracking)
+        if cls.dead is None:
+            cls.dead = torch.zeros((B,), dtype=torch.uint8, device=self.device)
+        key = id(staged.packed.staging)
+        staged.uploaded, decoded = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(self._decode_stream):
+            if key in self._consumed:
+                self._decode_stream.wait_event(self._consumed[key])
+            pix, _table, status = data.decode_packed(staged.packed, self.device, uploaded=staged.uploaded)
+            decoded.record()
+        # allocated under the decode stream, read on the tracking stream
+        pix.record_stream(tracking)
+        status.record_stream(tracking)
+        tracking.wait_event(decoded)
+        on_device = sum(staged.packed.jpeg.on_device)
+        self._on_device, self._on_host = self._on_device + on_device, self._on_host + staged.packed.n - on_device
+        active = _upload(rnd.active, torch.uint8, self.device)
+        cell_index = _upload(staged.cell_index, torch.int32, self.device)
+        start_index = _upload(staged.start_index, torch.int32, self.device)
+        P = _lib.ptr
+        _lib.check(_lib.lib().ntk_track_decode_mask(P(status), staged.packed.n, P(cell_index), P(start_index), P(d_ids), T, B,
+                                                    len(self.clips), P(cls.dead), P(active), P(self._dec_table), _lib.stream()),
+                   "ntk_track_decode_mask")
+        frame, n = H * W * 3, len(rnd.resets)
+        return pix[:T * B * frame].view(T, B, H, W, 3), pix[T * B * frame:(T * B + n) * frame].view(n, H, W, 3), active, key
+
     def _run(self, cls, rnd):
         from .online import _upload
         import torch
         T, B = rnd.active.shape
         H, W = cls.size
         ids = np.where(rnd.clip_of >= 0, np.asarray(cls.members, dtype=np.int64)[np.maximum(rnd.clip_of, 0)], -1).astype(np.int32)
+        staged = self._staged_round(cls) if cls.files else None
+        on_device = staged is not None and self.decode == "device"
+        active = key = None
+        if on_device:
+            d_ids = _upload(ids, torch.int32, self.device)
+            file_frames, file_firsts, active, key = self._decode_on_device(cls, rnd, staged, d_ids)
+        elif staged is not None:
+            file_frames, file_firsts = staged.host_frames()
+            self._on_host += staged.packed.n
         # (1) the slots that take a new clip
         if rnd.resets:
             slots = [s for s, _c in rnd.resets]
             new = [cls.members[c] for _s, c in rnd.resets]
-            firsts = [self._frames(i)[0] for i in new]
-            images = np.stack(firsts).astype(np.uint8 if all(f.dtype == np.uint8 for f in firsts) else np.float32, copy=False)
+            if staged is not None:
+                images = file_firsts if on_device else file_firsts.copy()      # staged in reset order; the host's copy is the
+                                                                               # caller's to keep, the pinned set is refilled
+            else:
+                firsts = [self._frames(i)[0] for i in new]
+                images = np.stack(firsts).astype(np.uint8 if all(f.dtype == np.uint8 for f in firsts) else np.float32, copy=False)
             regions = np.stack([self._init_region(i) for i in new])
             if cls.tracker is None:
                 assert slots == list(range(B))          # the first round of a schedule fills every slot, in order
@@ -448,39 +578,109 @@ class Validation(object):
             if cls.supervisor is not None:
                 cls.supervisor.start(slots)
         # (2) frames and ground truth of the round: zero frames (the crop kernel still reads them) and NaN boxes where inactive
-        held = [None if i < 0 else self._frames(int(i)) for i in ids]
-        u8 = all(h is None or h.dtype == np.uint8 for h in held)
-        frames = np.zeros((T, B, H, W, 3), dtype=np.uint8 if u8 else np.float32)
+        held = None
+        if on_device:
+            frames = file_frames                        # cells without a file hold whatever the buffer held: uint8, never read into a result
+        elif staged is not None:
+            # the pinned block (and the starting frames above) go up as they are, as track_clip would upload them; the prefetcher
+            # refills the set only after these copies have run
+            frames = _upload(file_frames, torch.uint8, self.device)
+            staged.uploaded = torch.cuda.Event()
+            staged.uploaded.record()
+        else:
+            held = [None if i < 0 else self._frames(int(i)) for i in ids]
+            u8 = all(h is None or h.dtype == np.uint8 for h in held)
+            frames = np.zeros((T, B, H, W, 3), dtype=np.uint8 if u8 else np.float32)
         gt = np.full((T, B, POLY_DOUBLES if self.polygons else 4), np.nan, dtype=np.float64)
         for b in range(B):
             n = int(rnd.active[:, b].sum())
             if n:
                 at = rnd.frame_index[:n, b]
-                frames[:n, b] = held[b][at[0]:at[-1] + 1]
                 gt[:n, b] = self._gt[int(ids[b])][at[0]:at[-1] + 1]
-                if at[-1] + 1 == len(self._gt[int(ids[b])]):
-                    del self._held[int(ids[b])]         # the clip has ended
-        active = _upload(rnd.active, torch.uint8, self.device)
+                if held is not None:
+                    frames[:n, b] = held[b][at[0]:at[-1] + 1]
+                    if at[-1] + 1 == len(self._gt[int(ids[b])]):
+                        del self._held[int(ids[b])]     # the clip has ended
+        if not on_device:
+            active = _upload(rnd.active, torch.uint8, self.device)
+            d_ids = _upload(ids, torch.int32, self.device)
         d_gt = _upload(gt, torch.float64, self.device)
-        d_ids = _upload(ids, torch.int32, self.device)
         # (3) one pass over the round, (4) one scoring launch
         if cls.supervisor is not None:
             out = cls.tracker.track_clip(frames, active=active, supervisor=cls.supervisor, gt=d_gt, clip_of=d_ids)
-            if self._keep is not None:
-                self._keep.append((out, rnd.frame_index, rnd.active, ids, cls.supervisor.codes))
-            return
-        out = cls.tracker.track_clip(frames, active=active)
-        self.scores.add(out, d_gt, d_ids, active=active)
+        else:
+            out = cls.tracker.track_clip(frames, active=active)
+            self.scores.add(out, d_gt, d_ids, active=active)
+        if on_device:                                   # "set k consumed": the decode stream may write the set's buffers again
+            self._consumed[key] = torch.cuda.Event()
+            self._consumed[key].record()
         if self._keep is not None:
-            self._keep.append((out, rnd.frame_index, rnd.active, ids, None))
+            # a decode="device" round keeps its masked active on the device: what was tracked is known when regions() reads it
+            self._keep.append((out, rnd.frame_index, active if on_device else rnd.active, ids,
+                               None if cls.supervisor is None else cls.supervisor.codes))
+
+    def close(self):
+        """Stops the prefetchers' threads and the decoder pool (finish() calls it; a run that is abandoned should)."""
+        for cls in self.classes:
+            if cls.prefetcher is not None:
+                cls.prefetcher.close()
+        if self._pool is not None:
+            self._pool.shutdown(wait=True)
+            self._pool = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _decode_report(self):
+        """The per-clip decode table, read once -> the ``decode`` part of the result (see validate)."""
+        n = len(self.clips)
+        table = np.zeros((n, CLIPDEC_HEAD), dtype=np.int64)
+        table[:, CLIPDEC_FIRST_FAILED] = -1
+        if self._dec_table is not None:
+            table = self._dec_table.cpu().numpy()
+        else:                                           # decode="host": a file that could not be decoded raised at its round
+            for i in range(n):
+                table[i, CLIPDEC_DECODED] = len(self._gt[i]) - 1 if self._is_file[i] else 0
+        failed_files = []
+        for i in np.nonzero((table[:, CLIPDEC_START_STATUS] != 0) | (table[:, CLIPDEC_FIRST_FAILED] >= 0))[0]:
+            start = table[i, CLIPDEC_START_STATUS] != 0
+            k = 0 if start else 1 + int(table[i, CLIPDEC_FIRST_FAILED])
+            f = self.clips[i].frames[k]
+            name = "<clip %d, frame %d>" % (i, k) if isinstance(f, (bytes, bytearray, memoryview)) else str(f)
+            failed_files.append((int(i), k, name, int(table[i, CLIPDEC_START_STATUS if start else CLIPDEC_FIRST_STATUS])))
+        col = lambda c: table[:, c].copy()
+        return {"clips": {"decoded": col(CLIPDEC_DECODED), "failed": col(CLIPDEC_FAILED), "masked": col(CLIPDEC_MASKED),
+                          "first_failed": col(CLIPDEC_FIRST_FAILED), "first_status": col(CLIPDEC_FIRST_STATUS),
+                          "start_status": col(CLIPDEC_START_STATUS)},
+                "decoded": int(table[:, CLIPDEC_DECODED].sum()), "failed": int(table[:, CLIPDEC_FAILED].sum()),
+                "masked": int(table[:, CLIPDEC_MASKED].sum()),
+                "clips_affected": len(failed_files), "frames_on_device": self._on_device, "frames_on_host": self._on_host,
+                "failed_files": [name for _i, _k, name, _s in failed_files], "_first": failed_files[:1]}
 
     def finish(self):
-        """Runs the remaining rounds; then asks every tracker that can tell (BatchDNCTracker.check) whether a launch failed."""
-        while self.step():
-            pass
+        """Runs the remaining rounds; then asks every tracker that can tell (BatchDNCTracker.check) whether a launch failed.  A
+        run with file clips then reads the decode table (once; ``decode_report``) and, with on_undecoded="raise", raises NtkError
+        naming the first undecodable file of the first affected clip."""
+        try:
+            while self.step():
+                pass
+        finally:
+            self.close()
         for cls in self.classes:
             if cls.tracker is not None and hasattr(cls.tracker, "check"):
                 cls.tracker.check()
+        if self.has_files and self.decode_report is None:
+            report = self._decode_report()
+            first = report.pop("_first")
+            self.decode_report = report
+            if first and self.on_undecoded == "raise":
+                from . import _lib, data
+                i, k, name, status = first[0]
+                raise _lib.NtkError("device JPEG decode of %s (clip %d, frame %d) failed: %s (status %d); %d clip(s) affected"
+                                    % (name, i, k, data.JPEG_STATUS.get(status, "unknown"), status, report["clips_affected"]))
         return self
 
     def regions(self):
@@ -490,6 +690,7 @@ class Validation(object):
         out = [np.full((len(g) - 1, 4), np.nan) for g in self._gt]
         for dev, frame_index, active, ids, codes in self._keep:
             host = dev.cpu().numpy()
+            active = active if isinstance(active, np.ndarray) else active.cpu().numpy()
             sat_out = None if codes is None else codes.cpu().numpy() == SUP_CODE_SKIPPED
             for t, b in zip(*np.nonzero(active)):
                 if sat_out is None or not sat_out[t, b]:
@@ -506,6 +707,7 @@ class Validation(object):
         out = [np.full((len(g) - 1,), SUP_CODE_INACTIVE, dtype=np.int8) for g in self._gt]
         for _dev, frame_index, active, ids, codes in self._keep:
             host = codes.cpu().numpy()
+            active = active if isinstance(active, np.ndarray) else active.cpu().numpy()
             for t, b in zip(*np.nonzero(active)):
                 out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
         return out
@@ -514,12 +716,20 @@ class Validation(object):
 def validate(make_tracker, clips, B, T, return_regions=False, **kw):
     """Validation(...) run to its end -> scores.result(), or (result, regions per clip) with return_regions=True.  With
     protocol="supervised" (and skip=, burn_in=, failure_overlap=) the result is the supervisor's (summarize_supervised) and
-    return_regions=True gives (result, regions per clip, codes per clip)."""
+    return_regions=True gives (result, regions per clip, codes per clip).  decode=, prefetch=, workers=, on_undecoded= go to
+    Validation; a run that had file clips gains ``result["decode"]``: ``clips`` (per clip ``decoded``, ``failed``, ``masked``,
+    ``first_failed``, ``first_status``, ``start_status``: the NTK_CLIPDEC_* row), the totals ``decoded``, ``failed``, ``masked``
+    and ``clips_affected``, ``frames_on_device`` / ``frames_on_host`` (files the device / Pillow decoded) and ``failed_files``
+    (per affected clip the file that failed first).  Results of runs without file clips keep their keys."""
     v = Validation(make_tracker, clips, B, T, return_regions=return_regions, **kw).finish()
     if v.protocol == "supervised":
         res = v.supervisor.result()
+    else:
+        res = v.scores.result()
+    if v.decode_report is not None:
+        res["decode"] = v.decode_report
+    if v.protocol == "supervised":
         return (res, v.regions(), v.codes()) if return_regions else res
-    res = v.scores.result()
     return (res, v.regions()) if return_regions else res
 
 
