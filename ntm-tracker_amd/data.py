@@ -211,10 +211,12 @@ def vot_clips(root, names=None, frames="arrays"):
     return clips
 
 
-def _decode_image(path):
+def _decode_image(file, dtype=np.float32):
+    """Pillow's RGB pixels of an image file (a path, or the file's bytes) -> `dtype` [H,W,3]: the one host decoder."""
+    import io
     from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert("RGB"), dtype=np.float32)
+    with Image.open(io.BytesIO(file) if isinstance(file, bytes) else file) as im:
+        return np.asarray(im.convert("RGB"), dtype=dtype)
 
 
 def preprocess_frame(image, cropbox, device, resize_to=(720, 1280), crop=224, out=None):
@@ -365,10 +367,11 @@ class Staging(object):
     def _new(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, pin_memory=self.pin)
 
-    def fits(self, nbytes, n):
-        return self.pixels.numel() >= nbytes and self.table.shape[0] >= n
+    def fits(self, nbytes, n, jpeg=None):
+        """Room for nbytes of pixels, n frames and, with `jpeg` = (stream bytes, segments), their JPEG part?"""
+        return self.pixels.numel() >= nbytes and self.table.shape[0] >= n and (jpeg is None or self.fits_jpeg(jpeg[0], n, jpeg[1]))
 
-    def ensure(self, nbytes, n):
+    def ensure(self, nbytes, n, jpeg=None):
         """Grow (with a quarter of headroom, so that batches of slightly different size do not grow it again)."""
         if self.pixels.numel() < nbytes:
             self.pixels = self._new((nbytes + nbytes // 4,), torch.uint8)
@@ -376,6 +379,8 @@ class Staging(object):
             self.table = self._new((n, FRAME_TABLE_COLS), torch.int64)
             self.boxes = self._new((n, 4), torch.float32)
             self.labels = self._new((n, 66), torch.float32)
+        if jpeg is not None:
+            self.ensure_jpeg(jpeg[0], n, jpeg[1])
 
     def fits_jpeg(self, stream_bytes, n, n_segments):
         return self.streams.numel() >= stream_bytes and self.descs.shape[0] >= n and self.segments.numel() >= n_segments
@@ -387,6 +392,21 @@ class Staging(object):
             self.descs = self._new((n, JPEG_DESC_BYTES), torch.uint8)
         if self.segments.numel() < n_segments:
             self.segments = self._new((n_segments + n_segments // 4,), torch.int32)
+
+    def adopt(self, packed):
+        """Move a batch that was packed into another set into this one: grow, copy what the batch uses of EVERY buffer a set has
+        (a buffer added above belongs in this list) -> the PackedFrames in this set."""
+        old, n, j = packed.staging, packed.n, packed.jpeg
+        jpeg = None if j is None else (j.stream_bytes, j.n_segments)
+        self.ensure(packed.nbytes, n, jpeg)
+        used = [("pixels", packed.nbytes), ("table", n), ("boxes", n), ("labels", n)]
+        if j is not None:
+            used += [("streams", jpeg[0]), ("descs", n), ("segments", jpeg[1])]
+        for name, k in used:
+            getattr(self, name)[:k].copy_(getattr(old, name)[:k])
+        moved = PackedFrames(self, packed.nbytes, n, packed.channels, packed.resize_to, packed.crop)
+        moved.jpeg = j
+        return moved
 
     def device_buffer(self, dev, name, numel, dtype):
         """The first `numel` elements of this set's device buffer `name` (grown with a quarter of headroom when too small)."""
@@ -408,6 +428,39 @@ class PackedFrames(object):
         self.status = None              # int32 [n] on the device after frames_crop_batch of such a batch
 
 
+def _check_pack(pack):
+    if pack not in ("rect", "full"):
+        raise ValueError("pack must be 'rect' or 'full', not %r" % (pack,))
+
+
+def _place(sizes, rects, channels, boxes, staging, grow, pad=0, offsets=None, jpeg=None):
+    """The layout-and-fit step of both packers.  sizes (H, W) and rects (y0, x0, h, w) per frame: the rectangles get their byte
+    offsets in the pixel buffer -- back to back behind `pad` bytes, or the caller's `offsets` = (offset per frame, the buffer's
+    size); the Staging set is chosen (`staging`, made when None; one that is too small for the pixels, the rows and the `jpeg` =
+    (stream bytes, segments) part grows, or with grow=False gives way to a fresh unpinned set); the frame table is written and
+    checked (check_frame_table) and the boxes (nullable) are written.  -> (the set, the table's rows, the pixel bytes)."""
+    n = len(rects)
+    rows, off = [], int(pad)
+    for i, ((H, W), (y0, x0, h, w)) in enumerate(zip(sizes, rects)):
+        if offsets is not None:
+            off = int(offsets[0][i])
+        rows.append((off, H, W, y0, x0, h, w))
+        off += h * w * channels
+    nbytes = off if offsets is None else int(offsets[1])
+    if staging is None:
+        staging = Staging()
+    if not staging.fits(nbytes, n, jpeg):
+        if not grow:
+            staging = Staging(pin=False)
+        staging.ensure(nbytes, n, jpeg)
+    table = staging.table.numpy()[:n]
+    table[:] = np.asarray(rows, dtype=np.int64)
+    check_frame_table(table, nbytes, channels)
+    if boxes is not None:
+        staging.boxes.numpy()[:n] = np.asarray(boxes, dtype=np.float64).reshape(n, 4).astype(np.float32)
+    return staging, rows, nbytes
+
+
 def pack_frames(images, cropboxes, resize_to=RESIZE_TO, crop=CROP, margin=2, pack="rect", staging=None, pad=0, grow=True):
     """uint8 images [H_i,W_i,C] and their crop boxes -> PackedFrames: the pixels ntk_frames_crop_batch may read, packed one frame
     after another behind `pad` leading bytes, with the int64 frame table and the fp32 boxes.  pack="rect" packs only
@@ -415,31 +468,18 @@ def pack_frames(images, cropboxes, resize_to=RESIZE_TO, crop=CROP, margin=2, pac
     fill (made when None); it grows when the batch needs more -- unless grow=False, when a batch that does not fit is packed
     into a fresh unpinned set instead (a thread that must make no device-runtime call packs this way).  Every table row is
     validated (check_frame_table)."""
-    if pack not in ("rect", "full"):
-        raise ValueError("pack must be 'rect' or 'full', not %r" % (pack,))
+    _check_pack(pack)
     n = len(images)
     if n < 1 or len(cropboxes) != n:
         raise ValueError("pack_frames: %d images, %d crop boxes" % (n, len(cropboxes)))
     C = int(images[0].shape[2])
-    rows, off = [], int(pad)
-    for img, box in zip(images, cropboxes):
+    for img in images:
         if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != C:
             raise ValueError("pack_frames: images must be uint8 [H,W,%d], not %s %s" % (C, img.dtype, img.shape))
-        H, W = img.shape[:2]
-        y0, x0, h, w = crop_source_rect((H, W), box, resize_to, crop, margin) if pack == "rect" else (0, 0, H, W)
-        rows.append((off, H, W, y0, x0, h, w))
-        off += h * w * C
-    nbytes = off
-    if staging is None:
-        staging = Staging()
-    if not staging.fits(nbytes, n):
-        if not grow:
-            staging = Staging(pin=False)
-        staging.ensure(nbytes, n)
-    table = staging.table.numpy()[:n]
-    table[:] = np.asarray(rows, dtype=np.int64)
-    check_frame_table(table, nbytes, C)
-    staging.boxes.numpy()[:n] = np.asarray(cropboxes, dtype=np.float64).reshape(n, 4).astype(np.float32)
+    sizes = [img.shape[:2] for img in images]
+    rects = [crop_source_rect(s, box, resize_to, crop, margin) if pack == "rect" else (0, 0) + tuple(s)
+             for s, box in zip(sizes, cropboxes)]
+    staging, rows, nbytes = _place(sizes, rects, C, cropboxes, staging, grow, pad=pad)
     buf = staging.pixels.numpy()
     buf[:pad] = 0
     for img, (o, _H, _W, y0, x0, h, w) in zip(images, rows):
@@ -481,16 +521,14 @@ def frames_crop_batch(packed, device="cuda", mean=None, flip_x=False, extrapolat
     return out
 
 
-def _decode_image_u8(path):
-    from PIL import Image
-    with Image.open(path) as im:
-        return np.asarray(im.convert("RGB"), dtype=np.uint8)
-
-
-def _load_frame(name, image_root):
+def _load_frame(name, image_root, decode="host"):
+    """-> (the frame's record, its image): decoded by Pillow (uint8 [H,W,3]), or with decode="device" probed (_probe_frame)."""
     rec = load_frame_record(name)
     path = rec["image_path"] if image_root is None else os.path.join(image_root, rec["image_path"])
-    return rec, _decode_image_u8(path)
+    if decode == "host":
+        return rec, _decode_image(path, np.uint8)
+    with open(path, "rb") as f:
+        return rec, _probe_frame(f.read(), path)
 
 
 class StagedBatch(object):
@@ -522,14 +560,16 @@ def stage_batch(frame_names_nosuffix, image_root=None, pool=None, pack="rect", s
     decode in upload_staged; any other file (PNG, progressive JPEG, ...) is decoded by Pillow as with decode="host" and its
     rectangle packed into the same set."""
     _check_decode(decode)
+    _check_pack(pack)
     names = list(frame_names_nosuffix)
-    if decode == "device":
-        return _stage_batch_device(names, image_root, pool, pack, staging, grow)
-    if pool is not None:
-        loaded = list(pool.map(lambda nm: _load_frame(nm, image_root), names))
+    load = lambda nm: _load_frame(nm, image_root, decode)
+    loaded = list(pool.map(load, names)) if pool is not None else [load(nm) for nm in names]
+    images, boxes = [img for _r, img in loaded], [r["cropbox"] for r, _i in loaded]
+    if decode == "host":
+        packed = pack_frames(images, boxes, pack=pack, staging=staging, grow=grow)
     else:
-        loaded = [_load_frame(nm, image_root) for nm in names]
-    packed = pack_frames([img for _r, img in loaded], [r["cropbox"] for r, _i in loaded], pack=pack, staging=staging, grow=grow)
+        rects = [crop_source_rect(pr["size"], box) if pack == "rect" else (0, 0) + tuple(pr["size"]) for pr, box in zip(images, boxes)]
+        packed = pack_jpeg_frames(images, rects, boxes, staging=staging, grow=grow, pool=pool)
     lab = packed.staging.labels.numpy()[:len(names)]
     for i, (rec, _img) in enumerate(loaded):
         lab[i, :64] = rec["gt"].reshape(-1)
@@ -591,7 +631,7 @@ def stage_round(spec, staging=None, pool=None, grow=True, decode="device"):
     def load(i):
         data, _what = _read_bytes(files[i])
         try:
-            return _probe_frame(data, names[i]) if decode == "device" else _pillow_frame(data, names[i])
+            return _probe_frame(data, names[i], decode)
         except _lib.NtkError:
             raise
         except Exception as e:          # Pillow's errors do not name the file
@@ -762,19 +802,8 @@ class InputPrefetcher(object):
         packed = getattr(staged, "packed", None)
         if packed is not None and packed.staging is not self._sets[k]:
             # the batch outgrew set k: grow the pinned set here, on the consumer's thread, and move the batch into it
-            old, st = packed.staging, self._sets[k]
-            st.ensure(packed.nbytes, packed.n)
-            st.pixels[:packed.nbytes].copy_(old.pixels[:packed.nbytes])
-            for a in ("table", "boxes", "labels"):
-                getattr(st, a)[:packed.n].copy_(getattr(old, a)[:packed.n])
-            staged.packed = PackedFrames(st, packed.nbytes, packed.n, packed.channels, packed.resize_to, packed.crop)
-            if packed.jpeg is not None:
-                j = staged.packed.jpeg = packed.jpeg
-                st.ensure_jpeg(j.stream_bytes, packed.n, j.n_segments)
-                st.streams[:j.stream_bytes].copy_(old.streams[:j.stream_bytes])
-                st.descs[:packed.n].copy_(old.descs[:packed.n])
-                st.segments[:j.n_segments].copy_(old.segments[:j.n_segments])
-            staged.labels = st.labels[:packed.n]
+            staged.packed = self._sets[k].adopt(packed)
+            staged.labels = self._sets[k].labels[:packed.n]
         return staged
 
     def close(self):
@@ -892,25 +921,18 @@ class JpegPart(object):
         self.on_device, self.host_ranges, self.paths = on_device, host_ranges, paths
 
 
-def _pillow_frame(data, what):
-    """File bytes -> _probe_frame's dict of a frame the host decodes: `image`, by Pillow (uint8 [H,W,3])."""
-    import io
-    from PIL import Image
-    with Image.open(io.BytesIO(data)) as im:
-        img = np.asarray(im.convert("RGB"), dtype=np.uint8)
-    return {"data": None, "image": img, "size": img.shape[:2], "what": what}
-
-
-def _probe_frame(data, what):
+def _probe_frame(data, what, decode="device"):
     """File bytes -> dict: for a device frame `data`, the frame's size and the sizes of its stream and segment table; for any
-    other file `image`, decoded by Pillow (uint8 [H,W,3])."""
-    desc = np.zeros(JPEG_DESC_BYTES, np.uint8)
-    rc, sbytes, nseg = _jpeg_parse_raw(data, desc, None, 0, 0, None, 0, 0, what)
-    if rc == JPEG_HOST_PATH:
-        return _pillow_frame(data, what)
-    hdr = desc[:4 * JPEG_DESC_HDR_WORDS].view(np.int32)
-    return {"data": data, "image": None, "size": (int(hdr[JPEG_DESC["H"]]), int(hdr[JPEG_DESC["W"]])), "stream_bytes": sbytes,
-            "n_segments": nseg, "what": what}
+    other file, and for every file with decode="host", `image`, decoded by Pillow (uint8 [H,W,3])."""
+    if decode == "device":
+        desc = np.zeros(JPEG_DESC_BYTES, np.uint8)
+        rc, sbytes, nseg = _jpeg_parse_raw(data, desc, None, 0, 0, None, 0, 0, what)
+        if rc != JPEG_HOST_PATH:
+            hdr = desc[:4 * JPEG_DESC_HDR_WORDS].view(np.int32)
+            return {"data": data, "image": None, "size": (int(hdr[JPEG_DESC["H"]]), int(hdr[JPEG_DESC["W"]])),
+                    "stream_bytes": sbytes, "n_segments": nseg, "what": what}
+    img = _decode_image(data, np.uint8)
+    return {"data": None, "image": img, "size": img.shape[:2], "what": what}
 
 
 def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, staging=None, grow=True, pool=None, offsets=None):
@@ -926,30 +948,15 @@ def pack_jpeg_frames(probed, rects, boxes=None, resize_to=RESIZE_TO, crop=CROP, 
         raise ValueError("pack_jpeg_frames: %d frames (1..%d), %d rectangles" % (n, MAX_FRAMES_PER_LAUNCH, len(rects)))
     if offsets is not None and len(offsets[0]) != n:
         raise ValueError("pack_jpeg_frames: %d offsets for %d frames" % (len(offsets[0]), n))
-    rows, off, soff, goff, place = [], 0, 0, 0, []
-    for i, (pr, (y0, x0, h, w)) in enumerate(zip(probed, rects)):
-        H, W = pr["size"]
-        if offsets is not None:
-            off = int(offsets[0][i])
-        rows.append((off, H, W, y0, x0, h, w))
-        off += h * w * 3
+    soff, goff, place = 0, 0, []
+    for pr in probed:
         place.append((soff, goff))
         if pr["data"] is not None:
             soff += (len(pr["data"]) + 15) // 16 * 16           # the unstuffed scan is shorter than the file
             goff += pr["n_segments"] + 1
-    nbytes, sbytes, nsegs = off if offsets is None else int(offsets[1]), max(soff, 16), max(goff, 2)
-    if staging is None:
-        staging = Staging()
-    if not (staging.fits(nbytes, n) and staging.fits_jpeg(sbytes, n, nsegs)):
-        if not grow:
-            staging = Staging(pin=False)
-        staging.ensure(nbytes, n)
-        staging.ensure_jpeg(sbytes, n, nsegs)
+    sbytes, nsegs = max(soff, 16), max(goff, 2)
+    staging, rows, nbytes = _place([pr["size"] for pr in probed], rects, 3, boxes, staging, grow, offsets=offsets, jpeg=(sbytes, nsegs))
     table = staging.table.numpy()[:n]
-    table[:] = np.asarray(rows, dtype=np.int64)
-    check_frame_table(table, nbytes, 3)
-    if boxes is not None:
-        staging.boxes.numpy()[:n] = np.asarray(boxes, dtype=np.float64).reshape(n, 4).astype(np.float32)
     buf, streams, descs, segs = staging.pixels.numpy(), staging.streams.numpy(), staging.descs.numpy(), staging.segments.numpy()
 
     def fill(i):
@@ -1036,28 +1043,3 @@ def decode_jpeg_batch(streams, rects=None, device="cuda", staging=None):
     packed = pack_jpeg_frames(probed, rects, staging=staging)
     pix, table, status = decode_packed(packed, device)
     return DecodedJpegs(packed, pix, table, status)
-
-
-def _load_frame_device(name, image_root):
-    rec = load_frame_record(name)
-    path = rec["image_path"] if image_root is None else os.path.join(image_root, rec["image_path"])
-    with open(path, "rb") as f:
-        data = f.read()
-    return rec, _probe_frame(data, path)
-
-
-def _stage_batch_device(names, image_root, pool, pack, staging, grow):
-    """stage_batch for decode="device"."""
-    if pack not in ("rect", "full"):
-        raise ValueError("pack must be 'rect' or 'full', not %r" % (pack,))
-    load = lambda nm: _load_frame_device(nm, image_root)
-    loaded = list(pool.map(load, names)) if pool is not None else [load(nm) for nm in names]
-    probed = [pr for _r, pr in loaded]
-    boxes = [r["cropbox"] for r, _p in loaded]
-    rects = [crop_source_rect(pr["size"], box) if pack == "rect" else (0, 0) + tuple(pr["size"]) for pr, box in zip(probed, boxes)]
-    packed = pack_jpeg_frames(probed, rects, boxes, staging=staging, grow=grow, pool=pool)
-    lab = packed.staging.labels.numpy()[:len(names)]
-    for i, (rec, _pr) in enumerate(loaded):
-        lab[i, :64] = rec["gt"].reshape(-1)
-        lab[i, 64], lab[i, 65] = rec["y_offset"], rec["x_offset"]
-    return StagedBatch(names, packed)

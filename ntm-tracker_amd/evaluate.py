@@ -7,9 +7,10 @@ accumulated in one device table (ntk_track_overlap_scores) that is read back onc
   Supervisor     the supervised protocol (a lost tracker is restarted from the ground truth): per-slot state and per-clip table
                  on the device (ntk_track_supervise), decided frame by frame without a read-back
   Validation     the driver: per round the resets, ONE track_clip and ONE scores.add, no host synchronisation after the first
-                 round of a frame size.  Clips given as image files are read a round at a time, a round ahead (data.stage_round,
-                 data.InputPrefetcher), and with decode="device" decoded on the device on a second stream
-                 (ntk_jpeg_decode_batch), ntk_track_decode_mask turning off the frames that could not be decoded
+                 round of a frame size.  The frames of a round come from the frame size's source: _ArraySource (arrays and
+                 callables), _HostFileSource (image files read a round at a time, a round ahead: data.stage_round,
+                 data.InputPrefetcher) or _DeviceFileSource (the files decoded on the device on a second stream,
+                 ntk_jpeg_decode_batch, ntk_track_decode_mask turning off the frames that could not be decoded)
   validate       runs a Validation to the end; protocol="one_pass" (the default) or "supervised"
   write_trajectory   the toolkit's trajectory file of one clip, from regions() and codes()
 
@@ -44,6 +45,13 @@ CLIPDEC_DECODED, CLIPDEC_FAILED, CLIPDEC_MASKED, CLIPDEC_FIRST_FAILED, CLIPDEC_F
 ON_UNDECODED = ("raise", "skip")
 
 Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
+
+
+def _upload(array, dtype, device):
+    """online._upload (host array -> device tensor through a pinned asynchronous copy: no synchronisation), imported at its first
+    use: this module stays importable without torch."""
+    from .online import _upload as upload
+    return upload(array, dtype, device)
 
 #: one clip of a validation set.  frames: [L,H,W,3] uint8 or float host array, or a callable returning one (called when the clip is
 #: scheduled), or a list / tuple of L image files (paths, or the files' bytes): a FILE CLIP, read a round at a time and never held
@@ -196,7 +204,6 @@ class OverlapScores(object):
 
     def _dev(self, x, dtype):
         import torch
-        from .online import _upload
         if torch.is_tensor(x) and x.device.type == self.device.type:
             return x.to(dtype).contiguous()
         return _upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, self.device)
@@ -290,7 +297,6 @@ class Supervisor(object):
 
     def start(self, slots):
         """The slots take a new clip: their state rows become (TRACK, 0, 0).  An index fill from a pinned upload: no synchronisation."""
-        from .online import _upload
         import torch
         slots = [int(s) for s in slots]
         if not all(0 <= s < self.B for s in slots):
@@ -342,11 +348,205 @@ def _as_clip(c):
 
 
 class _SizeClass(object):
-    def __init__(self, size, members):
-        self.size, self.members, self.tracker = size, members, None      # members: the caller's clip indices, in order
-        self.supervisor = None
-        self.files, self.prefetcher, self.dead = False, None, None       # file clips: their rounds' prefetcher; decode="device": the
-                                                                         # slots whose clip started from an undecodable frame
+    def __init__(self, size, members, schedule):
+        self.size, self.members, self.schedule = size, members, schedule      # members: the caller's clip indices, in order;
+        self.tracker = self.supervisor = None                                 # schedule() -> the ClipSchedule of their rounds
+        self.source = None              # where the rounds' frames come from: _ArraySource, _HostFileSource or _DeviceFileSource
+
+    def ids(self, rnd):
+        """int32 [B]: the caller's clip index of every slot of the round, -1 for a slot without a clip."""
+        return np.where(rnd.clip_of >= 0, np.asarray(self.members, dtype=np.int64)[np.maximum(rnd.clip_of, 0)], -1).astype(np.int32)
+
+
+RoundInput = collections.namedtuple("RoundInput", ["firsts", "frames", "active", "d_ids", "tracked"])
+
+
+class _Source(object):
+    """Where a size class's frames come from, one round at a time.  ``round(rnd, ids)`` -> RoundInput: firsts, the starting
+    images of the slots reset in the round, in reset order, as make_tracker and reset take them; frames [T,B,H,W,3], a host array
+    or a device tensor, as track_clip takes them; active uint8 [T,B] and d_ids int32 [B] on the device; tracked, the [T,B] mask
+    regions() reads: the schedule's, on the host, or `active` itself where the device turned frames off.  ``consumed()``: the
+    round's tracker and scoring launches are enqueued.  ``close()`` stops the source's own threads."""
+
+    def consumed(self):
+        pass
+
+    def close(self):
+        pass
+
+
+class _ArraySource(_Source):
+    """The frames of a size class whose clips are arrays or callables.  ``held``: clip index -> decoded frames, from the round
+    that resets the clip to the round that hands out its last frame."""
+
+    def __init__(self, cls, clips, lengths, device):
+        self.cls, self.clips, self.lengths, self.device, self.held = cls, clips, lengths, device, {}
+
+    def clip_frames(self, i):
+        if i not in self.held:
+            f = self.clips[i].frames
+            a = np.asarray(f() if callable(f) else f)
+            if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != self.lengths[i]:
+                raise ValueError("clip %d: frames %s for %d regions; expected [L,H,W,3]" % (i, a.shape, self.lengths[i]))
+            self.held[i] = a if a.dtype == np.uint8 else a.astype(np.float32, copy=False)
+        return self.held[i]
+
+    def host_round(self, rnd, ids):
+        """The host half (NumPy only) -> (firsts [n_resets,H,W,3] or None, frames [T,B,H,W,3]): uint8 where every clip involved
+        is, else float32; zero frames (the crop kernel still reads them) where a cell is inactive."""
+        T, B = rnd.active.shape
+        firsts = None
+        if rnd.resets:
+            firsts = [self.clip_frames(self.cls.members[c])[0] for _s, c in rnd.resets]
+            firsts = np.stack(firsts).astype(np.uint8 if all(f.dtype == np.uint8 for f in firsts) else np.float32, copy=False)
+        held = [None if i < 0 else self.clip_frames(int(i)) for i in ids]
+        u8 = all(h is None or h.dtype == np.uint8 for h in held)
+        frames = np.zeros((T, B) + tuple(self.cls.size) + (3,), dtype=np.uint8 if u8 else np.float32)
+        for b in range(B):
+            n = int(rnd.active[:, b].sum())
+            if n:
+                at = rnd.frame_index[:n, b]
+                frames[:n, b] = held[b][at[0]:at[-1] + 1]
+                if at[-1] + 1 == self.lengths[int(ids[b])]:
+                    del self.held[int(ids[b])]          # the clip has ended
+        return firsts, frames
+
+    def round(self, rnd, ids):
+        import torch
+        firsts, frames = self.host_round(rnd, ids)
+        return RoundInput(firsts, frames, _upload(rnd.active, torch.uint8, self.device), _upload(ids, torch.int32, self.device),
+                          rnd.active)
+
+
+class _FileDecoding(object):
+    """What the file sources of ONE Validation share: the pool of reader threads, the decode stream, the per-clip decode table
+    of all clips (ntk_track_decode_mask's) and the counts of files decoded on either side."""
+
+    def __init__(self, decode, prefetch, workers, n_clips, device):
+        self.decode, self.prefetch, self.workers, self.n_clips, self.device = decode, prefetch, workers, n_clips, device
+        self.pool = self.stream = self.table = None
+        self.frames_on_device = self.frames_on_host = 0
+
+    def reader_pool(self):
+        if self.pool is None and self.workers > 1:
+            from concurrent.futures import ThreadPoolExecutor
+            self.pool = ThreadPoolExecutor(max_workers=self.workers)
+        return self.pool
+
+    def decode_stream(self, tracking):
+        """The decode stream, made behind the tracking stream's work at its first use, with the decode table."""
+        import torch
+        if self.stream is None:
+            self.stream = torch.cuda.Stream(self.device)
+            self.table = torch.zeros((self.n_clips, CLIPDEC_HEAD), dtype=torch.int64, device=self.device)
+            self.table[:, CLIPDEC_FIRST_FAILED] = -1
+            self.stream.wait_stream(tracking)
+        return self.stream
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown(wait=True)
+            self.pool = None
+
+
+class _HostFileSource(_Source):
+    """The frames of a size class of file clips, decoded by Pillow: a data.InputPrefetcher (made with the first round) stages
+    round r + 1 while round r runs; the pinned block goes up as it is, as track_clip would upload it."""
+
+    def __init__(self, cls, clips, shared):
+        self.cls, self.shared, self.prefetcher = cls, shared, None
+        self.files = [clips[i].frames for i in cls.members]
+
+    def round_files(self, rnd):
+        """-> data.RoundFiles of a round: the file of every active cell and the starting frames of the resets."""
+        from .data import RoundFiles
+        T, B = rnd.active.shape
+        cells = [(int(t), int(b), self.files[int(rnd.clip_of[b])][int(rnd.frame_index[t, b])]) for t, b in zip(*np.nonzero(rnd.active))]
+        starts = [(int(s), self.files[c][0]) for s, c in rnd.resets]
+        return RoundFiles(self.cls.size, T, B, cells, starts)
+
+    def staged_round(self):
+        """The next staged round, in the schedule's order."""
+        from . import data
+        sh = self.shared
+        if self.prefetcher is None:
+            pool = sh.reader_pool()
+            specs = (self.round_files(rnd) for rnd in self.cls.schedule())
+            stage = lambda spec, staging: data.stage_round(spec, staging, pool, grow=False, decode=sh.decode)
+            self.prefetcher = data.InputPrefetcher(specs, depth=sh.prefetch, workers=1, stage=stage, decode=sh.decode)
+        try:
+            return next(self.prefetcher)
+        except StopIteration:
+            raise RuntimeError("Validation: the prefetcher ended before the schedule did")
+
+    def round(self, rnd, ids):
+        import torch
+        staged, dev = self.staged_round(), self.shared.device
+        frames, firsts = staged.host_frames()
+        self.shared.frames_on_host += staged.packed.n
+        firsts = firsts.copy()                          # the caller's to keep: the pinned set is refilled
+        frames = _upload(frames, torch.uint8, dev)
+        staged.uploaded = torch.cuda.Event()            # the prefetcher refills the set only after this copy has run
+        staged.uploaded.record()
+        return RoundInput(firsts, frames, _upload(rnd.active, torch.uint8, dev), _upload(ids, torch.int32, dev), rnd.active)
+
+    def close(self):
+        if self.prefetcher is not None:
+            self.prefetcher.close()
+
+
+class _DeviceFileSource(_HostFileSource):
+    """The same files decoded on the device: ONE ntk_jpeg_decode_batch per round on the shared decode stream, a round ahead of
+    the tracker, and ntk_track_decode_mask on the tracking stream.  The two streams are ordered by events alone: "set k decoded"
+    and "set k consumed" (the tracking stream has read the set's device buffers: the decode stream may write them again)."""
+
+    def __init__(self, cls, clips, shared):
+        _HostFileSource.__init__(self, cls, clips, shared)
+        self.dead = None                # uint8 [B] on the device: the slots whose clip started from an undecodable frame
+        self.was_consumed, self.current = {}, None      # id(staging set) -> its "consumed" event; the set of the round under way
+
+    def round(self, rnd, ids):
+        """-> frames [T,B,H,W,3] and starting frames [n_resets,H,W,3] as uint8 views of the set's device pixel buffer (cells
+        without a file hold whatever the buffer held: never read into a result) and the masked active."""
+        from . import _lib, data
+        import torch
+        sh, dev = self.shared, self.shared.device
+        T, B = rnd.active.shape
+        H, W = self.cls.size
+        staged = self.staged_round()
+        d_ids = _upload(ids, torch.int32, dev)
+        tracking = torch.cuda.current_stream(dev)
+        stream = sh.decode_stream(tracking)
+        if self.dead is None:
+            self.dead = torch.zeros((B,), dtype=torch.uint8, device=dev)
+        self.current = id(staged.packed.staging)
+        staged.uploaded, decoded = torch.cuda.Event(), torch.cuda.Event()
+        with torch.cuda.stream(stream):
+            if self.current in self.was_consumed:
+                stream.wait_event(self.was_consumed[self.current])
+            pix, _table, status = data.decode_packed(staged.packed, dev, uploaded=staged.uploaded)
+            decoded.record()
+        # allocated under the decode stream, read on the tracking stream
+        pix.record_stream(tracking)
+        status.record_stream(tracking)
+        tracking.wait_event(decoded)
+        on_device = sum(staged.packed.jpeg.on_device)
+        sh.frames_on_device, sh.frames_on_host = sh.frames_on_device + on_device, sh.frames_on_host + staged.packed.n - on_device
+        active = _upload(rnd.active, torch.uint8, dev)
+        cell_index = _upload(staged.cell_index, torch.int32, dev)
+        start_index = _upload(staged.start_index, torch.int32, dev)
+        P = _lib.ptr
+        _lib.check(_lib.lib().ntk_track_decode_mask(P(status), staged.packed.n, P(cell_index), P(start_index), P(d_ids), T, B,
+                                                    sh.n_clips, P(self.dead), P(active), P(sh.table), _lib.stream()),
+                   "ntk_track_decode_mask")
+        frame, n = H * W * 3, len(rnd.resets)
+        return RoundInput(pix[T * B * frame:(T * B + n) * frame].view(n, H, W, 3), pix[:T * B * frame].view(T, B, H, W, 3),
+                          active, d_ids, active)
+
+    def consumed(self):
+        import torch
+        event = self.was_consumed[self.current] = torch.cuda.Event()
+        event.record()
 
 
 class Validation(object):
@@ -404,25 +604,27 @@ class Validation(object):
         self.polygons = any(g.shape[1] != 4 for g in given)
         self._gt = [(rect_polygons(g) if g.shape[1] == 4 else pad_polygons(g)) for g in given] if self.polygons else given
         self._first = [g[0] if g.shape[1] == 4 else polygon_bounds(pad_polygons(g[0])) for g in given]
-        self._held = {}                                 # clip index -> decoded frames, from its reset to its last frame
         self._is_file = [isinstance(c.frames, (list, tuple)) for c in self.clips]
+        lengths = [len(g) for g in self._gt]
         for i, c in enumerate(self.clips):
-            if self._is_file[i] and len(c.frames) != len(self._gt[i]):
-                raise ValueError("clip %d: %d files for %d regions" % (i, len(c.frames), len(self._gt[i])))
+            if self._is_file[i] and len(c.frames) != lengths[i]:
+                raise ValueError("clip %d: %d files for %d regions" % (i, len(c.frames), lengths[i]))
         classes = collections.OrderedDict()
         for i, c in enumerate(self.clips):
             classes.setdefault(self._size(i), []).append(i)
-        self.classes = [_SizeClass(size, members) for size, members in classes.items()]
+        self.classes = [_SizeClass(size, members, lambda m=members: ClipSchedule([lengths[i] for i in m], self.B, self.T))
+                        for size, members in classes.items()]
+        self._files = _FileDecoding(decode, self.prefetch, self.workers, len(self.clips), self.device)
         for cls in self.classes:
-            cls.files = any(self._is_file[i] for i in cls.members)
-            if cls.files and not all(self._is_file[i] for i in cls.members):
+            if not any(self._is_file[i] for i in cls.members):
+                cls.source = _ArraySource(cls, self.clips, lengths, self.device)
+            elif all(self._is_file[i] for i in cls.members):
+                cls.source = (_DeviceFileSource if decode == "device" else _HostFileSource)(cls, self.clips, self._files)
+            else:
                 raise ValueError("Validation: the %dx%d clips are file clips and others (clips %s): a frame size holds either only "
                                  "file clips or none" % (cls.size + (cls.members,)))
         self.has_files = any(self._is_file)
         self.decode_report = None                       # set by finish() of a run that had file clips
-        self._pool = self._decode_stream = self._dec_table = None
-        self._on_device = self._on_host = 0
-        self._consumed = {}                             # id(staging set) -> event: the tracking stream has read the set's buffers
         self.scores = OverlapScores(len(self.clips), iou_thresholds, dist_thresholds, device=self.device)
         self._sup_args = (skip, burn_in, failure_overlap) if protocol == "supervised" else None
         self.supervisor = None                          # made with the first round: it needs the schedule's effective B
@@ -430,15 +632,6 @@ class Validation(object):
         self._rounds = self._all_rounds()
 
     # ---- clips
-    def _frames(self, i):
-        if i not in self._held:
-            f = self.clips[i].frames
-            a = np.asarray(f() if callable(f) else f)
-            if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != len(self._gt[i]):
-                raise ValueError("clip %d: frames %s for %d regions; expected [L,H,W,3]" % (i, a.shape, len(self._gt[i])))
-            self._held[i] = a if a.dtype == np.uint8 else a.astype(np.float32, copy=False)
-        return self._held[i]
-
     def _size(self, i):
         c = self.clips[i]
         if c.size is not None:
@@ -461,7 +654,7 @@ class Validation(object):
     # ---- rounds
     def _all_rounds(self):
         for cls in self.classes:
-            for rnd in ClipSchedule([len(self._gt[i]) for i in cls.members], self.B, self.T):
+            for rnd in cls.schedule():
                 yield cls, rnd
 
     def step(self):
@@ -471,102 +664,18 @@ class Validation(object):
         self._run(*nxt)
         return True
 
-    # ---- file clips: the round's files, staged a round ahead
-    def _round_files(self, cls, rnd):
-        """-> data.RoundFiles of a round of file clips: the file of every active cell and the starting frames of the resets."""
-        from .data import RoundFiles
-        T, B = rnd.active.shape
-        cells = [(int(t), int(b), self.clips[cls.members[int(rnd.clip_of[b])]].frames[int(rnd.frame_index[t, b])])
-                 for t, b in zip(*np.nonzero(rnd.active))]
-        starts = [(int(s), self.clips[cls.members[c]].frames[0]) for s, c in rnd.resets]
-        return RoundFiles(cls.size, T, B, cells, starts)
-
-    def _staged_round(self, cls):
-        """The next staged round of the class, from its prefetcher (made with the class's first round of files)."""
-        from . import data
-        if cls.prefetcher is None:
-            if self._pool is None and self.workers > 1:
-                from concurrent.futures import ThreadPoolExecutor
-                self._pool = ThreadPoolExecutor(max_workers=self.workers)
-            lengths = [len(self._gt[i]) for i in cls.members]
-            specs = (self._round_files(cls, rnd) for rnd in ClipSchedule(lengths, self.B, self.T))
-            stage = lambda spec, staging: data.stage_round(spec, staging, self._pool, grow=False, decode=self.decode)
-            cls.prefetcher = data.InputPrefetcher(specs, depth=self.prefetch, workers=1, stage=stage, decode=self.decode)
-        try:
-            return next(cls.prefetcher)
-        except StopIteration:
-            raise RuntimeError("Validation: the prefetcher ended before the schedule did")
-
-    def _decode_on_device(self, cls, rnd, staged, d_ids):
-        """Steps 1-3 of a decode="device" round: the uploads and ONE ntk_jpeg_decode_batch on the decode stream, then, on the
-        tracking stream and behind the "decoded" event, ntk_track_decode_mask.  -> (frames [T,B,H,W,3] and starting frames
-        [n_resets,H,W,3], uint8 views of the set's device pixel buffer, the masked active [T,B]); the caller records the set's
-        "consumed" event when the round's launches are enqueued."""
-        from . import _lib, data
-        from .online import _upload
-        import torch
-        T, B = rnd.active.shape
-        H, W = cls.size
-        tracking = torch.cuda.current_stream(self.device)
-        if self._decode_stream is None:
-            self._decode_stream = torch.cuda.Stream(self.device)
-            self._dec_table = torch.zeros((len(self.clips), CLIPDEC_HEAD), dtype=torch.int64, device=self.device)
-            self._dec_table[:, CLIPDEC_FIRST_FAILED] = -1
-            self._decode_stream.wait_stream(tracking)
-        if cls.dead is None:
-            cls.dead = torch.zeros((B,), dtype=torch.uint8, device=self.device)
-        key = id(staged.packed.staging)
-        staged.uploaded, decoded = torch.cuda.Event(), torch.cuda.Event()
-        with torch.cuda.stream(self._decode_stream):
-            if key in self._consumed:
-                self._decode_stream.wait_event(self._consumed[key])
-            pix, _table, status = data.decode_packed(staged.packed, self.device, uploaded=staged.uploaded)
-            decoded.record()
-        # allocated under the decode stream, read on the tracking stream
-        pix.record_stream(tracking)
-        status.record_stream(tracking)
-        tracking.wait_event(decoded)
-        on_device = sum(staged.packed.jpeg.on_device)
-        self._on_device, self._on_host = self._on_device + on_device, self._on_host + staged.packed.n - on_device
-        active = _upload(rnd.active, torch.uint8, self.device)
-        cell_index = _upload(staged.cell_index, torch.int32, self.device)
-        start_index = _upload(staged.start_index, torch.int32, self.device)
-        P = _lib.ptr
-        _lib.check(_lib.lib().ntk_track_decode_mask(P(status), staged.packed.n, P(cell_index), P(start_index), P(d_ids), T, B,
-                                                    len(self.clips), P(cls.dead), P(active), P(self._dec_table), _lib.stream()),
-                   "ntk_track_decode_mask")
-        frame, n = H * W * 3, len(rnd.resets)
-        return pix[:T * B * frame].view(T, B, H, W, 3), pix[T * B * frame:(T * B + n) * frame].view(n, H, W, 3), active, key
-
     def _run(self, cls, rnd):
-        from .online import _upload
         import torch
         T, B = rnd.active.shape
-        H, W = cls.size
-        ids = np.where(rnd.clip_of >= 0, np.asarray(cls.members, dtype=np.int64)[np.maximum(rnd.clip_of, 0)], -1).astype(np.int32)
-        staged = self._staged_round(cls) if cls.files else None
-        on_device = staged is not None and self.decode == "device"
-        active = key = None
-        if on_device:
-            d_ids = _upload(ids, torch.int32, self.device)
-            file_frames, file_firsts, active, key = self._decode_on_device(cls, rnd, staged, d_ids)
-        elif staged is not None:
-            file_frames, file_firsts = staged.host_frames()
-            self._on_host += staged.packed.n
+        ids = cls.ids(rnd)
+        inp = cls.source.round(rnd, ids)                # the round's frames, from wherever the class's clips keep them
         # (1) the slots that take a new clip
         if rnd.resets:
             slots = [s for s, _c in rnd.resets]
-            new = [cls.members[c] for _s, c in rnd.resets]
-            if staged is not None:
-                images = file_firsts if on_device else file_firsts.copy()      # staged in reset order; the host's copy is the
-                                                                               # caller's to keep, the pinned set is refilled
-            else:
-                firsts = [self._frames(i)[0] for i in new]
-                images = np.stack(firsts).astype(np.uint8 if all(f.dtype == np.uint8 for f in firsts) else np.float32, copy=False)
-            regions = np.stack([self._init_region(i) for i in new])
+            regions = np.stack([self._init_region(cls.members[c]) for _s, c in rnd.resets])
             if cls.tracker is None:
                 assert slots == list(range(B))          # the first round of a schedule fills every slot, in order
-                cls.tracker = self.make_tracker(images, regions)
+                cls.tracker = self.make_tracker(inp.firsts, regions)
                 if self._sup_args is not None:          # one state per frame size (its own B), one table for all
                     cls.supervisor = Supervisor(B, len(self.clips), *self._sup_args, device=self.device)
                     if self.supervisor is None:
@@ -574,59 +683,33 @@ class Validation(object):
                     else:
                         cls.supervisor.table = self.supervisor.table
             else:
-                cls.tracker.reset(slots, images, regions)
+                cls.tracker.reset(slots, inp.firsts, regions)
             if cls.supervisor is not None:
                 cls.supervisor.start(slots)
-        # (2) frames and ground truth of the round: zero frames (the crop kernel still reads them) and NaN boxes where inactive
-        held = None
-        if on_device:
-            frames = file_frames                        # cells without a file hold whatever the buffer held: uint8, never read into a result
-        elif staged is not None:
-            # the pinned block (and the starting frames above) go up as they are, as track_clip would upload them; the prefetcher
-            # refills the set only after these copies have run
-            frames = _upload(file_frames, torch.uint8, self.device)
-            staged.uploaded = torch.cuda.Event()
-            staged.uploaded.record()
-        else:
-            held = [None if i < 0 else self._frames(int(i)) for i in ids]
-            u8 = all(h is None or h.dtype == np.uint8 for h in held)
-            frames = np.zeros((T, B, H, W, 3), dtype=np.uint8 if u8 else np.float32)
+        # (2) the ground truth of the round: NaN boxes where inactive
         gt = np.full((T, B, POLY_DOUBLES if self.polygons else 4), np.nan, dtype=np.float64)
         for b in range(B):
             n = int(rnd.active[:, b].sum())
             if n:
                 at = rnd.frame_index[:n, b]
                 gt[:n, b] = self._gt[int(ids[b])][at[0]:at[-1] + 1]
-                if held is not None:
-                    frames[:n, b] = held[b][at[0]:at[-1] + 1]
-                    if at[-1] + 1 == len(self._gt[int(ids[b])]):
-                        del self._held[int(ids[b])]     # the clip has ended
-        if not on_device:
-            active = _upload(rnd.active, torch.uint8, self.device)
-            d_ids = _upload(ids, torch.int32, self.device)
         d_gt = _upload(gt, torch.float64, self.device)
         # (3) one pass over the round, (4) one scoring launch
         if cls.supervisor is not None:
-            out = cls.tracker.track_clip(frames, active=active, supervisor=cls.supervisor, gt=d_gt, clip_of=d_ids)
+            out = cls.tracker.track_clip(inp.frames, active=inp.active, supervisor=cls.supervisor, gt=d_gt, clip_of=inp.d_ids)
         else:
-            out = cls.tracker.track_clip(frames, active=active)
-            self.scores.add(out, d_gt, d_ids, active=active)
-        if on_device:                                   # "set k consumed": the decode stream may write the set's buffers again
-            self._consumed[key] = torch.cuda.Event()
-            self._consumed[key].record()
+            out = cls.tracker.track_clip(inp.frames, active=inp.active)
+            self.scores.add(out, d_gt, inp.d_ids, active=inp.active)
+        cls.source.consumed()                           # the round's launches are enqueued
         if self._keep is not None:
-            # a decode="device" round keeps its masked active on the device: what was tracked is known when regions() reads it
-            self._keep.append((out, rnd.frame_index, active if on_device else rnd.active, ids,
-                               None if cls.supervisor is None else cls.supervisor.codes))
+            self._keep.append((out, rnd.frame_index, inp.tracked, ids, None if cls.supervisor is None else cls.supervisor.codes))
 
     def close(self):
-        """Stops the prefetchers' threads and the decoder pool (finish() calls it; a run that is abandoned should)."""
+        """Stops the sources' threads and the reader pool (finish() calls it; a run that is abandoned should)."""
         for cls in self.classes:
-            if cls.prefetcher is not None:
-                cls.prefetcher.close()
-        if self._pool is not None:
-            self._pool.shutdown(wait=True)
-            self._pool = None
+            if cls.source is not None:
+                cls.source.close()
+        self._files.close()
 
     def __del__(self):
         try:
@@ -639,8 +722,8 @@ class Validation(object):
         n = len(self.clips)
         table = np.zeros((n, CLIPDEC_HEAD), dtype=np.int64)
         table[:, CLIPDEC_FIRST_FAILED] = -1
-        if self._dec_table is not None:
-            table = self._dec_table.cpu().numpy()
+        if self._files.table is not None:
+            table = self._files.table.cpu().numpy()
         else:                                           # decode="host": a file that could not be decoded raised at its round
             for i in range(n):
                 table[i, CLIPDEC_DECODED] = len(self._gt[i]) - 1 if self._is_file[i] else 0
@@ -657,7 +740,8 @@ class Validation(object):
                           "start_status": col(CLIPDEC_START_STATUS)},
                 "decoded": int(table[:, CLIPDEC_DECODED].sum()), "failed": int(table[:, CLIPDEC_FAILED].sum()),
                 "masked": int(table[:, CLIPDEC_MASKED].sum()),
-                "clips_affected": len(failed_files), "frames_on_device": self._on_device, "frames_on_host": self._on_host,
+                "clips_affected": len(failed_files), "frames_on_device": self._files.frames_on_device,
+                "frames_on_host": self._files.frames_on_host,
                 "failed_files": [name for _i, _k, name, _s in failed_files], "_first": failed_files[:1]}
 
     def finish(self):
@@ -688,14 +772,19 @@ class Validation(object):
         if self._keep is None:
             raise ValueError("Validation: made without return_regions=True")
         out = [np.full((len(g) - 1, 4), np.nan) for g in self._gt]
-        for dev, frame_index, active, ids, codes in self._keep:
-            host = dev.cpu().numpy()
-            active = active if isinstance(active, np.ndarray) else active.cpu().numpy()
-            sat_out = None if codes is None else codes.cpu().numpy() == SUP_CODE_SKIPPED
-            for t, b in zip(*np.nonzero(active)):
-                if sat_out is None or not sat_out[t, b]:
+        for host, codes, frame_index, ids, cells in self._kept(regions=True):
+            for t, b in cells:
+                if codes is None or codes[t, b] != SUP_CODE_SKIPPED:
                     out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
         return out
+
+    def _kept(self, regions):
+        """Per kept round -> (the tracked regions [T,B,4] when `regions` is set, the supervisor's codes [T,B] or None, frame_index,
+        clip ids, the tracked cells (t, b)): the device tensors as host arrays (synchronises)."""
+        for dev, frame_index, tracked, ids, codes in self._keep:
+            host = dev.cpu().numpy() if regions else None
+            tracked = tracked if isinstance(tracked, np.ndarray) else tracked.cpu().numpy()    # a mask the device decided
+            yield host, None if codes is None else codes.cpu().numpy(), frame_index, ids, list(zip(*np.nonzero(tracked)))
 
     def codes(self):
         """protocol="supervised": what each clip's slot did on each tracked frame, a list of [L-1] int8 host arrays beside
@@ -705,11 +794,9 @@ class Validation(object):
         if self._keep is None or self.protocol != "supervised":
             raise ValueError("Validation: codes() needs protocol=\"supervised\" and return_regions=True")
         out = [np.full((len(g) - 1,), SUP_CODE_INACTIVE, dtype=np.int8) for g in self._gt]
-        for _dev, frame_index, active, ids, codes in self._keep:
-            host = codes.cpu().numpy()
-            active = active if isinstance(active, np.ndarray) else active.cpu().numpy()
-            for t, b in zip(*np.nonzero(active)):
-                out[int(ids[b])][frame_index[t, b] - 1] = host[t, b]
+        for _host, codes, frame_index, ids, cells in self._kept(regions=False):
+            for t, b in cells:
+                out[int(ids[b])][frame_index[t, b] - 1] = codes[t, b]
         return out
 
 
@@ -722,15 +809,13 @@ def validate(make_tracker, clips, B, T, return_regions=False, **kw):
     and ``clips_affected``, ``frames_on_device`` / ``frames_on_host`` (files the device / Pillow decoded) and ``failed_files``
     (per affected clip the file that failed first).  Results of runs without file clips keep their keys."""
     v = Validation(make_tracker, clips, B, T, return_regions=return_regions, **kw).finish()
-    if v.protocol == "supervised":
-        res = v.supervisor.result()
-    else:
-        res = v.scores.result()
+    supervised = v.protocol == "supervised"
+    res = (v.supervisor if supervised else v.scores).result()
     if v.decode_report is not None:
         res["decode"] = v.decode_report
-    if v.protocol == "supervised":
-        return (res, v.regions(), v.codes()) if return_regions else res
-    return (res, v.regions()) if return_regions else res
+    if not return_regions:
+        return res
+    return (res, v.regions()) + ((v.codes(),) if supervised else ())
 
 
 def write_trajectory(path, first_region, regions, codes=None):

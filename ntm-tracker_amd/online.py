@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .evaluate import POLY_DOUBLES          # one polygon region of the ground truth (include/ntmtrack.h NTK_POLY_DOUBLES)
 from .ntm import NTMCell, _P, _np, gemm_nt
 from .tracker import GRID_N, GRID_START, GRID_STEP, NUM_FEATURES
 from .vgg import VGG16Conv43
@@ -122,7 +123,6 @@ class NTMTracker(object):
 # ---- batched online tracker: boxes, crops and state stay on the device ---------------------------------------------------
 
 STATE_DOUBLES = 10           # include/ntmtrack.h NTK_TRACK_STATE_*: [w, h, object box y1 x1 y2 x2, crop box y1 x1 y2 x2]
-POLY_DOUBLES = 16            # include/ntmtrack.h NTK_POLY_DOUBLES: one polygon region of the ground truth
 
 
 def _upload(array, dtype, device):

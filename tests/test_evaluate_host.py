@@ -192,5 +192,53 @@ def test_lazy_clips_without_a_size_are_probed_and_not_kept():
     clips = [E.Clip(lazy(0, 16, 24), regions), E.Clip(lazy(1, 32, 24), regions), E.Clip(lazy(2, 16, 24), regions, size=(16, 24)),
              {"frames": np.zeros((3, 32, 24, 3), dtype=np.uint8), "regions": regions}]
     v = E.Validation(None, clips, 2, 2, device="cpu")
-    assert calls == [0, 1] and v._held == {}
+    assert calls == [0, 1] and [c.source.held for c in v.classes] == [{}, {}]
     assert [(c.size, c.members) for c in v.classes] == [((16, 24), [0, 2]), ((32, 24), [1, 3])]
+
+
+@pytest.mark.parametrize("float_clip", [None, 2])
+def test_array_source_builds_every_round_on_the_host(float_clip):
+    """The host half of the array source (NumPy only: no device): over the whole schedule every active cell of the [T,B,H,W,3]
+    block holds its clip's frame and every inactive one zeros, the starting frames are frame 0 of the clips reset, in reset
+    order, a clip is held from its reset to the round that hands out its last frame, and a callable is called once when its
+    clip is scheduled (and once before, for its size, when it names none).  Frame k of clip i is filled with 16 i + k.  A round
+    that involves a float clip is float32, any other stays uint8."""
+    from ntmtrack import evaluate as E
+    lengths, H, W, B, T = [3, 2, 6, 4, 5], 8, 12, 2, 2
+    calls = []
+
+    def frames_of(i, dtype=np.uint8):
+        return np.stack([np.full((H, W, 3), 16 * i + k, dtype=dtype) for k in range(lengths[i])])
+
+    def lazy(i):
+        return lambda: calls.append(i) or frames_of(i)
+    regions = [np.tile(np.array([2.0, 2.0, 4.0, 4.0]), (n, 1)) for n in lengths]
+    clips = [E.Clip(frames_of(0), regions[0]), E.Clip(lazy(1), regions[1], size=(H, W)),
+             E.Clip(frames_of(2, np.uint8 if float_clip is None else np.float64), regions[2]), E.Clip(lazy(3), regions[3]),
+             E.Clip(frames_of(4), regions[4])]
+    v = E.Validation(None, clips, B, T, device="cpu")
+    (cls,) = v.classes
+    assert calls == [3] and cls.size == (H, W) and cls.source.held == {}
+    dtype_with = lambda members: np.float32 if float_clip in members else np.uint8
+    rounds = 0
+    for rnd in E.ClipSchedule(lengths, B, T):
+        ids = cls.ids(rnd)
+        assert ids.tolist() == rnd.clip_of.tolist()
+        firsts, frames = cls.source.host_round(rnd, ids)
+        assert frames.shape == (T, B, H, W, 3) and frames.dtype == dtype_with(ids.tolist())
+        left = set()
+        for b in range(B):
+            for t in range(T):
+                assert (frames[t, b] == (16 * ids[b] + rnd.frame_index[t, b] if rnd.active[t, b] else 0)).all()
+            n = int(rnd.active[:, b].sum())
+            if n and rnd.frame_index[n - 1, b] + 1 < lengths[ids[b]]:
+                left.add(int(ids[b]))
+        assert set(cls.source.held) == left                         # gone with the round that hands out its last frame
+        if rnd.resets:
+            new = [c for _s, c in rnd.resets]
+            assert firsts.shape == (len(new), H, W, 3) and firsts.dtype == dtype_with(new)
+            assert all((f == 16 * c).all() for f, c in zip(firsts, new))
+        else:
+            assert firsts is None
+        rounds += 1
+    assert rounds == 5 and cls.source.held == {} and calls == [3, 1, 3]

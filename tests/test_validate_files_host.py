@@ -85,7 +85,7 @@ def test_every_round_stages_its_own_files_and_no_other(file_clips, decode):
     cls = v.classes[0]
     seen, rounds = set(), 0
     for rnd in E.ClipSchedule(F.LENGTHS, B, T):
-        spec = v._round_files(cls, rnd)
+        spec = cls.source.round_files(rnd)
         staged = data.stage_round(spec, data.Staging(pin=False), decode=decode)
         rounds += 1
         want = [clips[int(rnd.clip_of[b])].frames[int(rnd.frame_index[t, b])] for t, b in zip(*np.nonzero(rnd.active))]
@@ -162,6 +162,54 @@ def test_pack_jpeg_frames_without_offsets_writes_todays_table(file_clips):
     assert (moved.table.numpy()[:, 1:] == packed.table.numpy()[:, 1:]).all()
     with pytest.raises(ValueError):                                 # a rectangle that leaves the buffer
         data.pack_jpeg_frames(probed, rects, staging=data.Staging(pin=False), offsets=([0, 20000, 49000], 50000))
+
+
+def test_the_two_packers_place_alike_and_a_packed_batch_moves_whole(file_clips):
+    """pack_frames and pack_jpeg_frames share one layout-and-fit step: on the same rectangles of the same files (Pillow's
+    pixels) they write the same table rows and pixel bytes, both pack a batch that does not fit with grow=False into an
+    unpinned set of its own, and Staging.adopt copies what a batch uses of every buffer a set has."""
+    import torch
+    from ntmtrack import data
+    _clips, contents = file_clips
+    files = [contents[0][0], contents[3][1], contents[4][2]]
+    rects = [(0, 0, F.H, F.W), (3, 5, 40, 33), (10, 0, 17, F.W)]
+    cut = [np.ascontiguousarray(J.pillow_decode(f)[y:y + h, x:x + w]) for f, (y, x, h, w) in zip(files, rects)]
+    boxes = [(0.1, 0.2, 0.8, 0.9), (0.0, 0.0, 1.0, 1.0), (0.3, 0.1, 0.6, 0.7)]
+    as_probed = [{"data": None, "image": img, "size": img.shape[:2], "what": "image %d" % i} for i, img in enumerate(cut)]
+    whole = [(0, 0) + img.shape[:2] for img in cut]
+    given = [data.Staging(pin=False), data.Staging(pin=False)]
+    a = data.pack_frames(cut, boxes, pack="full", staging=given[0], grow=False)
+    b = data.pack_jpeg_frames(as_probed, whole, boxes, staging=given[1], grow=False)
+    assert a.nbytes == b.nbytes == sum(img.size for img in cut) and a.n == b.n == 3
+    want = [[sum(i.size for i in cut[:k]), h, w, 0, 0, h, w] for k, (_y, _x, h, w) in enumerate(rects)]
+    assert a.table.numpy().tolist() == want and b.table.numpy().tolist() == want
+    assert a.pixels.numpy().tobytes() == b.pixels.numpy().tobytes() == b"".join(img.tobytes() for img in cut)
+    assert a.boxes.numpy().tobytes() == b.boxes.numpy().tobytes() == np.asarray(boxes, np.float32).tobytes()
+    for packed, st in zip((a, b), given):                           # did not fit, must not grow: a fresh unpinned set
+        assert packed.staging is not st and packed.staging.pin is False and st.pixels.numel() == 0 and st.table.shape[0] == 0
+    again = data.pack_frames(cut, boxes, pack="full", staging=given[0])
+    assert again.staging is given[0] and data.pack_jpeg_frames(as_probed, whole, boxes, staging=given[1]).staging is given[1]
+    assert again.table.numpy().tolist() == a.table.numpy().tolist()
+    # the same rectangles of the whole files, every file decoded by the host: the same offsets and pixel bytes
+    host = [data._probe_frame(f, "file %d" % i, decode="host") for i, f in enumerate(files)]
+    c = data.pack_jpeg_frames(host, rects, staging=data.Staging(pin=False))
+    assert c.jpeg.on_device == [False] * 3 and c.table.numpy()[:, 0].tolist() == a.table.numpy()[:, 0].tolist()
+    assert c.pixels.numpy().tobytes() == a.pixels.numpy().tobytes()
+    # adopt: frames for the device decoder, so that the streams, descriptors and segments are in use
+    probed = [data._probe_frame(f, "file %d" % i) for i, f in enumerate(files)]
+    old = data.pack_jpeg_frames(probed, rects, boxes, staging=data.Staging(pin=False))
+    assert old.jpeg.on_device == [True] * 3
+    old.staging.pixels.numpy()[:old.nbytes] = np.arange(old.nbytes) % 251   # the device frames' pixels are not written on the host
+    old.staging.labels.numpy()[:3] = np.arange(3 * 66, dtype=np.float32).reshape(3, 66)
+    new = data.Staging(pin=False)
+    moved = new.adopt(old)
+    j = old.jpeg
+    used = {"pixels": old.nbytes, "table": 3, "boxes": 3, "labels": 3, "streams": j.stream_bytes, "descs": 3, "segments": j.n_segments}
+    assert set(used) == {name for name, t in vars(new).items() if torch.is_tensor(t)}       # every buffer a set has
+    for name, k in used.items():
+        assert k > 0 and torch.equal(getattr(new, name)[:k], getattr(old.staging, name)[:k]), name
+    assert moved.staging is new and moved.jpeg is j and (moved.nbytes, moved.n, moved.channels) == (old.nbytes, 3, 3)
+    assert (moved.resize_to, moved.crop) == (old.resize_to, old.crop) and torch.equal(moved.table, old.table)
 
 
 # ------------------------------------------------------------------------------------------------- ntk_track_decode_mask
