@@ -1050,6 +1050,66 @@ int ntk_track_supervise_poly(int phase, const double* regions, const double* gt,
                              int B, int n_clips, int skip, int burn_in, double failure_overlap, int* state, double* table,
                              unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou, void* stream);
 
+/* Segmentation-mask ground truth (the VOT short-term sets from 2020 on annotate every frame with a run-length coded mask, the
+ * line "m x0,y0,w,h,c0,c1,..." of groundtruth.txt).  The tracker still emits rectangles: a mask is scored against the tracker's
+ * rectangle, the way the VOT toolkit scores a rectangle tracker on a mask set.  Nothing in the reference reads masks (its vot.py
+ * predates them) and the toolkit is not part of this project: THE RULES BELOW ARE THE CONTRACT.  They are modelled on the
+ * toolkit's behaviour; THE RULE THAT RASTERISES A FRACTIONAL RECTANGLE IS THE PROJECT'S OWN.
+ *
+ * A set of n masks on the device:
+ *   cells  int32 [n, NTK_MASK_CELL_INTS]: one mask is (x0, y0, w, h, first, count): (x0, y0, w, h) its box in frame pixels,
+ *          first and count name its counts rle[first, first + count)
+ *   rle    int32 [n_rle]: the toolkit's counts as they are.  Even-indexed counts (the first is index 0) are runs of zeros,
+ *          odd-indexed counts runs of ones, in row-major order over the w x h box.  Pixels the counts do not reach are zero;
+ *          pixels the counts run past w h are dropped (as NumPy's slice assignment drops them).
+ * A mask is PRESENT when w > 0, h > 0 and w h <= NTK_MASK_MAX_PIXELS; first >= 0, count >= 0 and first + count <= n_rle; every
+ * count is >= 0; and at least one pixel inside the box is set.  Anything else is an absent object, exactly as a non-finite or
+ * empty box is for the rectangle entries.  The kernels stay inside rle[0, n_rle) for ANY contents of cells.
+ * One 64-lane workgroup handles one mask and the counts are never rasterised: the workgroup walks the counts 64 at a time, a
+ * wave inclusive scan plus a carry gives every run its start s, and a run of ones [s, s + len), clipped to w h, is handled in
+ * closed form, in integer arithmetic: |M| gains len; the run bounds rows s / w .. (s + len - 1) / w, and columns s % w ..
+ * (s + len - 1) % w when it lies in one row, 0 .. w - 1 when it crosses a row end; |M n R| gains the first partial row, the last
+ * partial row and (middle rows inside R's rows) x (R's columns inside the box).  The sums are reduced across the wave; plain
+ * vector stores, no atomics.
+ *
+ * THE PIXEL SET OF A PREDICTED RECTANGLE (x, y, w, h): negative sizes are clamped to 0 and the rectangle is taken to corners
+ * first (x2 = x + w), like every other overlap here.  Pixel (c, r) belongs to it when its centre (c + 0.5, r + 0.5) lies in
+ * [x, x2) x [y, y2): the columns ceil(x - 0.5) .. ceil(x2 - 0.5) - 1, the rows by the same rule, so an integer rectangle covers
+ * exactly its w h pixels.  |R| is the product of the two counts as doubles (no FMA contraction).  The rectangle is NOT clipped to
+ * the frame, as for rectangles and polygons.  A rectangle that is not finite has |R| = |M n R| = 0.
+ *
+ * ntk_track_mask_bounds: rects double [n,4] = (min col, min row, max col + 1 - min col, max row + 1 - min row) over the set
+ * pixels, in frame pixels, and area double [n] = |M|; an absent mask gives four NaNs and a NaN area.  This rectangle starts and
+ * restarts a tracker, and the centre distance is taken to its centre.
+ * ntk_track_mask_overlaps: regions double [n,4] -> overlap double [n, NTK_MASK_OVERLAP_DOUBLES] = (|M n R|, |R|, |M|) per mask,
+ * every value an exact integer held in a double; an absent mask gives NaNs.
+ * Errors of both, before any launch: NTK_ERR_BAD_PTR for a null pointer; NTK_ERR_BAD_SHAPE, the values named in ntk_last_error,
+ * for n <= 0 or n_rle < 0.
+ *
+ * ntk_track_overlap_scores_mask: ntk_track_overlap_scores with gt replaced by rects double [T,B,4] (ntk_track_mask_bounds) and
+ * overlap double [T,B,NTK_MASK_OVERLAP_DOUBLES] (ntk_track_mask_overlaps of the regions).  "Ground truth finite with w > 0 and
+ * h > 0" is read on rects; the overlap is I / ((R + M) - I), one float64 division, and 0.0 when I == 0 (a prediction that is not
+ * finite scores 0 as everywhere); the centre distance goes to the centre of rects.  Table layout, skip rules, thresholds,
+ * frame_iou, row ownership, frame-order accumulation and the error checks (a null overlap included) are those of
+ * ntk_track_overlap_scores.  A filled integer rectangle as a mask, against an integer prediction, leaves the bits of
+ * ntk_track_overlap_scores on the two boxes.
+ * ntk_track_supervise_mask: ntk_track_supervise with gt replaced by rects double [B,4] and overlap double
+ * [B,NTK_MASK_OVERLAP_DOUBLES]; overlap is read by judge only and may be null in plan.  Every other rule and every error check
+ * is unchanged.  The caller hands the restarted slots' rects to ntk_track_restart_boxes. */
+#define NTK_MASK_CELL_INTS        6
+#define NTK_MASK_OVERLAP_DOUBLES  3
+#define NTK_MASK_MAX_PIXELS       (1 << 30)
+int ntk_track_mask_bounds(const int* cells, const int* rle, int n_rle, int n, double* rects, double* area, void* stream);
+int ntk_track_mask_overlaps(const double* regions, const int* cells, const int* rle, int n_rle, int n, double* overlap,
+                            void* stream);
+int ntk_track_overlap_scores_mask(const double* regions, const double* rects, const double* overlap, const unsigned char* active,
+                                  const int* clip_of, int T, int B, int n_clips, const double* iou_thr, int n_iou,
+                                  const double* dist_thr, int n_dist, double* table, double* frame_iou, void* stream);
+int ntk_track_supervise_mask(int phase, const double* regions, const double* rects, const double* overlap,
+                             const unsigned char* active, const int* clip_of, int B, int n_clips, int skip, int burn_in,
+                             double failure_overlap, int* state, double* table, unsigned char* track, unsigned char* restart,
+                             signed char* codes, double* frame_iou, void* stream);
+
 /* Validation from image files decoded on the device (ntk_jpeg_decode_batch): which frames of a round may be tracked and scored.
  * A file can turn out undecodable only on the device; this entry turns such a frame off in the round's mask before the tracker
  * and the scoring launch read it, so that nothing is read back per round.  One launch per round, one thread per slot, which

@@ -136,6 +136,10 @@ def _sig(lib):
         "ntk_track_poly_bounds": (c_int, [P, c_int, P, P]),
         "ntk_track_overlap_scores_poly": (c_int, [P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
         "ntk_track_supervise_poly": (c_int, [c_int, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
+        "ntk_track_mask_bounds": (c_int, [P, P, c_int, c_int, P, P, P]),
+        "ntk_track_mask_overlaps": (c_int, [P, P, P, c_int, c_int, P, P]),
+        "ntk_track_overlap_scores_mask": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
+        "ntk_track_supervise_mask": (c_int, [c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
         "ntk_track_decode_mask": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P]),
         "ntk_select_rows": (c_int, [P, P, P, P, c_int, c_int, P]),
         "ntk_dnc_state_keep": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),

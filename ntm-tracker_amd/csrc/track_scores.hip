@@ -1,6 +1,7 @@
-// The validation protocol on the device: the overlap of a tracked rectangle with rectangle or polygon ground truth (the VOT / OTB
-// overlap, float64; polygons by Sutherland-Hodgman clipping, contract: include/ntmtrack.h, NTK_POLY_*), the per-clip overlap
-// tables (NTK_SCORE_*) and the supervised protocol's state machine (NTK_SUP_*).  One thread per slot; no atomics.
+// The validation protocol on the device: the overlap of a tracked rectangle with rectangle, polygon or mask ground truth (the VOT /
+// OTB overlap, float64; polygons by Sutherland-Hodgman clipping, contract: include/ntmtrack.h, NTK_POLY_*; masks from the pixel
+// counts of ntk_track_mask_overlaps, track_masks.hip, NTK_MASK_*), the per-clip overlap tables (NTK_SCORE_*) and the supervised
+// protocol's state machine (NTK_SUP_*).  One thread per slot; no atomics.
 #include "common.h"
 
 namespace {      // the overlap functions; the kernels below keep their external names
@@ -46,18 +47,26 @@ __device__ __forceinline__ double shoelace_area(const double* pts, int n) {
     return fabs(s) / 2;
 }
 
-// The ground truth of one frame as both kernels see it: the rectangle (the region itself, or the polygon's bounding rectangle:
-// the true minimum and maximum over its vertices), and for a polygon its vertex count and area.
+// What the ground truth of a frame is: a rectangle, a polygon of NTK_POLY_DOUBLES doubles, or a mask, given as its bounding
+// rectangle (ntk_track_mask_bounds) beside the pixel counts of ntk_track_mask_overlaps.
+enum class Gt { RECT, POLY, MASK };
+
+template <Gt KIND>
+constexpr int gt_doubles() { return KIND == Gt::POLY ? NTK_POLY_DOUBLES : 4; }
+
+// The ground truth of one frame as both kernels see it: the rectangle (the region itself, the polygon's bounding rectangle -- the
+// true minimum and maximum over its vertices -- or the mask's), and for a polygon its vertex count and area.
 struct Truth {
     double x, y, w, h, area;
     int n;
 };
 
-// -> present.  POLY: at least 3 vertices, a bounding rectangle with w > 0 and h > 0, a shoelace area > 0.
-template <bool POLY>
+// -> present.  POLY: at least 3 vertices, a bounding rectangle with w > 0 and h > 0, a shoelace area > 0.  MASK: as RECT, on the
+// mask's bounding rectangle (four NaNs for an absent mask).
+template <Gt KIND>
 __device__ __forceinline__ bool read_truth(const double* g, Truth& tr) {
 #pragma clang fp contract(off)
-    if constexpr (!POLY) {
+    if constexpr (KIND != Gt::POLY) {
         tr.x = g[0]; tr.y = g[1]; tr.w = g[2]; tr.h = g[3];
         tr.area = 0.0; tr.n = 0;
         return finite4(g) && g[2] > 0 && g[3] > 0;
@@ -124,9 +133,19 @@ __device__ __forceinline__ double poly_iou(double px, double py, double pw, doub
     return iou > 1.0 ? 1.0 : iou;
 }
 
-template <bool POLY>
-__device__ __forceinline__ double truth_iou(double px, double py, double pw, double ph, const double* g, const Truth& tr) {
-    if constexpr (POLY) return poly_iou(px, py, pw, ph, g, tr);
+// Overlap with a mask from ov = (|M n R|, |R|, |M|), whole numbers in doubles: I / ((R + M) - I), one division; 0.0 when I == 0.
+__device__ __forceinline__ double mask_iou(const double* ov) {
+#pragma clang fp contract(off)
+    if (!(ov[0] > 0)) return 0.0;
+    return ov[0] / ((ov[1] + ov[2]) - ov[0]);
+}
+
+// ov: the frame's NTK_MASK_OVERLAP_DOUBLES counts, read for MASK only.
+template <Gt KIND>
+__device__ __forceinline__ double truth_iou(double px, double py, double pw, double ph, const double* g, const Truth& tr,
+                                            const double* ov) {
+    if constexpr (KIND == Gt::POLY) return poly_iou(px, py, pw, ph, g, tr);
+    else if constexpr (KIND == Gt::MASK) return mask_iou(ov);
     else return rect_iou(px, py, pw, ph, tr.x, tr.y, tr.w, tr.h);
 }
 
@@ -137,7 +156,7 @@ __global__ void track_poly_bounds_kernel(const double* __restrict__ poly, int n,
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Truth tr;
-    const bool present = read_truth<true>(poly + (size_t)NTK_POLY_DOUBLES * i, tr);
+    const bool present = read_truth<Gt::POLY>(poly + (size_t)NTK_POLY_DOUBLES * i, tr);
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
     double* r = rects + 4 * (size_t)i;
     r[0] = present ? tr.x : nan; r[1] = present ? tr.y : nan; r[2] = present ? tr.w : nan; r[3] = present ? tr.h : nan;
@@ -148,15 +167,17 @@ __global__ void track_poly_bounds_kernel(const double* __restrict__ poly, int n,
 // end, the threshold counts are incremented in place.  The row belongs to this thread alone (two slots never share a row: the
 // caller's contract), so a clip's sums are formed in frame order and no atomics are needed.  A slot whose row is outside
 // [0, n_clips) reads nothing but clip_of[b].  POLY: the ground truth is a polygon of NTK_POLY_DOUBLES doubles per frame; the
-// overlap is poly_iou and the centre distance is taken to the centre of its bounding rectangle.
-template <bool POLY>
+// overlap is poly_iou and the centre distance is taken to the centre of its bounding rectangle.  MASK: gt holds the masks'
+// bounding rectangles and `overlap` [T,B,NTK_MASK_OVERLAP_DOUBLES] their pixel counts against the regions (null otherwise).
+template <Gt KIND>
 __global__ void track_overlap_scores_kernel(const double* __restrict__ regions, const double* __restrict__ gt,
-                                            const unsigned char* __restrict__ active, const int* __restrict__ clip_of, int T, int B,
+                                            const double* __restrict__ overlap, const unsigned char* __restrict__ active,
+                                            const int* __restrict__ clip_of, int T, int B,
                                             int n_clips, const double* __restrict__ iou_thr, int n_iou,
                                             const double* __restrict__ dist_thr, int n_dist, double* __restrict__ table,
                                             double* __restrict__ frame_iou) {
 #pragma clang fp contract(off)
-    constexpr int GT = POLY ? NTK_POLY_DOUBLES : 4;
+    constexpr int GT = gt_doubles<KIND>();
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const double nan = __longlong_as_double(0x7ff8000000000000LL);
@@ -173,7 +194,7 @@ __global__ void track_overlap_scores_kernel(const double* __restrict__ regions, 
         const size_t at = (size_t)t * B + b;
         const double* g = gt + GT * at;
         Truth tr;
-        const bool scored = (!active || active[at]) && read_truth<POLY>(g, tr);
+        const bool scored = (!active || active[at]) && read_truth<KIND>(g, tr);
         if (!scored) {
             if (frame_iou) frame_iou[at] = nan;
             continue;
@@ -182,7 +203,7 @@ __global__ void track_overlap_scores_kernel(const double* __restrict__ regions, 
         double iou = 0.0;
         if (finite4(p)) {
             const double pw = fmax(p[2], 0.0), ph = fmax(p[3], 0.0);
-            iou = truth_iou<POLY>(p[0], p[1], pw, ph, g, tr);
+            iou = truth_iou<KIND>(p[0], p[1], pw, ph, g, tr, overlap + NTK_MASK_OVERLAP_DOUBLES * at);
             const double dx = (p[0] + pw / 2) - (tr.x + tr.w / 2), dy = (p[1] + ph / 2) - (tr.y + tr.h / 2);
             const double dist = sqrt(dx * dx + dy * dy);
             sum_dist += dist;
@@ -209,8 +230,8 @@ __global__ void track_overlap_scores_kernel(const double* __restrict__ regions, 
 // The supervised protocol's state machine (contract: include/ntmtrack.h, NTK_SUP_*), one thread per slot, one frame per call.
 // plan decides before the frame's pass what every slot does on it; judge scores the tracked slots after the pass with the one
 // overlap of the overlap table and moves a failed slot to WAIT.  The table row belongs to the slot's thread alone.  POLY: the ground
-// truth is a polygon, as in track_overlap_scores_kernel.
-template <bool POLY>
+// truth is a polygon, MASK: a mask (judge reads `overlap` [B,NTK_MASK_OVERLAP_DOUBLES]), as in track_overlap_scores_kernel.
+template <Gt KIND>
 __global__ void track_supervise_plan_kernel(const double* __restrict__ gt, const unsigned char* __restrict__ active,
                                             const int* __restrict__ clip_of, int B, int n_clips, int* __restrict__ state,
                                             double* __restrict__ table, unsigned char* __restrict__ track,
@@ -232,7 +253,7 @@ __global__ void track_supervise_plan_kernel(const double* __restrict__ gt, const
             const int left = st[NTK_SUP_STATE_COUNTDOWN] > 1 ? st[NTK_SUP_STATE_COUNTDOWN] - 1 : 0;
             st[NTK_SUP_STATE_COUNTDOWN] = left;
             Truth tr;
-            if (left == 0 && read_truth<POLY>(gt + (POLY ? NTK_POLY_DOUBLES : 4) * (size_t)b, tr)) {
+            if (left == 0 && read_truth<KIND>(gt + gt_doubles<KIND>() * (size_t)b, tr)) {
                 rs = 1;
                 code = NTK_SUP_CODE_RESTART;
                 row[NTK_SUP_RESTARTS] += 1.0;
@@ -249,9 +270,9 @@ __global__ void track_supervise_plan_kernel(const double* __restrict__ gt, const
     if (codes) codes[b] = code;
 }
 
-template <bool POLY>
+template <Gt KIND>
 __global__ void track_supervise_judge_kernel(const double* __restrict__ regions, const double* __restrict__ gt,
-                                             const unsigned char* __restrict__ track, const int* __restrict__ clip_of, int B,
+                                             const double* __restrict__ overlap, const unsigned char* __restrict__ track, const int* __restrict__ clip_of, int B,
                                              int n_clips, int skip, int burn_in, double failure_overlap, int* __restrict__ state,
                                              double* __restrict__ table, signed char* __restrict__ codes,
                                              double* __restrict__ frame_iou) {
@@ -261,16 +282,16 @@ __global__ void track_supervise_judge_kernel(const double* __restrict__ regions,
     const int clip = clip_of[b];
     if (clip < 0 || clip >= n_clips || !track[b]) return;
     int* st = state + (size_t)b * NTK_SUP_STATE_INTS;
-    const double* g = gt + (POLY ? NTK_POLY_DOUBLES : 4) * (size_t)b;
+    const double* g = gt + gt_doubles<KIND>() * (size_t)b;
     Truth tr;
-    if (!read_truth<POLY>(g, tr)) {                          // tracked, the object absent: the frame is counted nowhere
+    if (!read_truth<KIND>(g, tr)) {                          // tracked, the object absent: the frame is counted nowhere
         st[NTK_SUP_STATE_SINCE] += 1;
         if (codes) codes[b] = NTK_SUP_CODE_TRACKED;
         return;
     }
     const double* p = regions + 4 * (size_t)b;
     double iou = 0.0;
-    if (finite4(p)) iou = truth_iou<POLY>(p[0], p[1], fmax(p[2], 0.0), fmax(p[3], 0.0), g, tr);
+    if (finite4(p)) iou = truth_iou<KIND>(p[0], p[1], fmax(p[2], 0.0), fmax(p[3], 0.0), g, tr, overlap + NTK_MASK_OVERLAP_DOUBLES * (size_t)b);
     double* row = table + (size_t)clip * NTK_SUP_HEAD;
     const double tracked = row[NTK_SUP_TRACKED];
     row[NTK_SUP_TRACKED] = tracked + 1.0;
@@ -348,18 +369,18 @@ extern "C" int ntk_track_poly_bounds(const double* poly, int n, double* rects, v
     return NTK_OK;
 }
 
-template <bool POLY>
-static int track_overlap_scores(const char* name, const double* regions, const double* gt, const unsigned char* active,
-                                const int* clip_of, int T, int B, int n_clips, const double* iou_thr, int n_iou,
-                                const double* dist_thr, int n_dist, double* table, double* frame_iou, void* stream) {
-    NTK_REQUIRE(regions && gt && clip_of && table, NTK_ERR_BAD_PTR, "%s: null pointer", name);
+template <Gt KIND>
+static int track_overlap_scores(const char* name, const double* regions, const double* gt, const double* overlap,
+                                const unsigned char* active, const int* clip_of, int T, int B, int n_clips, const double* iou_thr,
+                                int n_iou, const double* dist_thr, int n_dist, double* table, double* frame_iou, void* stream) {
+    NTK_REQUIRE(regions && gt && clip_of && table && (KIND != Gt::MASK || overlap), NTK_ERR_BAD_PTR, "%s: null pointer", name);
     NTK_REQUIRE(T > 0 && B > 0 && B <= 65535 && n_clips > 0, NTK_ERR_BAD_SHAPE, "%s: T=%d B=%d (1..65535) n_clips=%d", name, T, B, n_clips);
     NTK_REQUIRE(n_iou >= 0 && n_iou <= NTK_SCORE_MAX_THRESHOLDS && n_dist >= 0 && n_dist <= NTK_SCORE_MAX_THRESHOLDS, NTK_ERR_BAD_SHAPE,
                 "%s: n_iou=%d n_dist=%d (0..%d each)", name, n_iou, n_dist, NTK_SCORE_MAX_THRESHOLDS);
     NTK_REQUIRE((n_iou == 0 || iou_thr) && (n_dist == 0 || dist_thr), NTK_ERR_BAD_SHAPE, "%s: n_iou=%d n_dist=%d but %s is null", name,
                 n_iou, n_dist, (n_iou > 0 && !iou_thr) ? "iou_thr" : "dist_thr");
-    track_overlap_scores_kernel<POLY><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, active, clip_of, T, B, n_clips, iou_thr,
-                                                                                    n_iou, dist_thr, n_dist, table, frame_iou);
+    track_overlap_scores_kernel<KIND><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, overlap, active, clip_of, T, B, n_clips,
+                                                                                    iou_thr, n_iou, dist_thr, n_dist, table, frame_iou);
     NTK_CHECK_LAUNCH(name);
     return NTK_OK;
 }
@@ -367,36 +388,45 @@ static int track_overlap_scores(const char* name, const double* regions, const d
 extern "C" int ntk_track_overlap_scores(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
                                         int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr,
                                         int n_dist, double* table, double* frame_iou, void* stream) {
-    return track_overlap_scores<false>("ntk_track_overlap_scores", regions, gt, active, clip_of, T, B, n_clips, iou_thr, n_iou, dist_thr,
-                                       n_dist, table, frame_iou, stream);
+    return track_overlap_scores<Gt::RECT>("ntk_track_overlap_scores", regions, gt, nullptr, active, clip_of, T, B, n_clips, iou_thr, n_iou,
+                                          dist_thr, n_dist, table, frame_iou, stream);
 }
 
 extern "C" int ntk_track_overlap_scores_poly(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
                                              int T, int B, int n_clips, const double* iou_thr, int n_iou, const double* dist_thr,
                                              int n_dist, double* table, double* frame_iou, void* stream) {
-    return track_overlap_scores<true>("ntk_track_overlap_scores_poly", regions, gt, active, clip_of, T, B, n_clips, iou_thr, n_iou,
-                                      dist_thr, n_dist, table, frame_iou, stream);
+    return track_overlap_scores<Gt::POLY>("ntk_track_overlap_scores_poly", regions, gt, nullptr, active, clip_of, T, B, n_clips, iou_thr,
+                                          n_iou, dist_thr, n_dist, table, frame_iou, stream);
 }
 
-template <bool POLY>
-static int track_supervise(const char* name, int phase, const double* regions, const double* gt, const unsigned char* active,
-                           const int* clip_of, int B, int n_clips, int skip, int burn_in, double failure_overlap, int* state,
+extern "C" int ntk_track_overlap_scores_mask(const double* regions, const double* rects, const double* overlap,
+                                             const unsigned char* active, const int* clip_of, int T, int B, int n_clips,
+                                             const double* iou_thr, int n_iou, const double* dist_thr, int n_dist, double* table,
+                                             double* frame_iou, void* stream) {
+    return track_overlap_scores<Gt::MASK>("ntk_track_overlap_scores_mask", regions, rects, overlap, active, clip_of, T, B, n_clips, iou_thr,
+                                          n_iou, dist_thr, n_dist, table, frame_iou, stream);
+}
+
+template <Gt KIND>
+static int track_supervise(const char* name, int phase, const double* regions, const double* gt, const double* overlap,
+                           const unsigned char* active, const int* clip_of, int B, int n_clips, int skip, int burn_in, double failure_overlap, int* state,
                            double* table, unsigned char* track, unsigned char* restart, signed char* codes, double* frame_iou,
                            void* stream) {
     NTK_REQUIRE(phase == NTK_SUP_PLAN || phase == NTK_SUP_JUDGE, NTK_ERR_BAD_SHAPE, "%s: phase=%d (NTK_SUP_PLAN or NTK_SUP_JUDGE)", name,
                 phase);
-    NTK_REQUIRE(gt && clip_of && state && table && track && (phase == NTK_SUP_PLAN ? restart != nullptr : regions != nullptr),
+    NTK_REQUIRE(gt && clip_of && state && table && track && (phase == NTK_SUP_PLAN ? restart != nullptr : regions != nullptr) &&
+                    (KIND != Gt::MASK || phase == NTK_SUP_PLAN || overlap),
                 NTK_ERR_BAD_PTR, "%s: null pointer", name);
     NTK_REQUIRE(B > 0 && B <= 65535 && n_clips > 0, NTK_ERR_BAD_SHAPE, "%s: B=%d (1..65535) n_clips=%d", name, B, n_clips);
     NTK_REQUIRE(skip >= 1 && burn_in >= 0 && failure_overlap >= 0 && failure_overlap < 1, NTK_ERR_BAD_SHAPE,
                 "%s: skip=%d (>= 1) burn_in=%d (>= 0) failure_overlap=%g (in [0,1))", name, skip, burn_in, failure_overlap);
     if (phase == NTK_SUP_PLAN)
-        track_supervise_plan_kernel<POLY><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(gt, active, clip_of, B, n_clips, state, table,
+        track_supervise_plan_kernel<KIND><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(gt, active, clip_of, B, n_clips, state, table,
                                                                                         track, restart, codes, frame_iou);
     else
-        track_supervise_judge_kernel<POLY><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, track, clip_of, B, n_clips, skip,
-                                                                                         burn_in, failure_overlap, state, table, codes,
-                                                                                         frame_iou);
+        track_supervise_judge_kernel<KIND><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, overlap, track, clip_of, B, n_clips,
+                                                                                         skip, burn_in, failure_overlap, state, table,
+                                                                                         codes, frame_iou);
     NTK_CHECK_LAUNCH(name);
     return NTK_OK;
 }
@@ -405,16 +435,24 @@ extern "C" int ntk_track_supervise(int phase, const double* regions, const doubl
                                    const int* clip_of, int B, int n_clips, int skip, int burn_in, double failure_overlap,
                                    int* state, double* table, unsigned char* track, unsigned char* restart, signed char* codes,
                                    double* frame_iou, void* stream) {
-    return track_supervise<false>("ntk_track_supervise", phase, regions, gt, active, clip_of, B, n_clips, skip, burn_in, failure_overlap,
-                                  state, table, track, restart, codes, frame_iou, stream);
+    return track_supervise<Gt::RECT>("ntk_track_supervise", phase, regions, gt, nullptr, active, clip_of, B, n_clips, skip, burn_in,
+                                     failure_overlap, state, table, track, restart, codes, frame_iou, stream);
 }
 
 extern "C" int ntk_track_supervise_poly(int phase, const double* regions, const double* gt, const unsigned char* active,
                                         const int* clip_of, int B, int n_clips, int skip, int burn_in, double failure_overlap,
                                         int* state, double* table, unsigned char* track, unsigned char* restart, signed char* codes,
                                         double* frame_iou, void* stream) {
-    return track_supervise<true>("ntk_track_supervise_poly", phase, regions, gt, active, clip_of, B, n_clips, skip, burn_in,
-                                 failure_overlap, state, table, track, restart, codes, frame_iou, stream);
+    return track_supervise<Gt::POLY>("ntk_track_supervise_poly", phase, regions, gt, nullptr, active, clip_of, B, n_clips, skip, burn_in,
+                                     failure_overlap, state, table, track, restart, codes, frame_iou, stream);
+}
+
+extern "C" int ntk_track_supervise_mask(int phase, const double* regions, const double* rects, const double* overlap,
+                                        const unsigned char* active, const int* clip_of, int B, int n_clips, int skip, int burn_in,
+                                        double failure_overlap, int* state, double* table, unsigned char* track,
+                                        unsigned char* restart, signed char* codes, double* frame_iou, void* stream) {
+    return track_supervise<Gt::MASK>("ntk_track_supervise_mask", phase, regions, rects, overlap, active, clip_of, B, n_clips, skip, burn_in,
+                                     failure_overlap, state, table, track, restart, codes, frame_iou, stream);
 }
 
 extern "C" int ntk_track_decode_mask(const int* status, int n_status, const int* cell_index, const int* start_index,

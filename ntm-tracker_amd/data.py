@@ -171,8 +171,62 @@ def parse_vot_region(line):
     return None
 
 
+def parse_vot_mask(line):
+    """One mask line of a VOT groundtruth.txt, ``m x0,y0,w,h,c0,c1,...`` (the sets from 2020 on): the mask's box in frame pixels
+    and the run-length counts over it, even-indexed counts runs of zeros, odd-indexed ones runs of ones, row-major.
+    -> (x0, y0, w, h, counts int32 array), the counts as they are written (evaluate.MaskRegions, include/ntmtrack.h NTK_MASK_*).
+    ValueError, with the reason: a line that does not begin with ``m``, fewer than four numbers, a number that is not an integer
+    (of 32 bits), a negative count, a box of more than evaluate.MASK_MAX_PIXELS pixels.  A box with w <= 0 or h <= 0 is returned as it is: an absent object."""
+    from .evaluate import MASK_MAX_PIXELS
+    text = line.strip()
+    if not text.startswith("m"):
+        raise ValueError("not a mask line (it does not begin with 'm'): %r" % (text[:40],))
+    tokens = [t.strip() for t in text[1:].split(",")]
+    if tokens == [""]:
+        tokens = []
+    if len(tokens) < 4:
+        raise ValueError("a mask line of %d number(s); at least x0,y0,w,h are needed" % len(tokens))
+    numbers = []
+    for t in tokens:
+        try:
+            v = int(t)
+        except ValueError:
+            raise ValueError("a mask line holds %r, which is not an integer" % (t,))
+        if not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("a mask line holds %d, which does not fit 32 bits" % v)
+        numbers.append(v)
+    x0, y0, w, h = numbers[:4]
+    if w > 0 and h > 0 and w * h > MASK_MAX_PIXELS:
+        raise ValueError("a mask box of %d x %d pixels; at most %d pixels are supported" % (w, h, MASK_MAX_PIXELS))
+    counts = np.asarray(numbers[4:], dtype=np.int32)
+    if (counts < 0).any():
+        raise ValueError("a mask line holds the negative count %d" % int(counts[counts < 0][0]))
+    return x0, y0, w, h, counts
+
+
+def _vot_mask_regions(path, lines):
+    """The lines of a groundtruth.txt that holds mask lines -> evaluate.MaskRegions: a line that is neither a mask nor parseable
+    is an absent object, a rectangle or polygon line among them a ValueError naming the file and the line."""
+    from .evaluate import MaskRegions
+    frames = []
+    for k, line in enumerate(lines):
+        try:
+            if line.strip().startswith("m"):
+                frames.append(parse_vot_mask(line))
+            elif parse_vot_region(line) is None:
+                frames.append(None)
+            else:
+                raise ValueError("a rectangle or polygon among mask lines")
+        except ValueError as e:
+            raise ValueError("%s, line %d: %s" % (path, k + 1, e))
+    return MaskRegions.from_lists(frames)
+
+
 def vot_clips(root, names=None, frames="arrays"):
     """The VOT directory layout -> one evaluate.Clip per sequence.  ``root/list.txt`` names the sequences when ``names`` is None.
+    A ``groundtruth.txt`` that holds mask lines (``m x0,y0,w,h,c0,...``: parse_vot_mask) gives a mask clip, its regions an
+    evaluate.MaskRegions; a line of it that is neither a mask nor parseable is an absent object, a rectangle or polygon line
+    among the mask lines a ValueError naming the file and the line.  Otherwise:
     A sequence folder holds ``groundtruth.txt``, one region per line (parse_vot_region; a line that is neither form is an absent
     object, a row of NaN), and its frames as ``color/%08d.jpg`` or ``%08d.jpg``, numbered from 1.  Regions are in pixels: [L,4]
     where every line is a rectangle or absent, else [L,16] polygons padded with NaN (a rectangle line among them as its 4-gon).
@@ -191,11 +245,14 @@ def vot_clips(root, names=None, frames="arrays"):
             lines = f.read().splitlines()
         while lines and not lines[-1].strip():
             lines.pop()
+        masks = any(line.strip().startswith("m") for line in lines)
         try:
-            parsed = [parse_vot_region(line) for line in lines]
+            parsed = lines if masks else [parse_vot_region(line) for line in lines]
         except ValueError as e:
             raise ValueError("%s: %s" % (os.path.join(folder, "groundtruth.txt"), e))
-        if any(r is not None and len(r) > 4 for r in parsed):
+        if masks:
+            regions = _vot_mask_regions(os.path.join(folder, "groundtruth.txt"), lines)
+        elif any(r is not None and len(r) > 4 for r in parsed):
             regions = np.full((len(parsed), POLY_DOUBLES), np.nan)
             for i, r in enumerate(parsed):
                 if r is not None:

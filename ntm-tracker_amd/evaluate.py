@@ -19,6 +19,11 @@ scored as the toolkit scores it -- the polygon against the tracker's rectangle (
 ntk_track_supervise_poly) -- while the tracker is started and restarted from the polygon's bounding rectangle, as the reference's
 vot.VOT("rectangle") hands it over.  A run without a polygon clip makes exactly the rectangle calls.
 
+Or it is a segmentation mask per frame (MaskRegions: the run-length coded masks of the VOT sets from 2020 on, include/ntmtrack.h
+NTK_MASK_*), scored straight from the counts against the pixel set of the tracker's rectangle (ntk_track_mask_overlaps,
+ntk_track_overlap_scores_mask, ntk_track_supervise_mask) while the tracker is started and restarted from the bounds of the set
+pixels (ntk_track_mask_bounds).  A run holds either only mask clips or none.
+
 The overlap is the VOT / OTB one on real-valued rectangles.  The reference's own bb_iou (test_tracker.py:59-83) is never called
 there, uses a +1 pixel convention and does not clamp an empty intersection: it is not the model here.
 """
@@ -43,6 +48,8 @@ POLY_MAX_POINTS, POLY_DOUBLES = 8, 16
 CLIPDEC_DECODED, CLIPDEC_FAILED, CLIPDEC_MASKED, CLIPDEC_FIRST_FAILED, CLIPDEC_FIRST_STATUS, CLIPDEC_START_STATUS, CLIPDEC_HEAD = \
     0, 1, 2, 3, 4, 5, 6
 ON_UNDECODED = ("raise", "skip")
+# include/ntmtrack.h NTK_MASK_*: a mask is (x0, y0, w, h, first, count) over a flat array of counts; its overlap (|M n R|, |R|, |M|)
+MASK_CELL_INTS, MASK_OVERLAP_DOUBLES, MASK_MAX_PIXELS = 6, 3, 1 << 30
 
 Round = collections.namedtuple("Round", ["resets", "frame_index", "active", "clip_of"])
 
@@ -56,7 +63,8 @@ def _upload(array, dtype, device):
 #: one clip of a validation set.  frames: [L,H,W,3] uint8 or float host array, or a callable returning one (called when the clip is
 #: scheduled), or a list / tuple of L image files (paths, or the files' bytes): a FILE CLIP, read a round at a time and never held
 #: whole (size may then be None: it is read from the first file's header).  regions: [L,4] ground truth (x, y, w, h) in pixels, row 0 starts the tracker; or [L,2P] polygons (x0, y0, x1, y1,
-#: ...) of 3 <= P <= 8 vertices, rows with fewer padded with NaN, the tracker then starts from row 0's bounding rectangle.  init:
+#: ...) of 3 <= P <= 8 vertices, rows with fewer padded with NaN, the tracker then starts from row 0's bounding rectangle; or a
+#: MaskRegions (a segmentation mask per frame), the tracker then starts from the bounds of frame 0's set pixels.  init:
 #: the region the tracker is started with when it is not that (the reference passes it normalised).  size: (H, W) where frames is a callable, so that
 #: clips can be grouped by frame size without decoding them.
 Clip = collections.namedtuple("Clip", ["frames", "regions", "init", "size"])
@@ -109,6 +117,174 @@ def polygon_bounds(polys):
         if w > 0 and h > 0 and abs(twice) / 2 > 0:
             out[i] = (x.min(), y.min(), w, h)
     return out.reshape(polys.shape[:-1] + (4,))
+
+
+class MaskRegions(object):
+    """The ground truth of one clip as run-length coded masks (include/ntmtrack.h NTK_MASK_*): ``boxes`` int32 [L,4], frame i's
+    mask box (x0, y0, w, h) in frame pixels; ``counts`` int32, the counts of all frames one after the other, as the toolkit
+    writes them (even-indexed counts of a frame are runs of zeros, odd-indexed ones runs of ones, row-major over the box);
+    ``offsets`` int64 [L+1], frame i's counts are counts[offsets[i]:offsets[i+1]] -- so the frames of a slot in a round are one
+    slice.  A frame whose mask is not PRESENT (an empty box, a negative count, no pixel set) is an absent object."""
+
+    def __init__(self, boxes, counts, offsets):
+        self.boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+        self.counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if (len(self.offsets) != len(self.boxes) + 1 or self.offsets[0] != 0 or self.offsets[-1] != len(self.counts)
+                or (np.diff(self.offsets) < 0).any()):
+            raise ValueError("MaskRegions: %d boxes, %d counts and offsets %s" % (len(self.boxes), len(self.counts), self.offsets.tolist()))
+
+    def __len__(self):
+        return len(self.boxes)
+
+    @classmethod
+    def from_lists(cls, frames):
+        """frames: per frame (x0, y0, w, h, counts), or None for an absent object (an empty box without counts)."""
+        boxes = [(0, 0, 0, 0) if f is None else tuple(f[:4]) for f in frames]
+        counts = [np.zeros(0, dtype=np.int32) if f is None else np.asarray(f[4], dtype=np.int32).reshape(-1) for f in frames]
+        offsets = np.concatenate([[0], np.cumsum([len(c) for c in counts])])
+        return cls(np.asarray(boxes, dtype=np.int32).reshape(-1, 4), np.concatenate(counts) if counts else counts, offsets)
+
+    @classmethod
+    def from_arrays(cls, masks):
+        """Dense masks [L,H,W] (nonzero = object) -> the masks coded over their tight boxes; an all-zero frame is an absent
+        object."""
+        masks = np.asarray(masks)
+        if masks.ndim != 3:
+            raise ValueError("MaskRegions.from_arrays: masks %s; expected [L,H,W]" % (masks.shape,))
+        frames = []
+        for m in masks != 0:
+            rows, cols = np.nonzero(m.any(axis=1))[0], np.nonzero(m.any(axis=0))[0]
+            if not len(rows):
+                frames.append(None)
+                continue
+            x0, y0, x1, y1 = cols[0], rows[0], cols[-1] + 1, rows[-1] + 1
+            flat = m[y0:y1, x0:x1].reshape(-1)
+            edges = np.nonzero(flat[1:] != flat[:-1])[0] + 1              # where a run starts
+            runs = np.diff(np.concatenate([[0], edges, [len(flat)]]))
+            if flat[0]:
+                runs = np.concatenate([[0], runs])                        # the mask begins with a one
+            if len(runs) % 2:
+                runs = runs[:-1]                                          # trailing zeros: pixels the counts do not reach
+            frames.append((x0, y0, x1 - x0, y1 - y0, runs))
+        return cls.from_lists(frames)
+
+    def frame(self, i):
+        """-> (x0, y0, w, h, counts) of frame i."""
+        x0, y0, w, h = (int(v) for v in self.boxes[i])
+        return x0, y0, w, h, self.counts[self.offsets[i]:self.offsets[i + 1]]
+
+    def ones_runs(self, i):
+        """The runs of ones of frame i clipped to its box -> (w, starts, ends) with ends > starts, or None where the mask is not
+        present."""
+        _x0, _y0, w, h, c = self.frame(i)
+        if w <= 0 or h <= 0 or w * h > MASK_MAX_PIXELS or (c < 0).any():
+            return None
+        ends = np.cumsum(c.astype(np.int64))
+        s, e = np.minimum((ends - c)[1::2], w * h), np.minimum(ends[1::2], w * h)
+        keep = e > s
+        return (w, s[keep], e[keep]) if keep.any() else None
+
+    def dense(self, i, H, W):
+        """Frame i decoded -> bool [H,W] (the part of the box inside the frame); all False for an absent object."""
+        out = np.zeros((H, W), dtype=bool)
+        runs = self.ones_runs(i)
+        if runs is None:
+            return out
+        x0, y0, w, h, _c = self.frame(i)
+        _w, s, e = runs
+        d = np.zeros(w * h + 1, dtype=np.int64)
+        np.add.at(d, s, 1)
+        np.add.at(d, e, -1)
+        box = (np.cumsum(d)[:w * h] > 0).reshape(h, w)
+        ya, yb, xa, xb = max(y0, 0), min(y0 + h, H), max(x0, 0), min(x0 + w, W)
+        if yb > ya and xb > xa:
+            out[ya:yb, xa:xb] = box[ya - y0:yb - y0, xa - x0:xb - x0]
+        return out
+
+    def cells(self, lo, hi):
+        """Frames [lo, hi) in the device layout -> (cells int32 [hi-lo, MASK_CELL_INTS] whose ``first`` counts from the start of
+        the returned counts, the counts of those frames: one slice)."""
+        a, b = int(self.offsets[lo]), int(self.offsets[hi])
+        cells = np.empty((hi - lo, MASK_CELL_INTS), dtype=np.int32)
+        cells[:, :4] = self.boxes[lo:hi]
+        cells[:, 4] = self.offsets[lo:hi] - a
+        cells[:, 5] = np.diff(self.offsets[lo:hi + 1])
+        return cells, self.counts[a:b]
+
+
+def mask_bounds(regions, i=None):
+    """The host's ntk_track_mask_bounds: MaskRegions -> float64 [L,4] (or [4] of frame i): (min col, min row, max col + 1 - min col,
+    max row + 1 - min row) over the set pixels in frame pixels, NaN for a mask that is not present.  What a clip's tracker starts
+    from."""
+    if i is not None:
+        out = np.full(4, np.nan)
+        runs = regions.ones_runs(i)
+        if runs is not None:
+            w, s, e = runs
+            r0, r1 = s // w, (e - 1) // w
+            one_row = bool((r0 == r1).all())                                # else a run crosses a row end: every column
+            c_min, c_max = (int((s % w).min()), int(((e - 1) % w).max())) if one_row else (0, w - 1)
+            out[:] = (int(regions.boxes[i, 0]) + c_min, int(regions.boxes[i, 1]) + int(r0.min()), c_max + 1 - c_min,
+                      int(r1.max()) + 1 - int(r0.min()))
+        return out
+    return np.stack([mask_bounds(regions, k) for k in range(len(regions))]) if len(regions) else np.zeros((0, 4))
+
+
+class MaskRound(object):
+    """The mask ground truth of a round (or of one of its frames) on the device: ``cells`` int32 [T,B,MASK_CELL_INTS] (or [B,...])
+    and ``rle`` int32 with ``n_rle`` counts as ntk_track_mask_* take them; ``rects`` float64 [T,B,4] and ``area`` [T,B] as
+    ntk_track_mask_bounds left them; ``overlap`` float64 [..., MASK_OVERLAP_DOUBLES], set by whoever ran ntk_track_mask_overlaps
+    on the tracked regions.  ``round[t]`` is frame t (views: nothing is copied)."""
+
+    def __init__(self, cells, rle, n_rle, rects, area, overlap=None):
+        self.cells, self.rle, self.n_rle, self.rects, self.area, self.overlap = cells, rle, int(n_rle), rects, area, overlap
+
+    def __getitem__(self, t):
+        return MaskRound(self.cells[t], self.rle, self.n_rle, self.rects[t], self.area[t],
+                         None if self.overlap is None else self.overlap[t])
+
+    def overlaps(self, regions, out=None):
+        """One ntk_track_mask_overlaps of regions float64 [..., 4] (device) against these masks -> ``overlap`` (also kept)."""
+        import torch
+        from . import _lib
+        n = self.cells.numel() // MASK_CELL_INTS
+        if out is None:
+            out = torch.empty(tuple(self.cells.shape[:-1]) + (MASK_OVERLAP_DOUBLES,), dtype=torch.float64, device=self.cells.device)
+        if (regions.dtype != torch.float64 or regions.numel() != 4 * n or out.numel() != MASK_OVERLAP_DOUBLES * n
+                or self.cells.dtype != torch.int32 or self.rle.dtype != torch.int32 or self.rle.numel() < max(self.n_rle, 1)):
+            raise _lib.NtkError("MaskRound.overlaps: regions %s for %d masks" % (tuple(regions.shape), n))
+        P = _lib.ptr
+        _lib.check(_lib.lib().ntk_track_mask_overlaps(P(regions), P(self.cells), P(self.rle), self.n_rle, n, P(out), _lib.stream()),
+                   "ntk_track_mask_overlaps")
+        self.overlap = out
+        return out
+
+
+def upload_masks(per_cell, shape, device):
+    """per_cell: ((index tuple into ``shape``), cells [k,6], counts) blocks, each filling k consecutive cells along the FIRST axis
+    at the given index of the others -> MaskRound on the device: the cells with ``first`` rebased onto the concatenated counts,
+    both through the pinned asynchronous upload, and ONE ntk_track_mask_bounds.  Cells no block names are absent objects."""
+    import torch
+    from . import _lib
+    cells = np.zeros(tuple(shape) + (MASK_CELL_INTS,), dtype=np.int32)
+    parts, n_rle = [], 0
+    for index, c, counts in per_cell:
+        c = c.copy()
+        c[:, 4] += n_rle
+        cells[(slice(0, len(c)),) + tuple(index)] = c
+        parts.append(counts)
+        n_rle += len(counts)
+    if n_rle >= 2 ** 31:
+        raise ValueError("the masks of a round hold %d counts; fewer than 2^31 fit" % n_rle)
+    rle = np.concatenate(parts) if n_rle else np.zeros(1, dtype=np.int32)             # never an empty buffer
+    d_cells, d_rle = _upload(cells, torch.int32, device), _upload(rle, torch.int32, device)
+    rects = torch.empty(tuple(shape) + (4,), dtype=torch.float64, device=d_cells.device)
+    area = torch.empty(tuple(shape), dtype=torch.float64, device=d_cells.device)
+    P = _lib.ptr
+    _lib.check(_lib.lib().ntk_track_mask_bounds(P(d_cells), P(d_rle), n_rle, cells.size // MASK_CELL_INTS, P(rects), P(area),
+                                                _lib.stream()), "ntk_track_mask_bounds")
+    return MaskRound(d_cells, d_rle, n_rle, rects, area)
 
 
 class ClipSchedule(object):
@@ -210,12 +386,14 @@ class OverlapScores(object):
 
     def add(self, regions, gt, clip_of, active=None, frame_iou=False):
         """regions, gt: [T,B,4] or [B,4] (x, y, w, h) pixels, or gt [T,B,16] / [B,16] polygons (then one launch of
-        ntk_track_overlap_scores_poly); clip_of [B]: the table row of slot b, no row twice (a row outside
+        ntk_track_overlap_scores_poly), or gt a MaskRound of [T,B] / [B] masks (then one ntk_track_mask_overlaps of the regions
+        against the masks and one ntk_track_overlap_scores_mask); clip_of [B]: the table row of slot b, no row twice (a row outside
         the table skips the slot); active [T,B] or [B], nullable.  Device tensors are taken as they are, host arrays go up through
         a pinned asynchronous copy.  frame_iou=True returns the per-frame IoUs [T,B] (NaN where a frame was not scored)."""
         import torch
         from . import _lib
-        regions, gt = self._dev(regions, torch.float64), self._dev(gt, torch.float64)
+        masks = gt if isinstance(gt, MaskRound) else None
+        regions, gt = self._dev(regions, torch.float64), masks.rects if masks is not None else self._dev(gt, torch.float64)
         if regions.dim() == 2:
             regions, gt = regions.unsqueeze(0), gt.unsqueeze(0)
         poly = gt.dim() == 3 and gt.shape[2] == POLY_DOUBLES
@@ -231,8 +409,9 @@ class OverlapScores(object):
                                 % (tuple(clip_of.shape), None if mask is None else tuple(mask.shape), T, B))
         out = torch.empty((T, B), dtype=torch.float64, device=self.device) if frame_iou else None
         P = _lib.ptr
-        name = "ntk_track_overlap_scores_poly" if poly else "ntk_track_overlap_scores"
-        _lib.check(getattr(_lib.lib(), name)(P(regions), P(gt), P(mask), P(clip_of), T, B, self.n_clips,
+        name = "ntk_track_overlap_scores" + ("_mask" if masks is not None else "_poly" if poly else "")
+        truth = (P(gt),) if masks is None else (P(gt), P(masks.overlaps(regions)))
+        _lib.check(getattr(_lib.lib(), name)(P(regions), *truth, P(mask), P(clip_of), T, B, self.n_clips,
                                              P(self._iou) if len(self.iou_thresholds) else None, len(self.iou_thresholds),
                                              P(self._dist) if len(self.dist_thresholds) else None, len(self.dist_thresholds),
                                              P(self.table), P(out), _lib.stream()), name)
@@ -307,6 +486,13 @@ class Supervisor(object):
     def _call(self, phase, regions, gt, active, clip_of, codes, frame_iou):
         import torch
         from . import _lib
+        masks = gt if isinstance(gt, MaskRound) else None          # plan and judge on the masks' rects; judge reads their overlap
+        if masks is not None:
+            gt = masks.rects
+            if phase == SUP_JUDGE and (not torch.is_tensor(masks.overlap) or masks.overlap.dtype != torch.float64
+                                       or tuple(masks.overlap.shape) != (self.B, MASK_OVERLAP_DOUBLES)):
+                raise _lib.NtkError("Supervisor: judge needs the masks' overlap, a float64 tensor of shape %s"
+                                    % ((self.B, MASK_OVERLAP_DOUBLES),))
         poly = torch.is_tensor(gt) and gt.dim() == 2 and gt.shape[1] == POLY_DOUBLES
         for name, t, dtype, shape in (("regions", regions, torch.float64, (self.B, 4)),
                                       ("gt", gt, torch.float64, (self.B, POLY_DOUBLES if poly else 4)),
@@ -315,13 +501,14 @@ class Supervisor(object):
             if t is not None and (not torch.is_tensor(t) or t.dtype != dtype or tuple(t.shape) != shape):
                 raise _lib.NtkError("Supervisor: %s must be a %s tensor of shape %s" % (name, dtype, shape))
         P = _lib.ptr
-        fn = "ntk_track_supervise_poly" if poly else "ntk_track_supervise"
-        _lib.check(getattr(_lib.lib(), fn)(phase, P(regions), P(gt), P(active), P(clip_of), self.B, self.n_clips, self.skip,
+        fn = "ntk_track_supervise_mask" if masks is not None else "ntk_track_supervise_poly" if poly else "ntk_track_supervise"
+        truth = (P(gt),) if masks is None else (P(gt), P(masks.overlap) if phase == SUP_JUDGE else None)
+        _lib.check(getattr(_lib.lib(), fn)(phase, P(regions), *truth, P(active), P(clip_of), self.B, self.n_clips, self.skip,
                                            self.burn_in, self.failure_overlap, P(self.state), P(self.table), P(self.track),
                                            P(self.restart), P(codes), P(frame_iou), _lib.stream()), fn)
 
     def plan(self, gt_t, active_t, clip_of, codes=None, frame_iou=None):
-        """Before the frame's pass.  gt_t float64 [B,4] (or [B,16] polygons: ntk_track_supervise_poly), active_t uint8 [B] (nullable), clip_of int32 [B], on the device.
+        """Before the frame's pass.  gt_t float64 [B,4] (or [B,16] polygons: ntk_track_supervise_poly; or a frame of a MaskRound: ntk_track_supervise_mask), active_t uint8 [B] (nullable), clip_of int32 [B], on the device.
         -> (track, restart) uint8 [B]: the masks of the pass (the supervisor's own buffers, overwritten by the next plan).  codes
         int8 [B] and frame_iou float64 [B] (nullable) are filled for every slot."""
         self._call(SUP_PLAN, None, gt_t, active_t, clip_of, codes, frame_iou)
@@ -566,6 +753,12 @@ class Validation(object):
     the polygons' bounding rectangles.  Rectangle clips in the same run are scored as 4-gons.  The polygons go up through the same
     pinned asynchronous copy, so a round still makes no host synchronisation.
 
+    Clips whose regions are MaskRegions (segmentation masks) are scored against the masks in both protocols, straight from the
+    run-length counts: per round the cells [T,B,6] and the concatenated counts go up through the same pinned copy, ONE
+    ntk_track_mask_bounds gives the rectangles the trackers start and restart from, and the one-pass protocol adds ONE
+    ntk_track_mask_overlaps and ONE ntk_track_overlap_scores_mask (the supervised one: track_clip with a MaskRound).  A run holds
+    either only mask clips or none (ValueError); a run without mask clips makes exactly the calls it made before.
+
     File clips (Clip.frames a list of paths or bytes) are read a round at a time: a background data.InputPrefetcher reads round
     r + 1 with ``workers`` pool threads (data.default_workers() when None) into one of ``prefetch`` pinned sets while round r
     runs.  ``decode="host"``: Pillow decodes on those threads and the round runs as it does from arrays.  ``decode="device"``:
@@ -598,12 +791,23 @@ class Validation(object):
         if not self.clips:
             raise ValueError("Validation: no clips")
         self.B, self.T = int(B), int(T)
-        # ground truth per clip: [L,4], or, as soon as one clip has polygons, [L,16] for every clip (a rectangle clip as 4-gons)
-        given = [np.asarray(c.regions, dtype=np.float64) for c in self.clips]
-        given = [g if g.ndim == 2 and g.shape[1] != 4 else g.reshape(-1, 4) for g in given]
-        self.polygons = any(g.shape[1] != 4 for g in given)
-        self._gt = [(rect_polygons(g) if g.shape[1] == 4 else pad_polygons(g)) for g in given] if self.polygons else given
-        self._first = [g[0] if g.shape[1] == 4 else polygon_bounds(pad_polygons(g[0])) for g in given]
+        is_mask = [isinstance(c.regions, MaskRegions) for c in self.clips]
+        self.masks = any(is_mask)
+        if self.masks and not all(is_mask):
+            raise ValueError("Validation: clips %s have mask regions and clips %s have not: a run holds either only mask clips or none"
+                             % ([i for i, m in enumerate(is_mask) if m], [i for i, m in enumerate(is_mask) if not m]))
+        if self.masks:
+            # ground truth per clip: the MaskRegions themselves; a tracker starts from the bounds of its clip's first mask
+            self.polygons = False
+            self._gt = [c.regions for c in self.clips]
+            self._first = [mask_bounds(g, 0) if len(g) else None for g in self._gt]
+        else:
+            # ground truth per clip: [L,4], or, as soon as one clip has polygons, [L,16] for every clip (a rectangle clip as 4-gons)
+            given = [np.asarray(c.regions, dtype=np.float64) for c in self.clips]
+            given = [g if g.ndim == 2 and g.shape[1] != 4 else g.reshape(-1, 4) for g in given]
+            self.polygons = any(g.shape[1] != 4 for g in given)
+            self._gt = [(rect_polygons(g) if g.shape[1] == 4 else pad_polygons(g)) for g in given] if self.polygons else given
+            self._first = [g[0] if g.shape[1] == 4 else polygon_bounds(pad_polygons(g[0])) for g in given]
         self._is_file = [isinstance(c.frames, (list, tuple)) for c in self.clips]
         lengths = [len(g) for g in self._gt]
         for i, c in enumerate(self.clips):
@@ -686,14 +890,17 @@ class Validation(object):
                 cls.tracker.reset(slots, inp.firsts, regions)
             if cls.supervisor is not None:
                 cls.supervisor.start(slots)
-        # (2) the ground truth of the round: NaN boxes where inactive
-        gt = np.full((T, B, POLY_DOUBLES if self.polygons else 4), np.nan, dtype=np.float64)
-        for b in range(B):
-            n = int(rnd.active[:, b].sum())
-            if n:
-                at = rnd.frame_index[:n, b]
-                gt[:n, b] = self._gt[int(ids[b])][at[0]:at[-1] + 1]
-        d_gt = _upload(gt, torch.float64, self.device)
+        # (2) the ground truth of the round: NaN boxes (absent masks) where inactive
+        if self.masks:
+            d_gt = self._round_masks(rnd, ids)
+        else:
+            gt = np.full((T, B, POLY_DOUBLES if self.polygons else 4), np.nan, dtype=np.float64)
+            for b in range(B):
+                n = int(rnd.active[:, b].sum())
+                if n:
+                    at = rnd.frame_index[:n, b]
+                    gt[:n, b] = self._gt[int(ids[b])][at[0]:at[-1] + 1]
+            d_gt = _upload(gt, torch.float64, self.device)
         # (3) one pass over the round, (4) one scoring launch
         if cls.supervisor is not None:
             out = cls.tracker.track_clip(inp.frames, active=inp.active, supervisor=cls.supervisor, gt=d_gt, clip_of=inp.d_ids)
@@ -703,6 +910,17 @@ class Validation(object):
         cls.source.consumed()                           # the round's launches are enqueued
         if self._keep is not None:
             self._keep.append((out, rnd.frame_index, inp.tracked, ids, None if cls.supervisor is None else cls.supervisor.codes))
+
+    def _round_masks(self, rnd, ids):
+        """The masks of a round -> MaskRound: a slot's frames are one slice of its clip's counts; two uploads, one
+        ntk_track_mask_bounds."""
+        blocks = []
+        for b in range(rnd.active.shape[1]):
+            n = int(rnd.active[:, b].sum())
+            if n:
+                at = rnd.frame_index[:n, b]
+                blocks.append(((b,),) + self._gt[int(ids[b])].cells(int(at[0]), int(at[-1]) + 1))
+        return upload_masks(blocks, rnd.active.shape, self.device)
 
     def close(self):
         """Stops the sources' threads and the reader pool (finish() calls it; a run that is abandoned should)."""

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib
 from .evaluate import POLY_DOUBLES          # one polygon region of the ground truth (include/ntmtrack.h NTK_POLY_DOUBLES)
+from .evaluate import MASK_OVERLAP_DOUBLES, MaskRound       # mask ground truth of a round (include/ntmtrack.h NTK_MASK_*)
 from .ntm import NTMCell, _P, _np, gemm_nt
 from .tracker import GRID_N, GRID_START, GRID_STEP, NUM_FEATURES
 from .vgg import VGG16Conv43
@@ -406,7 +407,9 @@ class BatchNTMTracker(object):
         and ``clip_of`` int32 [B] on the device, every frame is plan -> the pass with the planned masks -> judge: a slot that
         lost its object is restarted from the ground truth inside the pass.  ``gt`` may be [T,B,16] polygons (include/ntmtrack.h,
         NTK_POLY_*): plan and judge take the polygons, a restart starts from the polygon's bounding rectangle, which one
-        ntk_track_poly_bounds launch computes for the whole round.  The supervisor's ``codes`` [T,B] int8 then say what
+        ntk_track_poly_bounds launch computes for the whole round.  ``gt`` may be an evaluate.MaskRound (segmentation masks,
+        NTK_MASK_*): per frame plan on the masks' rects[t], the pass with restarts from rects[t], one ntk_track_mask_overlaps
+        of the frame's B masks against the tracked regions, judge.  The supervisor's ``codes`` [T,B] int8 then say what
         each slot did on each frame; a slot that sat a frame out repeats its last region."""
         T = len(frames)
         if not torch.is_tensor(frames) and not isinstance(frames, (list, tuple)):
@@ -414,6 +417,23 @@ class BatchNTMTracker(object):
             frames = _upload(a, torch.uint8 if a.dtype == np.uint8 else torch.float32, self.device)
         masks = None if active is None else self._mask(active, (T, self.B))
         out = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
+        if supervisor is not None and isinstance(gt, MaskRound):
+            if not (tuple(gt.rects.shape) == (T, self.B, 4) and gt.rects.is_cuda and gt.rects.dtype == torch.float64
+                    and gt.rects.is_contiguous() and gt.cells.is_contiguous() and clip_of is not None):
+                raise _lib.NtkError("track_clip: a supervisor with masks needs a MaskRound of [%d,%d] masks on the device and "
+                                    "clip_of" % (T, self.B))
+            codes = torch.empty((T, self.B), device=self.device, dtype=torch.int8)
+            overlap = torch.empty((T, self.B, MASK_OVERLAP_DOUBLES), device=self.device, dtype=torch.float64)
+            for t in range(T):
+                frame = gt[t]
+                track, restart = supervisor.plan(frame, None if masks is None else masks[t], clip_of, codes=codes[t])
+                self._step_restart(self._images(frames[t]), track, restart, frame.rects)
+                frame.overlaps(self.regions, out=overlap[t])
+                supervisor.judge(self.regions, frame, clip_of, codes=codes[t])
+                out[t].copy_(self.regions)
+            gt.overlap = overlap
+            supervisor.codes = codes
+            return out
         if supervisor is not None:
             if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float64 and gt.dim() == 3
                     and tuple(gt.shape[:2]) == (T, self.B) and gt.shape[2] in (4, POLY_DOUBLES) and gt.is_contiguous()
