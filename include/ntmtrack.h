@@ -1110,6 +1110,76 @@ int ntk_track_supervise_mask(int phase, const double* regions, const double* rec
                              double failure_overlap, int* state, double* table, unsigned char* track, unsigned char* restart,
                              signed char* codes, double* frame_iou, void* stream);
 
+/* The multi-start (anchor-based) protocol of the VOT sets from 2020 on: a tracker is started at an anchor frame and run ONCE to an
+ * end of its sequence, a run ends when the overlap stays low, and the figures are accuracy, robustness and the expected average
+ * overlap (EAO).  A RUN is a clip to the validator (its frames in run order, built on the host); these entries score the rounds of
+ * the runs and reduce the result.  The rules are this project's statement of the protocol after the wording of the VOT2020
+ * report; where the report is silent the choice is marked (own rule).  No bit parity with the toolkit is claimed.
+ *
+ * ntk_track_multistart: one launch per round, one thread per slot, which walks its T frames in order.  ALL protocol state lives
+ * in the run's table row, which belongs to the slot that holds the run (NO TWO SLOTS MAY NAME ONE ROW): no per-slot state, no
+ * atomics, plain vector loads and stores; a slot that takes another run in a later round names another row.
+ *   regions, gt, active, clip_of, T, B, frame_iou: as for ntk_track_overlap_scores; clip_of[b] is the RUN of slot b, a row
+ *     outside [0, n_runs) skips the slot (only clip_of[b] is read; its frame_iou is NaN)
+ *   table        double [n_runs, NTK_MS_HEAD], THE OWNER INITIALISES IT TO 0; every field a double, every count exact:
+ *     [NTK_MS_FRAMES]   N: the scored frames of the run so far, those after a failure included
+ *     [NTK_MS_TRACKED]  scored frames committed: the ordinal at which the open streak began, or FRAMES when none is open.  Of a
+ *                       failed run it is the failure's ordinal f = N_F
+ *     [NTK_MS_SUM_IOU]  sum of the committed frames' overlaps, added in frame order
+ *     [NTK_MS_FAILED]   0 / 1
+ *     [NTK_MS_LOW]      length of the open streak of low frames (0 <= LOW <= patience; 0 once the run has failed)
+ *     [NTK_MS_PENDING]  what SUM_IOU becomes if the open streak is forgiven: SUM_IOU and then the streak's overlaps, added in
+ *                       frame order.  Equal to SUM_IOU when no streak is open.
+ *   trace_first  int64 [n_runs + 1], ascending: the run's overlaps are trace[trace_first[r] : trace_first[r + 1]]
+ *   trace        double [trace_first[n_runs]]: the overlap of the run's scored frame of ordinal i goes to trace[trace_first[r]
+ *                + i]; an ordinal that would reach trace_first[r + 1] is counted and NOT stored (a run of L frames needs L - 1)
+ * A SCORED frame is active, has ground truth present (the rule of ntk_track_overlap_scores for the kind of ground truth) and gets
+ * the overlap o of ntk_track_overlap_scores: the same device function, the same bits.  An inactive frame, or one whose ground
+ * truth is absent, does not exist for the protocol (own rule): it gets no ordinal and neither extends nor breaks a streak.  With
+ * i = FRAMES the ordinal of a scored frame, in order:
+ *   trace[...] = o, frame_iou = o, FRAMES += 1; a run that has FAILED takes nothing more;
+ *   o <= failure_overlap (LOW frame, the supervised protocol's <=): LOW += 1, PENDING += o; when LOW == patience + 1 the run has
+ *     FAILED at ordinal f = TRACKED: frames f ... f + patience are all low.  FAILED = 1, LOW = 0, PENDING = SUM_IOU;
+ *   otherwise the streak, if any, is forgiven and its frames count normally: PENDING += o, SUM_IOU = PENDING, TRACKED += LOW + 1,
+ *     LOW = 0.
+ * A streak still open when the run ends is not a failure (own rule), so of a finished run
+ *   N = FRAMES, N_F = FAILED ? TRACKED : FRAMES, sum = FAILED ? SUM_IOU : PENDING = the sum of o_i over i < N_F in frame order,
+ *   accuracy = sum / N_F (NaN for N_F = 0), robustness = N_F / N; a run with N = 0 takes part in nothing.
+ * Rounds are separate calls and the row carries everything, so any split of a run's frames into calls leaves the same bits.
+ * ntk_track_multistart_poly: gt double [T,B,NTK_POLY_DOUBLES]; ntk_track_multistart_mask: rects and overlap as for
+ * ntk_track_overlap_scores_mask.  Everything else is unchanged.
+ * Errors, before any launch: NTK_ERR_BAD_PTR for a null regions, gt / rects, overlap (mask), clip_of, table, trace_first or trace
+ * (active and frame_iou are nullable); NTK_ERR_BAD_SHAPE, the value named in ntk_last_error, for T, B or n_runs <= 0, B > 65535,
+ * patience < 0 or failure_overlap outside [0,1).
+ *
+ * ntk_track_eao_curve: the EAO curve of the finished runs, on the device (a long-term-sized set holds 1e8 trace entries: neither
+ * the trace nor the reduction goes to the host).  With o^_s(i) = o_i for i < N_F and 0 afterwards -- of a failed run without end,
+ * the report's "padded with zeros" -- and S_n = the failed runs and the unfailed runs with N >= n (runs with N = 0 never):
+ *   curve[n - 1] = Phi(n) = (1 / |S_n|) sum over s in S_n of (1 / n) sum over i < n of o^_s(i), n = 1 ... n_max; NaN for an empty S_n.
+ * Two kernels: (a) one 64-lane wavefront per run turns its o_i, i < min(N_F, n_max), into inclusive prefix sums in prefix (the
+ * layout of trace, caller-provided, nothing stored beyond): chunks of 64 frames, a wave scan and a carried total; (b) one thread
+ * per n adds P_s(min(n, N_F)) / n over the runs of S_n in run order.  Fixed orders and no atomics: the same input gives the same
+ * bits.  N_F is cut to the run's trace length.  prefix double [trace_first[n_runs]], curve double [n_max].
+ * Errors: NTK_ERR_BAD_PTR for any null pointer; NTK_ERR_BAD_SHAPE, the value named, for n_runs <= 0 or n_max <= 0. */
+#define NTK_MS_FRAMES   0
+#define NTK_MS_TRACKED  1
+#define NTK_MS_SUM_IOU  2
+#define NTK_MS_FAILED   3
+#define NTK_MS_LOW      4
+#define NTK_MS_PENDING  5
+#define NTK_MS_HEAD     6
+int ntk_track_multistart(const double* regions, const double* gt, const unsigned char* active, const int* clip_of, int T, int B,
+                         int n_runs, double failure_overlap, int patience, double* table, const long long* trace_first,
+                         double* trace, double* frame_iou, void* stream);
+int ntk_track_multistart_poly(const double* regions, const double* gt, const unsigned char* active, const int* clip_of, int T,
+                              int B, int n_runs, double failure_overlap, int patience, double* table,
+                              const long long* trace_first, double* trace, double* frame_iou, void* stream);
+int ntk_track_multistart_mask(const double* regions, const double* rects, const double* overlap, const unsigned char* active,
+                              const int* clip_of, int T, int B, int n_runs, double failure_overlap, int patience, double* table,
+                              const long long* trace_first, double* trace, double* frame_iou, void* stream);
+int ntk_track_eao_curve(const double* table, const long long* trace_first, const double* trace, int n_runs, int n_max,
+                        double* prefix, double* curve, void* stream);
+
 /* Validation from image files decoded on the device (ntk_jpeg_decode_batch): which frames of a round may be tracked and scored.
  * A file can turn out undecodable only on the device; this entry turns such a frame off in the round's mask before the tracker
  * and the scoring launch read it, so that nothing is read back per round.  One launch per round, one thread per slot, which

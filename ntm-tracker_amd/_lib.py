@@ -140,7 +140,11 @@ def _sig(lib):
         "ntk_track_mask_overlaps": (c_int, [P, P, P, c_int, c_int, P, P]),
         "ntk_track_overlap_scores_mask": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P]),
         "ntk_track_supervise_mask": (c_int, [c_int, P, P, P, P, P, c_int, c_int, c_int, c_int, ctypes.c_double] + [P] * 6 + [P]),
-        "ntk_track_decode_mask": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P]),
+        "ntk_track_multistart": (c_int, [P, P, P, P, c_int, c_int, c_int, ctypes.c_double, c_int] + [P] * 4 + [P]),
+        "ntk_track_multistart_poly": (c_int, [P, P, P, P, c_int, c_int, c_int, ctypes.c_double, c_int] + [P] * 4 + [P]),
+        "ntk_track_multistart_mask": (c_int, [P, P, P, P, P, c_int, c_int, c_int, ctypes.c_double, c_int] + [P] * 4 + [P]),
+        "ntk_track_eao_curve": (c_int, [P, P, P, c_int, c_int, P, P, P]),
+        "ntk_track_decode_mask":(c_int, [P, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P]),
         "ntk_select_rows": (c_int, [P, P, P, P, c_int, c_int, P]),
         "ntk_dnc_state_keep": (c_int, [P, c_int, c_int, c_int, P, P, P, P]),
         "ntk_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),

@@ -1,7 +1,8 @@
 // The validation protocol on the device: the overlap of a tracked rectangle with rectangle, polygon or mask ground truth (the VOT /
 // OTB overlap, float64; polygons by Sutherland-Hodgman clipping, contract: include/ntmtrack.h, NTK_POLY_*; masks from the pixel
 // counts of ntk_track_mask_overlaps, track_masks.hip, NTK_MASK_*), the per-clip overlap tables (NTK_SCORE_*) and the supervised
-// protocol's state machine (NTK_SUP_*).  One thread per slot; no atomics.
+// protocol's state machine (NTK_SUP_*) and the multi-start protocol's run table (NTK_MS_*; its EAO reduction: track_eao.hip).  One
+// thread per slot; no atomics.
 #include "common.h"
 
 namespace {      // the overlap functions; the kernels below keep their external names
@@ -313,6 +314,71 @@ __global__ void track_supervise_judge_kernel(const double* __restrict__ regions,
     if (codes) codes[b] = NTK_SUP_CODE_TRACKED;
 }
 
+// The multi-start protocol's scoring (contract: include/ntmtrack.h, NTK_MS_*): one thread per slot walks its T frames in order.
+// Everything the protocol remembers -- the open streak of low frames included, which is what lets the failure look-ahead cross a
+// round -- is in the run's table row: the row is carried in registers and written back at the end.  The row and the run's stretch
+// of the trace belong to this thread alone.  A slot whose run is outside [0, n_runs) reads nothing but clip_of[b].
+template <Gt KIND>
+__global__ void track_multistart_kernel(const double* __restrict__ regions, const double* __restrict__ gt,
+                                        const double* __restrict__ overlap, const unsigned char* __restrict__ active,
+                                        const int* __restrict__ clip_of, int T, int B, int n_runs, double failure_overlap,
+                                        int patience, double* __restrict__ table, const long long* __restrict__ trace_first,
+                                        double* __restrict__ trace, double* __restrict__ frame_iou) {
+#pragma clang fp contract(off)
+    constexpr int GT = gt_doubles<KIND>();
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const int run = clip_of[b];
+    if (run < 0 || run >= n_runs) {
+        if (frame_iou)
+            for (int t = 0; t < T; ++t) frame_iou[(size_t)t * B + b] = nan;
+        return;
+    }
+    double* row = table + (size_t)run * NTK_MS_HEAD;
+    double frames = row[NTK_MS_FRAMES], tracked = row[NTK_MS_TRACKED], sum_iou = row[NTK_MS_SUM_IOU];
+    double failed = row[NTK_MS_FAILED], low = row[NTK_MS_LOW], pending = row[NTK_MS_PENDING];
+    const long long first = trace_first[run], room = trace_first[run + 1] - first;
+    for (int t = 0; t < T; ++t) {
+        const size_t at = (size_t)t * B + b;
+        const double* g = gt + GT * at;
+        Truth tr;
+        const bool scored = (!active || active[at]) && read_truth<KIND>(g, tr);
+        if (!scored) {
+            if (frame_iou) frame_iou[at] = nan;
+            continue;
+        }
+        const double* p = regions + 4 * at;
+        double iou = 0.0;
+        if (finite4(p))
+            iou = truth_iou<KIND>(p[0], p[1], fmax(p[2], 0.0), fmax(p[3], 0.0), g, tr, overlap + NTK_MASK_OVERLAP_DOUBLES * at);
+        const long long i = (long long)frames;
+        if (first >= 0 && i < room) trace[first + i] = iou;
+        if (frame_iou) frame_iou[at] = iou;
+        frames += 1.0;
+        if (failed != 0.0) continue;
+        pending += iou;
+        if (iou <= failure_overlap) {
+            low += 1.0;
+            if (low > (double)patience) {       // frames TRACKED ... TRACKED + patience are all low
+                failed = 1.0;
+                low = 0.0;
+                pending = sum_iou;
+            }
+        } else {                                // the streak, if one was open, is forgiven
+            sum_iou = pending;
+            tracked += low + 1.0;
+            low = 0.0;
+        }
+    }
+    row[NTK_MS_FRAMES] = frames;
+    row[NTK_MS_TRACKED] = tracked;
+    row[NTK_MS_SUM_IOU] = sum_iou;
+    row[NTK_MS_FAILED] = failed;
+    row[NTK_MS_LOW] = low;
+    row[NTK_MS_PENDING] = pending;
+}
+
 // Which frames of a round a file-fed validation may use (contract: include/ntmtrack.h, NTK_CLIPDEC_*): one thread per slot walks
 // its T frames in order, turns off every active frame whose pixels the decoder did not deliver and counts in the row clip_of[b]
 // of the table, which belongs to this thread alone.  status is read only at indices inside [0, n_status).
@@ -453,6 +519,45 @@ extern "C" int ntk_track_supervise_mask(int phase, const double* regions, const 
                                         unsigned char* restart, signed char* codes, double* frame_iou, void* stream) {
     return track_supervise<Gt::MASK>("ntk_track_supervise_mask", phase, regions, rects, overlap, active, clip_of, B, n_clips, skip, burn_in,
                                      failure_overlap, state, table, track, restart, codes, frame_iou, stream);
+}
+
+template <Gt KIND>
+static int track_multistart(const char* name, const double* regions, const double* gt, const double* overlap,
+                            const unsigned char* active, const int* clip_of, int T, int B, int n_runs, double failure_overlap,
+                            int patience, double* table, const long long* trace_first, double* trace, double* frame_iou,
+                            void* stream) {
+    NTK_REQUIRE(regions && gt && clip_of && table && trace_first && trace && (KIND != Gt::MASK || overlap), NTK_ERR_BAD_PTR,
+                "%s: null pointer", name);
+    NTK_REQUIRE(T > 0 && B > 0 && B <= 65535 && n_runs > 0, NTK_ERR_BAD_SHAPE, "%s: T=%d B=%d (1..65535) n_runs=%d", name, T, B, n_runs);
+    NTK_REQUIRE(patience >= 0 && failure_overlap >= 0 && failure_overlap < 1, NTK_ERR_BAD_SHAPE,
+                "%s: patience=%d (>= 0) failure_overlap=%g (in [0,1))", name, patience, failure_overlap);
+    track_multistart_kernel<KIND><<<(B + 63) / 64, 64, 0, (hipStream_t)stream>>>(regions, gt, overlap, active, clip_of, T, B, n_runs,
+                                                                                failure_overlap, patience, table, trace_first, trace,
+                                                                                frame_iou);
+    NTK_CHECK_LAUNCH(name);
+    return NTK_OK;
+}
+
+extern "C" int ntk_track_multistart(const double* regions, const double* gt, const unsigned char* active, const int* clip_of, int T,
+                                    int B, int n_runs, double failure_overlap, int patience, double* table,
+                                    const long long* trace_first, double* trace, double* frame_iou, void* stream) {
+    return track_multistart<Gt::RECT>("ntk_track_multistart", regions, gt, nullptr, active, clip_of, T, B, n_runs, failure_overlap,
+                                      patience, table, trace_first, trace, frame_iou, stream);
+}
+
+extern "C" int ntk_track_multistart_poly(const double* regions, const double* gt, const unsigned char* active, const int* clip_of,
+                                         int T, int B, int n_runs, double failure_overlap, int patience, double* table,
+                                         const long long* trace_first, double* trace, double* frame_iou, void* stream) {
+    return track_multistart<Gt::POLY>("ntk_track_multistart_poly", regions, gt, nullptr, active, clip_of, T, B, n_runs, failure_overlap,
+                                      patience, table, trace_first, trace, frame_iou, stream);
+}
+
+extern "C" int ntk_track_multistart_mask(const double* regions, const double* rects, const double* overlap,
+                                         const unsigned char* active, const int* clip_of, int T, int B, int n_runs,
+                                         double failure_overlap, int patience, double* table, const long long* trace_first,
+                                         double* trace, double* frame_iou, void* stream) {
+    return track_multistart<Gt::MASK>("ntk_track_multistart_mask", regions, rects, overlap, active, clip_of, T, B, n_runs,
+                                      failure_overlap, patience, table, trace_first, trace, frame_iou, stream);
 }
 
 extern "C" int ntk_track_decode_mask(const int* status, int n_status, const int* cell_index, const int* start_index,

@@ -11,7 +11,11 @@ accumulated in one device table (ntk_track_overlap_scores) that is read back onc
                  callables), _HostFileSource (image files read a round at a time, a round ahead: data.stage_round,
                  data.InputPrefetcher) or _DeviceFileSource (the files decoded on the device on a second stream,
                  ntk_jpeg_decode_batch, ntk_track_decode_mask turning off the frames that could not be decoded)
-  validate       runs a Validation to the end; protocol="one_pass" (the default) or "supervised"
+  multistart_runs    the multi-start protocol's runs of a set of clips (host arithmetic only): a run is a clip whose frames are
+                 read in another order
+  MultiStart     the multi-start protocol's run table and overlap trace on the device (ntk_track_multistart) and the EAO
+                 reduction (ntk_track_eao_curve)
+  validate       runs a Validation to the end; protocol="one_pass" (the default), "supervised" or "multistart"
   write_trajectory   the toolkit's trajectory file of one clip, from regions() and codes()
 
 The ground truth of a clip is a rectangle per frame ([L,4]) or a polygon per frame ([L,2P], 3 <= P <= 8: VOT regions), which is
@@ -41,7 +45,9 @@ SUP_STATE_MODE, SUP_STATE_COUNTDOWN, SUP_STATE_SINCE, SUP_STATE_INTS = 0, 1, 2, 
 SUP_MODE_TRACK, SUP_MODE_WAIT = 0, 1
 SUP_PLAN, SUP_JUDGE = 0, 1
 SUP_CODE_INACTIVE, SUP_CODE_TRACKED, SUP_CODE_RESTART, SUP_CODE_FAILURE, SUP_CODE_SKIPPED = -1, 0, 1, 2, 3
-PROTOCOLS = ("one_pass", "supervised")
+PROTOCOLS = ("one_pass", "supervised", "multistart")
+# include/ntmtrack.h NTK_MS_*: the multi-start protocol's table row, one per run
+MS_FRAMES, MS_TRACKED, MS_SUM_IOU, MS_FAILED, MS_LOW, MS_PENDING, MS_HEAD = 0, 1, 2, 3, 4, 5, 6
 # include/ntmtrack.h NTK_POLY_*: a polygon region is POLY_DOUBLES doubles, the leading finite pairs its vertices, NaN after them
 POLY_MAX_POINTS, POLY_DOUBLES = 8, 16
 # include/ntmtrack.h NTK_CLIPDEC_*: the per-clip row of ntk_track_decode_mask (validation from files decoded on the device)
@@ -202,6 +208,19 @@ class MaskRegions(object):
             out[ya:yb, xa:xb] = box[ya - y0:yb - y0, xa - x0:xb - x0]
         return out
 
+    def take(self, indices):
+        """-> MaskRegions of the frames ``indices``, in that order: the boxes re-ordered, the counts re-concatenated, the offsets
+        rebuilt."""
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        if len(idx) and (idx.min() < 0 or idx.max() >= len(self)):
+            raise ValueError("MaskRegions.take: indices outside [0,%d)" % len(self))
+        sizes = self.offsets[idx + 1] - self.offsets[idx]
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        # element k of the new counts: its frame j = the last one whose offset is <= k, the same place inside the old frame
+        j = np.repeat(np.arange(len(idx)), sizes)
+        counts = self.counts[self.offsets[idx][j] + (np.arange(offsets[-1]) - offsets[j])]
+        return MaskRegions(self.boxes[idx], counts, offsets)
+
     def cells(self, lo, hi):
         """Frames [lo, hi) in the device layout -> (cells int32 [hi-lo, MASK_CELL_INTS] whose ``first`` counts from the start of
         the returned counts, the counts of those frames: one slice)."""
@@ -332,6 +351,91 @@ class ClipSchedule(object):
             yield Round(resets, frame_index, active, clip_of)
 
 
+def regions_present(regions):
+    """bool [L]: the frames of a clip whose ground truth is present, by the rule the score kernels use for its kind: a rectangle
+    finite with w > 0 and h > 0, a polygon with a bounding rectangle (polygon_bounds), a mask with set pixels (mask_bounds)."""
+    if isinstance(regions, MaskRegions):
+        return np.isfinite(mask_bounds(regions)).all(axis=1)
+    g = np.asarray(regions, dtype=np.float64)
+    g = g if g.ndim == 2 and g.shape[1] != 4 else g.reshape(-1, 4)
+    if g.shape[1] != 4:
+        return np.isfinite(polygon_bounds(pad_polygons(g))).all(axis=1)
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(g).all(axis=1) & (g[:, 2] > 0) & (g[:, 3] > 0)
+
+
+class _DecodedOnce(object):
+    """A callable clip behind its runs: ``frames()`` decodes the clip, or returns the decoded array while a run still holds a view
+    of it.  The array is held weakly: the run views keep it alive through ``.base``, and it goes when the last of them does."""
+
+    def __init__(self, decode):
+        self.decode, self.held = decode, None
+
+    def frames(self):
+        import weakref
+        a = None if self.held is None else self.held()
+        if a is None:
+            a = np.asarray(self.decode())
+            a = a if a.dtype == np.uint8 else a.astype(np.float32, copy=False)      # what _ArraySource keeps: its views stay views
+            if a.base is not None:
+                a = a.copy()                            # a view of somebody else's memory cannot be the base of the run views
+            self.held = weakref.ref(a)
+        return a
+
+
+def multistart_runs(clips, spacing=50, anchors=None):
+    """The runs of the multi-start protocol (the rules: include/ntmtrack.h, NTK_MS_*) -> (run_clips, runs): ``runs``
+    int64 [n_runs,4] = (clip, anchor, direction +1 / -1, length), ordered by clip, then by anchor; ``run_clips`` one ordinary Clip
+    per run with the run's frames and regions in run order.
+
+    The anchors of a clip of L >= 2 frames are {0, spacing, 2 spacing, ...} and L - 1, or ``anchors[i]`` where ``anchors`` is given
+    (a list per clip).  An anchor a runs forward over a ... L - 1 when L - 1 - a >= a, else backward over a ... 0.  An anchor whose
+    ground truth is absent (regions_present) moves along its own direction to the first frame where it is present (own rule); a
+    run left with fewer than 2 frames is dropped, two runs with the same start and direction are one (the order is that of the
+    anchors as given, which moving keeps within a direction).  A set without a run is a ValueError.
+
+    Array frames become views, file lists re-ordered lists; a callable clip is decoded once for all of its runs that are alive at
+    the same time (_DecodedOnce).  ``init`` goes only to the forward run from frame 0; ``size`` is copied."""
+    if int(spacing) < 1:
+        raise ValueError("multistart_runs: spacing=%d; at least 1" % spacing)
+    clips = [_as_clip(c) for c in clips]
+    if anchors is not None and len(anchors) != len(clips):
+        raise ValueError("multistart_runs: %d anchor lists for %d clips" % (len(anchors), len(clips)))
+    run_clips, runs = [], []
+    for i, c in enumerate(clips):
+        present = regions_present(c.regions)
+        L = len(present)
+        if L < 2:
+            raise ValueError("multistart_runs: clip %d has %d frame(s); a clip needs 2" % (i, L))
+        given = range(0, L, int(spacing)) if anchors is None else [int(a) for a in anchors[i]]
+        if not all(0 <= a < L for a in given):
+            raise ValueError("multistart_runs: clip %d: anchors %s outside [0,%d)" % (i, list(given), L))
+        starts = []
+        for a in sorted(set(given) | ({L - 1} if anchors is None else set())):
+            step = 1 if L - 1 - a >= a else -1
+            while 0 <= a < L and not present[a]:
+                a += step
+            if 0 <= a < L and (L - a if step > 0 else a + 1) >= 2 and (a, step) not in starts:
+                starts.append((a, step))
+        shared = _DecodedOnce(c.frames) if callable(c.frames) and starts else None
+        is_mask = isinstance(c.regions, MaskRegions)
+        for a, step in starts:
+            order = np.arange(a, L) if step > 0 else np.arange(a, -1, -1)
+            cut = slice(a, None) if step > 0 else slice(a, None, -1)
+            if shared is not None:
+                frames = lambda shared=shared, cut=cut: shared.frames()[cut]
+            elif isinstance(c.frames, (list, tuple)):
+                frames = [c.frames[k] for k in order]
+            else:
+                frames = np.asarray(c.frames)[cut]
+            regions = c.regions.take(order) if is_mask else np.asarray(c.regions, dtype=np.float64).reshape(L, -1)[order]
+            run_clips.append(Clip(frames, regions, c.init if (a, step) == (0, 1) else None, c.size))
+            runs.append((i, a, step, len(order)))
+    if not runs:
+        raise ValueError("multistart_runs: the %d clip(s) yield no run" % len(clips))
+    return run_clips, np.asarray(runs, dtype=np.int64).reshape(-1, 4)
+
+
 def summarize(table, iou_thresholds, dist_thresholds):
     """The host arithmetic of OverlapScores.result(): table [n_clips, SCORE_HEAD + n_iou + n_dist] float64 -> dict (see result)."""
     table = np.asarray(table, dtype=np.float64)
@@ -359,6 +463,41 @@ def summarize(table, iou_thresholds, dist_thresholds):
             "clips_never_lost": int((scored & (table[:, SCORE_FIRST_LOST] < 0)).sum())}
 
 
+def _scoring_call(who, entry, device, regions, gt, clip_of, active, frame_iou):
+    """What OverlapScores.add and MultiStart.add share: the arguments of one scoring launch over a round, checked and on the device
+    (tensors there are taken as they are, host arrays go up through the pinned asynchronous copy).  -> (the entry point's name for
+    the kind of ground truth, regions [T,B,4], the ground truth's pointers -- for a MaskRound after its ONE ntk_track_mask_overlaps
+    --, active [T,B] or None, clip_of [B], T, B, the frame_iou buffer or None, the tensors behind those pointers: held by the caller
+    until it has launched)."""
+    import torch
+    from . import _lib
+
+    def dev(x, dtype):
+        if torch.is_tensor(x) and x.device.type == device.type:
+            return x.to(dtype).contiguous()
+        return _upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, device)
+    masks = gt if isinstance(gt, MaskRound) else None
+    regions, gt = dev(regions, torch.float64), masks.rects if masks is not None else dev(gt, torch.float64)
+    if regions.dim() == 2:
+        regions, gt = regions.unsqueeze(0), gt.unsqueeze(0)
+    poly = gt.dim() == 3 and gt.shape[2] == POLY_DOUBLES
+    if (regions.dim() != 3 or regions.shape[2] != 4 or gt.dim() != 3 or gt.shape[:2] != regions.shape[:2]
+            or gt.shape[2] not in (4, POLY_DOUBLES)):
+        raise _lib.NtkError("%s: regions %s must be [T,B,4] and gt %s [T,B,4] or [T,B,%d]"
+                            % (who, tuple(regions.shape), tuple(gt.shape), POLY_DOUBLES))
+    T, B = regions.shape[:2]
+    clip_of = dev(clip_of, torch.int32)
+    mask = None if active is None else dev(active, torch.uint8).reshape(-1, B)
+    if tuple(clip_of.shape) != (B,) or (mask is not None and tuple(mask.shape) != (T, B)):
+        raise _lib.NtkError("%s: clip_of %s / active %s for [T,B] = [%d,%d]"
+                            % (who, tuple(clip_of.shape), None if mask is None else tuple(mask.shape), T, B))
+    out = torch.empty((T, B), dtype=torch.float64, device=device) if frame_iou else None
+    P = _lib.ptr
+    name = entry + ("_mask" if masks is not None else "_poly" if poly else "")
+    truth = (P(gt),) if masks is None else (P(gt), P(masks.overlaps(regions)))
+    return name, regions, truth, mask, clip_of, T, B, out, (gt, masks)
+
+
 class OverlapScores(object):
     """The score table of n_clips clips ([n_clips, SCORE_HEAD + n_iou + n_dist] float64, ``self.table``) and the two threshold
     arrays, on the device.  ``add`` is one launch of ntk_track_overlap_scores and synchronises nothing; ``result`` is the one
@@ -378,39 +517,16 @@ class OverlapScores(object):
         self._iou = torch.as_tensor(self.iou_thresholds).to(self.device)
         self._dist = torch.as_tensor(self.dist_thresholds).to(self.device)
 
-    def _dev(self, x, dtype):
-        import torch
-        if torch.is_tensor(x) and x.device.type == self.device.type:
-            return x.to(dtype).contiguous()
-        return _upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, self.device)
-
     def add(self, regions, gt, clip_of, active=None, frame_iou=False):
         """regions, gt: [T,B,4] or [B,4] (x, y, w, h) pixels, or gt [T,B,16] / [B,16] polygons (then one launch of
         ntk_track_overlap_scores_poly), or gt a MaskRound of [T,B] / [B] masks (then one ntk_track_mask_overlaps of the regions
         against the masks and one ntk_track_overlap_scores_mask); clip_of [B]: the table row of slot b, no row twice (a row outside
         the table skips the slot); active [T,B] or [B], nullable.  Device tensors are taken as they are, host arrays go up through
         a pinned asynchronous copy.  frame_iou=True returns the per-frame IoUs [T,B] (NaN where a frame was not scored)."""
-        import torch
         from . import _lib
-        masks = gt if isinstance(gt, MaskRound) else None
-        regions, gt = self._dev(regions, torch.float64), masks.rects if masks is not None else self._dev(gt, torch.float64)
-        if regions.dim() == 2:
-            regions, gt = regions.unsqueeze(0), gt.unsqueeze(0)
-        poly = gt.dim() == 3 and gt.shape[2] == POLY_DOUBLES
-        if (regions.dim() != 3 or regions.shape[2] != 4 or gt.dim() != 3 or gt.shape[:2] != regions.shape[:2]
-                or gt.shape[2] not in (4, POLY_DOUBLES)):
-            raise _lib.NtkError("OverlapScores.add: regions %s must be [T,B,4] and gt %s [T,B,4] or [T,B,%d]"
-                                % (tuple(regions.shape), tuple(gt.shape), POLY_DOUBLES))
-        T, B = regions.shape[:2]
-        clip_of = self._dev(clip_of, torch.int32)
-        mask = None if active is None else self._dev(active, torch.uint8).reshape(-1, B)
-        if tuple(clip_of.shape) != (B,) or (mask is not None and tuple(mask.shape) != (T, B)):
-            raise _lib.NtkError("OverlapScores.add: clip_of %s / active %s for [T,B] = [%d,%d]"
-                                % (tuple(clip_of.shape), None if mask is None else tuple(mask.shape), T, B))
-        out = torch.empty((T, B), dtype=torch.float64, device=self.device) if frame_iou else None
         P = _lib.ptr
-        name = "ntk_track_overlap_scores" + ("_mask" if masks is not None else "_poly" if poly else "")
-        truth = (P(gt),) if masks is None else (P(gt), P(masks.overlaps(regions)))
+        name, regions, truth, mask, clip_of, T, B, out, _held = _scoring_call("OverlapScores.add", "ntk_track_overlap_scores",
+                                                                              self.device, regions, gt, clip_of, active, frame_iou)
         _lib.check(getattr(_lib.lib(), name)(P(regions), *truth, P(mask), P(clip_of), T, B, self.n_clips,
                                              P(self._iou) if len(self.iou_thresholds) else None, len(self.iou_thresholds),
                                              P(self._dist) if len(self.dist_thresholds) else None, len(self.dist_thresholds),
@@ -522,6 +638,103 @@ class Supervisor(object):
     def result(self):
         """Reads the table back (the one synchronisation) -> summarize_supervised(table)."""
         return summarize_supervised(self.table.cpu().numpy())
+
+
+def summarize_multistart(table, runs, curve, eao_interval, n_clips=None):
+    """The host arithmetic of MultiStart.result(): table [n_runs, MS_HEAD] float64 of FINISHED runs, runs int64 [n_runs,4] (clip,
+    anchor, direction, length: multistart_runs), curve [n_max] = Phi(1 ... n_max) (ntk_track_eao_curve), eao_interval (lo, hi)
+    -> dict.  Of a run: N = FRAMES; N_F = TRACKED if it FAILED, else N (a streak open at the end is forgiven); sum = SUM_IOU if
+    it failed, else PENDING.  ``per_run`` holds per run ``clip``, ``anchor``, ``direction``, ``frames`` (N), ``tracked`` (N_F),
+    ``failed``, ``accuracy`` (sum / N_F, NaN for N_F = 0) and ``robustness`` (N_F / N, NaN for N = 0); ``clips`` per clip (n_clips
+    of them, by default as many as the runs name) ``runs``, ``accuracy`` (sum of the sums / sum of N_F over its runs) and
+    ``robustness`` (sum of N_F / sum of N), NaN where the denominator is 0; over the set ``accuracy`` and ``robustness`` by the same
+    two formulas, ``eao`` (the mean of the curve's non-NaN points over n in [lo, hi]; NaN without one), ``eao_points`` (how many
+    they were), ``eao_curve``, ``eao_interval``, ``failures``, ``runs`` (their number), ``runs_without_frames`` (N = 0: such a run takes part
+    in nothing) and ``clips_without_runs``."""
+    table = np.asarray(table, dtype=np.float64).reshape(-1, MS_HEAD)
+    runs = np.asarray(runs, dtype=np.int64).reshape(-1, 4)
+    curve = np.asarray(curve, dtype=np.float64).reshape(-1)
+    lo, hi = int(eao_interval[0]), int(eao_interval[1])
+    if len(runs) != len(table) or lo < 1 or hi < lo or hi > len(curve):
+        raise ValueError("summarize_multistart: %d runs for %d table rows, eao_interval (%d, %d) on a curve of %d points"
+                         % (len(runs), len(table), lo, hi, len(curve)))
+    failed = table[:, MS_FAILED] != 0
+    n = table[:, MS_FRAMES]
+    n_f = np.where(failed, table[:, MS_TRACKED], n)
+    total = np.where(failed, table[:, MS_SUM_IOU], table[:, MS_PENDING])
+    has = n > 0
+    n_f, total, failed = np.where(has, n_f, 0.0), np.where(has, total, 0.0), failed & has
+    over = lambda a, b: a / np.where(b > 0, b, np.nan)
+    n_clips = (int(runs[:, 0].max()) + 1 if len(runs) else 0) if n_clips is None else int(n_clips)
+    per_clip = lambda v: np.bincount(runs[:, 0], weights=v, minlength=n_clips)
+    runs_of = np.bincount(runs[:, 0], minlength=n_clips)
+    window = curve[lo - 1:hi]
+    used = ~np.isnan(window)
+    return {"per_run": {"clip": runs[:, 0].copy(), "anchor": runs[:, 1].copy(), "direction": runs[:, 2].copy(),
+                        "frames": n.astype(np.int64), "tracked": n_f.astype(np.int64), "failed": failed,
+                        "accuracy": over(total, n_f), "robustness": over(n_f, n)},
+            "clips": {"runs": runs_of, "accuracy": over(per_clip(total), per_clip(n_f)), "robustness": over(per_clip(n_f), per_clip(n))},
+            "accuracy": float(over(total.sum(), n_f.sum())), "robustness": float(over(n_f.sum(), n.sum())),
+            "eao": float(window[used].mean()) if used.any() else np.nan, "eao_points": int(used.sum()), "eao_curve": curve,
+            "eao_interval": (lo, hi), "failures": int(failed.sum()), "runs": len(runs),
+            "runs_without_frames": int((~has).sum()), "clips_without_runs": int((runs_of == 0).sum())}
+
+
+class MultiStart(object):
+    """The multi-start protocol for n_runs runs on the device (the rules: include/ntmtrack.h, ntk_track_multistart): ``table``
+    float64 [n_runs, MS_HEAD], one row per run, which holds ALL of the protocol's state -- there is nothing per slot and nothing
+    to start --, and ``trace`` float64 [trace_first[n_runs]], every scored frame's overlap, run r's from trace_first[r] on.
+    ``trace_first`` int64 [n_runs + 1] (a run of L frames takes L - 1 entries) is uploaded once.  ``add`` is one launch and
+    synchronises nothing; ``result`` launches the EAO reduction and is the one synchronising call."""
+
+    def __init__(self, n_runs, trace_first, failure_overlap=0.1, patience=10, device="cuda"):
+        import torch
+        self.n_runs, self.failure_overlap, self.patience = int(n_runs), float(failure_overlap), int(patience)
+        first = np.ascontiguousarray(trace_first, dtype=np.int64).reshape(-1)
+        if (self.n_runs < 1 or len(first) != self.n_runs + 1 or first[0] != 0 or (np.diff(first) < 0).any() or self.patience < 0
+                or not 0 <= self.failure_overlap < 1):
+            raise ValueError("MultiStart: n_runs=%d, %d ascending trace_first entries from 0 (n_runs + 1), patience=%d (>= 0), "
+                             "failure_overlap=%g (in [0,1))" % (self.n_runs, len(first), self.patience, self.failure_overlap))
+        self.device = torch.device(device)
+        self.trace_first = first
+        self._first = _upload(first, torch.int64, self.device)
+        self.table = torch.zeros((self.n_runs, MS_HEAD), dtype=torch.float64, device=self.device)
+        self.trace = torch.zeros((max(int(first[-1]), 1),), dtype=torch.float64, device=self.device)      # never an empty buffer
+
+    def add(self, regions, gt, clip_of, active=None, frame_iou=False):
+        """OverlapScores.add's arguments (clip_of [B]: the RUN of slot b) -> one ntk_track_multistart, _poly or (after the
+        MaskRound's one ntk_track_mask_overlaps) _mask."""
+        from . import _lib
+        P = _lib.ptr
+        name, regions, truth, mask, clip_of, T, B, out, _held = _scoring_call("MultiStart.add", "ntk_track_multistart", self.device,
+                                                                              regions, gt, clip_of, active, frame_iou)
+        _lib.check(getattr(_lib.lib(), name)(P(regions), *truth, P(mask), P(clip_of), T, B, self.n_runs, self.failure_overlap,
+                                             self.patience, P(self.table), P(self._first), P(self.trace), P(out), _lib.stream()), name)
+        return out
+
+    def curve(self, n_max):
+        """One ntk_track_eao_curve over the runs as they stand -> Phi(1 ... n_max), float64 [n_max] on the device (no
+        synchronisation; the prefix sums go to a buffer of the trace's size that lives for this call)."""
+        import torch
+        from . import _lib
+        P = _lib.ptr
+        prefix = torch.empty_like(self.trace)
+        curve = torch.empty((int(n_max),), dtype=torch.float64, device=self.device)
+        _lib.check(_lib.lib().ntk_track_eao_curve(P(self.table), P(self._first), P(self.trace), self.n_runs, int(n_max), P(prefix),
+                                                  P(curve), _lib.stream()), "ntk_track_eao_curve")
+        return curve
+
+    def result(self, eao_interval=(115, 755), runs=None, n_clips=None):
+        """Launches the EAO reduction (n_max = hi) and reads the table and the curve back in ONE copy (the one synchronisation)
+        -> summarize_multistart.  runs: multistart_runs' (by default every run is its own clip, started at frame 0)."""
+        import torch
+        hi = int(eao_interval[1])
+        if int(eao_interval[0]) < 1 or hi < int(eao_interval[0]):
+            raise ValueError("MultiStart.result: eao_interval=%s; 1 <= lo <= hi" % (tuple(eao_interval),))
+        host = torch.cat([self.table.reshape(-1), self.curve(hi)]).cpu().numpy()
+        if runs is None:
+            runs = np.stack([np.arange(self.n_runs), np.zeros(self.n_runs), np.ones(self.n_runs), np.diff(self.trace_first) + 1], axis=1)
+        return summarize_multistart(host[:self.n_runs * MS_HEAD], runs, host[self.n_runs * MS_HEAD:], eao_interval, n_clips)
 
 
 def _as_clip(c):
@@ -749,6 +962,13 @@ class Validation(object):
     truth inside the pass.  ``supervisor`` then holds the table (``scores`` stays empty), ``codes()`` the per-frame codes per clip
     beside ``regions()``, whose skipped frames hold NaN.  Still no host synchronisation after the first round of a frame size.
 
+    ``protocol="multistart"`` runs the multi-start (anchor-based) protocol of the VOT sets from 2020 on (``spacing``, ``anchors``,
+    ``failure_overlap``, 0.1 unless given, ``patience``, ``eao_interval``): the clips are expanded into their runs (multistart_runs;
+    ``runs``, ``source_clips``), the runs are scheduled exactly as clips are -- ``clips``, ``regions()`` and every table are per
+    RUN, in run order -- and a round's scoring launch is ONE ``multistart.add`` (MultiStart) in place of scores.add (``scores``
+    stays empty).  The schedule is static: a run that has failed is still tracked to its scheduled end, which costs the frames
+    behind every failure.  Still no host synchronisation after the first round of a frame size.
+
     Clips with polygon regions ([L,2P]) are scored against the polygons in both protocols; their trackers start, and restart, from
     the polygons' bounding rectangles.  Rectangle clips in the same run are scored as 4-gons.  The polygons go up through the same
     pinned asynchronous copy, so a round still makes no host synchronisation.
@@ -772,12 +992,23 @@ class Validation(object):
     ran, whatever ``decode`` says."""
 
     def __init__(self, make_tracker, clips, B, T, iou_thresholds=None, dist_thresholds=None, return_regions=False, device="cuda",
-                 protocol="one_pass", skip=5, burn_in=10, failure_overlap=0.0, decode="host", prefetch=2, workers=None,
-                 on_undecoded="raise"):
+                 protocol="one_pass", skip=5, burn_in=10, failure_overlap=None, decode="host", prefetch=2, workers=None,
+                 on_undecoded="raise", spacing=50, anchors=None, patience=10, eao_interval=(115, 755)):
         import torch
         from . import data
         if protocol not in PROTOCOLS:
             raise ValueError("Validation: protocol %r; one of %s" % (protocol, ", ".join(PROTOCOLS)))
+        if failure_overlap is None:                     # the supervised protocol's 0, the multi-start protocol's 0.1
+            failure_overlap = 0.1 if protocol == "multistart" else 0.0
+        self.runs = self.source_clips = self.multistart = None
+        if protocol == "multistart":
+            lo, hi = (int(v) for v in eao_interval)
+            if int(spacing) < 1 or int(patience) < 0 or not 0 <= float(failure_overlap) < 1 or lo < 1 or hi < lo:
+                raise ValueError("Validation: spacing=%d (>= 1) patience=%d (>= 0) failure_overlap=%g (in [0,1)) eao_interval=(%d, %d) "
+                                 "(1 <= lo <= hi)" % (spacing, patience, failure_overlap, lo, hi))
+            self.eao_interval = (lo, hi)
+            self.source_clips = [_as_clip(c) for c in clips]
+            clips, self.runs = multistart_runs(self.source_clips, spacing, anchors)      # from here on a run is a clip
         data._check_decode(decode)
         if on_undecoded not in ON_UNDECODED:
             raise ValueError("Validation: on_undecoded %r; one of %s" % (on_undecoded, ", ".join(ON_UNDECODED)))
@@ -832,6 +1063,9 @@ class Validation(object):
         self.scores = OverlapScores(len(self.clips), iou_thresholds, dist_thresholds, device=self.device)
         self._sup_args = (skip, burn_in, failure_overlap) if protocol == "supervised" else None
         self.supervisor = None                          # made with the first round: it needs the schedule's effective B
+        if protocol == "multistart":                    # one table row and one stretch of the trace per run
+            first = np.concatenate([[0], np.cumsum([n - 1 for n in lengths])])
+            self.multistart = MultiStart(len(self.clips), first, failure_overlap, patience, device=self.device)
         self._keep = [] if return_regions else None     # (device regions [T,B,4], frame_index, active, clip ids) per round
         self._rounds = self._all_rounds()
 
@@ -906,7 +1140,7 @@ class Validation(object):
             out = cls.tracker.track_clip(inp.frames, active=inp.active, supervisor=cls.supervisor, gt=d_gt, clip_of=inp.d_ids)
         else:
             out = cls.tracker.track_clip(inp.frames, active=inp.active)
-            self.scores.add(out, d_gt, inp.d_ids, active=inp.active)
+            (self.scores if self.multistart is None else self.multistart).add(out, d_gt, inp.d_ids, active=inp.active)
         cls.source.consumed()                           # the round's launches are enqueued
         if self._keep is not None:
             self._keep.append((out, rnd.frame_index, inp.tracked, ids, None if cls.supervisor is None else cls.supervisor.codes))
@@ -1021,14 +1255,19 @@ class Validation(object):
 def validate(make_tracker, clips, B, T, return_regions=False, **kw):
     """Validation(...) run to its end -> scores.result(), or (result, regions per clip) with return_regions=True.  With
     protocol="supervised" (and skip=, burn_in=, failure_overlap=) the result is the supervisor's (summarize_supervised) and
-    return_regions=True gives (result, regions per clip, codes per clip).  decode=, prefetch=, workers=, on_undecoded= go to
+    return_regions=True gives (result, regions per clip, codes per clip).  With protocol="multistart" (and spacing=, anchors=,
+    failure_overlap=, patience=, eao_interval=) the result is summarize_multistart's and the regions are per RUN, in run order.
+    decode=, prefetch=, workers=, on_undecoded= go to
     Validation; a run that had file clips gains ``result["decode"]``: ``clips`` (per clip ``decoded``, ``failed``, ``masked``,
     ``first_failed``, ``first_status``, ``start_status``: the NTK_CLIPDEC_* row), the totals ``decoded``, ``failed``, ``masked``
     and ``clips_affected``, ``frames_on_device`` / ``frames_on_host`` (files the device / Pillow decoded) and ``failed_files``
     (per affected clip the file that failed first).  Results of runs without file clips keep their keys."""
     v = Validation(make_tracker, clips, B, T, return_regions=return_regions, **kw).finish()
     supervised = v.protocol == "supervised"
-    res = (v.supervisor if supervised else v.scores).result()
+    if v.multistart is not None:
+        res = v.multistart.result(v.eao_interval, v.runs, len(v.source_clips))
+    else:
+        res = (v.supervisor if supervised else v.scores).result()
     if v.decode_report is not None:
         res["decode"] = v.decode_report
     if not return_regions:
