@@ -1270,6 +1270,38 @@ int ntk_two_step_ce_loss(const float* logits, const float* gt, float* probs, flo
  * sigmoid(logits)) (mean over all n elements, epsilon 1e-7) and d loss / d logits (nullable). */
 int ntk_log_loss(const float* logits, const float* labels, float* loss, float* dlogits, int n, void* stream);
 
+/* Repeat-copy task of the vendored DNC (dnc/repeat_copy.py, dnc/train.py).
+ *
+ * ntk_repeat_copy_pack lays out one batch in ONE launch (repeat_copy.py:252-377).  bits [B, max_length, num_bits] fp32 in
+ * {0, 1}; lengths [B], repeats [B] int32 ON THE DEVICE; S the padded step count.  Outputs, every element written:
+ *   X [B, S, ldx]               observations, batch-major, in the sequence kernels' input layout (ldx >= num_bits + 2, a multiple
+ *                               of 4; the padding columns num_bits + 2 .. ldx - 1 are written as zero)
+ *   target [B, S, num_bits + 1] and mask [B, S].
+ * A sequence of pattern length L and r repeats: step 0 carries the start flag (channel num_bits), steps 1..L the pattern, step
+ * L + 1 carries r / norm_max (channel num_bits + 1); target rows L + 2 .. L + 1 + L r hold the pattern tiled r times, row
+ * L + 2 + L r the end marker (channel num_bits); the mask is 1 on rows L + 2 .. L + 2 + L r; all else is zero, and so is
+ * everything from the sequence's own length L (r + 1) + 3 to S.
+ * Range contract: lengths lie in [min_length, max_length] and repeats in [min_repeats, max_repeats] (min_length >= 1,
+ * min_repeats >= 0); the kernel CLAMPS values outside, it does not trust them, so a bad table cannot index past bits.
+ * The launcher cannot see the device tables: it refuses S < min_length (min_repeats + 1) + 3; rows at or past S are never
+ * written (a sequence longer than S is cut). */
+int ntk_repeat_copy_pack(const float* bits, const int* lengths, const int* repeats, float* X, float* target, float* mask,
+                         int B, int S, int num_bits, int ldx, int min_length, int max_length, int min_repeats, int max_repeats,
+                         float norm_max, void* stream);
+
+/* masked_sigmoid_cross_entropy (repeat_copy.py:29-66) with its gradient and the copy score, in one pass.  logits, target
+ * [B, S, O] batch-major (what the sequence kernels write), mask [B, S].  xent = max(x, 0) - x z + log1p(exp(-|x|)), summed
+ * over channels, then over steps times their mask; with time_average divided by (sum of the mask + FLT_EPSILON); that is
+ * loss_batch [B]; loss [1] = sum(loss_batch) / B, divided by ln 2 with log_prob_in_bits.  dlogits [B, S, O] (nullable:
+ * loss only) = (sigmoid(x) - z) times the same factors.  score [B, 2] int32 (nullable): the scored bits of the sequence and
+ * those where (logit > 0) != (target > 0.5), i.e. where train.py:104-105's rounded output differs from the target.
+ * Departure from the reference: a step whose mask is 0 is SELECTED out, not multiplied out -- it adds exactly 0 and its
+ * dlogits are +0.0 whatever its logits hold, NaN included.  One workgroup per sequence, then a fixed-order batch sum:
+ * the same bits from run to run. */
+int ntk_masked_sigmoid_xent(const float* logits, const float* target, const float* mask, float* loss, float* loss_batch,
+                            float* dlogits, int* score, int B, int S, int O, int time_average, int log_prob_in_bits,
+                            void* stream);
+
 /* ------------------------------------------------------------------------
  * optimiser (direct_offset_output.py:620-626): tf.clip_by_global_norm +
  * tf.train.RMSPropOptimizer on one flat buffer

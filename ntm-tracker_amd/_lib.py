@@ -150,6 +150,8 @@ def _sig(lib):
         "ntk_resize_bilinear": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, P]),
         "ntk_offset_loss": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
         "ntk_log_loss": (c_int, [P, P, P, P, c_int, P]),
+        "ntk_repeat_copy_pack": (c_int, [P] * 6 + [c_int] * 8 + [ctypes.c_float, P]),
+        "ntk_masked_sigmoid_xent": (c_int, [P] * 7 + [c_int] * 5 + [P]),
         "ntk_serialize_sequential": (c_int, [P, P, P] + [c_int] * 5 + [P]),
         "ntk_heatmap_ce_loss": (c_int, [P] * 5 + [c_int] * 3 + [P]),
         "ntk_serialize_two_step": (c_int, [P, P, P] + [c_int] * 5 + [P]),
