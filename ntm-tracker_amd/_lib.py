@@ -6,6 +6,7 @@ call fails, an exception is raised.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -207,3 +208,18 @@ def ptr(t):
 
 def stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def upload(array, dtype, device):
+    """Host array -> device tensor without a synchronising call: through a pinned staging tensor and an asynchronous copy
+    on the current stream (the pinned block is not reused before that copy has run)."""
+    t = torch.as_tensor(np.ascontiguousarray(array)).to(dtype)
+    return t.pin_memory().to(device, non_blocking=True)
+
+
+def on_device(x, dtype, device):
+    """A tensor on the device is taken as it is (converted only where its type or layout differs); a host array or tensor goes
+    up through ``upload``."""
+    if torch.is_tensor(x) and x.device.type == device.type:
+        return x.to(dtype).contiguous()
+    return upload(x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x), dtype, device)

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from .geometry import apply_transformation, calculate_transformation, discrete_gauss
+from .regions import MASK_MAX_PIXELS, POLY_DOUBLES, POLY_MAX_POINTS, Clip, MaskRegions, rect_polygons
 
 VGG_MEAN = (123.68, 116.78, 103.94)
 
@@ -140,7 +141,6 @@ def validation_clips(seqs, image_root=None, frames="arrays"):
     with the first region NORMALISED, as the reference passes it (the trackers take a region whose four numbers are below 1 as
     normalised); the ground truth for scoring is in pixels."""
     from PIL import Image
-    from .evaluate import Clip
     _check_clip_frames(frames)
     clips = []
     for folder, stems in seqs:
@@ -157,7 +157,6 @@ def parse_vot_region(line):
     """One line of a VOT groundtruth.txt as vot.py:27-33 (parse_region) reads it: 4 numbers are a rectangle (x, y, w, h), an even
     count above 4 a polygon (x0, y0, x1, y1, ...).  -> a list of 4 or of 2P floats, or None for a line that is neither (an absent
     object).  A polygon of more than evaluate.POLY_MAX_POINTS points is an error: the device layout cannot hold it."""
-    from .evaluate import POLY_DOUBLES, POLY_MAX_POINTS
     try:
         tokens = [float(t) for t in line.strip().split(',')]
     except ValueError:
@@ -177,7 +176,6 @@ def parse_vot_mask(line):
     -> (x0, y0, w, h, counts int32 array), the counts as they are written (evaluate.MaskRegions, include/ntmtrack.h NTK_MASK_*).
     ValueError, with the reason: a line that does not begin with ``m``, fewer than four numbers, a number that is not an integer
     (of 32 bits), a negative count, a box of more than evaluate.MASK_MAX_PIXELS pixels.  A box with w <= 0 or h <= 0 is returned as it is: an absent object."""
-    from .evaluate import MASK_MAX_PIXELS
     text = line.strip()
     if not text.startswith("m"):
         raise ValueError("not a mask line (it does not begin with 'm'): %r" % (text[:40],))
@@ -207,7 +205,6 @@ def parse_vot_mask(line):
 def _vot_mask_regions(path, lines):
     """The lines of a groundtruth.txt that holds mask lines -> evaluate.MaskRegions: a line that is neither a mask nor parseable
     is an absent object, a rectangle or polygon line among them a ValueError naming the file and the line."""
-    from .evaluate import MaskRegions
     frames = []
     for k, line in enumerate(lines):
         try:
@@ -233,7 +230,6 @@ def vot_clips(root, names=None, frames="arrays"):
     Only the first image's header is opened here (for ``size``); a clip's frames are decoded when the validator schedules it
     (frames="files": a round at a time, from the paths; _clip_frames)."""
     from PIL import Image
-    from .evaluate import Clip, POLY_DOUBLES, rect_polygons
     _check_clip_frames(frames)
     if names is None:
         with open(os.path.join(root, "list.txt")) as f:

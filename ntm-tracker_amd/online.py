@@ -16,9 +16,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluate import POLY_DOUBLES          # one polygon region of the ground truth (include/ntmtrack.h NTK_POLY_DOUBLES)
-from .evaluate import MASK_OVERLAP_DOUBLES, MaskRound       # mask ground truth of a round (include/ntmtrack.h NTK_MASK_*)
+from ._lib import upload as _upload         # host array -> device tensor through a pinned asynchronous copy: no synchronisation
 from .ntm import NTMCell, _P, _np, gemm_nt
+from .regions import as_round_truth         # a round's ground truth by kind: rectangles, polygons or masks
+from .regions import MASK_OVERLAP_DOUBLES, POLY_DOUBLES     # noqa: F401  (not used here any more; callers read them as online.X)
 from .tracker import GRID_N, GRID_START, GRID_STEP, NUM_FEATURES
 from .vgg import VGG16Conv43
 
@@ -124,13 +125,6 @@ class NTMTracker(object):
 # ---- batched online tracker: boxes, crops and state stay on the device ---------------------------------------------------
 
 STATE_DOUBLES = 10           # include/ntmtrack.h NTK_TRACK_STATE_*: [w, h, object box y1 x1 y2 x2, crop box y1 x1 y2 x2]
-
-
-def _upload(array, dtype, device):
-    """Host array -> device tensor without a synchronising call: through a pinned staging tensor and an asynchronous copy
-    on the current stream (the pinned block is not reused before that copy has run)."""
-    t = torch.as_tensor(np.ascontiguousarray(array)).to(dtype)
-    return t.pin_memory().to(device, non_blocking=True)
 
 
 def crop_and_resize_batch(images, frame_of, boxes, crop=224, mean=None, out=None):
@@ -409,46 +403,27 @@ class BatchNTMTracker(object):
         NTK_POLY_*): plan and judge take the polygons, a restart starts from the polygon's bounding rectangle, which one
         ntk_track_poly_bounds launch computes for the whole round.  ``gt`` may be an evaluate.MaskRound (segmentation masks,
         NTK_MASK_*): per frame plan on the masks' rects[t], the pass with restarts from rects[t], one ntk_track_mask_overlaps
-        of the frame's B masks against the tracked regions, judge.  The supervisor's ``codes`` [T,B] int8 then say what
-        each slot did on each frame; a slot that sat a frame out repeats its last region."""
+        of the frame's B masks against the tracked regions, judge; the round's ``gt.overlap`` [T,B,3] holds them afterwards.
+        The loop is one for the three kinds (regions.as_round_truth: ``rects``, ``after_pass``).  The supervisor's ``codes``
+        [T,B] int8 then say what each slot did on each frame; a slot that sat a frame out repeats its last region."""
         T = len(frames)
         if not torch.is_tensor(frames) and not isinstance(frames, (list, tuple)):
             a = np.asarray(frames)
             frames = _upload(a, torch.uint8 if a.dtype == np.uint8 else torch.float32, self.device)
         masks = None if active is None else self._mask(active, (T, self.B))
         out = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
-        if supervisor is not None and isinstance(gt, MaskRound):
-            if not (tuple(gt.rects.shape) == (T, self.B, 4) and gt.rects.is_cuda and gt.rects.dtype == torch.float64
-                    and gt.rects.is_contiguous() and gt.cells.is_contiguous() and clip_of is not None):
-                raise _lib.NtkError("track_clip: a supervisor with masks needs a MaskRound of [%d,%d] masks on the device and "
-                                    "clip_of" % (T, self.B))
-            codes = torch.empty((T, self.B), device=self.device, dtype=torch.int8)
-            overlap = torch.empty((T, self.B, MASK_OVERLAP_DOUBLES), device=self.device, dtype=torch.float64)
-            for t in range(T):
-                frame = gt[t]
-                track, restart = supervisor.plan(frame, None if masks is None else masks[t], clip_of, codes=codes[t])
-                self._step_restart(self._images(frames[t]), track, restart, frame.rects)
-                frame.overlaps(self.regions, out=overlap[t])
-                supervisor.judge(self.regions, frame, clip_of, codes=codes[t])
-                out[t].copy_(self.regions)
-            gt.overlap = overlap
-            supervisor.codes = codes
-            return out
         if supervisor is not None:
-            if not (torch.is_tensor(gt) and gt.is_cuda and gt.dtype == torch.float64 and gt.dim() == 3
-                    and tuple(gt.shape[:2]) == (T, self.B) and gt.shape[2] in (4, POLY_DOUBLES) and gt.is_contiguous()
-                    and clip_of is not None):
-                raise _lib.NtkError("track_clip: a supervisor needs gt as a contiguous float64 [%d,%d,4] (or [%d,%d,%d]) device "
-                                    "tensor and clip_of" % (T, self.B, T, self.B, POLY_DOUBLES))
-            rects = gt
-            if gt.shape[2] == POLY_DOUBLES:             # what a restart starts from: the polygons' bounding rectangles
-                rects = torch.empty((T, self.B, 4), device=self.device, dtype=torch.float64)
-                _lib.check(_lib.lib().ntk_track_poly_bounds(_P(gt), T * self.B, _P(rects), _lib.stream()), "ntk_track_poly_bounds")
+            if clip_of is None:
+                raise _lib.NtkError("track_clip: a supervisor needs gt and clip_of")
+            truth = as_round_truth(gt, self.device, "track_clip with a supervisor", shape=(T, self.B))
+            rects = truth.rects                         # what a restart starts from, for the whole round
             codes = torch.empty((T, self.B), device=self.device, dtype=torch.int8)
             for t in range(T):
-                track, restart = supervisor.plan(gt[t], None if masks is None else masks[t], clip_of, codes=codes[t])
+                frame = truth[t]
+                track, restart = supervisor.plan(frame, None if masks is None else masks[t], clip_of, codes=codes[t])
                 self._step_restart(self._images(frames[t]), track, restart, rects[t])
-                supervisor.judge(self.regions, gt[t], clip_of, codes=codes[t])
+                frame.after_pass(self.regions)
+                supervisor.judge(self.regions, frame, clip_of, codes=codes[t])
                 out[t].copy_(self.regions)
             supervisor.codes = codes
             return out

@@ -86,7 +86,7 @@ def make_clips(n, seed):
 
 
 def round_counts(clips, B):
-    """The counts of every round's upload: n_rle per round, as Validation._round_masks concatenates them."""
+    """The counts of every round's upload: n_rle per round, as MaskTruth.round concatenates them."""
     out = []
     for rnd in evaluate.ClipSchedule([len(c.regions) for c in clips], B, T):
         n_rle = 0

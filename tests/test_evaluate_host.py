@@ -70,6 +70,60 @@ def test_schedule_refuses_a_clip_without_a_frame_to_track(lengths):
         ClipSchedule(lengths, 2, 2)
 
 
+def test_round_slices_reproduce_frame_index_and_active():
+    """Round.slices() names a slot's frames once, for the frames and the ground truth alike.  [5, 2, 9, 3] over 3 slots of 4 frames
+    is the smallest schedule with a clip that ends mid-round (clip 1), a slot that idles (slot 1 in round 1) and a slot refilled in
+    the next round (slot 0, clip 3)."""
+    from ntmtrack.evaluate import ClipSchedule
+    rounds = list(ClipSchedule([5, 2, 9, 3], 3, 4))
+    for r in rounds:
+        frame_index, active = np.zeros_like(r.frame_index), np.zeros_like(r.active)
+        for b, lo, hi in r.slices():
+            assert hi > lo
+            frame_index[:hi - lo, b], active[:hi - lo, b] = np.arange(lo, hi), 1
+        assert np.array_equal(frame_index, r.frame_index) and np.array_equal(active, r.active)
+    assert [list(r.slices()) for r in rounds] == [[(0, 1, 5), (1, 1, 2), (2, 1, 5)], [(0, 1, 3), (2, 5, 9)]]
+    assert rounds[1].resets == [(0, 3)] and rounds[1].clip_of.tolist() == [3, -1, 2]
+
+
+def test_the_three_kinds_of_host_truth_agree_with_the_functions_they_wrap():
+    """A 4-frame clip whose object is absent on frame 2, written as rectangles, as 5-gons and as masks: present(), first() and
+    take() of its truth object against regions_present, polygon_bounds / mask_bounds and fancy indexing / MaskRegions.take."""
+    from ntmtrack import evaluate as E
+    order = [3, 2, 1, 0]
+    rects = np.array([[1.0, 2.0, 4.0, 3.0], [2.0, 2.0, 4.0, 3.0], [np.nan] * 4, [3.0, 1.0, 2.0, 5.0]])
+    t = E.as_truth(rects)
+    assert type(t) is E.RectTruth and len(t) == 4
+    assert t.present().tolist() == E.regions_present(rects).tolist() == [True, True, False, True]
+    assert t.first().tobytes() == rects[0].tobytes()
+    assert type(t.take(order)) is E.RectTruth and t.take(order).regions.tobytes() == rects[order].tobytes()
+
+    gons = np.array([[x, y, x + 4, y, x + 5, y + 2, x + 2, y + 4, x, y + 3] for x, y in ((1.0, 2.0), (2.0, 2.5), (0.0, 0.0), (3.5, 1.0))])
+    gons[2] = np.nan
+    t = E.as_truth(gons)
+    assert type(t) is E.PolyTruth and len(t) == 4 and t.regions.shape == (4, E.POLY_DOUBLES)
+    assert t.present().tolist() == E.regions_present(gons).tolist() == [True, True, False, True]
+    assert t.first().tobytes() == E.polygon_bounds(E.pad_polygons(gons[0])).tobytes() and t.first().tolist() == [1.0, 2.0, 5.0, 4.0]
+    assert type(t.take(order)) is E.PolyTruth and np.array_equal(t.take(order).regions, E.pad_polygons(gons)[order], equal_nan=True)
+    # rectangles promoted to 4-gons (a set with a polygon clip) keep the rectangle they start from, bit for bit
+    promoted = E.as_truth(rects).as_polygons()
+    assert type(promoted) is E.PolyTruth and promoted.first().tobytes() == rects[0].tobytes()
+    assert np.array_equal(promoted.regions, E.rect_polygons(rects), equal_nan=True) and promoted.present().tolist() == [True, True, False, True]
+
+    dense = np.zeros((4, 6, 8), dtype=np.uint8)
+    dense[0, 1:4, 2:5], dense[1, 2:5, 3:7], dense[3, 0:2, 5:8] = 1, 1, 1
+    dense[1, 3, 4] = 0                                              # a hole: more than one run per row
+    masks = E.MaskRegions.from_arrays(dense)
+    t = E.as_truth(masks)
+    assert type(t) is E.MaskTruth and len(t) == 4
+    assert t.present().tolist() == E.regions_present(masks).tolist() == [True, True, False, True]
+    assert t.first().tobytes() == E.mask_bounds(masks, 0).tobytes() and t.first().tolist() == [2.0, 1.0, 3.0, 3.0]
+    got, want = t.take(order).regions, masks.take(order)
+    assert type(t.take(order)) is E.MaskTruth
+    assert all(np.array_equal(getattr(got, k), getattr(want, k)) for k in ("boxes", "counts", "offsets"))
+    assert all(np.array_equal(got.dense(k, 6, 8), dense[i] != 0) for k, i in enumerate(order))
+
+
 # ---------------------------------------------------------------------------------------------------- the validation records
 def write_record(folder, stem, normalized_xywh, image_path):
     """A format-(B) record as the offline preparation writes it: crop box, the object box in crop coordinates, image path."""
