@@ -85,10 +85,17 @@ int ntk_vgg_conv3x3_relu_f32_to_bf16(const float* in, const float* w_packed, con
 
 /* The SPLIT form of the fp32 trunk (csrc/conv_bf16p.hip, template flag X3; round 4): the same fp32 operator (vgg.py:155-161) on the
  * fp16 matrix pipe.  Every fp32 value v travels as two fp16 numbers, hi = fp16(v) rounded toward zero and lo = fp16(v - hi) rounded to
- * nearest (v = hi + lo to 2^-22 |v|); a product x w is accumulated in fp32 as xh wh + xh wl + xl wh (per layer 0.7e-6 .. 1.7e-6 of the
- * activation scale).  A split map is [frames][H][W][C / 16][2][16] fp16 (hi x16 | lo x16 per group of 16 channels: the bytes of the fp32
- * map); it holds magnitudes up to 131008 (hi saturates at 65504, lo carries the rest): larger activations saturate there instead of
- * overflowing.  The weights are scaled by a power of two when packed (exact; the epilogue multiplies the sums by the inverse).
+ * nearest; a product x w is accumulated in fp32 as xh wh + xh wl + xl wh (per layer 0.7e-6 .. 1.7e-6 of the activation scale).
+ * PRECISION of the parts: an activation v = hi + lo to 2^-22 |v| for 2^-3 <= |v| <= 65504; below 2^-3 lo is an fp16 subnormal and the
+ * error is an ABSOLUTE 2^-25 (a map, or a channel, whose values are all small keeps fewer bits: at 2^-16 of unit scale, 2^-9 relative --
+ * activations have no scale of their own); from 65504 to 131008 hi is 65504 and lo carries the rest at fp16's spacing there (up to 16).
+ * A weight is exact to 2^-22 |w| down to 2^-17 of the layer's largest (one power-of-two scale per layer), to 2^-38 of the largest
+ * below.  The matrix pipe keeps fp16 subnormal operands (measured, profiles/conv_values.txt).  The weights are scaled by a power of
+ * two when packed (exact; the epilogue multiplies the sums by the inverse).
+ * A split map is [frames][H][W][C / 16][2][16] fp16 (hi x16 | lo x16 per group of 16 channels: the bytes of the fp32 map).  Larger
+ * activations saturate at 131008 instead of overflowing: on the way in (a split map holds no more; the staging of an fp32 map
+ * clamps) and in the epilogue that writes a split map.  An fp32 OUTPUT (out_f32 = 1) is not clamped: sums beyond 131008 are written
+ * as they are.
  * Shapes (ntk_vgg_split3_supported): H, W multiples of 8, or W = 28 with H >= 20 and no pool (runs of rows); cin a multiple of 16, cout
  * of 64.  Packed weights: ntk_vgg_split3_packed_elems(cin, cout) = 18 * cin * cout + 8 fp16 elements, packed per layer and frame shape:
  * the hi / lo parts, then a 16-byte tail the packing writes its scales into -- size the buffer with ntk_vgg_split3_packed_elems

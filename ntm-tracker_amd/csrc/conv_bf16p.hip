@@ -84,7 +84,9 @@ __device__ __forceinline__ ph16x8 p_as_f16x8(const f32x4& v) {
 }
 // The split form's two parts of four fp32 values: hi = fp16(v) rounded TOWARD ZERO (v_cvt_pkrtz_f16_f32: a value beyond the fp16
 // range saturates at 65504 instead of becoming infinite, and lo then carries the rest up to 131008), lo = fp16(v - hi) rounded to
-// nearest: v = hi + lo to 2^-22 |v| (eleven + eleven bits) for 6e-5 < |v| < 65504; below, to fp16's absolute 6e-8.
+// nearest: v = hi + lo to 2^-22 |v| (eleven + eleven bits) for 2^-3 <= |v| <= 65504; below 2^-3 lo is an fp16 SUBNORMAL (a multiple of
+// 2^-24) and the error is an absolute 2^-25; above 65504 hi is 65504 and lo carries v - 65504 at fp16's spacing there (up to 16 at
+// 131008).  tests/conv_value_util.py dx() is this statement, tests/test_conv_values_gpu.py holds the kernels to it element by element.
 // PRECONDITION: |v| <= S3_MAX = 131008 (the callers clamp: the epilogues with the same v_med3_f32 that is their ReLU) -- so that
 // lo cannot overflow either.
 __device__ __forceinline__ void s3_split4(const f32x4& v, ph16x4& hi, ph16x4& lo) {

@@ -355,7 +355,10 @@ class VGG16Conv43(object):
 
     weights: {layer_name: (w_hwio [3,3,Cin,Cout], b [Cout])} as numpy arrays or tensors.
     dtype "f32" (BASELINE configs 2-4: fp32 values and accumulators; `algo` picks the form -- None / "split3": conv1_2 .. conv4_3
-    as three fp16 MFMA products per fp32 product of hi / lo parts (DESIGN.md 4.0''; error at or below the Winograd form's),
+    as three fp16 MFMA products per fp32 product of hi / lo parts (DESIGN.md 4.0''; error at or below the Winograd form's;
+    an activation is carried to 2^-22 relative from 2^-3 up to 65504, to an absolute 2^-25 below 2^-3 and at fp16's spacing from
+    65504 to the clamp at 131008, a weight to 2^-22 relative down to 2^-17 of its layer's largest; conv4_3's fp32 output is not
+    clamped: include/ntmtrack.h, tests/test_conv_values_gpu.py),
     "winograd" / "winograd2": fused Winograd on the fp32 MFMA pipe, "direct": the implicit-GEMM kernel; NTK_TRUNK_ALGO overrides
     the default) or "bf16" (config 5: bf16 operands, fp32 accumulate; conv1_1 reads the fp32 frames, conv4_3 writes fp32 for the
     memory cell).
